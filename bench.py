@@ -4,6 +4,7 @@
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config g241|g121|g61|g16] [--kernel-width 1024]
     python bench.py --train [--gpus N] ...          # training-step mode (BASELINE config 5 shape, see below)
     python bench.py --split-graph [--gpus N] ...    # ONE graph split by destination rows over the ranks (strong scaling)
+    python bench.py ... --dump-outputs DIR          # + the last timed step's outputs as DIR/<name>.npy (same inputs every run)
 
 One "step" = one `conv(x, edge_index, edge_attr)` forward of the headline operator on one PDE sample: the
 Darcy-241^2 r=0.10 lattice radius graph (N = 58,081 nodes, E = 95,539,625 edges, BASELINE.json configs[1])
@@ -85,8 +86,30 @@ TRAFFIC_FILE = next((f for f in (os.path.join(REPO, "profiles", f"traffic_r0{k}.
                     os.path.join(REPO, "profiles", "traffic_r05.json"))      # newest committed PMC record of the headline kernel
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6   # --dump-outputs: 64 MB in all, with room for the .npy headers
+
+
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: what the timed path returned in its last step, one `<name>.npy` per array (float64 stays float64,
+    everything else float32).  Within DUMP_BUDGET_BYTES in all: smallest first, an array within an equal share of what is
+    left is written whole, a larger one as that share of its flattened elements, drawn by a fixed seed - the same shapes
+    give the same positions, so two builds compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32) for k, v in arrays.items()}
+    left = DUMP_BUDGET_BYTES
+    for i, (name, t) in enumerate(sorted(host.items(), key=lambda kv: kv[1].numel() * kv[1].element_size())):
+        keep = min(t.numel(), left // (len(host) - i) // t.element_size())
+        if keep < t.numel():
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t.reshape(-1)[idx]
+        left -= t.numel() * t.element_size()
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+    log(f"[bench] --dump-outputs: {len(host)} array(s) -> {out_dir}")
 
 
 def algorithmic_flops_per_edge(dims, w=64):
@@ -367,6 +390,7 @@ def train_mode(args, rank, world, dev, use_dist, barrier):
     g = torch.Generator(device=dev).manual_seed(10 + rank)
     feat = torch.randn(n, 6, device=dev, generator=g)
     y = torch.randn(n, device=dev, generator=g)
+    last = {}
 
     def step():
         opt.zero_grad(set_to_none=True)
@@ -376,6 +400,7 @@ def train_mode(args, rank, world, dev, use_dist, barrier):
         out = fc2(h).view(-1)
         loss = torch.norm(out - y, 1)                                      # UAI1:265
         loss.backward()
+        last["loss"], last["out"] = loss, out
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         n_red = parallel.allreduce_gradients(params, world=world if use_dist else 1)
@@ -390,6 +415,9 @@ def train_mode(args, rank, world, dev, use_dist, barrier):
     evs = [step() for _ in range(args.steps)]
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {**last, **{f"{m}.{k}": p for m, mod in (("fc1", fc1), ("conv", conv), ("fc2", fc2))
+                                                    for k, p in mod.named_parameters()}})
     ar_ms = sum(a.elapsed_time(b) for a, b, _ in evs) / max(args.steps, 1)
     mine = {"rank": rank, "ms_per_step": round(1e3 * elapsed / max(args.steps, 1), 2), "allreduce_ms": round(ar_ms, 3),
             "peak_GiB": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1)}
@@ -479,6 +507,8 @@ def split_graph_mode(args, rank, world, dev, use_dist, barrier):
         out = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"out": out})
     block_ms = statistics.median(a.elapsed_time(b) for a, b, _ in ev)
     gather_ms = statistics.median(b.elapsed_time(c) for _, b, c in ev)
     mine = {"rank": rank, "rows": [part.lo, part.hi], "edges": part.n_edges, "block_ms": round(block_ms, 3),
@@ -543,7 +573,12 @@ def main():
                          "each rank's block from the positions")
     ap.add_argument("--split-graph", action="store_true",
                     help="strong-scaling mode: ONE graph split by destination rows over the ranks (all-gather per forward)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (rank 0): "
+                         "`out` of the forward; --train: `loss`, `out` and the parameters after the optimizer step")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.config is None:
         args.config = "g61" if args.train else "g241"
 
@@ -551,16 +586,17 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world == 1 and args.gpus > 1 and "RANK" not in os.environ:
-        # started as plain `python bench.py --gpus N`: re-exec under torch.distributed.run, one rank per GPU over RCCL
-        # (the same command line the driver's launcher uses)
+        # started as plain `python bench.py --gpus N`: run it again under torch.distributed.run, one rank per GPU over RCCL
+        # (the same command line the driver's launcher uses), as a child process - this one has already opened the GPU
         have = torch.cuda.device_count()
         if have < args.gpus:
             log(f"--gpus {args.gpus}: only {have} GPU(s) visible on this node")
             sys.exit(2)
         import socket
+        import subprocess
         sk = socket.socket(); sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]; sk.close()
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        sys.exit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
+                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
     if args.gpus != world:
         log(f"--gpus {args.gpus} but WORLD_SIZE={world}: the two must agree")
         sys.exit(2)
@@ -658,6 +694,8 @@ def main():
     elapsed = time.perf_counter() - t_start
     kinds = _lib.profile_end()
     step_ms = [a.elapsed_time(b) for a, b in evs]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"out": out})       # before the legs below reuse `out`
     if use_dist:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
