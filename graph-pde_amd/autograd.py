@@ -50,8 +50,9 @@ class NNConvFunction(torch.autograd.Function):
         # a prebuilt ops.Csr (message() / update(): one-off graphs that must not enter the CSR cache) or edge_index
         csr = edge_index if isinstance(edge_index, ops.Csr) else ops.csr_for(edge_index, x.size(0))
         pm = ops.pack_mlp(weights, biases)
+        per_edge = ops.per_edge_association(csr, pm.dims, aggr)
         # training: keep Z for the backward's dW_3 (ops.z_buffer: None when it does not pay / fit)
-        ctx.z = ops.z_buffer(csr, pm.dims, x.device) if any(ctx.needs_input_grad) and aggr in ("add", "mean") else None
+        ctx.z = ops.z_buffer(csr, pm.dims, x.device) if any(ctx.needs_input_grad) and aggr in ("add", "mean") and not per_edge else None
         ctx.h = None
         if ctx.z is not None and not edge_attr.requires_grad and ops.keep_hidden(csr, pm.dims, x.device):
             # round 5: the last hidden activations are WRITTEN by the forward (store kernel), aggregated from there, and handed to
@@ -60,7 +61,9 @@ class NNConvFunction(torch.autograd.Function):
                 ctx.h, hmax = ops.hidden_forward_raw(csr, edge_attr.detach(), pm, weights, biases)
             except torch.OutOfMemoryError:
                 ctx.h = None
-        if ctx.h is not None:
+        if per_edge:
+            out = ops.nnconv_forward_per_edge_raw(x.detach(), csr, edge_attr, pm, weights, biases, root, bias, aggr)
+        elif ctx.h is not None:
             ops.n_kept_hidden += 1
             out = ops.nnconv_forward_hidden_raw(x.detach(), csr, ctx.h, pm, root, bias, aggr, hmax=hmax, z_keep=ctx.z)
         else:

@@ -264,6 +264,26 @@ FusedChoice choose_fused(const GpdePackLayout& L, int mode, uint32_t flags, int6
     return c;
 }
 
+// Whether a forward call takes the per-edge last layer (fwd_impl's low in-degree branch) -- ONE place, used by fwd_impl
+// and by the query gpde_nnconv_fwd_edge_path.  `hidden`: the last hidden activations are given (with their maximum:
+// `hidden_absmax`); `mixed` / `kt`: the mixed and node-table forwards, which never take it.
+bool takes_edge_path(const Plan& P, uint32_t flags, int64_t n_nodes, int64_t n_edges, bool hidden, bool hidden_absmax,
+                     bool mixed, int kt) {
+    const GpdePackLayout& L = P.L;
+    bool store_ok = false;
+    if (L.mode == 1 && L.k0 + 1 <= 8) {
+        GpdeFusedArgs probe{};
+        probe.k0 = L.k0; probe.K1P = L.K1P; probe.K2P = L.K2P;
+        store_ok = gpde_fused_store_supported(probe);
+    }
+    return ((flags & GPDE_FWD_F16SPLIT) || (hidden && hidden_absmax)) && !mixed && !kt && L.has_w3s && P.n_chunks == 1 &&
+           n_edges >= 4096 && n_edges <= 4 * n_nodes && n_edges < ((int64_t)1 << 24) &&
+           !(flags & GPDE_FWD_NO_EDGE_PATH) &&
+           (hidden || (L.mode == 1 && store_ok)) &&   // H by a fused store kernel (its own support check: LDS limits, chunk parity)
+           (size_t)(n_edges) * L.K2P + gpde_edge_messages_ws_floats(n_edges, GP_W * GP_W) <=
+               (size_t)n_nodes * GP_W * L.K2P;
+}
+
 }  // namespace
 
 int gpde_num_cus() { return num_cus_impl(); }
@@ -276,6 +296,15 @@ extern "C" const char* gpde_nnconv_fwd_kernel(int64_t n_edges, int n_layers, con
         case FK_V3: return "gpde_fused_f16v3_kernel";
         default: return "gpde_fused_kernel";
     }
+}
+
+extern "C" int gpde_nnconv_fwd_edge_path(int64_t n_nodes, int64_t n_edges, int n_layers, const int32_t* dims, uint32_t flags,
+                                         size_t ws_bytes) {
+    Plan P;
+    if (!dims || n_nodes < 0 || n_edges < 0) { gpde_set_error("gpde_nnconv_fwd_edge_path: null/negative argument"); return GPDE_EINVAL; }
+    int rc = make_plan(n_nodes, n_edges, n_layers, dims, ws_bytes, false, &P, nullptr);
+    if (rc != GPDE_OK) return rc;
+    return takes_edge_path(P, flags, n_nodes, n_edges, false, false, false, 0) ? 1 : 0;
 }
 
 extern "C" size_t gpde_nnconv_fwd_workspace_bytes(int64_t n_nodes, int64_t n_edges, int n_layers,
@@ -365,20 +394,8 @@ int fwd_impl(const float* x, int64_t n_nodes, const float* edge_attr, int64_t n_
     // trip per node - a loss when a node has two or three in-edges (MGKN-orthogonal Burgers: 8192 nodes, 16 k edges,
     // 2 x 2.1 GB of Z per call).  There W_e = W3 . h_e is formed tile by tile on the split-f16 GEMM and contracted
     // with x_j in its epilogue ([E][4096] never exists), messages are summed per destination in CSR order.
-    bool store_ok = false;
-    if (L.mode == 1 && L.k0 + 1 <= 8) {
-        GpdeFusedArgs probe{};
-        probe.k0 = L.k0; probe.K1P = L.K1P; probe.K2P = L.K2P;
-        store_ok = gpde_fused_store_supported(probe);
-    }
-    // z_keep: the caller wants Z_i = sum_e x_j (x) H_e of EVERY node ([N][64][K2P], zero-initialised by the caller: nodes
-    // without in-edges are not written) - the backward's dW_3 reads it instead of re-aggregating (gpde_nnconv_fwd_keepz)
-    const bool edge_path = !z_keep && ((flags & GPDE_FWD_F16SPLIT) || (hidden && hidden_absmax)) && !mixed && !kt && L.has_w3s && P.n_chunks == 1 &&
-                           n_edges >= 4096 && n_edges <= 4 * n_nodes && n_edges < ((int64_t)1 << 24) &&
-                           !(flags & GPDE_FWD_NO_EDGE_PATH) &&
-                           (hidden || (L.mode == 1 && store_ok)) &&   // H by a fused store kernel (its own support check: LDS limits, chunk parity)
-                           (size_t)(n_edges) * L.K2P + gpde_edge_messages_ws_floats(n_edges, GP_W * GP_W) <=
-                               (size_t)n_nodes * GP_W * L.K2P;
+    const bool edge_path = !z_keep && takes_edge_path(P, flags, n_nodes, n_edges, hidden != nullptr, hidden_absmax != nullptr,
+                                                      mixed, kt);
     if (edge_path) {
         float* Hbuf = zbuf;                                  // the Z region is free on this path
         float* ews = zbuf + (hidden ? 0 : (size_t)n_edges * L.K2P);

@@ -258,6 +258,10 @@ class NNConv_old(MessagePassing):
         if self.aggr == "max":
             if pseudo.dtype != torch.float32 or x.dtype != torch.float32:
                 raise NotImplementedError(f"aggr='max': float32 only (got x {x.dtype}, edge_attr {pseudo.dtype})")
+            csr = ops.csr_for(edge_index, x.size(0))
+            if csr.n_edges == 0:
+                # a graph without edges: every segment is empty, its max is 0 (PyG's fill) exactly as its sum - update() alone
+                return NNConvFunction.apply(x, csr, pseudo, root, bias, "add", len(weights), *weights, *biases)
             raise NotImplementedError(
                 f"aggr='max': the per-edge weights of this call ({ops.csr_for(edge_index, x.size(0)).n_edges} edges x 16 KiB) "
                 "exceed the cache budget (GPDE_HIDDEN_CACHE_GB / GPDE_EDGE_WEIGHT_CACHE_GB)")

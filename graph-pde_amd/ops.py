@@ -35,6 +35,15 @@ class Csr:
     _attr_sorted: Optional[dict] = None      # edge_attr tensors gathered into CSR slot order (attr_in_slot_order)
     _identity: Optional[torch.Tensor] = None
     _perm_is_identity: bool = False
+    _max_in_degree: Optional[int] = None
+
+    @property
+    def max_in_degree(self) -> int:
+        """Largest in-degree of a node (build_csr records it with its one sync; other CSRs read rowptr_host once)."""
+        if self._max_in_degree is None:
+            rp = self.rowptr_host.to(torch.int64)
+            self._max_in_degree = int((rp[1:] - rp[:-1]).max()) if self.n_nodes > 0 else 0
+        return self._max_in_degree
 
     @property
     def src_order(self):
@@ -269,10 +278,11 @@ def build_csr(edge_index: torch.Tensor, n_nodes: int) -> Csr:
                                    perm.data_ptr(), n_bad.data_ptr(), ws.data_ptr(), ws_bytes,
                                    _stream_ptr(dev))
     _lib.check(rc, "gpde_csr_from_coo")
-    bad = int(n_bad.item())          # one sync per *new* graph (the result is cached)
+    # one sync per *new* graph (the result is cached): the bad-edge count and the largest in-degree together
+    bad, max_deg = (int(v) for v in torch.stack([n_bad[0], (rowptr[1:] - rowptr[:-1]).max()]).cpu())
     if bad:
         raise IndexError(f"edge_index has {bad} edges with an endpoint outside [0, {n_nodes})")
-    return Csr(n_nodes, e, rowptr, src, dst, perm)
+    return Csr(n_nodes, e, rowptr, src, dst, perm, _max_in_degree=max_deg)
 
 
 _csr_cache: "dict[tuple, tuple]" = {}      # key -> (storage kept alive, nbytes, Csr); LRU order
@@ -460,6 +470,25 @@ _PRECISION = {"f32": _lib.GPDE_FWD_DEFAULT, "f16split": _lib.GPDE_FWD_F16SPLIT,
               "f16split_agg32": _lib.GPDE_FWD_F16SPLIT | _lib.GPDE_FWD_AGG_F32,  # aggregation on fp32 MFMA regardless of size
               "f16split_noedge": _lib.GPDE_FWD_F16SPLIT | _lib.GPDE_FWD_NO_EDGE_PATH}  # never the per-edge last layer of low in-degree graphs
 DEFAULT_PRECISION = os.environ.get("GPDE_PRECISION", "f16split")
+# The per-edge last layer of low in-degree graphs forms W_e = W3 h_e on split-f16 operands (2^-22 of a block's
+# largest magnitude where fp32 carries 2^-24): each message carries ~4 x the reference's rounding, and a node that sums many of
+# them cancels it up.  Measured on the MI355X (mean in-degree <= 4, the in-edges gathered on a few destinations, no root / bias):
+# err / e32 = 1.4 at a largest in-degree of ~11, 2.3 at ~50, 2.9 at ~85, 3.5 at ~157, 4.1 at ~290, 4.3 - 5.6 at 630 - 1040, where
+# the re-associated path stays at 1.0 - 1.8.  With the default precision a call takes the per-edge last layer only up to
+# EDGE_PATH_MAX_IN_DEGREE (the largest in-degree is recorded by build_csr: no device sync per call).
+EDGE_PATH_MAX_IN_DEGREE = 64
+
+
+def _fwd_flags(csr: "Csr", precision: Optional[str]) -> int:
+    """GPDE_FWD_* flags of a forward call: the precision's, plus GPDE_FWD_NO_EDGE_PATH under the default precision when a node
+    has more than EDGE_PATH_MAX_IN_DEGREE in-edges."""
+    name = DEFAULT_PRECISION if precision is None else precision
+    if name not in _PRECISION:
+        raise ValueError(f"precision must be one of {sorted(_PRECISION)}, got {name!r}")
+    flags = _PRECISION[name]
+    if precision is None and (flags & _lib.GPDE_FWD_F16SPLIT) and csr.n_edges > 0 and csr.max_in_degree > EDGE_PATH_MAX_IN_DEGREE:
+        flags |= _lib.GPDE_FWD_NO_EDGE_PATH
+    return flags
 
 
 def workspace_bytes(n_nodes: int, n_edges: int, pm: PackedMlp) -> int:
@@ -611,9 +640,8 @@ def nnconv_forward_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor, pm: P
         raise NotImplementedError(
             f"aggr={aggr!r}: the fused MI355X operator implements 'add' and 'mean' (every reference "
             "script uses 'mean'); 'max' cannot use the re-associated contraction")
+    flags = _fwd_flags(csr, precision)
     precision = DEFAULT_PRECISION if precision is None else precision
-    if precision not in _PRECISION:
-        raise ValueError(f"precision must be one of {sorted(_PRECISION)}, got {precision!r}")
     if x.dtype != torch.float32 or edge_attr.dtype != torch.float32:
         raise NotImplementedError(f"float32 only (got x {x.dtype}, edge_attr {edge_attr.dtype})")
     if x.dim() != 2 or x.size(1) != WIDTH:
@@ -640,7 +668,7 @@ def nnconv_forward_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor, pm: P
             rc = lib.gpde_nnconv_fwd_keepz(x.data_ptr(), n, edge_attr.data_ptr(), None, None, e, csr.rowptr.data_ptr(),
                                            csr.src.data_ptr(), csr.dst.data_ptr(), perm.data_ptr(), len(pm.dims) - 1, pm.dims_c,
                                            pm.packed.data_ptr(), None if root_c is None else root_c.data_ptr(),
-                                           None if bias_c is None else bias_c.data_ptr(), _AGGR[aggr], _PRECISION[precision],
+                                           None if bias_c is None else bias_c.data_ptr(), _AGGR[aggr], flags,
                                            z_keep.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(x.device))
         elif residual is None and not relu:
             rc = lib.gpde_nnconv_fwd(x.data_ptr(), n, edge_attr.data_ptr(), e, csr.rowptr.data_ptr(),
@@ -648,14 +676,14 @@ def nnconv_forward_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor, pm: P
                                      len(pm.dims) - 1, pm.dims_c, pm.packed.data_ptr(),
                                      None if root_c is None else root_c.data_ptr(),
                                      None if bias_c is None else bias_c.data_ptr(), _AGGR[aggr],
-                                     _PRECISION[precision], out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(x.device))
+                                     flags, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(x.device))
         else:
             rc = lib.gpde_nnconv_fwd_act(x.data_ptr(), n, edge_attr.data_ptr(), e, csr.rowptr.data_ptr(),
                                          csr.src.data_ptr(), csr.dst.data_ptr(), perm.data_ptr(),
                                          len(pm.dims) - 1, pm.dims_c, pm.packed.data_ptr(),
                                          None if root_c is None else root_c.data_ptr(),
                                          None if bias_c is None else bias_c.data_ptr(), _AGGR[aggr],
-                                         _PRECISION[precision], None if residual is None else residual.data_ptr(),
+                                         flags, None if residual is None else residual.data_ptr(),
                                          1 if relu else 0, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(x.device))
     _lib.check(rc, "gpde_nnconv_fwd")
     _lib.n_native_calls += 1
@@ -763,6 +791,58 @@ def nnconv_forward_nodeattr_raw(x: torch.Tensor, csr: Csr, na: NodeAttr, pm: Pac
     return out
 
 
+# Precision policy of the forward: which ASSOCIATION a call's sum is computed in.  The fused operator re-associates
+# sum_e x_j . (W3 h_e + b3) as (sum_e x_j (x) h_e) . W3: Z_i sums x_j h_e over the in-edges of node i.  When a
+# node has more in-edges than the graph has nodes, its edges repeat sources, the Z sums of one source's positive
+# activations grow with the in-degree instead of cancelling, and the fp32 rounding of Z, which the contraction with W3 then
+# cancels down, reaches 4 - 18 x the reference's own fp32 error on the same inputs at in-degrees 1,000 - 8,000.  The
+# arithmetic is not the cause: the fp32 MFMA kernel and the split-f16 kernels give the same error, and so does an fp32 CPU
+# restatement of the re-associated sum.  Such calls take the reference's association instead: the per-edge weights
+# W_e = nn(pseudo_e) (gpde_edge_weights_fwd) and one streaming message / aggregate / update kernel over them
+# (gpde_nnconv_fwd_edgeweights).  Radius graphs have in-degrees far below their node count (the 241^2 grid:
+# 1,793 of 58,081) and keep the fused kernels; the per-edge weights take 16 KiB per edge, so calls above
+# PER_EDGE_MAX_EDGES edges keep them too.
+PER_EDGE_MAX_EDGES = 1 << 17
+
+
+def per_edge_association(csr: Csr, dims: Sequence[int], aggr: str) -> bool:
+    """Whether a forward call of this graph and kernel MLP takes the reference's association (see above).  Host only:
+    the in-degree was recorded when the CSR was built."""
+    return aggr in ("add", "mean") and 0 < csr.n_edges <= PER_EDGE_MAX_EDGES and csr.max_in_degree > csr.n_nodes
+
+
+def nnconv_forward_per_edge_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor, pm: PackedMlp,
+                                weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Tensor]],
+                                root: Optional[torch.Tensor], bias: Optional[torch.Tensor], aggr: str) -> torch.Tensor:
+    """The forward in the reference's association: hidden activations on fp32 MFMA (gpde_hidden_fwd), W_e = W3 h_e + b3
+    per CSR slot (gpde_edge_weights_fwd), m_e = x_j . W_e summed per destination (gpde_nnconv_fwd_edgeweights)."""
+    hidden, _ = hidden_forward_raw(csr, edge_attr.detach().contiguous(), pm, list(weights[:-1]) + [None],
+                                   list(biases[:-1]) + [None], "f32")
+    we = edge_weights_raw(hidden, pm, weights[-1], biases[-1])
+    del hidden
+    return nnconv_forward_edgeweights_raw(x.detach().contiguous(), csr, we, root, bias, aggr)
+
+
+def forward_route(csr: Csr, pm: PackedMlp, aggr: str = "mean", precision: Optional[str] = None,
+                  ws_bytes: Optional[int] = None) -> dict:
+    """How NNConvFunction's forward of this graph runs (host-side queries, no device work): "association" is
+    "per_edge" (per_edge_association) or "node" (the fused operator); for the latter "kernel" names the fused edge
+    kernel, "edge_path" says whether the per-edge last layer of low in-degree graphs runs instead, "n_chunks" is
+    the node chunking of the plan for `ws_bytes` (default: the recommended workspace).  `precision` None: the default
+    precision with its routing (EDGE_PATH_MAX_IN_DEGREE), as nnconv_forward_raw applies it."""
+    if per_edge_association(csr, pm.dims, aggr):
+        return {"association": "per_edge"}
+    flags = _fwd_flags(csr, precision)
+    precision = DEFAULT_PRECISION if precision is None else precision
+    n, e = csr.n_nodes, csr.n_edges
+    ws_bytes = workspace_bytes(n, e, pm) if ws_bytes is None else int(ws_bytes)
+    rc = _lib.lib().gpde_nnconv_fwd_edge_path(n, e, len(pm.dims) - 1, pm.dims_c, flags, ws_bytes)
+    if rc < 0:
+        _lib.check(rc, "gpde_nnconv_fwd_edge_path")
+    return {"association": "node", "kernel": fused_kernel_name(n, e, pm, precision), "edge_path": rc == 1,
+            "n_chunks": launch_plan(n, e, pm, ws_bytes)["n_chunks"]}
+
+
 def launch_plan(n_nodes: int, n_edges: int, pm: PackedMlp, ws_bytes: int):
     lib = _lib.lib()
     nch, npc, wgs, mode = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
@@ -822,6 +902,13 @@ def nnconv_backward_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor,
     gbias = torch.empty(WIDTH, dtype=torch.float32, device=dev) if need_bias else None
     P = ctypes.c_void_p
     arr = lambda ts: (P * nl)(*[None if t is None else t.data_ptr() for t in ts])
+    if n == 0:
+        # a graph without nodes (message() of an edgeless graph runs the operator on E = 0 one-edge graphs): every sum is empty
+        for t in gW + gb + [groot, gbias]:
+            if t is not None:
+                t.zero_()
+        ga = torch.zeros(e, dims[0], dtype=torch.float32, device=dev) if need_attr else None
+        return (gx, gW, gb, groot, gbias, ga) if need_attr else (gx, gW, gb, groot, gbias)
     if ws is None:
         ws = alloc_bwd_ws(lib, n, e, nl, dims_c, dev, 0 if hidden_saved is None else e * hidden_width(dims) * 4)
     rph = csr.rowptr_host

@@ -185,6 +185,12 @@ GPDE_API int gpde_nnconv_fwd_plan(int64_t n_nodes, int64_t n_edges, int n_layers
  * whether it does depends on the node count and the workspace, which this query does not see. */
 GPDE_API const char* gpde_nnconv_fwd_kernel(int64_t n_edges, int n_layers, const int32_t* dims, uint32_t flags);
 
+/* 1 when gpde_nnconv_fwd with these sizes, kernel MLP, flags and `ws_bytes` of workspace takes the per-edge last layer
+ * (W_e = W3 . h_e per edge, gpde_gemm_f16s_nt_kernel) instead of the re-associated path gpde_nnconv_fwd_kernel names; 0 when
+ * it does not; < 0 (GpdeStatus) on invalid arguments or a workspace too small for the call.  Host only, no device work. */
+GPDE_API int gpde_nnconv_fwd_edge_path(int64_t n_nodes, int64_t n_edges, int n_layers, const int32_t* dims, uint32_t flags,
+                                       size_t ws_bytes);
+
 /* ---------------------------------------------------------------------------------------------
  * Backward of the fused NNConv (what autograd computes through nn_conv.py:267-282,
  * utilities.py:223-227 and PyG's gather/scatter on `loss.backward()`,
