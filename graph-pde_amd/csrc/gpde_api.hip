@@ -66,18 +66,7 @@ GpdeSwitches load_switches() {
     GpdeSwitches s{};
     s.bwd_gemm_f32 = on("GPDE_BWD_GEMM_F32");
     s.bwd_dw2_f32 = on("GPDE_BWD_DW2_F32");
-    s.bwd_recompute_f32 = on("GPDE_BWD_RECOMPUTE_F32");
     s.bwd_h1_materialize = on("GPDE_BWD_H1_MATERIALIZE");
-    s.bwd_h1_gemm = on("GPDE_BWD_H1_GEMM");
-    s.bwd_h1_image = on("GPDE_BWD_H1_IMAGE");
-    s.bwd_dw1_pass = on("GPDE_BWD_DW1_PASS");
-    s.bwd_zagg_f32 = on("GPDE_BWD_ZAGG_F32");
-    s.bwd_node_terms_gemm = on("GPDE_BWD_NODE_TERMS_GEMM");
-    s.bwd_dw1_gemm = on("GPDE_BWD_DW1_GEMM");
-    s.bwd_du_passes = on("GPDE_BWD_DU_PASSES");
-    s.bwd_du_transpose_pass = on("GPDE_BWD_DU_TRANSPOSE_PASS");
-    s.bwd_one_pass = on("GPDE_BWD_ONE_PASS");
-    s.store_v3 = on("GPDE_STORE_V3");
     s.nt_no_prefetch = on("GPDE_NT_NO_PREFETCH");
     s.tn_no_ks_xcd = on("GPDE_TN_NO_KS_XCD");
     s.edge_bwd = num("GPDE_EDGE_BWD");

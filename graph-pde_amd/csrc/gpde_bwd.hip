@@ -662,7 +662,7 @@ namespace {
 // Ordered mode: dx[j] += sum of the per-edge contributions of the out-edges of j that lie in this chunk's slot range
 // [e0, e1), in ascending slot order (src_slots is ascending inside a source: the chunk's part is one sub-range).
 // One wave per source node, lane = channel: a single owner per dx element, no atomics -> bit-reproducible.
-// `nparts` > 1 (the one-pass kernel): dxe holds nparts partial rows per edge, part s at dxe + s * part_stride; an edge's
+// `nparts` > 1 (written for the retired one-pass kernel; every caller now passes 1): dxe holds nparts partial rows per edge, part s at dxe + s * part_stride; an edge's
 // contribution is their sum in ascending s (fixed order).
 __global__ __launch_bounds__(256) void k_dx_reduce(const float* __restrict__ dxe, const int32_t* __restrict__ srp,
                                                    const int32_t* __restrict__ ssl, int n_nodes, int e0, int e1,
@@ -754,7 +754,7 @@ struct BwdPlan {
     size_t off_tcs, off_tcm;          // per 32-slot tile column sums / max bits of dU_2 [Ec / 32 + 1][KP2] (gpde_edge_bwd3.hip -> dW_2 GEMM)
     size_t off_amax8;                 // [8] words: bits of max |attribute slot d| over ALL edges of the call (in-kernel first layer: one set of scales for every chunk)
     size_t off_xs;                    // [N][64] words: x as split-f16 pairs for the Z re-aggregation (gpde_zagg_kernel<true>); off_scal[0] = its scale, off_scal[2] = the H bound
-    size_t off_scal;                  // [2] words: bits of max_e B_e for the one-pass kernel's global H scale (gpde_launch_attr_bound)
+    size_t off_scal;                  // [4] words: bits of max |x| and of max_e B_e (gpde_launch_g2_prep), [2] the H bound word (k_h_bound_word)
     size_t total;
     size_t one_chunk;                 // workspace bytes with which everything is one chunk
 };
@@ -987,7 +987,7 @@ int bwd_node_terms(const float* x, int N, const float* root, const float* grad_o
                    float* part, size_t part_floats, hipStream_t st, int acc_root = 0, int acc_bias = 0) {
     int rc;
     const size_t rec = (size_t)GP_W * GP_W + GP_W;
-    if (!gpde_switches().bwd_node_terms_gemm && N > 0 && (grad_root || grad_bias || (root && dx)) && (!grad_root || x) && part_floats >= rec) {
+    if (N > 0 && (grad_root || grad_bias || (root && dx)) && (!grad_root || x) && part_floats >= rec) {
         // one pass: workgroups of contiguous 64-node strips, as many as the partial buffer holds (<= 256)
         const int strips = (N + GP_W - 1) / GP_W;
         int nwg = strips < 256 ? strips : 256;
@@ -1321,8 +1321,7 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
     GpdePackLayout PL;
     bool fast_last = false;
     const bool recomputes = phase == BWD_FULL || phase == BWD_LIGHT || phase == BWD_DEFER;
-    if (recomputes && P.pack_bytes && rowptr && (phase != BWD_FULL || !SW.bwd_recompute_f32) &&
-        gpde_pack_layout(n, dims, &PL) == GPDE_OK && PL.mode == 1) {
+    if (recomputes && P.pack_bytes && rowptr && gpde_pack_layout(n, dims, &PL) == GPDE_OK && PL.mode == 1) {
         GpdeFusedArgs probe{};
         probe.k0 = PL.k0; probe.K1P = PL.K1P; probe.K2P = PL.K2P;
         if (gpde_fused_store_supported(probe)) {
@@ -1333,8 +1332,7 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
     // 3-Linear kernels on the split-f16 GEMMs: the first hidden layer H_1 is never written.  Its only consumers in the
     // backward are dW_2 = dU_2^T . H_1 (operand image generated straight from the 8 attribute slots, k_first_layer_pack)
     // and the ReLU mask of dU_1 (128 bytes of bits per edge instead of 4 KiB).  GPDE_BWD_H1_MATERIALIZE=1: the tensor (A/B).
-    const bool h1_on_the_fly = n == 3 && f16s_du1 && f16s_dw2 && dims[0] <= 8 && P.KP[0] >= 8 && !SW.bwd_h1_materialize &&
-                               !SW.bwd_h1_gemm;
+    const bool h1_on_the_fly = n == 3 && f16s_du1 && f16s_dw2 && dims[0] <= 8 && P.KP[0] >= 8 && !SW.bwd_h1_materialize;
     auto skip_h1 = [&](int rows) { return h1_on_the_fly && rows >= 8192; };
     const bool call_amax = do_mlp && h1_on_the_fly && n_edges > 0 && dims[0] <= 7 && (!kt || (src && dst));
     if (call_amax) {
@@ -1362,35 +1360,18 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
         gpde_set_error("gpde_nnconv_bwd: node-table attributes need the 3-Linear split-f16 form (and src / dst)");
         return GPDE_EUNSUPPORTED;
     }
-    // ---- the one-pass kernel (round 5, gpde_fused_f16v6_kernel<2>): K loop of the recompute + both per-edge products, H_2 neither
-    // written nor read.  Needs: the fused store kernel's shape, Z kept by the forward (dW_3 wants Z, and Z from H_2 is what this
-    // path no longer has), the source-ordered slots (its dx comes out as per-slice partial rows for k_dx_reduce), and - in the
-    // full backward - the split GEMMs that take the by-products.  OPT-IN (GPDE_BWD_ONE_PASS=1 or GPDE_EDGE_BWD=4): measured at
-    // s=121 the kernel takes 52.6 ms where recompute-store + gpde_edge_bwd3_kernel take 32.1 + 17.5 - a one-wave-per-SIMD kernel
-    // cannot hide the products' conversions, cross-lane column statistics and 12 KiB per edge of stores under anything
-    // (ablations: profiles/r05_onepass_ablation.txt).
-    bool onepass_ok = false;
-    if ((phase == BWD_FULL || light) && fast_last && n == 3 && (SW.bwd_one_pass || SW.edge_bwd == 4) && (SW.edge_bwd == 0 || SW.edge_bwd == 4) && z_saved &&
-        src_rowptr && src_slots && src && dst && K2P % GP_TN == 0 && K2P / GP_TN <= GP_W && n_edges > 0) {
-        GpdeFusedArgs probe{};
-        probe.k0 = PL.k0; probe.K1P = PL.K1P; probe.K2P = PL.K2P; probe.xs = (const unsigned*)x;
-        onepass_ok = gpde_fused_f16v6_supported(probe);
-        if (onepass_ok && (rc = gpde_launch_attr_bound(edge_attr, n_edges, PL.k0, F(P.off_pack) + PL.off_w1 + (size_t)PL.K1P * 8,
-                                                       (unsigned*)F(P.off_scal), st, kt, kt ? nas.sel : nullptr, src, dst)) != GPDE_OK) return rc;
-    }
     // Z re-aggregation (no Z kept by the forward: G241, the light passes) on the split-f16 aggregation kernel the forward's
     // given-H path uses (gpde_zagg_kernel<true>, ~3x the fp32-MFMA form's rate): x as split pairs once per call, and ONE bound for
     // every H value - the forward's a-priori bound max|b2| + max_k ||W2_k||_1 . max_e B_e, which holds for recomputed and for
-    // given (partial-H) rows alike since both come from this kernel MLP.  GPDE_BWD_ZAGG_F32=1: the fp32 kernel (A/B).
+    // given (partial-H) rows alike since both come from this kernel MLP.
     bool zagg16 = false;
-    if ((phase == BWD_FULL || light) && fast_last && !z_saved && !SW.bwd_zagg_f32 && n_edges >= 32768 && N > 0 && x) {
+    if ((phase == BWD_FULL || light) && fast_last && !z_saved && n_edges >= 32768 && N > 0 && x) {
         if ((rc = gpde_launch_g2_prep(x, N, edge_attr, n_edges, PL.k0, F(P.off_pack) + PL.off_w1 + (size_t)PL.K1P * 8, (unsigned*)F(P.off_scal),
                                       (unsigned*)F(P.off_xs), st, kt, kt ? nas.sel : nullptr, src, dst)) != GPDE_OK) return rc;
         hipLaunchKernelGGL(k_h_bound_word, dim3(1), dim3(1), 0, st, F(P.off_pack) + PL.off_fcol, (const unsigned*)F(P.off_scal), (unsigned*)F(P.off_scal) + 2);
         zagg16 = true;
     }
     const float* chunk_h = nullptr;          // the current chunk's last hidden activations when they are given (hpart)
-    bool skip_store = false;                 // the chunk runs the one-pass kernel: the last hidden layer is not written
     auto recompute = [&](int e0, int rows, int last) -> int {
         if (!light) {    // (the light pass needs the last hidden layer only, which the fused kernel forms from the attributes itself)
             if (kt) hipLaunchKernelGGL(k_gather_attr_nodes, dim3(nblk((size_t)rows * P.KP[0])), dim3(T), 0, st, edge_attr, nas, src, dst, e0,
@@ -1399,7 +1380,6 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
                                     rows, dims[0], P.KP[0], F(P.off_H[0]));
         }
         if (last == n - 1 && chunk_h) last = n - 2;          // given (partial H of the caller / H kept by the forward): read, not recomputed
-        else if (fast_last && last == n - 1 && skip_store) last = n - 2;
         else if (fast_last && last == n - 1) {
             const float* pk = F(P.off_pack);
             GpdeFusedArgs f{};
@@ -1422,7 +1402,7 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
         if (light) return GPDE_OK;
         for (int l = 1; l <= last; ++l) {
             if (l == 1 && last == 1 && skip_h1(rows)) continue;
-            if (l == 1 && dims[0] <= 8 && P.KP[0] >= 8 && P.KP[1] % 4 == 0 && rows >= 1024 && !SW.bwd_h1_gemm) {
+            if (l == 1 && dims[0] <= 8 && P.KP[0] >= 8 && P.KP[1] % 4 == 0 && rows >= 1024) {
                 const int cb = (P.KP[1] + 255) / 256;
                 int rb = rows / 64; if (rb > 4096 / cb) rb = 4096 / cb; if (rb < 1) rb = 1;
                 hipLaunchKernelGGL(k_first_layer, dim3(cb, rb), dim3(T), 0, st, F(P.off_H[0]), P.KP[0], F(P.off_wp[1]), P.KP[0],
@@ -1464,7 +1444,7 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
                 hipLaunchKernelGGL(k_grad_attr, dim3((rows + 3) / 4), dim3(T), 0, st, dUc, Kl, F(P.off_wp[1]), Kin, perm, mlp_e0, rows,
                                    dims[0], grad_attr);
             if (l == 1 && dw1_done) continue;
-            if (l == 1 && dims[0] <= 8 && Kin >= 8 && Kin % 4 == 0 && Kl % 4 == 0 && rows >= 1024 && !SW.bwd_dw1_gemm) {
+            if (l == 1 && dims[0] <= 8 && Kin >= 8 && Kin % 4 == 0 && Kl % 4 == 0 && rows >= 1024) {
                 // dW_1 and db_1 from one pass over dU_1 (k_dw_first; attribute slots beyond k0 are zero columns of H_0)
                 const int cb = (Kl + 255) / 256;
                 int splits = 1; while (splits < 256 && cb * splits < 1024 && rows / (splits * 2) >= 64) splits *= 2;
@@ -1477,9 +1457,8 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
                 }
             }
             const bool tn_split = l == 2 && f16s_dw2 && rows >= 8192;
-            // one pass over dU_2 for its transposed copy, db_2, and the row scales of the dU_1 GEMM (GPDE_BWD_DU_PASSES=1:
-            // the separate k_colsum / k_row_scale_kernel passes of round 2, A/B)
-            const bool du_one_pass = tn_split && f16s_du1 && !SW.bwd_du_passes;
+            // one pass over dU_2 for its transposed copy, db_2, and the row scales of the dU_1 GEMM
+            const bool du_one_pass = tn_split && f16s_du1;
             unsigned* du_bits = tn_split ? (unsigned*)F(P.off_dubits) : nullptr;
             if (!du_one_pass) {   // db_l = column sums of dU_l; the same pass collects the column maxima the split dW_2 GEMM scales with
                 const int cb = (Kl + 255) / 256;
@@ -1509,11 +1488,10 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
                 g.A = dUc; g.lda = Kl; g.M = rows; g.bsplit = F(P.off_w2ts); g.ucol = F(P.off_ucol2);
                 g.mask = F(P.off_H[l - 1]); g.ldmask = Kin; g.C = dUo; g.ldc = Kin; g.K = Kl; g.N = Kin;
                 if (tn_split && skip_h1(rows)) { g.mask = nullptr; g.ldmask = 0; g.maskbits = (const uint32_t*)F(P.off_maskbits); g.ldmb = Kin / 32; }
-                if (tn_split && fl_in_kernel && !SW.bwd_dw1_pass && dims[0] <= 7 && !grad_attr &&
+                if (tn_split && fl_in_kernel && dims[0] <= 7 && !grad_attr &&
                     gpde_gemm_f16s_dw_part_floats(rows, Kin) <= (size_t)rows * Kin) {
                     // round 6: this GEMM's epilogue forms dW_1 / db_1 from the tile in its registers: dU_1 (4 KiB per edge) is neither
-                    // written nor read back by k_dw_first - unless the attribute gradient wants the tensor (GPDE_BWD_DW1_PASS=1: the
-                    // separate pass, A/B).  Scratch of the tile partials: the dU_1 buffer itself (512 bytes per row of its 4 KiB)
+                    // written nor read back by k_dw_first - unless the attribute gradient wants the tensor.  Scratch of the tile partials: the dU_1 buffer itself (512 bytes per row of its 4 KiB)
                     g.fl_mode = 2; g.fl_attr = F(P.off_H[0]); g.fl_ld0 = P.KP[0]; g.fl_rows = rows;
                     g.fl_dw_part = dUo; g.fl_dw_out = F(P.off_dwp[1]); g.fl_dw_ld = P.KP[0]; g.fl_db_out = F(P.off_dbp[1]);
                     g.fl_skip_store = 1;
@@ -1607,14 +1585,8 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
         }
         hipLaunchKernelGGL(k_scale_g, dim3((nn + 3) / 4), dim3(T), 0, st, grad_out, rowptr, aggr, na, nn, gT);
         if (rows > 0) {
-            // the chunk's per-edge part on the one-pass kernel: in-degree >= 32 (a 64-slot tile rarely spans more than two
-            // destinations), H not given, and - full backward - enough rows for the split GEMMs that take its by-products
-            const bool use1 = onepass_ok && !chunk_h && (int64_t)rows >= (int64_t)32 * nn;
-            const bool use1_by = use1 && !light && f16s_dw2 && f16s_du1 && rows >= 8192 && !SW.bwd_du_passes && !SW.bwd_du_transpose_pass;
             // hidden activations of the chunk's edges: recomputed, or rows of the given cache
-            skip_store = use1;
             if (phase == BWD_FULL || light) { rc_na = na; rc_nb = nb; if ((rc = recompute(e0, rows, n - 1)) != GPDE_OK) return rc; }
-            skip_store = false;
             const float* Hlast = chunk_h ? chunk_h : (phase == BWD_FULL || light) ? F(P.off_H[n - 1]) : hidden + (size_t)e0 * K2P;
             // Z of the chunk's nodes: kept by the forward (gpde_nnconv_fwd_keepz), else re-aggregated from the recomputed /
             // given activations
@@ -1667,77 +1639,41 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
             }
             // per-edge backward through the aggregation -> dU_{n-1}, dx_j
             float* dUc = phase == BWD_FULL ? F(P.off_dU[0]) : light ? nullptr : grad_hidden_out + (size_t)e0 * K2P;   // light: dx only
-            if (use1) {
-                // dZ_i as the two split images (img2 in place, img1 into the Z buffer - Z itself is the forward's: z_saved), then
-                // ONE kernel: K loop + dU_2 (+ transposed copy, row maxima, tile column statistics) + per-slice partial dx rows
-                du_pre = false;
-                if (!dx) { gpde_set_error("gpde_nnconv_bwd: grad_x must be provided"); return GPDE_EINVAL; }
-                if ((rc = gpde_launch_dz_images(dZ, nn, K2P, F(P.off_Z), F(P.off_dzun), st)) != GPDE_OK) return rc;
-                const float* pk = F(P.off_pack);
-                GpdeFusedArgs f{};
-                f.attr = edge_attr; f.rowptr = rowptr; f.perm = perm; f.src = src; f.dst = dst; f.kt = kt;
-                for (int d_ = 0; d_ < 8; ++d_) f.sel[d_] = nas.sel[d_];
-                f.w1 = pk + PL.off_w1; f.w2t = pk + PL.off_w2t; f.b2 = pk + PL.off_b2;
-                f.w2h = pk + PL.off_w2h; f.ucol = pk + PL.off_ucol; f.w1h = pk + PL.off_w1h; f.fcol = pk + PL.off_fcol;
-                f.k0 = PL.k0; f.K1P = PL.K1P; f.K2P = PL.K2P; f.nc0 = na; f.nc1 = nb; f.e_chunk0 = e0;
-                f.xs = (const unsigned*)x; f.scal = (const unsigned*)F(P.off_scal);
-                f.bw_img1 = F(P.off_Z); f.bw_img2 = dZ; f.bw_unscale = F(P.off_dzun); f.bw_dS = dS;
-                f.bw_dxp = F(P.off_H[n - 1]); f.bw_rows = rows;
-                const int ns = K2P / GP_TN;
-                if (dUc) f.bw_dU = dUc;
-                if (use1_by) {
-                    f.bw_dUt = gpde_gemm_f16s_tn_at(F(P.off_tnws), rows, tn_ksplits(rows, P.KP[2], P.KP[1]), &f.bw_ldt);
-                    f.bw_rowmax = F(P.off_dxe);            // [ns][rows] (the per-edge dx rows of the two-pass form are not used)
-                    f.bw_csum = F(P.off_tcs); f.bw_cmax = (unsigned*)F(P.off_tcm);
-                }
-                int groups = gpde_num_cus() / ns; if (groups < 1) groups = 1;
-                const int gcap = (rows / 64 + GP_WAVES) / GP_WAVES; if (groups > gcap) groups = gcap;
-                f.n_groups = groups;
-                if ((rc = gpde_launch_fused_bwd(f, st)) != GPDE_OK) return rc;
-                if (use1_by) {
-                    if ((rc = gpde_launch_row_scales_from_slices(F(P.off_dxe), ns, rows, F(P.off_rowsc), F(P.off_rowsc) + rows, st)) != GPDE_OK) return rc;
+            const bool ordered = src_rowptr && src_slots;
+            EdgeBwdArgs ea{x, rowptr, src, dst, dZ, dS, Hlast, dUc, dx, e0, e1, na, K2P, ordered ? F(P.off_dxe) : nullptr};
+            const size_t lds = (size_t)4 * (32 * EB_XS + 32 * EB_HS) * 4;
+            const size_t lds2 = (size_t)(2 * EB2_DZ + 4 * 2 * EB2_H) * 4 + 4 * 64 * 4;
+            static GpdeLdsOnce once;
+            if (int rc_ = once.ensure(gpde_edge_bwd_kernel, gpde_edge_bwd2_kernel)) return rc_;
+            if (!dx) { gpde_set_error("gpde_nnconv_bwd: grad_x must be provided"); return GPDE_EINVAL; }
+            // staged kernel where a 128-slot group rarely spans more than two destinations
+            const int force = SW.edge_bwd;                     // GPDE_EDGE_BWD = 1 / 2 / 3: force a variant (tests, A/B)
+            // (accumulating dL/dU lives in the split-f16 kernel: it is correct for any in-degree, the host asks for it on dense graphs)
+            const bool gh_acc = gh_accumulate && phase == BWD_CONV;
+            // (round 6: from mean in-degree 4 - the split-f16 kernel is correct for any in-degree and measured faster on the MGKN
+            // levels of in-degree 6 - 22 too: 1.4 ms of a 30 ms training step of config 4)
+            const bool staged = force ? force >= 2 : (gh_acc || (int64_t)rows >= (int64_t)(K2P % 32 == 0 ? 4 : 32) * nn);
+            du_pre = false;
+            if (staged && force != 2 && K2P % 32 == 0) {      // split-f16 MFMA (default); GPDE_EDGE_BWD=2: the fp32-MFMA staged kernel
+                if ((rc = gpde_launch_dz_split(dZ, nn, K2P, F(P.off_dzun), st)) != GPDE_OK) return rc;
+                GpdeEdgeBwd3Args e3{x, src, dst, dZ, F(P.off_dzun), dS, Hlast, dUc, dx, ordered ? F(P.off_dxe) : nullptr, e0, e1, na, K2P};
+                e3.du_accumulate = gh_acc;
+                // full backward on the split GEMMs: the kernel also leaves what the dW_2 GEMM's pass over dU_2 would form
+                // (mlp_backward's tn_split && du_one_pass case)
+                if (phase == BWD_FULL && n == 3 && f16s_dw2 && f16s_du1 && rows >= 8192) {
+                    e3.dUt = gpde_gemm_f16s_tn_at(F(P.off_tnws), rows, tn_ksplits(rows, P.KP[2], P.KP[1]), &e3.ldt);
+                    e3.row_sc = F(P.off_rowsc); e3.row_isc = F(P.off_rowsc) + rows;
+                    e3.csum_part = F(P.off_tcs); e3.cmax_part = (unsigned*)F(P.off_tcm);
                     du_pre = true;
                 }
-                hipLaunchKernelGGL(k_dx_reduce, dim3((N + 3) / 4), dim3(T), 0, st, F(P.off_H[n - 1]), src_rowptr, src_slots, N, e0, e1, dx, ns,
-                                   (size_t)rows * GP_W, 0);
-            } else {
-                const bool ordered = src_rowptr && src_slots;
-                EdgeBwdArgs ea{x, rowptr, src, dst, dZ, dS, Hlast, dUc, dx, e0, e1, na, K2P, ordered ? F(P.off_dxe) : nullptr};
-                const size_t lds = (size_t)4 * (32 * EB_XS + 32 * EB_HS) * 4;
-                const size_t lds2 = (size_t)(2 * EB2_DZ + 4 * 2 * EB2_H) * 4 + 4 * 64 * 4;
-                static GpdeLdsOnce once;
-                if (int rc_ = once.ensure(gpde_edge_bwd_kernel, gpde_edge_bwd2_kernel)) return rc_;
-                if (!dx) { gpde_set_error("gpde_nnconv_bwd: grad_x must be provided"); return GPDE_EINVAL; }
-                // staged kernel where a 128-slot group rarely spans more than two destinations
-                const int force = SW.edge_bwd;                     // GPDE_EDGE_BWD = 1 / 2 / 3: force a variant (tests, A/B)
-                // (accumulating dL/dU lives in the split-f16 kernel: it is correct for any in-degree, the host asks for it on dense graphs)
-                const bool gh_acc = gh_accumulate && phase == BWD_CONV;
-                // (round 6: from mean in-degree 4 - the split-f16 kernel is correct for any in-degree and measured faster on the MGKN
-                // levels of in-degree 6 - 22 too: 1.4 ms of a 30 ms training step of config 4)
-                const bool staged = force ? force >= 2 : (gh_acc || (int64_t)rows >= (int64_t)(K2P % 32 == 0 ? 4 : 32) * nn);
-                du_pre = false;
-                if (staged && force != 2 && K2P % 32 == 0) {      // split-f16 MFMA (default); GPDE_EDGE_BWD=2: the fp32-MFMA staged kernel
-                    if ((rc = gpde_launch_dz_split(dZ, nn, K2P, F(P.off_dzun), st)) != GPDE_OK) return rc;
-                    GpdeEdgeBwd3Args e3{x, src, dst, dZ, F(P.off_dzun), dS, Hlast, dUc, dx, ordered ? F(P.off_dxe) : nullptr, e0, e1, na, K2P};
-                    e3.du_accumulate = gh_acc;
-                    // full backward on the split GEMMs: the kernel also leaves what the dW_2 GEMM's pass over dU_2 would form
-                    // (mlp_backward's tn_split && du_one_pass case; GPDE_BWD_DU_TRANSPOSE_PASS=1: that pass, A/B)
-                    if (phase == BWD_FULL && n == 3 && f16s_dw2 && f16s_du1 && rows >= 8192 && !SW.bwd_du_passes &&
-                        !SW.bwd_du_transpose_pass) {
-                        e3.dUt = gpde_gemm_f16s_tn_at(F(P.off_tnws), rows, tn_ksplits(rows, P.KP[2], P.KP[1]), &e3.ldt);
-                        e3.row_sc = F(P.off_rowsc); e3.row_isc = F(P.off_rowsc) + rows;
-                        e3.csum_part = F(P.off_tcs); e3.cmax_part = (unsigned*)F(P.off_tcm);
-                        du_pre = true;
-                    }
-                    if ((rc = gpde_launch_edge_bwd3(e3, st)) != GPDE_OK) return rc;
-                } else if (gh_acc) {
-                    gpde_set_error("gpde_nnconv_bwd: GPDE_BWD_ACCUMULATE_GRAD_HIDDEN is built into the split-f16 per-edge kernel only "
-                                   "(GPDE_EDGE_BWD=2 forces the other one)");
-                    return GPDE_EUNSUPPORTED;
-                } else if (staged) hipLaunchKernelGGL(gpde_edge_bwd2_kernel, dim3(((rows + 127) / 128 + 7) / 8 * 8), dim3(T), lds2, st, ea);
-                else hipLaunchKernelGGL(gpde_edge_bwd_kernel, dim3((rows + 127) / 128), dim3(T), lds, st, ea);
-                if (ordered) hipLaunchKernelGGL(k_dx_reduce, dim3((N + 3) / 4), dim3(T), 0, st, F(P.off_dxe), src_rowptr, src_slots, N, e0, e1, dx, 1, (size_t)0, 0);
-            }
+                if ((rc = gpde_launch_edge_bwd3(e3, st)) != GPDE_OK) return rc;
+            } else if (gh_acc) {
+                gpde_set_error("gpde_nnconv_bwd: GPDE_BWD_ACCUMULATE_GRAD_HIDDEN is built into the split-f16 per-edge kernel only "
+                               "(GPDE_EDGE_BWD=2 forces the other one)");
+                return GPDE_EUNSUPPORTED;
+            } else if (staged) hipLaunchKernelGGL(gpde_edge_bwd2_kernel, dim3(((rows + 127) / 128 + 7) / 8 * 8), dim3(T), lds2, st, ea);
+            else hipLaunchKernelGGL(gpde_edge_bwd_kernel, dim3((rows + 127) / 128), dim3(T), lds, st, ea);
+            if (ordered) hipLaunchKernelGGL(k_dx_reduce, dim3((N + 3) / 4), dim3(T), 0, st, F(P.off_dxe), src_rowptr, src_slots, N, e0, e1, dx, 1, (size_t)0, 0);
             // MLP backward over the chunk's edges
             if (phase == BWD_FULL) { mlp_e0 = e0; if ((rc = mlp_backward(dUc, rows)) != GPDE_OK) return rc; }
         }

@@ -1370,10 +1370,9 @@ int gpde_launch_gemm_f16s_tn(const float* dU, int ldu, int n_out, const float* H
 }
 
 // Whether gpde_launch_gemm_f16s_tn generates the first hidden layer inside its GEMM for this spec (`maskbits` receives the mask words
-// either way): a free slot for the bias, 16-byte aligned attribute rows,
-// the split-K form (ksplits > 1), and not switched off (GPDE_BWD_H1_IMAGE=1: rounds 3-5's image + mask bits, A/B)
+// either way): a free slot for the bias, 16-byte aligned attribute rows and the split-K form (ksplits > 1)
 bool gpde_first_layer_in_kernel(const GpdeFirstLayerSpec& f, int rows, int ksplits) {
-    return f.k0 >= 1 && f.k0 <= 7 && f.ld0 >= 8 && f.ld0 % 4 == 0 && rows >= 1 && ksplits > 1 && !gpde_switches().bwd_h1_image;     // (a K split is >= 256 edges = 8 chunks)
+    return f.k0 >= 1 && f.k0 <= 7 && f.ld0 >= 8 && f.ld0 % 4 == 0 && rows >= 1 && ksplits > 1;     // (a K split is >= 256 edges = 8 chunks)
 }
 
 // ---- gather form: operands and launcher (depth-deferred backward, gpde_bwd.hip) ------------------------------------------

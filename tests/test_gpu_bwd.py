@@ -312,3 +312,112 @@ def test_one_chunk_backward_agrees_with_the_default_chunking_at_s121():
     for l in range(3):
         assert rel_l2(a[1][l].cpu(), b[1][l].cpu()) <= 1.5e-5, (f"dW{l + 1}", rel_l2(a[1][l].cpu(), b[1][l].cpu()))
         assert rel_l2(a[2][l].cpu(), b[2][l].cpu()) <= 1.5e-5, (f"db{l + 1}", rel_l2(a[2][l].cpu(), b[2][l].cpu()))
+
+
+# ---- the default (two-pass) backward after the keep-Z forward: recompute-store + gpde_edge_bwd3_kernel, raw calls ------------
+# (cases of the retired one-pass kernel's tests: destinations with 1 .. 2000 in-edges, nodes without in-edges, a ragged last tile)
+
+def _kz_case(dims, n, e, seed):
+    from tests.helpers.kinks import edges_off_the_kink
+    torch.manual_seed(seed)
+    dst = torch.randint(0, n - 5, (e,))                      # the last 5 nodes: no in-edges
+    dst[: e // 10] = 3                                       # one destination with ~e / 10 in-edges (dozens of tiles)
+    dst[e // 10: e // 10 + 7] = 11                           # ... and short runs: several nodes inside one 64-slot tile
+    ei = torch.stack([torch.randint(0, n, (e,)), dst])
+    ea, x = torch.randn(e, dims[0]), torch.randn(n, 64)
+    mlp = torch.nn.Sequential(*sum([[torch.nn.Linear(dims[i], dims[i + 1]), torch.nn.ReLU()] for i in range(3)], [])[:-1])
+    W = [l.weight.detach() for l in mlp if isinstance(l, torch.nn.Linear)]
+    B = [l.bias.detach() for l in mlp if isinstance(l, torch.nn.Linear)]
+    keep = edges_off_the_kink(ea, W, B)
+    ei, ea = ei[:, keep].contiguous(), ea[keep].contiguous()
+    root = torch.empty(64, 64).uniform_(-0.125, 0.125)
+    bias = torch.empty(64).uniform_(-0.125, 0.125)
+    return x, ei, ea, W, B, root, bias, torch.randn(n, 64)
+
+
+def _kz_run(x, ei, ea, W, B, root, bias, gout, aggr="mean", light=False, ws_div=1, edge_attr=None):
+    """keep-Z forward, then the backward with the kept Z (the module's training path)."""
+    from graph_pde_amd import _lib
+    d = dev()
+    n = x.shape[0]
+    csr = ops.build_csr(ei.to(d), n)
+    Wd, Bd = [w.to(d) for w in W], [b.to(d) for b in B]
+    pm = ops.pack_mlp(Wd, Bd)
+    ead = ea.to(d) if edge_attr is None else edge_attr
+    z = torch.zeros(n, 64 * ops.hidden_width(pm.dims), dtype=torch.float32, device=d)
+    ops.nnconv_forward_raw(x.to(d), csr, ead, pm, root.to(d), bias.to(d), aggr, z_keep=z)
+    ws = None
+    if ws_div > 1:
+        dims = [W[0].shape[1]] + [w.shape[0] for w in W]
+        full = int(_lib.lib().gpde_nnconv_bwd_workspace_bytes(n, ei.shape[1], 3, _lib.dims_array(dims)))
+        ws = torch.empty(full // ws_div, dtype=torch.uint8, device=d)
+    if light:
+        out = ops.nnconv_backward_light_raw(x.to(d), csr, ead, Wd, Bd, root.to(d), aggr, gout.to(d), z_saved=z)
+    else:
+        out = ops.nnconv_backward_raw(x.to(d), csr, ead, Wd, Bd, root.to(d), aggr, gout.to(d), ws=ws, z_saved=z)
+    torch.cuda.synchronize()
+    return out
+
+
+def _flat(res):
+    gx, gW, gb, groot, gbias = res
+    return [("dx", gx)] + [(f"dW{l + 1}", w) for l, w in enumerate(gW)] + [(f"db{l + 1}", b) for l, b in enumerate(gb)] + \
+        [("droot", groot), ("dbias", gbias)]
+
+
+@pytest.mark.parametrize("dims,n,e,aggr", [([6, 256, 256, 4096], 200, 20011, "mean"), ([6, 1024, 1024, 4096], 150, 12345, "mean"),
+                                           ([4, 512, 384, 4096], 120, 9000, "add"), ([6, 300, 500, 4096], 160, 14000, "mean")])
+def test_keep_z_backward_matches_float64(dims, n, e, aggr):
+    from oracle.nnconv_oracle import nnconv_grads
+    case = _kz_case(dims, n, e, sum(dims) + e)
+    x, ei, ea, W, B, root, bias, gout = case
+    rx, rW, rb, rroot, rbias = nnconv_grads(x, ei, ea, W, B, root, bias, aggr, gout, chunk_edges=4096)
+    ref = dict([("dx", rx)] + [(f"dW{l + 1}", w) for l, w in enumerate(rW)] + [(f"db{l + 1}", b) for l, b in enumerate(rb)] +
+               [("droot", rroot), ("dbias", rbias)])
+    errs = {k: rel_l2(t.cpu(), ref[k]) for k, t in _flat(_kz_run(*case, aggr=aggr))}
+    print(dims, {k: f"{v:.1e}" for k, v in errs.items()})
+    for k, err in errs.items():
+        assert err <= TOL, (k, "vs float64", err)
+
+
+def test_keep_z_light_pass_and_chunking(monkeypatch):
+    dims, n, e = [6, 256, 256, 4096], 300, 40000
+    case = _kz_case(dims, n, e, 5)
+    fx, fW, fb, froot, fbias = _kz_run(*case)
+    lx, lw, lb, lroot, lbias = _kz_run(*case, light=True)
+    assert torch.equal(lx, fx) and torch.equal(lw, fW[-1]) and torch.equal(lb, fb[-1])
+    assert torch.equal(lroot, froot) and torch.equal(lbias, fbias)
+    # several node / edge chunks: grad_x keeps its bits (per-edge rows, one owner per element, chunks in order), the
+    # weight gradients move by the split-K summation order only
+    cx, cW, cb, croot, cbias = _kz_run(*case, ws_div=2)      # (three edge chunks: the call-wide buffers of a 256-wide MLP are a quarter of `full` here)
+    assert torch.equal(cx, fx)
+    for l in range(3):
+        assert rel_l2(cW[l].cpu(), fW[l].cpu()) <= 5e-6 and rel_l2(cb[l].cpu(), fb[l].cpu()) <= 5e-6, l
+    # workgroup skew (odd column slices of the GEMMs start late) leaves every bit
+    monkeypatch.setenv("GPDE_DEBUG_SKEW_US", "150")
+    sx, sW, sb, sroot, sbias = _kz_run(*case)
+    monkeypatch.delenv("GPDE_DEBUG_SKEW_US")
+    assert torch.equal(sx, fx) and all(torch.equal(a, b) for a, b in zip(sW, fW)) and all(torch.equal(a, b) for a, b in zip(sb, fb))
+
+
+def test_keep_z_backward_with_node_table_attributes_is_bitwise_the_tensor_path():
+    """Row f3 in training: the attributes come from node data inside the kernel (`GpdeNodeAttr`): same floats, same bits."""
+    from graph_pde_amd import synth
+    d = dev()
+    s = 41
+    ei, ea, n = synth.darcy_graph(s, 0.10)
+    pos, a = synth.lattice_positions(s), synth.darcy_coefficient(s, 0)
+    na = ops.NodeAttr.darcy(pos.to(d), a.to(d))
+    torch.manual_seed(3)
+    dims = [6, 256, 256, 4096]
+    mlp = torch.nn.Sequential(*sum([[torch.nn.Linear(dims[i], dims[i + 1]), torch.nn.ReLU()] for i in range(3)], [])[:-1])
+    W = [l.weight.detach() for l in mlp if isinstance(l, torch.nn.Linear)]
+    B = [l.bias.detach() for l in mlp if isinstance(l, torch.nn.Linear)]
+    x, gout = torch.randn(n, 64), torch.randn(n, 64)
+    root, bias = torch.empty(64, 64).uniform_(-0.125, 0.125), torch.empty(64).uniform_(-0.125, 0.125)
+    ea_t = na.materialize(ei.to(d))                               # the tensor the reference builds (utilities.py:274-277)
+    assert rel_l2(ea_t.cpu(), ea) <= 1e-6
+    t = _kz_run(x, ei, ea, W, B, root, bias, gout, edge_attr=ea_t)
+    v = _kz_run(x, ei, ea, W, B, root, bias, gout, edge_attr=na)
+    for (k, p), (_, q) in zip(_flat(t), _flat(v)):
+        assert torch.equal(p, q), k
