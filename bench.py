@@ -5,6 +5,15 @@
     python bench.py --train [--gpus N] ...          # training-step mode (BASELINE config 5 shape, see below)
     python bench.py --split-graph [--gpus N] ...    # ONE graph split by destination rows over the ranks (strong scaling)
     python bench.py ... --dump-outputs DIR          # + the last timed step's outputs as DIR/<name>.npy (same inputs every run)
+    python bench.py --full ...                      # + every leg beyond the headline figure (below; minutes)
+
+A plain run does what the headline figure needs and nothing else: it builds the inputs, warms up, times the K steps, writes
+--dump-outputs and prints the line.  Its `roofline` comes from the timed steps' own launches and the committed PMC record.
+Every other leg - the CPU baseline and its parity sample, the other precision, the node-table attributes, the MGKN
+configurations, the depth-reuse probe, the backward and G241 training-step figures, the in-run traffic measurement (its own
+rocprofv3 child runs) - runs only with `--full`, on one GPU, after the timed steps; the `--no-*` options leave single legs
+out of it.  `--full` also times the next sample's attribute reorder: during set-up, before the warm-up, on every rank.
+Without `--full` these fields are null.
 
 One "step" = one `conv(x, edge_index, edge_attr)` forward of the headline operator on one PDE sample: the
 Darcy-241^2 r=0.10 lattice radius graph (N = 58,081 nodes, E = 95,539,625 edges, BASELINE.json configs[1])
@@ -22,7 +31,8 @@ Round 6: the printed line is <= 2.5 KB - the contract's keys, a compact `rooflin
 other leg's headline figure (graph preparation, MGKN forwards / training steps, the backward in both forms with its roofline
 fraction and traffic, the G241 depth-6 training step on the same sample / distinct samples with its peak memory).  EVERYTHING
 measured - the full objects described below, per-kernel counters, notes - goes to `bench_detail.json` (`--detail-out`), whose path
-the line carries as `detail`.  Objects (in the detail file; `roofline` / `cpu_baseline` compact on the line):
+the line carries as `detail`.  Objects (in the detail file; `roofline` / `cpu_baseline` compact on the line; all but
+`roofline` from --full legs):
   roofline      of the dominant kernel (its symbol from gpde_nnconv_fwd_kernel).  The path is compute bound
                 (SURVEY.md §8d), so `bound` = "mfma".  `achieved` = MFMA FLOPs the kernel EXECUTES per launch /
                 average launch duration (HIP events inside libgpde.so on the kernel's own stream), `peak` = the
@@ -170,8 +180,7 @@ def measure_traffic(args, kernel):
     if shutil.which("rocprofv3") is None:
         return None, "rocprofv3 not on PATH"
     child = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "0", "--config", args.config,
-             "--kernel-width", str(args.kernel_width), "--no-cpu-baseline", "--no-reuse-probe", "--no-mgkn", "--no-alt",
-             "--no-backward-probe", "--no-measure-traffic"] + (["--precision", args.precision] if args.precision else [])
+             "--kernel-width", str(args.kernel_width)] + (["--precision", args.precision] if args.precision else [])
     got = {}
     tmp = tempfile.mkdtemp(prefix="gpde_traffic_", dir="/tmp")
     env = dict(os.environ, TMPDIR="/tmp")
@@ -199,6 +208,15 @@ def measure_traffic(args, kernel):
            "FETCH_SIZE_corrected_bytes_per_launch": round(2 * f_b), "WRITE_SIZE_bytes_per_launch": round(w_b),
            "hbm_bytes_per_launch": round(2 * f_b + w_b)}
     return rec, "measured in this run: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over a one-step child run of bench.py"
+
+
+def measures_traffic_by_default(args, world):
+    """Whether this run measures roofline.traffic itself without being asked (--measure-traffic): a --full run of the headline
+    configuration on one GPU, when rocprofv3 is installed and this run is not itself one of its children."""
+    import shutil
+    under_profiler = any(k_.startswith(("ROCPROF", "ROCP_")) for k_ in os.environ)
+    return bool(args.full and world == 1 and not args.measure_traffic and not args.no_measure_traffic and args.config == "g241"
+                and shutil.which("rocprofv3") and not under_profiler)
 
 
 def make_conv(kw, dev, k0=6, seed=0):
@@ -549,6 +567,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS))
     ap.add_argument("--kernel-width", type=int, default=1024)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure (see the module docstring); --train and --split-graph have none")
     ap.add_argument("--cpu-rows", type=int, default=640, help="destination rows of the CPU sample (>= 1 M edges on g241)")
     ap.add_argument("--cpu-threads", type=int, default=64, help="threads of the CPU baseline leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -560,8 +580,8 @@ def main():
     ap.add_argument("--no-alt", action="store_true", help="skip the exact-fp32 leg")
     ap.add_argument("--measure-traffic", action="store_true",
                     help="re-derive roofline.traffic in THIS run: two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of a one-step "
-                         "child run of this script.  Since round 5 this is the DEFAULT for the headline configuration on one GPU "
-                         "when rocprofv3 is on the box (adds ~1-2 minutes); --no-measure-traffic keeps the committed record")
+                         "child run of this script.  With --full this is the DEFAULT for the headline configuration on one GPU "
+                         "when rocprofv3 is installed (adds ~1-2 minutes); --no-measure-traffic keeps the committed record")
     ap.add_argument("--no-measure-traffic", action="store_true", help="roofline.traffic from the committed profiles/traffic_r*.json")
     ap.add_argument("--precision", default=None, choices=["f32", "f16split", "f16split_8wave", "f16split_static", "f16split_agg16", "f16split_agg32", "f16split_noedge"],
                     help="arithmetic of the hidden layer (default: graph_pde_amd.ops.DEFAULT_PRECISION)")
@@ -645,27 +665,30 @@ def main():
     ops.attr_in_slot_order(csr, ea)              # edge_attr rows in CSR slot order (gpde_gather_rows): once per (graph, edge_attr)
     torch.cuda.synchronize()
     t3 = time.time()
-    # ... and for a SECOND edge_attr tensor on the same graph (a new sample of the same mesh): the gather alone.  The first call above also
-    # pays the process's first launches of these kernels and the identity probe of `perm` (22 - 108 ms across boxes); the cache entry of the
-    # probe tensor is dropped again (2.3 GB)
-    ea2 = ea.clone()
-    torch.cuda.synchronize()
-    t4 = time.time()
-    ops.attr_in_slot_order(csr, ea2)
-    torch.cuda.synchronize()
-    t5 = time.time()
-    if getattr(csr, "_attr_sorted", None):
-        for k_ in [k_ for k_, v_ in csr._attr_sorted.items() if v_[0] is ea2]:
-            csr._attr_sorted.pop(k_)
-    del ea2
+    next_ms = None
+    if args.full:
+        # ... and for a SECOND edge_attr tensor on the same graph (a new sample of the same mesh): the gather alone.  The first call above also
+        # pays the process's first launches of these kernels and the identity probe of `perm` (22 - 108 ms, depending on the machine); the cache entry of the
+        # probe tensor is dropped again (2.3 GB)
+        ea2 = ea.clone()
+        torch.cuda.synchronize()
+        t4 = time.time()
+        ops.attr_in_slot_order(csr, ea2)
+        torch.cuda.synchronize()
+        next_ms = 1e3 * (time.time() - t4)
+        if getattr(csr, "_attr_sorted", None):
+            for k_ in [k_ for k_, v_ in csr._attr_sorted.items() if v_[0] is ea2]:
+                csr._attr_sorted.pop(k_)
+        del ea2
     # per-(graph, edge_attr) preparation every NEW sample pays before its first forward; never inside the timed region
     graph_prep = {"csr_build_ms": round(1e3 * (t2 - t1), 2), "attr_reorder_ms": round(1e3 * (t3 - t2), 2),
-                  "attr_reorder_next_sample_ms": round(1e3 * (t5 - t4), 2),
+                  "attr_reorder_next_sample_ms": None if next_ms is None else round(next_ms, 2),
                   "note": "gpde_csr_from_coo (stable sort by destination of the int64 [2,E] list) and gpde_gather_rows (edge_attr into "
                           "CSR slot order); both cached per tensor + version, `depth` applications and every epoch reuse them"}
     if rank == 0:
-        log(f"[bench] graph {args.config}: N={n} E={e} generated in {t1 - t0:.2f}s; "
-            f"dst-CSR build {1e3 * (t2 - t1):.1f} ms, attribute reorder {1e3 * (t3 - t2):.1f} ms (first call; next sample {1e3 * (t5 - t4):.1f} ms; not in the timed region)")
+        log(f"[bench] graph {args.config}: N={n} E={e} generated in {t1 - t0:.2f}s; dst-CSR build {1e3 * (t2 - t1):.1f} ms, "
+            f"attribute reorder {1e3 * (t3 - t2):.1f} ms (first call{'' if next_ms is None else f'; next sample {next_ms:.1f} ms'}; "
+            "not in the timed region)")
 
     lin = ops.mlp_linears(conv.nn)
     pm = ops.pack_mlp([l.weight for l in lin], [l.bias for l in lin])
@@ -708,6 +731,7 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * e / (elapsed / args.steps) / 1e6                  # M-edges/s, whole job
     med = statistics.median(step_ms)
+    full = args.full and world == 1                   # the legs below: only when asked for, and on one GPU
 
     # ---- roofline of the dominant kernel (rank 0's launches) --------------------------------------
     fused_ms, launches = kinds["fused"]
@@ -724,10 +748,7 @@ def main():
     n_param = sum(p.numel() for p in conv.parameters())
     alg_bytes_per_launch = (40.0 * e + 512.0 * n + 4.0 * n_param) * edges_per_launch / e   # SURVEY §8(d) x units per launch
     rec, src = traffic_record(args.config, kw, kernel)
-    import shutil as _sh
-    under_profiler = any(k_.startswith(("ROCPROF", "ROCP_")) for k_ in os.environ)        # (this run is itself a rocprofv3 child)
-    if not args.measure_traffic and not args.no_measure_traffic and world == 1 and args.config == "g241" and _sh.which("rocprofv3") and \
-            not under_profiler:
+    if measures_traffic_by_default(args, world):
         args.measure_traffic = True
     if args.measure_traffic and world == 1:
         del ws
@@ -775,7 +796,7 @@ def main():
 
     # ---- row f3 on the headline kernel: attributes read from the node table (no [E, 6] tensor, no perm) -----------
     nodeattr = None
-    if world == 1 and not args.no_alt and kernel == "gpde_fused_f16v6_kernel":
+    if full and not args.no_alt and kernel == "gpde_fused_f16v6_kernel":
         try:
             pos_n = synth.lattice_positions(s, dev)
             a_n = synth.darcy_coefficient(s, rank).to(dev)
@@ -797,7 +818,7 @@ def main():
 
     # ---- the exact-fp32 arithmetic on the same inputs: median of >= 5 steps -------------------------
     alt = None
-    if world == 1 and not args.no_alt:
+    if full and not args.no_alt:
         other = "f32" if precision != "f32" else "f16split"
         out_main = out.clone()
         alt_steps = max(5, min(args.steps, 10))
@@ -811,7 +832,7 @@ def main():
     # ---- CPU baseline + parity on a bounded sample --------------------------------------------------
     cpu = None
     rel = None
-    if not args.no_cpu_baseline and world == 1:
+    if full and not args.no_cpu_baseline:
         from oracle.nnconv_oracle import nnconv_forward, rel_l2
         # plain PyTorch CPU GEMMs stop scaling (and then regress) far below the 256 hardware
         # threads of the GPU box; `cores` reports the threads actually used
@@ -847,14 +868,14 @@ def main():
 
     # ---- MGKN configurations -----------------------------------------------------------------------------
     mgkn = None
-    if not args.no_mgkn and world == 1:
+    if full and not args.no_mgkn:
         mgkn = mgkn_probe(dev)
 
     # ---- cross-depth reuse: depth applications of ONE module, as KernelNN.forward does
     #      (UAI1_full_resolution.py:29-30), on the reference's own training resolution s=61 r=0.10 -- the
     #      headline graph's hidden activations (E x 4 KiB = 391 GB) do not fit one GPU.  Not part of `value`.
     reuse = None
-    if not args.no_reuse_probe and world == 1:
+    if full and not args.no_reuse_probe:
         from graph_pde_amd import hidden_cache
         ei6, ea6, n6 = synth.darcy_graph(61, 0.1, device=dev, seed=0)
         x6 = torch.randn(n6, 64, device=dev)
@@ -942,7 +963,7 @@ def main():
     #      edge through the same operator (dx, dW_1..3, db_1..3, droot, dbias), hidden-activation cache off so that the
     #      recompute is inside the time.  Not part of `value`.
     backward = None
-    if not args.no_backward_probe and world == 1:
+    if full and not args.no_backward_probe:
         from graph_pde_amd import hidden_cache
         mode0 = hidden_cache.MODE
         hidden_cache.MODE = "off"

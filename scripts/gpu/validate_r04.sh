@@ -10,7 +10,7 @@ O=gpurun_out/validate_r04
 mkdir -p $O
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 < /dev/null | grep -v amdgpu.ids | tail -2
 ( time timeout 1500 python -m pytest tests -x -q -m gpu ) > $O/pytest.log 2>&1 < /dev/null; echo "pytest rc=$?"; grep -v amdgpu.ids $O/pytest.log | tail -6
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err < /dev/null; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err < /dev/null; echo "bench rc=$?"
 grep "\[bench\]" $O/bench.err | tail -8
 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --no-alt --no-mgkn --no-reuse-probe --no-backward-probe 2>/dev/null < /dev/null | tail -1 > $O/bench_torchrun_n1.json; cut -c1-160 $O/bench_torchrun_n1.json
 timeout 300 python bench.py --split-graph --steps 3 --warmup 1 2>/dev/null < /dev/null | tail -1 > $O/split_positions.json; cut -c1-200 $O/split_positions.json

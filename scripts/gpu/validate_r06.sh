@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; cd $R
 O=gpurun_out/validate_r06; mkdir -p $O
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 < /dev/null | grep -v amdgpu.ids | tail -2
-( time timeout 900 python bench.py --detail-out $O/bench_detail.json > $O/bench.json 2> $O/bench.err < /dev/null ); echo "bench rc=$?"
+( time timeout 900 python bench.py --full --detail-out $O/bench_detail.json > $O/bench.json 2> $O/bench.err < /dev/null ); echo "bench rc=$?"
 grep "\[bench\]" $O/bench.err | tail -12; wc -c $O/bench.json
 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --train --steps 3 --warmup 1 2>/dev/null < /dev/null | tail -1 > $O/bench_train_torchrun_n1.json; cut -c1-400 $O/bench_train_torchrun_n1.json
 bash scripts/gpu/profile.sh r06 < /dev/null | grep "rc="

@@ -493,6 +493,31 @@ def test_bench_refuses_a_traffic_record_of_another_kernel(tmp_path, monkeypatch)
     assert rec is None
 
 
+def test_bench_measures_traffic_unasked_only_in_a_full_run(monkeypatch):
+    """The in-run traffic measurement (two rocprofv3 child runs) is a --full leg: a plain run never starts it."""
+    import argparse, importlib.util, os, shutil
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(os.path.dirname(os.path.dirname(
+        os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(shutil, "which", lambda name: "/usr/bin/" + name)
+    for k in [k for k in os.environ if k.startswith(("ROCPROF", "ROCP_"))]:
+        monkeypatch.delenv(k)
+
+    def args(**kw):
+        return argparse.Namespace(**{"full": False, "measure_traffic": False, "no_measure_traffic": False, "config": "g241", **kw})
+    assert not bench.measures_traffic_by_default(args(), 1)
+    assert bench.measures_traffic_by_default(args(full=True), 1)
+    assert not bench.measures_traffic_by_default(args(full=True), 2)
+    assert not bench.measures_traffic_by_default(args(full=True, no_measure_traffic=True), 1)
+    assert not bench.measures_traffic_by_default(args(full=True, config="g16"), 1)
+    monkeypatch.setenv("ROCPROF_OUTPUT_PATH", "x")                    # this run is itself a rocprofv3 child
+    assert not bench.measures_traffic_by_default(args(full=True), 1)
+    monkeypatch.delenv("ROCPROF_OUTPUT_PATH")
+    monkeypatch.setattr(shutil, "which", lambda name: None)
+    assert not bench.measures_traffic_by_default(args(full=True), 1)
+
+
 def test_module_derives_message_passing_and_accepts_new_pyg_root_key():
     """The reference class derives PyG's MessagePassing and calls self.propagate (nn_conv.py:197, 242, 271); newer
     PyG state dicts name the root weight `lin.weight [out, in]`."""
