@@ -95,6 +95,45 @@ def profile_end():
     check(lib().gpde_profile_end_kinds(ms, n), "gpde_profile_end_kinds")
     return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(PROF_KINDS)}
 
+
+# GPDE_BWD_TRACE_* of include/gpde.h: the record's fields in offset order (tests/test_host_logic.py checks them against the header),
+# and the names of the coded values (index = the value the library writes)
+BWD_TRACE_FIELDS = ("phase", "na", "nb", "e0", "rows", "edge_kernel", "z", "hlast", "h1", "call_amax", "du1", "dw2", "dw1",
+                    "du_pre", "ordered", "grad_attr", "from_h")
+BWD_TRACE_CODES = {
+    "phase": ("full", "conv", "mlp", "light", "deferred"),
+    "z": ("none", "kept", "zagg32", "zagg16"),
+    "hlast": ("none", "given", "store", "layers"),
+    "h1": ("none", "gemm", "first_layer", "on_the_fly"),
+    "du1": ("none", "f16s", "f32"),
+    "dw2": ("none", "tn_split", "tn_acc"),
+    "dw1": ("none", "epilogue", "dw_first", "tn_acc"),
+}
+BWD_TRACE_CAPACITY = 4096
+
+
+def bwd_trace_begin():
+    """Arm the backward's branch trace on this thread (gpde_bwd_trace_begin); bwd_trace_end() returns what it recorded."""
+    check(lib().gpde_bwd_trace_begin(), "gpde_bwd_trace_begin")
+
+
+def bwd_trace_end() -> list:
+    """One dict per chunk the native backward processed on this thread since bwd_trace_begin(), in order; coded fields as names
+    (BWD_TRACE_CODES), the rest as ints.  Disarms the trace.  Host only: the records are written when the calls are issued."""
+    nf = len(BWD_TRACE_FIELDS)
+    buf = (ctypes.c_int32 * (nf * BWD_TRACE_CAPACITY))()
+    n = ctypes.c_int32()
+    check(lib().gpde_bwd_trace_end(buf, BWD_TRACE_CAPACITY, ctypes.byref(n)), "gpde_bwd_trace_end")
+    if n.value > BWD_TRACE_CAPACITY:
+        raise GpdeError(f"gpde_bwd_trace_end: {n.value} records, more than the {BWD_TRACE_CAPACITY} this binding reads")
+    out = []
+    for r in range(n.value):
+        rec = dict(zip(BWD_TRACE_FIELDS, buf[r * nf:(r + 1) * nf]))
+        for k, names in BWD_TRACE_CODES.items():
+            rec[k] = names[rec[k]]
+        out.append(rec)
+    return out
+
 _lib = None
 _lock = threading.Lock()
 n_native_calls = 0          # incremented by every gpde_nnconv_fwd call (tests assert it moves)

@@ -1254,6 +1254,12 @@ namespace {
 //                                       dU_2 = (sum_l x_j^(l) . dZ_i^(l)) (.) [H_2 > 0]  (a K = 64 L contraction), then ONE MLP backward
 enum BwdPhase { BWD_FULL = 0, BWD_CONV = 1, BWD_MLP = 2, BWD_LIGHT = 3, BWD_DEFER = 4 };
 
+// gpde_bwd_trace_begin / _end (include/gpde.h): one GPDE_BWD_TRACE_FIELDS record per chunk bwd_impl processes, on this thread
+// (a record type of this namespace: the vector's instantiations stay internal, -fvisibility=hidden does not cover std::)
+struct BwdTraceRec { int32_t f[GPDE_BWD_TRACE_FIELDS]; };
+thread_local bool g_bwd_trace_on = false;
+thread_local std::vector<BwdTraceRec> g_bwd_trace;
+
 int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_attr, int64_t n_edges,
              const int32_t* rowptr, const int32_t* src, const int32_t* dst, const int32_t* perm,
              const int32_t* rowptr_host, int n_layers, const int32_t* dims, const float* const* W,
@@ -1279,6 +1285,20 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
     if (rc != GPDE_OK) return rc;
     const int n = n_layers, K2P = P.K2P;
     const int N = (int)n_nodes;
+    // the record of the chunk in progress: each field is set (trs) where its branch is taken.  Unarmed, the trace costs the one
+    // thread-local read here: every write below tests the local `trace` first
+    const bool trace = g_bwd_trace_on;
+    BwdTraceRec trr{};
+    int32_t* tr = trr.f;
+    int tr_amax = 0;
+    auto trs = [&](int field, int value) { if (trace) tr[field] = value; };
+    auto tr_begin = [&](int na_, int nb_, int e0_, int rows_) {
+        if (!trace) return;
+        for (int f_ = 0; f_ < GPDE_BWD_TRACE_FIELDS; ++f_) tr[f_] = 0;
+        tr[GPDE_BWD_TRACE_PHASE] = phase; tr[GPDE_BWD_TRACE_CALL_AMAX] = tr_amax;
+        tr[GPDE_BWD_TRACE_NA] = na_; tr[GPDE_BWD_TRACE_NB] = nb_; tr[GPDE_BWD_TRACE_E0] = e0_; tr[GPDE_BWD_TRACE_ROWS] = rows_;
+    };
+    auto tr_emit = [&]() { if (trace) g_bwd_trace.push_back(trr); };
     char* w = (char*)(((uintptr_t)ws + 255) / 256 * 256);
     auto F = [&](size_t off) { return (float*)(w + off); };
     const int T = 256;
@@ -1336,6 +1356,7 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
     auto skip_h1 = [&](int rows) { return h1_on_the_fly && rows >= 8192; };
     const bool call_amax = do_mlp && h1_on_the_fly && n_edges > 0 && dims[0] <= 7 && (!kt || (src && dst));
     if (call_amax) {
+        tr_amax = 1;
         // one bound per attribute slot for the whole call (k_attr_absmax_all): 24 bytes per edge read once - 0.1 ms at s=121
         GP_HIP_CHECK(gpde_zero_async(F(P.off_amax8), 16 * 4, st));
         NodeAttrSel ns_{};
@@ -1379,8 +1400,11 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
             else hipLaunchKernelGGL(k_gather_attr, dim3(nblk((size_t)rows * P.KP[0])), dim3(T), 0, st, edge_attr, perm, e0,
                                     rows, dims[0], P.KP[0], F(P.off_H[0]));
         }
-        if (last == n - 1 && chunk_h) last = n - 2;          // given (partial H of the caller / H kept by the forward): read, not recomputed
-        else if (fast_last && last == n - 1) {
+        if (last == n - 1 && chunk_h) {                     // given (partial H of the caller / H kept by the forward): read, not recomputed
+            last = n - 2;
+            trs(GPDE_BWD_TRACE_HLAST, 1); trs(GPDE_BWD_TRACE_FROM_H, 1);
+        } else if (fast_last && last == n - 1) {
+            trs(GPDE_BWD_TRACE_HLAST, 2);
             const float* pk = F(P.off_pack);
             GpdeFusedArgs f{};
             f.attr = edge_attr; f.rowptr = rowptr; f.perm = perm;
@@ -1401,14 +1425,17 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
         }
         if (light) return GPDE_OK;
         for (int l = 1; l <= last; ++l) {
-            if (l == 1 && last == 1 && skip_h1(rows)) continue;
+            if (l == 1 && last == 1 && skip_h1(rows)) { trs(GPDE_BWD_TRACE_H1, 3); continue; }
+            if (l == n - 1) trs(GPDE_BWD_TRACE_HLAST, 3);
             if (l == 1 && dims[0] <= 8 && P.KP[0] >= 8 && P.KP[1] % 4 == 0 && rows >= 1024) {
+                trs(GPDE_BWD_TRACE_H1, 2);
                 const int cb = (P.KP[1] + 255) / 256;
                 int rb = rows / 64; if (rb > 4096 / cb) rb = 4096 / cb; if (rb < 1) rb = 1;
                 hipLaunchKernelGGL(k_first_layer, dim3(cb, rb), dim3(T), 0, st, F(P.off_H[0]), P.KP[0], F(P.off_wp[1]), P.KP[0],
                                    F(P.off_bp[1]), rows, P.KP[1], F(P.off_H[1]));
                 continue;
             }
+            if (l == 1) trs(GPDE_BWD_TRACE_H1, 1);
             GpdeGemmArgs g = gemm0();
             g.A = F(P.off_H[l - 1]); g.lda = P.KP[l - 1]; g.B = F(P.off_wp[l]); g.ldb = P.KP[l - 1];
             g.C = F(P.off_H[l]); g.ldc = P.KP[l]; g.M = rows; g.N = P.KP[l]; g.K = P.KP[l - 1];
@@ -1440,9 +1467,11 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
         for (int l = n - 1; l >= 1; --l) {
             const int Kl = P.KP[l], Kin = P.KP[l - 1];
             int rc2;
-            if (l == 1 && grad_attr)         // dU_1 is complete here: the gradient of the attributes through W_1
+            if (l == 1 && grad_attr) {       // dU_1 is complete here: the gradient of the attributes through W_1
+                trs(GPDE_BWD_TRACE_GRAD_ATTR, 1);
                 hipLaunchKernelGGL(k_grad_attr, dim3((rows + 3) / 4), dim3(T), 0, st, dUc, Kl, F(P.off_wp[1]), Kin, perm, mlp_e0, rows,
                                    dims[0], grad_attr);
+            }
             if (l == 1 && dw1_done) continue;
             if (l == 1 && dims[0] <= 8 && Kin >= 8 && Kin % 4 == 0 && Kl % 4 == 0 && rows >= 1024) {
                 // dW_1 and db_1 from one pass over dU_1 (k_dw_first; attribute slots beyond k0 are zero columns of H_0)
@@ -1450,6 +1479,7 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
                 int splits = 1; while (splits < 256 && cb * splits < 1024 && rows / (splits * 2) >= 64) splits *= 2;
                 while (splits > 1 && (size_t)splits * Kl * 9 > P.part_floats) splits /= 2;
                 if ((size_t)splits * Kl * 9 <= P.part_floats) {
+                    trs(GPDE_BWD_TRACE_DW1, 2);
                     hipLaunchKernelGGL(k_dw_first, dim3(cb, splits), dim3(T), 0, st, dUc, F(P.off_H[0]), Kin, rows, Kl, splits, F(P.off_part));
                     hipLaunchKernelGGL(k_dw_first_reduce, dim3(nblk((size_t)Kl * 9)), dim3(T), 0, st, F(P.off_part), splits, Kl, Kin,
                                        F(P.off_dwp[l]), F(P.off_dbp[l]));
@@ -1470,9 +1500,11 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
             }
             if (tn_split) {
                 // dW_2 += dU_2^T . H_1 on the split-f16 GEMM (contraction over the edges: both operands transposed)
+                trs(GPDE_BWD_TRACE_DW2, 1);
                 GpdeFirstLayerSpec fl{F(P.off_H[0]), P.KP[0], F(P.off_wp[1]), P.KP[0], F(P.off_bp[1]), (uint32_t*)F(P.off_maskbits), dims[0],
                                       call_amax ? (const unsigned*)F(P.off_amax8) : nullptr};
                 fl_in_kernel = skip_h1(rows) && gpde_first_layer_in_kernel(fl, rows, tn_ksplits(rows, P.KP[2], P.KP[1]));
+                if (fl_in_kernel) trs(GPDE_BWD_TRACE_H1, 3);
                 GpdeDuStats dst_{F(P.off_dbp[l]), F(P.off_rowsc), F(P.off_rowsc) + rows,
                                  du_pre ? F(P.off_tcs) : nullptr, du_pre ? (const unsigned*)F(P.off_tcm) : nullptr};
                 if ((rc2 = gpde_launch_gemm_f16s_tn(dUc, Kl, Kl, F(P.off_H[l - 1]), Kin, Kin, rows, tn_ksplits(rows, P.KP[2], P.KP[1]),
@@ -1480,9 +1512,14 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
                                                     skip_h1(rows) ? &fl : nullptr, du_one_pass ? &dst_ : nullptr)) != GPDE_OK) return rc2;
                 if ((rc2 = gpde_launch_reduce_splits(F(P.off_part), (size_t)Kl * Kin, tn_ksplits(rows, P.KP[2], P.KP[1]), (size_t)Kl * Kin,
                                                      F(P.off_dwp[l]), 1, st)) != GPDE_OK) return rc2;
-            } else if ((rc2 = gemm_tn_acc(dUc, Kl, Kl, F(P.off_H[l - 1]), Kin, Kin, rows, F(P.off_dwp[l]), Kin,
-                                          F(P.off_part), P.part_floats, 1, st)) != GPDE_OK) return rc2;
+            } else {
+                if (l == 2) trs(GPDE_BWD_TRACE_DW2, 2);
+                if (l == 1) trs(GPDE_BWD_TRACE_DW1, 3);
+                if ((rc2 = gemm_tn_acc(dUc, Kl, Kl, F(P.off_H[l - 1]), Kin, Kin, rows, F(P.off_dwp[l]), Kin,
+                                       F(P.off_part), P.part_floats, 1, st)) != GPDE_OK) return rc2;
+            }
             if (l > 1 && l == 2 && f16s_du1 && rows >= 64) {
+                trs(GPDE_BWD_TRACE_DU1, 1);
                 float* dUo = bufs[nb_]; nb_ ^= 1;
                 GpdeGemmF16sArgs g{};
                 g.A = dUc; g.lda = Kl; g.M = rows; g.bsplit = F(P.off_w2ts); g.ucol = F(P.off_ucol2);
@@ -1496,6 +1533,7 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
                     g.fl_dw_part = dUo; g.fl_dw_out = F(P.off_dwp[1]); g.fl_dw_ld = P.KP[0]; g.fl_db_out = F(P.off_dbp[1]);
                     g.fl_skip_store = 1;
                     dw1_done = true;
+                    trs(GPDE_BWD_TRACE_DW1, 1);
                 }
                 // (row scales: a pass over dU_2, 3.9 ms at s=121.  Collecting the row maxima inside gpde_edge_bwd2_kernel was
                 // tried in round 3: 16 more registers spill 15 VGPRs of a kernel that sits at its 256-register limit, +5 ms.)
@@ -1505,6 +1543,7 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
                 } else if ((rc2 = gpde_launch_gemm_f16s_nt(g, F(P.off_rowsc), st)) != GPDE_OK) return rc2;
                 dUc = dUo;
             } else if (l > 1) {
+                if (l == 2) trs(GPDE_BWD_TRACE_DU1, 2);
                 float* dUo = bufs[nb_]; nb_ ^= 1;
                 GpdeGemmArgs g = gemm0();
                 g.A = dUc; g.lda = Kl; g.B = F(P.off_wp[l]); g.ldb = Kin; g.b_kcontig = 0;
@@ -1521,10 +1560,12 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
         // plain edge chunks: nothing here depends on the destination structure
         for (int64_t e0 = 0; e0 < n_edges; e0 += P.Ec) {
             const int rows = (int)((n_edges - e0) < P.Ec ? (n_edges - e0) : P.Ec);
+            tr_begin(-1, -1, (int)e0, rows);
             if ((rc = recompute((int)e0, rows, n - 2)) != GPDE_OK) return rc;
             // activations below the last hidden layer are recomputed; the last one is needed only as
             // the ReLU mask, which the incoming dL/dU already carries
             if ((rc = mlp_backward(grad_hidden_in + (size_t)e0 * K2P, rows)) != GPDE_OK) return rc;
+            tr_emit();
         }
         GP_LAUNCH_CHECK("gpde_hidden_bwd kernels");
     }
@@ -1554,6 +1595,7 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
         float* gT = F(P.off_gT); float* S = F(P.off_S); float* dS = F(P.off_dS);
         float* Z = F(P.off_Z); float* dZ = F(P.off_dZ);
         chunk_h = from_h ? hpart + (size_t)e0 * K2P : nullptr;
+        tr_begin(na, nb, e0, rows);
         if (phase == BWD_DEFER) {
             if (rows > 0) {
                 rc_na = na; rc_nb = nb;
@@ -1580,6 +1622,7 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
                                                        F(P.off_dzimg), F(P.off_nscale) + P.Nc, H2, K2P, dU2, K2P, K2P, st)) != GPDE_OK) return rc;
                 if ((rc = mlp_backward(dU2, rows)) != GPDE_OK) return rc;
             }
+            tr_emit();
             na = nb;
             continue;
         }
@@ -1587,17 +1630,19 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
         if (rows > 0) {
             // hidden activations of the chunk's edges: recomputed, or rows of the given cache
             if (phase == BWD_FULL || light) { rc_na = na; rc_nb = nb; if ((rc = recompute(e0, rows, n - 1)) != GPDE_OK) return rc; }
-            const float* Hlast = chunk_h ? chunk_h : (phase == BWD_FULL || light) ? F(P.off_H[n - 1]) : hidden + (size_t)e0 * K2P;
+            const float* Hlast = chunk_h ? chunk_h : (phase == BWD_FULL || light) ? F(P.off_H[n - 1]) : nullptr;
+            if (!Hlast) { Hlast = hidden + (size_t)e0 * K2P; trs(GPDE_BWD_TRACE_HLAST, 1); trs(GPDE_BWD_TRACE_FROM_H, 1); }
             // Z of the chunk's nodes: kept by the forward (gpde_nnconv_fwd_keepz), else re-aggregated from the recomputed /
             // given activations
-            if (z_saved) Z = const_cast<float*>(z_saved) + (size_t)na * GP_W * K2P;      // read only below
+            if (z_saved) { Z = const_cast<float*>(z_saved) + (size_t)na * GP_W * K2P; trs(GPDE_BWD_TRACE_Z, 1); }     // read only below
             else GP_HIP_CHECK(gpde_zero_async(Z, (size_t)nn * GP_W * K2P * 4, st));
             if (!z_saved) {
                 GpdeFusedArgs f{};
                 f.x = x; f.attr = edge_attr; f.rowptr = rowptr; f.src = src; f.dst = dst; f.perm = perm;
                 f.hbuf = Hlast; f.zbuf = Z; f.k0 = dims[0]; f.K1P = 32; f.K2P = K2P;
                 f.nc0 = na; f.nc1 = nb; f.e_chunk0 = e0;
-                if (zagg16) { f.xs = (const unsigned*)F(P.off_xs); f.scal = (const unsigned*)F(P.off_scal); f.hmax = (const unsigned*)F(P.off_scal) + 2; }
+                trs(GPDE_BWD_TRACE_Z, 2);
+                if (zagg16) { f.xs = (const unsigned*)F(P.off_xs); f.scal = (const unsigned*)F(P.off_scal); f.hmax = (const unsigned*)F(P.off_scal) + 2; trs(GPDE_BWD_TRACE_Z, 3); }
                 const int ns = K2P / GP_TN;
                 int groups = gpde_num_cus() / ns; if (groups < 1) groups = 1;
                 const int gcap = (rows / GP_TE + GP_WAVES) / GP_WAVES; if (groups > gcap) groups = gcap;
@@ -1655,6 +1700,7 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
             const bool staged = force ? force >= 2 : (gh_acc || (int64_t)rows >= (int64_t)(K2P % 32 == 0 ? 4 : 32) * nn);
             du_pre = false;
             if (staged && force != 2 && K2P % 32 == 0) {      // split-f16 MFMA (default); GPDE_EDGE_BWD=2: the fp32-MFMA staged kernel
+                trs(GPDE_BWD_TRACE_EDGE_KERNEL, 3);
                 if ((rc = gpde_launch_dz_split(dZ, nn, K2P, F(P.off_dzun), st)) != GPDE_OK) return rc;
                 GpdeEdgeBwd3Args e3{x, src, dst, dZ, F(P.off_dzun), dS, Hlast, dUc, dx, ordered ? F(P.off_dxe) : nullptr, e0, e1, na, K2P};
                 e3.du_accumulate = gh_acc;
@@ -1665,18 +1711,26 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
                     e3.row_sc = F(P.off_rowsc); e3.row_isc = F(P.off_rowsc) + rows;
                     e3.csum_part = F(P.off_tcs); e3.cmax_part = (unsigned*)F(P.off_tcm);
                     du_pre = true;
+                    trs(GPDE_BWD_TRACE_DU_PRE, 1);
                 }
                 if ((rc = gpde_launch_edge_bwd3(e3, st)) != GPDE_OK) return rc;
             } else if (gh_acc) {
                 gpde_set_error("gpde_nnconv_bwd: GPDE_BWD_ACCUMULATE_GRAD_HIDDEN is built into the split-f16 per-edge kernel only "
                                "(GPDE_EDGE_BWD=2 forces the other one)");
                 return GPDE_EUNSUPPORTED;
-            } else if (staged) hipLaunchKernelGGL(gpde_edge_bwd2_kernel, dim3(((rows + 127) / 128 + 7) / 8 * 8), dim3(T), lds2, st, ea);
-            else hipLaunchKernelGGL(gpde_edge_bwd_kernel, dim3((rows + 127) / 128), dim3(T), lds, st, ea);
+            } else if (staged) {
+                trs(GPDE_BWD_TRACE_EDGE_KERNEL, 2);
+                hipLaunchKernelGGL(gpde_edge_bwd2_kernel, dim3(((rows + 127) / 128 + 7) / 8 * 8), dim3(T), lds2, st, ea);
+            } else {
+                trs(GPDE_BWD_TRACE_EDGE_KERNEL, 1);
+                hipLaunchKernelGGL(gpde_edge_bwd_kernel, dim3((rows + 127) / 128), dim3(T), lds, st, ea);
+            }
+            if (ordered) trs(GPDE_BWD_TRACE_ORDERED, 1);
             if (ordered) hipLaunchKernelGGL(k_dx_reduce, dim3((N + 3) / 4), dim3(T), 0, st, F(P.off_dxe), src_rowptr, src_slots, N, e0, e1, dx, 1, (size_t)0, 0);
             // MLP backward over the chunk's edges
             if (phase == BWD_FULL) { mlp_e0 = e0; if ((rc = mlp_backward(dUc, rows)) != GPDE_OK) return rc; }
         }
+        tr_emit();
         na = nb;
     }
     GP_LAUNCH_CHECK("gpde_nnconv_bwd kernels");
@@ -1701,6 +1755,34 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
 }
 
 }  // namespace
+
+extern "C" int gpde_nnconv_bwd_plan(int64_t n_nodes, int64_t n_edges, int n_layers, const int32_t* dims, size_t ws_bytes,
+                                    int n_defer, int h_given, int64_t* edges_per_chunk, int64_t* nodes_per_chunk) {
+    BwdPlan P;
+    if (!dims || n_nodes < 0 || n_edges < 0 || n_defer < 0) { gpde_set_error("gpde_nnconv_bwd_plan: invalid arguments"); return GPDE_EINVAL; }
+    const int rc = make_bwd_plan(n_nodes, n_edges, n_layers, dims, ws_bytes, false, &P, n_defer, h_given != 0);
+    if (rc != GPDE_OK) return rc;
+    if (edges_per_chunk) *edges_per_chunk = P.Ec;
+    if (nodes_per_chunk) *nodes_per_chunk = P.Nc;
+    return GPDE_OK;
+}
+
+extern "C" int gpde_bwd_trace_begin(void) {
+    g_bwd_trace.clear();
+    g_bwd_trace_on = true;
+    return GPDE_OK;
+}
+
+extern "C" int gpde_bwd_trace_end(int32_t* records, int32_t capacity, int32_t* n_records) {
+    g_bwd_trace_on = false;
+    const size_t n = g_bwd_trace.size();
+    const size_t k = records && capacity > 0 ? (n < (size_t)capacity ? n : (size_t)capacity) : 0;
+    for (size_t i = 0; i < k; ++i)
+        for (int f = 0; f < GPDE_BWD_TRACE_FIELDS; ++f) records[i * GPDE_BWD_TRACE_FIELDS + f] = g_bwd_trace[i].f[f];
+    if (n_records) *n_records = (int32_t)n;
+    g_bwd_trace.clear();
+    return GPDE_OK;
+}
 
 extern "C" size_t gpde_nnconv_bwd_workspace_bytes_one_chunk(int64_t n_nodes, int64_t n_edges, int n_layers, const int32_t* dims) {
     BwdPlan P;

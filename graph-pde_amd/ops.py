@@ -527,6 +527,17 @@ def bwd_workspace_bytes(lib, n: int, e: int, nl: int, dims_c, dev, h_given_bytes
     return nbytes
 
 
+def bwd_plan(n_nodes: int, n_edges: int, dims: Sequence[int], ws_bytes: int, n_defer: int = 0, h_given: bool = False) -> dict:
+    """The node chunking the native backward plans for `ws_bytes` of workspace (gpde_nnconv_bwd_plan, host only): edges and nodes
+    per node-aligned chunk.  `n_defer` > 0: gpde_nnconv_bwd_deferred of that many applications; `h_given`: the last hidden
+    activations of every edge come from the forward (nnconv_backward_raw's `hidden_saved`)."""
+    ec, nc = ctypes.c_int64(), ctypes.c_int64()
+    rc = _lib.lib().gpde_nnconv_bwd_plan(int(n_nodes), int(n_edges), len(dims) - 1, _lib.dims_array(dims), int(ws_bytes),
+                                         int(n_defer), int(bool(h_given)), ctypes.byref(ec), ctypes.byref(nc))
+    _lib.check(rc, "gpde_nnconv_bwd_plan")
+    return {"edges_per_chunk": ec.value, "nodes_per_chunk": nc.value}
+
+
 def device_free_bytes(dev):
     """(bytes an allocation can still get, device total): what the driver reports free PLUS what torch's caching allocator
     holds in freed blocks (it returns them to the driver when a large request needs the room) - after a training step the

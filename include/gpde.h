@@ -210,6 +210,12 @@ GPDE_API size_t gpde_nnconv_bwd_workspace_bytes(int64_t n_nodes, int64_t n_edges
  * memory). */
 GPDE_API size_t gpde_nnconv_bwd_workspace_bytes_one_chunk(int64_t n_nodes, int64_t n_edges, int n_layers,
                                                  const int32_t* dims);
+/* The node chunking gpde_nnconv_bwd (n_defer = 0) or gpde_nnconv_bwd_deferred (n_defer = L) plans for these sizes and `ws_bytes` of
+ * workspace: edges and nodes per node-aligned chunk (a chunk ends at the last node whose in-edges still fit both).  h_given: the last
+ * hidden activations of every edge come from the caller (gpde_nnconv_bwd's `hidden` + attribute source form).  Host only, no device
+ * work; GPDE_EWORKSPACE when the workspace is too small. */
+GPDE_API int gpde_nnconv_bwd_plan(int64_t n_nodes, int64_t n_edges, int n_layers, const int32_t* dims, size_t ws_bytes,
+                                  int n_defer, int h_given, int64_t* edges_per_chunk, int64_t* nodes_per_chunk);
 enum { GPDE_BWD_ACCUMULATE_GRAD_HIDDEN = 1 /* gpde_nnconv_bwd `flags`, `hidden` form: grad_hidden += dL/dU instead of = (see below) */ };
 GPDE_API int gpde_nnconv_bwd(const float* x, int64_t n_nodes, const float* edge_attr, const GpdeNodeAttr* node_attr,
                     const float* hidden, int64_t n_edges, const int32_t* rowptr, const int32_t* src, const int32_t* dst,
@@ -497,6 +503,36 @@ enum {
     GPDE_PROF_KINDS = 5
 };
 GPDE_API int gpde_profile_end_kinds(double* ms_by_kind, int32_t* launches_by_kind);
+
+/* Which branches the native backward took (tests).  gpde_bwd_trace_begin() arms a trace on the calling thread and empties it;
+ * while it is armed every gpde_nnconv_bwd / _light / _deferred / gpde_hidden_bwd call appends one record of
+ * GPDE_BWD_TRACE_FIELDS int32 per chunk it processes (node-aligned chunks; the edge chunks of gpde_hidden_bwd with na = nb = -1).
+ * Each field is written where the backward takes that decision.  gpde_bwd_trace_end() disarms it, copies up to `capacity` records
+ * to `records`, writes the number recorded to *n_records and empties the trace.  Host only, no device work; unarmed, a call pays
+ * one thread-local read. */
+GPDE_API int gpde_bwd_trace_begin(void);
+GPDE_API int gpde_bwd_trace_end(int32_t* records, int32_t capacity, int32_t* n_records);
+enum {
+    GPDE_BWD_TRACE_PHASE = 0,       /* 0 full, 1 conv (given H, dL/dU written), 2 mlp (gpde_hidden_bwd), 3 light, 4 deferred */
+    GPDE_BWD_TRACE_NA = 1,          /* first node of the chunk */
+    GPDE_BWD_TRACE_NB = 2,          /* one past its last node */
+    GPDE_BWD_TRACE_E0 = 3,          /* first CSR slot */
+    GPDE_BWD_TRACE_ROWS = 4,        /* edges (CSR slots) of the chunk */
+    GPDE_BWD_TRACE_EDGE_KERNEL = 5, /* 0 none, 1 gpde_edge_bwd_kernel, 2 gpde_edge_bwd2_kernel, 3 gpde_edge_bwd3_kernel (split f16) */
+    GPDE_BWD_TRACE_Z = 6,           /* source of Z: 0 none, 1 kept by the forward, 2 gpde_zagg_kernel (fp32), 3 gpde_zagg_kernel<true> */
+    GPDE_BWD_TRACE_HLAST = 7,       /* last hidden layer: 0 not needed, 1 given, 2 fused store kernel, 3 the layer loop */
+    GPDE_BWD_TRACE_H1 = 8,          /* H_1: 0 not formed here, 1 fp32 GEMM, 2 k_first_layer, 3 on the fly (never written) */
+    GPDE_BWD_TRACE_CALL_AMAX = 9,   /* 1: one attribute bound per slot for the whole call */
+    GPDE_BWD_TRACE_DU1 = 10,        /* dU_1: 0 not formed, 1 split-f16 NT GEMM, 2 fp32 GEMM */
+    GPDE_BWD_TRACE_DW2 = 11,        /* dW_2: 0 not formed, 1 split-f16 TN GEMM, 2 gemm_tn_acc */
+    GPDE_BWD_TRACE_DW1 = 12,        /* dW_1, db_1: 0 not formed, 1 dU_1 GEMM epilogue, 2 k_dw_first, 3 gemm_tn_acc */
+    GPDE_BWD_TRACE_DU_PRE = 13,     /* 1: the per-edge kernel left dU_2^T, its row scales and tile column partials */
+    GPDE_BWD_TRACE_ORDERED = 14,    /* 1: grad_x summed per source in slot order (k_dx_reduce); 0: atomics */
+    GPDE_BWD_TRACE_GRAD_ATTR = 15,  /* 1: dL/d edge_attr formed (k_grad_attr) */
+    GPDE_BWD_TRACE_FROM_H = 16,     /* 1: the chunk read last hidden activations the caller gave (hidden_saved, a partial H, the
+                                       `hidden` form) instead of recomputing them */
+    GPDE_BWD_TRACE_FIELDS = 17
+};
 
 #ifdef __cplusplus
 }

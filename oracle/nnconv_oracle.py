@@ -117,16 +117,17 @@ def nnconv_forward(x: torch.Tensor, edge_index: torch.Tensor, edge_attr: torch.T
 def nnconv_grads(x: torch.Tensor, edge_index: torch.Tensor, edge_attr: torch.Tensor,
                  weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Tensor]],
                  root: Optional[torch.Tensor], bias: Optional[torch.Tensor], aggr: str,
-                 grad_out: torch.Tensor, chunk_edges: Optional[int] = None):
+                 grad_out: torch.Tensor, chunk_edges: Optional[int] = None, need_attr: bool = False):
     """float64 autograd through the restated operator = the reference's `loss.backward()`
     (UAI1_full_resolution.py:266) for loss = sum(out * grad_out).  Pinned against autograd through
     the reference's own module by tests/golden/*_grad.npz.
     `chunk_edges`: the loss is a sum over edges (out_i = sum_{e -> i} m_e / deg_i + x_i root + bias), so the edges may be
     differentiated in pieces and the gradients accumulated - same mathematics, bounds the [E, 4096] float64 tensor of the
     MGKN-scale calls (tests/test_oracle_golden.py checks chunked == whole).
-    Returns (grad_x, [grad_W], [grad_b], grad_root or None, grad_bias or None)."""
+    Returns (grad_x, [grad_W], [grad_b], grad_root or None, grad_bias or None); with `need_attr` a sixth element, dL/d edge_attr."""
     n = x.shape[0]
     xs = x.double().requires_grad_(True)
+    ea = edge_attr.detach().double().requires_grad_(need_attr)     # (a leaf of its own: the caller's tensor is left alone)
     Ws = [w.double().requires_grad_(True) for w in weights]
     Bs = [None if b is None else b.double().requires_grad_(True) for b in biases]
     r = None if root is None else root.double().requires_grad_(True)
@@ -136,7 +137,7 @@ def nnconv_grads(x: torch.Tensor, edge_index: torch.Tensor, edge_attr: torch.Ten
         raise ValueError(aggr)
     e = int(src.numel())
     if chunk_edges is None or e <= chunk_edges:
-        h = densenet_forward(edge_attr.double(), Ws, Bs)
+        h = densenet_forward(ea, Ws, Bs)
         m = torch.matmul(xs[src].unsqueeze(1), h.view(-1, xs.shape[1], h.shape[1] // xs.shape[1])).squeeze(1)
         out = torch.zeros(n, m.shape[1], dtype=torch.float64).index_add(0, dst, m)
         if aggr == "mean":
@@ -152,7 +153,7 @@ def nnconv_grads(x: torch.Tensor, edge_index: torch.Tensor, edge_attr: torch.Ten
             gT = gT / torch.bincount(dst, minlength=n).clamp(min=1).double().unsqueeze(1)
         for lo in range(0, e, chunk_edges):
             sl = slice(lo, lo + chunk_edges)
-            h = densenet_forward(edge_attr[sl].double(), Ws, Bs)
+            h = densenet_forward(ea[sl], Ws, Bs)
             m = torch.matmul(xs[src[sl]].unsqueeze(1), h.view(-1, xs.shape[1], h.shape[1] // xs.shape[1])).squeeze(1)
             (m * gT[dst[sl]]).sum().backward()
         node = torch.zeros(n, grad_out.shape[1], dtype=torch.float64)
@@ -163,8 +164,9 @@ def nnconv_grads(x: torch.Tensor, edge_index: torch.Tensor, edge_attr: torch.Ten
         if r is not None or bb is not None:
             (node * grad_out.double()).sum().backward()
     zero = lambda t: torch.zeros_like(t) if t.grad is None else t.grad
-    return (zero(xs), [zero(w) for w in Ws], [None if b is None else zero(b) for b in Bs], None if r is None else zero(r),
-            None if bb is None else zero(bb))
+    res = (zero(xs), [zero(w) for w in Ws], [None if b is None else zero(b) for b in Bs], None if r is None else zero(r),
+           None if bb is None else zero(bb))
+    return res + (zero(ea),) if need_attr else res
 
 
 def nnconv_grads_shared(xs: Sequence[torch.Tensor], edge_index: torch.Tensor, edge_attr: torch.Tensor,

@@ -762,3 +762,58 @@ def test_token_of_hands_out_the_shared_h_token_only_where_h_has_one_kind_of_cons
     ent.token.valid = False
     assert hidden_cache.token_of(m, h, dense) is None
     assert hidden_cache.token_of(torch.nn.Linear(2, 2), h, dense) is None
+
+
+@pytest.mark.parametrize("dims,n,e,n_defer", [([6, 256, 256, 4096], 200, 12000, 0), ([3, 128, 4096], 50, 900, 0),
+                                              ([6, 1024, 1024, 4096], 3000, 200000, 0), ([6, 256, 256, 4096], 300, 20000, 3),
+                                              ([4, 64, 200, 64, 4096], 120, 5000, 0)])
+def test_bwd_plan_agrees_with_the_workspace_queries(dims, n, e, n_defer):
+    """ops.bwd_plan (gpde_nnconv_bwd_plan, host only): one chunk at the one-chunk size, a smaller plan below it; the node count per
+    chunk never falls as the workspace grows and the edge count never falls while the node count holds (each node added takes
+    per-node bytes from the edges: the edge count may dip there)."""
+    from graph_pde_amd import _lib
+    lib, dc, nl = _lib.lib(), _lib.dims_array(dims), len(dims) - 1
+    if n_defer:
+        one = int(lib.gpde_nnconv_bwd_deferred_workspace_bytes(n, e, nl, dc, n_defer))
+    else:
+        one = int(lib.gpde_nnconv_bwd_workspace_bytes_one_chunk(n, e, nl, dc))
+        assert one >= int(lib.gpde_nnconv_bwd_workspace_bytes(n, e, nl, dc)) > 0
+    assert ops.bwd_plan(n, e, dims, one, n_defer) == {"edges_per_chunk": e, "nodes_per_chunk": n}
+    with pytest.raises(_lib.GpdeError, match="too small"):
+        ops.bwd_plan(n, e, dims, 1 << 20, n_defer)
+    prev, seen, smallest = None, 0, None
+    for ws in range(one // 40, one + one // 20, max(1, one // 1500)):
+        try:
+            p = ops.bwd_plan(n, e, dims, ws, n_defer)
+        except _lib.GpdeError:
+            assert prev is None, ws                      # too small only below every size that plans
+            continue
+        seen += 1
+        smallest = smallest or (ws, p)
+        assert 1 <= p["edges_per_chunk"] <= e and 1 <= p["nodes_per_chunk"] <= n, (ws, p)
+        if prev is not None:
+            assert p["nodes_per_chunk"] >= prev["nodes_per_chunk"], (ws, prev, p)
+            if p["nodes_per_chunk"] == prev["nodes_per_chunk"]:
+                assert p["edges_per_chunk"] >= prev["edges_per_chunk"], (ws, prev, p)
+        prev = p
+    assert seen > 100 and prev == {"edges_per_chunk": e, "nodes_per_chunk": n}
+    # the given-H form leaves the last hidden layer's per-edge buffer out of the workspace: at least as many edges per chunk
+    ws, below = smallest
+    assert below["edges_per_chunk"] < e or below["nodes_per_chunk"] < n, below           # more than one chunk below the one-chunk size
+    if not n_defer:
+        h = ops.bwd_plan(n, e, dims, ws, 0, h_given=True)
+        assert h["nodes_per_chunk"] == below["nodes_per_chunk"] and h["edges_per_chunk"] >= below["edges_per_chunk"], (h, below)
+
+
+def test_bwd_trace_offsets_match_the_header_and_an_unarmed_end_is_empty():
+    """The GPDE_BWD_TRACE_* offsets of include/gpde.h are the field order _lib.bwd_trace_end() reads; without a begin (or after an
+    end) the trace holds no record."""
+    import re
+    from graph_pde_amd import _lib
+    src = open(_lib.HEADER_PATH).read()
+    found = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"\bGPDE_BWD_TRACE_([A-Z0-9_]+)\s*=\s*(\d+)", src)}
+    assert found.pop("fields") == len(_lib.BWD_TRACE_FIELDS)
+    assert found == {f: i for i, f in enumerate(_lib.BWD_TRACE_FIELDS)}
+    assert _lib.bwd_trace_end() == []
+    _lib.bwd_trace_begin()
+    assert _lib.bwd_trace_end() == [] and _lib.bwd_trace_end() == []
