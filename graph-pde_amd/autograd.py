@@ -387,3 +387,25 @@ class WeConvFunction(torch.autograd.Function):
         if share and tid >= 0:
             tok.gh_acc, tok.gh_tid, tok.gh_adds, tok.side_acc = gwe, tid, 0, (groot, gbias)
         return gx, gwe, None, groot, gbias if ctx.has_bias else None, None, None
+
+
+class WeConvAnyFunction(torch.autograd.Function):
+    """The operator given the per-edge weights at ANY width 1 .. 256 (gpde_nnconv_fwd_edgeweights_any: gather, message, add /
+    mean, update in one streaming kernel), differentiable in x, W_e [E, in * out], root and bias
+    (gpde_nnconv_bwd_edgeweights_any).  The sibling of WeConvFunction for modules whose widths are not (64, 64): W_e is the
+    caller's own tensor (`nn(pseudo)`), nothing is shared between applications."""
+
+    @staticmethod
+    def forward(ctx, x, we, csr, root, bias, aggr):
+        out = ops.nnconv_forward_edgeweights_any_raw(x.detach(), csr, we.detach(), root, bias, aggr)
+        ctx.csr, ctx.aggr, ctx.has_bias = csr, aggr, bias is not None
+        ctx.save_for_backward(x, we, root)
+        return out
+
+    @staticmethod
+    @once_differentiable        # the native backward is not itself differentiable: create_graph=True raises
+    def backward(ctx, grad_out):
+        x, we, root = ctx.saved_tensors
+        gx, gwe, groot, gbias = ops.nnconv_backward_edgeweights_any_raw(x, ctx.csr, we, root, ctx.aggr, grad_out,
+                                                                        need_root=root is not None, need_bias=ctx.has_bias)
+        return gx, gwe, None, groot, gbias if ctx.has_bias else None, None

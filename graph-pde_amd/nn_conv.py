@@ -23,7 +23,7 @@ from torch.nn import Parameter
 
 from . import hidden_cache, ops
 from . import autograd as _ag
-from .autograd import NNConvDeferredFunction, NNConvFunction, NNConvHiddenFunction, SharedParamFunction, WeConvFunction
+from .autograd import NNConvDeferredFunction, NNConvFunction, NNConvHiddenFunction, SharedParamFunction, WeConvAnyFunction, WeConvFunction
 from .message_passing import MessagePassing
 
 
@@ -55,7 +55,13 @@ def _uniform(size, tensor):
 class NNConv_old(MessagePassing):
     r"""x'_i = Theta x_i + aggr_{j in N(i)} x_j . h_Theta(e_ij)   with h_Theta a kernel MLP emitting
     in_channels*out_channels values per edge (nn_conv.py:197-232).  Derives `MessagePassing` like the reference
-    (nn_conv.py:197, 242) and overrides `propagate` with the fused HIP operator."""
+    (nn_conv.py:197, 242) and overrides `propagate` with the fused HIP operator.
+
+    Widths: 64 -> 64 (every reference configuration) runs the re-associated fused kernels.  Any other pair of
+    1 <= in_channels, out_channels <= 256 takes the reference's own order for every kernel network: `weight =
+    self.nn(pseudo)` by the caller's module ([E, in * out], as nn_conv.py:274 materialises it), then message / aggregate /
+    update as ONE native kernel over it (`_propagate_any_width`, csrc/gpde_weconv_any.hip).  Wider raises
+    NotImplementedError."""
 
     def __init__(self, in_channels, out_channels, nn, aggr="add", root_weight=True, bias=True,
                  **kwargs):
@@ -109,6 +115,13 @@ class NNConv_old(MessagePassing):
         if residual is not None or activation is not None:
             return self._forward_act(x, edge_index, edge_attr, residual, activation == "relu")
         x = x.unsqueeze(-1) if x.dim() == 1 else x
+        if not self._is_width_64():
+            # any other width: attributes as the tensor the reference builds, then propagate() (-> _propagate_any_width)
+            self._check_width()
+            if isinstance(edge_attr, ops.NodeAttr):
+                edge_attr = edge_attr.materialize(edge_index.edge_index if isinstance(edge_index, ops.Csr) else edge_index)
+            pseudo = edge_attr.unsqueeze(-1) if edge_attr.dim() == 1 else edge_attr
+            return self.propagate(edge_index, x=x, pseudo=pseudo)
         if not x.is_cuda:
             return self._forward_staged(x, edge_index, edge_attr)
         if isinstance(edge_attr, ops.NodeAttr) and not self._nn_is_linear_relu_chain():
@@ -152,6 +165,8 @@ class NNConv_old(MessagePassing):
             sz = list(size) if isinstance(size, (list, tuple)) else [size, size]
             if any(v is not None and int(v) != x.size(0) for v in sz):
                 raise NotImplementedError("bipartite propagate (size != [N, N]) is not built: no graph-pde script uses it")
+        if not self._is_width_64():
+            return self._propagate_any_width(x, edge_index, pseudo)
         if not x.is_cuda:
             return self._forward_staged(x, edge_index, pseudo)
         if not self._nn_is_linear_relu_chain():
@@ -206,6 +221,14 @@ class NNConv_old(MessagePassing):
                                                   any(p.requires_grad for p in self.parameters()))
         fusable = x.is_cuda and x.dim() == 2 and not isinstance(edge_attr, ops.NodeAttr) and not needs_grad and \
             x.dtype == torch.float32 and (residual is None or residual.device == x.device) and self._nn_is_linear_relu_chain()
+        if not self._is_width_64():
+            self._check_width()
+            if x.is_cuda and x.dim() == 2 and not needs_grad and x.dtype == torch.float32 and torch.is_tensor(edge_attr) and \
+                    (residual is None or residual.device == x.device):
+                # fused into the any-width kernel's epilogue (inference on device tensors, as at 64)
+                pseudo = edge_attr.unsqueeze(-1) if edge_attr.dim() == 1 else edge_attr
+                return self._propagate_any_width(x, edge_index, pseudo, residual=residual, relu=relu)
+            fusable = False
         if not fusable:
             y = self.forward(x, edge_index, edge_attr)
             if residual is not None:
@@ -228,11 +251,68 @@ class NNConv_old(MessagePassing):
                                                      hmax=hit[1], residual=residual, relu=relu)
         return ops.nnconv_forward_raw(x, csr, pseudo, pm, self.root, self.bias, self.aggr, residual=residual, relu=relu)
 
+    def _is_width_64(self) -> bool:
+        """64 -> 64: the width of every reference configuration, the one the fused (re-associated) kernels are built for."""
+        return self.in_channels == ops.WIDTH and self.out_channels == ops.WIDTH
+
     def _check_width(self):
-        if self.in_channels != ops.WIDTH or self.out_channels != ops.WIDTH:
+        if not ops.width_supported(self.in_channels, self.out_channels):
             raise NotImplementedError(
-                f"the MI355X operator is built for in_channels = out_channels = {ops.WIDTH} (the "
-                f"width of every reference configuration), got {self.in_channels}->{self.out_channels}")
+                f"the MI355X operator is built for 1 <= in_channels, out_channels <= {ops.ANY_MAX_WIDTH} (fused kernels at "
+                f"{ops.WIDTH} -> {ops.WIDTH}, the per-edge-weight kernels of gpde_weconv_any.hip at every other width), "
+                f"got {self.in_channels}->{self.out_channels}")
+
+    def _propagate_any_width(self, x, edge_index, pseudo, residual=None, relu=False):
+        """propagate() of a module whose widths are not (64, 64), for EVERY kernel network (the Linear / ReLU chain included):
+        the route of `_propagate_general_nn` at run-time widths.  `weight = self.nn(pseudo)` by the caller's module where it
+        lives, rows in CSR slot order, [E, in * out] - the tensor the reference materialises (nn_conv.py:274) - then gather,
+        message, aggregate and update() (nn_conv.py:275-282) as ONE native kernel (gpde_nnconv_fwd_edgeweights_any; backward
+        gpde_nnconv_bwd_edgeweights_any, whose dL/dW_e autograd carries back into `nn`).  CPU tensors are staged to the HIP
+        device around the operator (`.to()` is differentiable) and the result returns to the caller's device.  `residual` /
+        `relu`: fused into the kernel's epilogue; callers pass them only when no gradient is needed.  aggr='max': the native
+        kernel when no gradient is needed, else PyG's chain over the native `message()` / `update()`, as at 64."""
+        self._check_width()
+        cin, cout = int(self.in_channels), int(self.out_channels)
+        if x.dim() != 2 or x.size(1) != cin:
+            raise ValueError(f"x must be [N, {cin}] (in_channels), got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise NotImplementedError(f"widths other than {ops.WIDTH} -> {ops.WIDTH}: float32 only (x is {x.dtype})")
+        needs_grad = torch.is_grad_enabled() and (x.requires_grad or pseudo.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if self.aggr == "max" and needs_grad:
+            return MessagePassing.propagate(self, edge_index.edge_index if isinstance(edge_index, ops.Csr) else edge_index, x=x, pseudo=pseudo)
+        dev = x.device if x.is_cuda else ops.staging_device()
+        if isinstance(edge_index, ops.Csr):
+            csr = edge_index
+        else:
+            csr = ops.csr_for(edge_index if edge_index.device == dev else ops.stage_const(edge_index, dev), x.size(0))
+        need = csr.n_edges * cin * cout * 4
+        free, _ = ops.device_free_bytes(dev)
+        if 2 * need > free:
+            raise RuntimeError(f"{self!r}: at widths other than {ops.WIDTH} -> {ops.WIDTH} the per-edge weights are materialised as in the reference "
+                               f"(nn_conv.py:274) - {csr.n_edges} edges x {cin} x {cout} x 4 B = {need / 2**30:.2f} GiB (twice that with "
+                               f"gradients), {free / 2**30:.2f} GiB free")
+        # rows in CSR slot order (the order the kernels address W_e in); `nn` acts row by row, batch statistics are order-free
+        pseudo_s = pseudo if bool(getattr(csr, "_perm_is_identity", False)) else pseudo.index_select(0, csr.perm.long().to(pseudo.device))
+        weight = self.nn(pseudo_s)
+        if weight.dim() != 2 or weight.size(0) != csr.n_edges or weight.size(1) != cin * cout:
+            raise ValueError(f"nn(pseudo) must be [E, {cin * cout}] = [{csr.n_edges}, in_channels * out_channels] (nn_conv.py:274), got {tuple(weight.shape)}")
+        weight = weight.float().to(dev).contiguous()
+
+        def on_dev(t):
+            if t is None or t.device == dev:
+                return t
+            return t.to(dev) if needs_grad and t.requires_grad else ops.stage_const(t, dev)
+        root, bias = on_dev(self.root), on_dev(self.bias)
+        if needs_grad:
+            out = WeConvAnyFunction.apply(x.to(dev), weight, csr, root, bias, self.aggr)
+            if residual is not None:
+                out = residual.to(dev) + out
+            if relu:
+                out = torch.relu(out)
+        else:
+            out = ops.nnconv_forward_edgeweights_any_raw(x.detach().to(dev), csr, weight.detach(), root, bias, self.aggr,
+                                                         residual=None if residual is None else residual.to(dev), relu=relu)
+        return out.to(x.device)
 
     def _propagate(self, x, edge_index, pseudo, weights, biases, root, bias, use_hidden_cache):
         """propagate() of the reference (gather, message, aggregate, update) as ONE native operator on device
@@ -350,14 +430,26 @@ class NNConv_old(MessagePassing):
         """m_e = x_j[e] . W(pseudo_e)  ([E, in] x [E, in, out] -> [E, out]).  Computed by the same native
         operator on the graph in which every edge has its own target (E nodes, edge e: e -> e, aggr='add', no
         root / bias): out[e] = x_j[e] . h_Theta(pseudo_e), exactly the reference's message."""
+        self._check_width()
         x_j = x_j.unsqueeze(-1) if x_j.dim() == 1 else x_j
         pseudo = pseudo.unsqueeze(-1) if pseudo.dim() == 1 else pseudo
         e = x_j.size(0)
         dev = x_j.device if x_j.is_cuda else ops.staging_device()
         ar = torch.arange(e, device=dev, dtype=torch.int64)
         ident = torch.stack([ar, ar])
+        if not self._is_width_64():
+            # any other width: `weight = self.nn(pseudo)` (nn_conv.py:274), then the native operator on the identity graph
+            weight = self.nn(pseudo)
+            if weight.dim() != 2 or tuple(weight.shape) != (e, self.in_channels * self.out_channels):
+                raise ValueError(f"nn(pseudo) must be [E, {self.in_channels * self.out_channels}] (nn_conv.py:274), got {tuple(weight.shape)}")
+            weight = weight.float().to(dev).contiguous()
+            csr = ops.build_csr(ident, e)
+            if torch.is_grad_enabled() and (x_j.requires_grad or weight.requires_grad):
+                out = WeConvAnyFunction.apply(x_j.float().to(dev), weight, csr, None, None, "add")
+            else:
+                out = ops.nnconv_forward_edgeweights_any_raw(x_j.detach().float().to(dev), csr, weight.detach(), None, None, "add")
+            return out.to(x_j.device)
         weights, biases, _, _ = self._params_on(dev, torch.is_grad_enabled())
-        self._check_width()
         out = NNConvFunction.apply(x_j.to(dev), ops.build_csr(ident, e), pseudo.to(dev), None, None, "add", len(weights),
                                    *weights, *biases)
         return out.to(x_j.device)
@@ -371,6 +463,23 @@ class NNConv_old(MessagePassing):
         dev = x.device if x.is_cuda else ops.staging_device()
         empty = torch.empty(2, 0, dtype=torch.int64, device=dev)
         need_grad = torch.is_grad_enabled()
+        if not self._is_width_64():
+            # any other width: x . root + bias is the any-width operator on the graph without edges
+            cin, cout = int(self.in_channels), int(self.out_channels)
+            x = x.unsqueeze(-1) if x.dim() == 1 else x
+            wants = need_grad and (x.requires_grad or any(t is not None and t.requires_grad for t in (self.root, self.bias)))
+
+            def on_dev(t):
+                if t is None or t.device == dev:
+                    return t
+                return t.to(dev) if wants and t.requires_grad else ops.stage_const(t, dev)
+            csr = ops.build_csr(empty, x.size(0))
+            no_we = torch.empty(0, cin * cout, dtype=torch.float32, device=dev)
+            if wants:
+                term = WeConvAnyFunction.apply(x.float().to(dev), no_we, csr, on_dev(self.root), on_dev(self.bias), "add")
+            else:
+                term = ops.nnconv_forward_edgeweights_any_raw(x.detach().float().to(dev), csr, no_we, on_dev(self.root), on_dev(self.bias), "add")
+            return aggr_out + term.to(aggr_out.device)
         weights, biases, root, bias = self._params_on(dev, need_grad)
         k0 = weights[0].size(1)
         if not (need_grad and (x.requires_grad or any(t is not None and t.requires_grad for t in (root, bias)))):
@@ -418,8 +527,8 @@ def nnconv_group(calls):
                                                   (torch.is_tensor(edge_attr) and edge_attr.requires_grad) or
                                                   any(p.requires_grad for p in conv.parameters()))
         if not needs_grad and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and torch.is_tensor(edge_attr) and \
-                edge_attr.dtype == torch.float32 and (residual is None or residual.device == x.device):
-            conv._check_width()
+                edge_attr.dtype == torch.float32 and (residual is None or residual.device == x.device) and conv._is_width_64():
+            # (a module of another width simply runs on its own, below)
             pseudo = edge_attr.unsqueeze(-1) if edge_attr.dim() == 1 else edge_attr
             lin = ops.mlp_linears(conv.nn)
             weights, biases = [l.weight for l in lin], [l.bias for l in lin]

@@ -1310,6 +1310,109 @@ def nnconv_backward_edgeweights_raw(x: torch.Tensor, csr: Csr, edge_weights: tor
     return gx, gwe, groot, gbias
 
 
+# ... at any width (include/gpde.h gpde_nnconv_fwd_edgeweights_any / gpde_nnconv_bwd_edgeweights_any; csrc/gpde_weconv_any.hip)
+ANY_MAX_WIDTH = _lib.GPDE_WECONV_ANY_MAX_WIDTH
+
+
+def width_supported(in_channels, out_channels) -> bool:
+    """Whether `in_channels -> out_channels` is a width the native operator runs: 64 -> 64 on every path, any other pair of
+    1 .. ANY_MAX_WIDTH (256) on the per-edge-weight kernels of gpde_weconv_any.hip."""
+    try:
+        i, o = int(in_channels), int(out_channels)
+    except (TypeError, ValueError):
+        return False
+    return i == in_channels and o == out_channels and 1 <= i <= ANY_MAX_WIDTH and 1 <= o <= ANY_MAX_WIDTH
+
+
+def _any_widths(x: torch.Tensor, csr: Csr, edge_weights: torch.Tensor, out_channels: Optional[int]):
+    """(in_channels, out_channels) of a call of the any-width operator from its tensors, shapes checked."""
+    n, e = csr.n_nodes, csr.n_edges
+    if x.dtype != torch.float32 or x.dim() != 2 or x.size(0) != n or x.size(1) < 1:
+        raise ValueError(f"x must be float32 [{n}, in_channels], got {x.dtype} {tuple(x.shape)}")
+    cin = int(x.size(1))
+    we = edge_weights
+    if we.dtype != torch.float32 or we.dim() != 2 or we.size(0) != e or we.size(1) % cin != 0 or we.size(1) == 0 or \
+            not we.is_contiguous() or we.device != x.device:
+        raise ValueError(f"edge_weights must be contiguous float32 [{e}, {cin} * out_channels] on {x.device}, got {we.dtype} {tuple(we.shape)}")
+    cout = int(we.size(1)) // cin
+    if out_channels is not None and int(out_channels) != cout:
+        raise ValueError(f"edge_weights has {we.size(1)} columns = {cin} x {cout}, not {cin} x {out_channels}")
+    if not width_supported(cin, cout):
+        raise NotImplementedError(f"in_channels {cin} -> out_channels {cout}: the native operator is built for widths 1 .. {ANY_MAX_WIDTH}")
+    return cin, cout
+
+
+def nnconv_forward_edgeweights_any_raw(x, csr: Csr, edge_weights, root, bias, aggr: str, residual=None, relu: bool = False,
+                                       out_channels: Optional[int] = None) -> torch.Tensor:
+    """gpde_nnconv_fwd_edgeweights_any: the operator given the per-edge weights [E, in * out] (CSR slot order) at any width
+    1 .. 256 - gather, message, add / mean / max, update() (+ residual [N, out], ReLU) in one launch."""
+    lib = _lib.lib()
+    _require_cuda(x, "x")
+    if aggr not in _AGGR_WE:
+        raise NotImplementedError(f"aggr={aggr!r}")
+    cin, cout = _any_widths(x, csr, edge_weights, out_channels)
+    n, e, dev = csr.n_nodes, csr.n_edges, x.device
+    x_c = x.detach().contiguous()
+    we = edge_weights.detach()
+    root_c = None if root is None else root.detach().contiguous()
+    bias_c = None if bias is None else bias.detach().contiguous()
+    if root_c is not None and (root_c.dtype != torch.float32 or tuple(root_c.shape) != (cin, cout) or root_c.device != dev):
+        raise ValueError(f"root must be float32 [{cin},{cout}] on {dev}, got {root_c.dtype} {tuple(root_c.shape)}")
+    if bias_c is not None and (bias_c.dtype != torch.float32 or tuple(bias_c.shape) != (cout,) or bias_c.device != dev):
+        raise ValueError(f"bias must be float32 [{cout}] on {dev}, got {bias_c.dtype} {tuple(bias_c.shape)}")
+    res = None
+    if residual is not None:
+        _require_cuda(residual, "residual")
+        if residual.dtype != torch.float32 or tuple(residual.shape) != (n, cout) or residual.device != dev:
+            raise ValueError(f"residual must be float32 [{n},{cout}] on {dev}, got {residual.dtype} {tuple(residual.shape)}")
+        res = residual.detach().contiguous()
+    out = torch.empty(n, cout, dtype=torch.float32, device=dev)
+    p = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        rc = lib.gpde_nnconv_fwd_edgeweights_any(x_c.data_ptr(), n, we.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(), p(root_c),
+                                                 p(bias_c), p(res), 1 if relu else 0, _AGGR_WE[aggr], cin, cout, out.data_ptr(),
+                                                 _stream_ptr(dev))
+    _lib.check(rc, "gpde_nnconv_fwd_edgeweights_any")
+    _lib.n_native_calls += 1
+    return out
+
+
+def nnconv_backward_edgeweights_any_raw(x: torch.Tensor, csr: Csr, edge_weights: torch.Tensor, root: Optional[torch.Tensor], aggr: str,
+                                        grad_out: torch.Tensor, need_root: bool = True, need_bias: bool = True):
+    """gpde_nnconv_bwd_edgeweights_any: backward of the any-width operator given the per-edge weights ('add' / 'mean').  Returns
+    (grad_x [N, in], grad_edge_weights [E, in * out], grad_root [in, out] or None, grad_bias [out] or None)."""
+    lib = _lib.lib()
+    for t, nm in ((x, "x"), (edge_weights, "edge_weights"), (grad_out, "grad_out")):
+        _require_cuda(t, nm)
+    if aggr not in _AGGR:
+        raise NotImplementedError(f"aggr={aggr!r}: the gradient of the per-edge weight operator is built for 'add' and 'mean'")
+    cin, cout = _any_widths(x, csr, edge_weights, None)
+    n, e, dev = csr.n_nodes, csr.n_edges, x.device
+    x = x.detach().contiguous()
+    grad_out = grad_out.detach().contiguous().float()
+    if tuple(grad_out.shape) != (n, cout):
+        raise ValueError(f"grad_out must be [{n},{cout}], got {tuple(grad_out.shape)}")
+    we = edge_weights.detach()
+    root_c = None if root is None else root.detach().contiguous()
+    if root_c is not None and (root_c.dtype != torch.float32 or tuple(root_c.shape) != (cin, cout)):
+        raise ValueError(f"root must be float32 [{cin},{cout}], got {root_c.dtype} {tuple(root_c.shape)}")
+    want_root = need_root and root is not None
+    gx = torch.empty(n, cin, dtype=torch.float32, device=dev)
+    gwe = torch.empty(e, cin * cout, dtype=torch.float32, device=dev)
+    groot = torch.empty(cin, cout, dtype=torch.float32, device=dev) if want_root else None
+    gbias = torch.empty(cout, dtype=torch.float32, device=dev) if need_bias else None
+    ws = _alloc_ws(int(lib.gpde_nnconv_bwd_edgeweights_any_workspace_bytes(n, e, cin, cout)), dev)
+    srp, ssl = csr.src_order
+    p = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        rc = lib.gpde_nnconv_bwd_edgeweights_any(x.data_ptr(), n, we.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(), p(srp), p(ssl),
+                                                 p(root_c), _AGGR[aggr], cin, cout, grad_out.data_ptr(), gx.data_ptr(), gwe.data_ptr(),
+                                                 p(groot), p(gbias), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+    _lib.check(rc, "gpde_nnconv_bwd_edgeweights_any")
+    _lib.n_native_calls += 1
+    return gx, gwe, groot, gbias
+
+
 def edge_weights_backward_raw(grad_we: torch.Tensor, hidden: torch.Tensor, dims: Sequence[int], w_last: torch.Tensor,
                               need_b: bool = True):
     """gpde_edge_weights_bwd: (grad_hidden [E, K2P] already masked by hidden > 0, grad_w_last, grad_b_last or None) from the

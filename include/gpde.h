@@ -439,6 +439,32 @@ GPDE_API int gpde_edge_weights_bwd(const float* grad_edge_weights, const float* 
                           const int32_t* dims, const float* w_last, float* grad_hidden, float* grad_w_last,
                           float* grad_b_last, void* ws, size_t ws_bytes, void* stream);
 
+/* The operator given the per-edge weights at ANY width (gpde_weconv_any.hip): the reference's classes take any in_channels and
+ * out_channels (nn_conv.py:234-241; the message is `nn(pseudo).view(-1, in_channels, out_channels)`, nn_conv.py:274), the calls
+ * above are built for 64 -> 64.  Same mathematics, run-time widths 1 <= in_channels, out_channels <= GPDE_WECONV_ANY_MAX_WIDTH:
+ *   x [N][in], edge_weights [E][in * out] (row-major [in][out] per edge, rows in CSR slot order), root [in][out] or NULL,
+ *   bias [out] or NULL, residual [N][out] or NULL (must not alias out), out [N][out]; aggr add / mean / max in the forward
+ *   (mean divides by clamp(count, 1); a node without in-edges aggregates to 0, also for max), add / mean in the backward
+ *   (GPDE_AGGR_MAX: GPDE_EUNSUPPORTED - its gradient is composed by the caller).
+ *   Backward outputs grad_x [N][in], grad_edge_weights [E][in * out] (required when n_edges > 0), grad_root [in][out],
+ *   grad_bias [out]; NULL skips grad_x / grad_root / grad_bias.  grad_x is summed over each source's out-edges in ascending slot
+ *   order when src_rowptr / src_slots (gpde_csr_source_order) are given, else by fp32 atomics.
+ * Plain fp32 fmaf in a summation order fixed by the shapes: two calls give the same bits.  Widths outside the range:
+ * GPDE_EUNSUPPORTED; zero nodes / zero edges are valid calls.  These entry points are additions: GPDE_VERSION is unchanged, and
+ * a binding generated from this header fails to load a library that lacks them (it resolves every declared symbol). */
+#define GPDE_WECONV_ANY_MAX_WIDTH 256
+GPDE_API int gpde_nnconv_fwd_edgeweights_any(const float* x, int64_t n_nodes, const float* edge_weights, int64_t n_edges,
+                                    const int32_t* rowptr, const int32_t* src, const float* root, const float* bias,
+                                    const float* residual, int relu, int aggr, int in_channels, int out_channels,
+                                    float* out, void* stream);
+GPDE_API size_t gpde_nnconv_bwd_edgeweights_any_workspace_bytes(int64_t n_nodes, int64_t n_edges, int in_channels,
+                                                       int out_channels);
+GPDE_API int gpde_nnconv_bwd_edgeweights_any(const float* x, int64_t n_nodes, const float* edge_weights, int64_t n_edges,
+                                    const int32_t* rowptr, const int32_t* src, const int32_t* src_rowptr,
+                                    const int32_t* src_slots, const float* root, int aggr, int in_channels,
+                                    int out_channels, const float* grad_out, float* grad_x, float* grad_edge_weights,
+                                    float* grad_root, float* grad_bias, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Edge attributes on the fly (opt-in): the `node_attr` argument (GpdeNodeAttr, declared at the top).
  * The reference materialises edge_attr[e] = [pos_src(2), pos_dst(2), a_src, a_dst] from node data
