@@ -20,7 +20,9 @@
 //     es           ES = 64 / LC / R edge slots: at 8 x 8 an edge is 256 B and 8 edges share the wave, at 128 x 128 (64 KiB)
 //                      the whole wave streams one edge.
 // The forward gathers the x_j rows of a batch of B * ES in-edges into LDS (<= 4 KiB), then issues the W_e rows of 4 edges before
-// the first FMA (4 KiB in flight per wave, unrolled over two rows; at <= 64 VGPRs the SIMD holds 8 such waves).
+// the first FMA (4 KiB in flight per wave, unrolled over two rows; at <= 64 VGPRs the SIMD holds 8 such waves).  The products of
+// a batch are summed on their own and the batch's partial added to the node's running sum (a hub row of 8,192 in-edges of 256
+// rows is then 2,048 additions deep, not 2 M: DESIGN.md §3 records the measured error before and after).
 // Nodes of 2-3 in-edges cost one small wave each; a few hundred in-edges per node are one wave's sequential stream, and the
 // machine is filled by the other nodes' waves (DESIGN.md §3 records the measured rates).
 // All offsets into W_e are size_t: E * cin * cout passes 2^31 at 33 k edges of 256 x 256.
@@ -138,6 +140,9 @@ __global__ __launch_bounds__(64) void gpde_weconv_any_kernel(AnyFwdArgs a) {
             __syncthreads();
             if (lane_on) {
                 const float* __restrict__ wb = a.we + (size_t)eb * mat;
+                // two-level sum: the pass's products into `part`, `part` into the running sum - a row of thousands of in-edges
+                // adds one partial per pass instead of in_degree * in_channels / R products to one fp32 accumulator
+                float part[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 2
                 for (int c = r; c < cin; c += R) {
                     for (int b0 = 0; b0 < B; b0 += 4) {          // the row of 4 edges in flight before the first FMA
@@ -152,9 +157,11 @@ __global__ __launch_bounds__(64) void gpde_weconv_any_kernel(AnyFwdArgs a) {
 #pragma unroll
                         for (int u = 0; u < 4; ++u)
 #pragma unroll
-                            for (int k = 0; k < 4; ++k) acc[k] = fmaf(xv[u], v[u][k], acc[k]);
+                            for (int k = 0; k < 4; ++k) part[k] = fmaf(xv[u], v[u][k], part[k]);
                     }
                 }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[k] += part[k];
             }
         }
     }
@@ -378,6 +385,18 @@ extern "C" size_t gpde_nnconv_bwd_edgeweights_any_workspace_bytes(int64_t n_node
     if (n_nodes < 0 || n_edges < 0 || in_channels < 1 || out_channels < 1 || in_channels > ANY_MAXW || out_channels > ANY_MAXW) return 0;
     return any_al((size_t)(n_edges > 0 ? n_edges : 1) * in_channels * 4) +                                   // dxe [E][cin]
            any_al((size_t)ANY_MAX_STRIPS * ((size_t)in_channels * out_channels + out_channels) * 4) + 1024;  // droot / dbias partials
+}
+
+extern "C" int gpde_nnconv_edgeweights_any_plan(int in_channels, int out_channels, int vec4, int aggr, int32_t* out) {
+    if (!out || (aggr != GPDE_AGGR_ADD && aggr != GPDE_AGGR_MEAN && aggr != GPDE_AGGR_MAX)) {
+        gpde_set_error("gpde_nnconv_edgeweights_any_plan: null out or unknown aggr");
+        return GPDE_EINVAL;
+    }
+    int rc = any_check_widths("gpde_nnconv_edgeweights_any_plan", in_channels, out_channels);
+    if (rc != GPDE_OK) return rc;
+    const AnyPlan p = any_plan(in_channels, out_channels, vec4 && out_channels % 4 == 0, aggr == GPDE_AGGR_MAX);
+    out[0] = p.V; out[1] = p.LC; out[2] = p.R; out[3] = p.ES; out[4] = p.B; out[5] = p.LC * p.R * p.ES;
+    return GPDE_OK;
 }
 
 extern "C" int gpde_nnconv_bwd_edgeweights_any(const float* x, int64_t n_nodes, const float* edge_weights, int64_t n_edges,

@@ -1324,6 +1324,18 @@ def width_supported(in_channels, out_channels) -> bool:
     return i == in_channels and o == out_channels and 1 <= i <= ANY_MAX_WIDTH and 1 <= o <= ANY_MAX_WIDTH
 
 
+def any_width_plan(in_channels: int, out_channels: int, aligned: bool = True, aggr: str = "add") -> dict:
+    """gpde_nnconv_edgeweights_any_plan: the lane tiling the any-width kernels run at these widths - V (floats per column access),
+    LC (column lanes), R (row lanes), ES (edge slots per wave), B (x_j batches per pass: a pass is B * ES in-edges) and the lanes
+    in use.  `aligned`: every buffer of the call is 16-byte aligned (else V = 1 at every width).  Host arithmetic, no device."""
+    if aggr not in _AGGR_WE:
+        raise NotImplementedError(f"aggr={aggr!r}")
+    out = (ctypes.c_int32 * 6)()
+    _lib.check(_lib.lib().gpde_nnconv_edgeweights_any_plan(int(in_channels), int(out_channels), 1 if aligned else 0, _AGGR_WE[aggr], out),
+               "gpde_nnconv_edgeweights_any_plan")
+    return dict(zip(("V", "LC", "R", "ES", "B", "lanes"), (int(v) for v in out)))
+
+
 def _any_widths(x: torch.Tensor, csr: Csr, edge_weights: torch.Tensor, out_channels: Optional[int]):
     """(in_channels, out_channels) of a call of the any-width operator from its tensors, shapes checked."""
     n, e = csr.n_nodes, csr.n_edges

@@ -459,6 +459,13 @@ GPDE_API int gpde_nnconv_fwd_edgeweights_any(const float* x, int64_t n_nodes, co
                                     float* out, void* stream);
 GPDE_API size_t gpde_nnconv_bwd_edgeweights_any_workspace_bytes(int64_t n_nodes, int64_t n_edges, int in_channels,
                                                        int out_channels);
+/* Host only: the lane tiling gpde_weconv_any.hip runs at these widths - out[0..5] = V (floats per column access: 4 or 1),
+ * LC (column lanes), R (row lanes), ES (edge slots per wave), B (x_j batches gathered into LDS per pass; a pass is B * ES
+ * in-edges), LC * R * ES (lanes of the 64 in use) - from the function the two launchers call.  vec4 != 0: out_channels % 4 == 0 and
+ * every buffer 16-byte aligned (what the launchers test; at out_channels % 4 != 0 the answer is the V = 1 tiling either way);
+ * aggr GPDE_AGGR_MAX: the forward's tiling for 'max' (R = 1).  GPDE_EUNSUPPORTED outside the widths, GPDE_EINVAL for a NULL out or
+ * an unknown aggr. */
+GPDE_API int gpde_nnconv_edgeweights_any_plan(int in_channels, int out_channels, int vec4, int aggr, int32_t* out);
 GPDE_API int gpde_nnconv_bwd_edgeweights_any(const float* x, int64_t n_nodes, const float* edge_weights, int64_t n_edges,
                                     const int32_t* rowptr, const int32_t* src, const int32_t* src_rowptr,
                                     const int32_t* src_slots, const float* root, int aggr, int in_channels,

@@ -16,10 +16,12 @@ import graph_pde_amd as gp
 from graph_pde_amd import _lib, ops
 from oracle.nnconv_oracle import nnconv_forward, nnconv_grads, rel_l2
 from tests.conftest import GOLDEN, REPO, load_golden
+from tests.helpers import any_tilings as at
 from tests.test_oracle_golden import load_golden_grads
 
 RECT_CASES = {"nnconv_rect_24x40_mean": (24, 40), "nnconv_rect_40x24_add": (40, 24), "nnconv_rect_1x8_mean": (1, 8)}
-ANY_ENTRY_POINTS = ["gpde_nnconv_fwd_edgeweights_any", "gpde_nnconv_bwd_edgeweights_any_workspace_bytes", "gpde_nnconv_bwd_edgeweights_any"]
+ANY_ENTRY_POINTS = ["gpde_nnconv_fwd_edgeweights_any", "gpde_nnconv_bwd_edgeweights_any_workspace_bytes", "gpde_nnconv_bwd_edgeweights_any",
+                    "gpde_nnconv_edgeweights_any_plan"]
 
 
 @pytest.mark.parametrize("name", sorted(RECT_CASES))
@@ -159,3 +161,107 @@ def test_a_rectangular_lin_weight_state_dict_loads_transposed():
     conv2 = gp.NNConv_old(24, 40, torch.nn.Linear(3, 960), aggr="add")
     conv2.load_state_dict(conv.state_dict())
     assert torch.equal(conv2.root.detach(), conv.root.detach())
+
+
+# ---- the lane tiling of csrc/gpde_weconv_any.hip, through its host query (ops.any_width_plan) -----------------------------------
+ANY_XS = 1024        # floats of LDS per wave (gpde_weconv_any.hip)
+
+
+def test_plan_query_is_declared_with_its_signature():
+    ret, args = _lib.header_prototypes()["gpde_nnconv_edgeweights_any_plan"]
+    assert ret == "int" and args == ["int", "int", "int", "int", "int32_t*"]
+
+
+@pytest.mark.parametrize("aggr", ["add", "mean", "max"])
+@pytest.mark.parametrize("aligned", [True, False])
+def test_every_tiling_fits_the_wave_the_columns_and_the_lds(aligned, aggr):
+    """All 256 x 256 widths: the lanes in use fit the wave, 4 column steps of LC lanes cover a row, LC is a power of two (the
+    backward's xor shuffles), a pass of x_j rows fits the LDS array, 'max' keeps whole columns in a lane."""
+    for cin in range(1, 257):
+        for cout in range(1, 257):
+            p = ops.any_width_plan(cin, cout, aligned=aligned, aggr=aggr)
+            what = (cin, cout, aligned, aggr, p)
+            assert p["V"] == (4 if aligned and cout % 4 == 0 else 1), what
+            assert min(p.values()) >= 1 and p["lanes"] == p["LC"] * p["R"] * p["ES"] <= 64, what
+            assert 4 * p["LC"] >= -(-cout // p["V"]) and (p["V"] == 1 or p["LC"] >= cout // 4), what   # V = 4: one access per lane
+            assert p["LC"] & (p["LC"] - 1) == 0, what
+            assert p["R"] <= cin, what
+            if aggr == "max":
+                assert p["R"] == 1, what
+            else:
+                assert p["B"] in (4, 8) and p["B"] * p["ES"] * cin <= ANY_XS, what
+    assert ops.any_width_plan(24, 40, aggr="mean") == ops.any_width_plan(24, 40, aggr="add")
+
+
+def test_plan_query_rejects_what_the_launchers_reject():
+    l = _lib.lib()
+    out = (np.zeros(6, dtype=np.int32)).ctypes.data
+    for cin, cout in ((0, 8), (8, 0), (257, 8), (8, 257), (-1, 8)):
+        assert l.gpde_nnconv_edgeweights_any_plan(cin, cout, 1, _lib.GPDE_AGGR_ADD, out) == -2                      # GPDE_EUNSUPPORTED
+        assert "256" in l.gpde_last_error().decode()
+        with pytest.raises(NotImplementedError, match="256"):
+            ops.any_width_plan(cin, cout)
+    assert l.gpde_nnconv_edgeweights_any_plan(8, 8, 1, 7, out) == -1 and l.gpde_nnconv_edgeweights_any_plan(8, 8, 1, 0, None) == -1
+    with pytest.raises(NotImplementedError):
+        ops.any_width_plan(8, 8, aggr="min")
+    assert l.gpde_nnconv_edgeweights_any_plan(256, 256, 1, _lib.GPDE_AGGR_ADD, out) == _lib.GPDE_OK
+
+
+def test_the_tiling_classes_number_128():
+    """What tests/test_gpu_width_tilings.py parametrises over.  Another count: the classifier (tests/helpers/any_tilings.py) or
+    the plan changed - either way the GPU tier's cases have to be looked at again."""
+    cl = at.classes("add")
+    assert len(cl) == at.N_CLASSES == 128, len(cl)
+    assert sum(len(v) for v in cl.values()) == 256 * 256
+    assert at.classes("mean") == cl
+    reps = at.representatives()
+    assert len({nm for nm, *_ in reps}) == 128                                       # the names tell the classes apart
+    for nm, k, cin, cout in reps:
+        assert at.tiling_class(cin, cout, ops.any_width_plan(cin, cout)) == k
+    # the `k >= 1` arm of row_load<1> / row_store<1>: a class of its own for every number of column steps
+    assert {k[5] for k in cl if k[0] == 1} == {1, 2, 3, 4} and {k[5] for k in cl if k[0] == 4} == {1}
+    assert len(at.max_representatives()) == len({(p["V"], p["LC"], p["ES"]) for p in (
+        ops.any_width_plan(1, co, aggr="max") for co in range(1, 257))})
+
+
+def test_ladder_graph_has_the_rows_it_promises():
+    g = torch.Generator().manual_seed(1)
+    for cin, cout in ((1, 1), (3, 5), (64, 255), (256, 132)):
+        plan = ops.any_width_plan(cin, cout)
+        ei, n, by_deg = at.ladder_graph(plan, g)
+        deg = torch.bincount(ei[1], minlength=n)
+        es, eb = plan["ES"], plan["B"] * plan["ES"]
+        assert {0, 1, es, es + 1, eb - 1, eb, eb + 1, 2 * eb + 3, 4 * eb + es + 1} <= set(by_deg)
+        for d, nodes in by_deg.items():
+            assert all(int(deg[i]) == d for i in nodes)
+        out_deg = torch.bincount(ei[0], minlength=n)
+        assert int(out_deg[0]) == 0 and int(out_deg[1]) >= ei.shape[1] // 8 and int(deg[-3:].sum() + out_deg[-3:].sum()) == 0
+        assert int((ei[0] == ei[1]).sum()) >= 1 and ei.shape[1] - torch.unique(ei, dim=1).shape[1] >= 1
+        assert not bool((ei[1][1:] >= ei[1][:-1]).all())                              # unsorted
+        assert ei.shape[1] <= 24 * eb + 64
+
+
+@pytest.mark.parametrize("cin,cout", [(1, 1), (64, 255), (256, 132)])
+def test_fp32_reference_chain_stays_far_inside_the_row_bars_on_the_ladder(cin, cout):
+    """The row-by-row bars of tests/test_gpu_width_tilings.py (forward 1e-5, gradients 2e-5 of max(row norm, rms row norm)) leave
+    room for correct fp32 arithmetic: the reference's own fp32 chain (oracle.nnconv_forward, float32) and fp32 autograd of the
+    same statement, against float64 on the ladder graph, stay below a fifth of them."""
+    g = torch.Generator().manual_seed(cin * 1000 + cout)
+    plan = ops.any_width_plan(cin, cout)
+    ei, n, _ = at.ladder_graph(plan, g)
+    e = ei.shape[1]
+    ea = torch.randn(e, 4, generator=g)
+    wl, bl = torch.randn(cin * cout, 4, generator=g) / (2 * cin ** 0.5), torch.randn(cin * cout, generator=g) / (2 * cin ** 0.5)
+    x, _, root, bias, _, gout = at.draw_inputs(n, e, cin, cout, g)
+    for aggr in ("add", "mean"):
+        w = torch.nn.functional.linear(ea, wl, bl)                                   # the fp32 W_e both sides see
+        y32 = nnconv_forward(x, ei, ea, [wl], [bl], root, bias, aggr=aggr, dtype=torch.float32)
+        leaves64 = [t.double().requires_grad_(True) for t in (x, w, root, bias)]
+        ref = at.reference64(leaves64[0], ei, leaves64[1], leaves64[2], leaves64[3], aggr)
+        (ref * gout.double()).sum().backward()
+        leaves32 = [t.clone().requires_grad_(True) for t in (x, w, root, bias)]
+        (at.reference64(leaves32[0], ei, leaves32[1], leaves32[2], leaves32[3], aggr) * gout).sum().backward()
+        figs = {"out": at.worst_row(y32, ref), "dW_e": at.worst_row(leaves32[1].grad, leaves64[1].grad),
+                "dx": at.worst_row(leaves32[0].grad, leaves64[0].grad)}
+        print(f"[ladder fp32 chain] {cin}->{cout} {aggr}: " + " ".join(f"{k}={v:.2e}" for k, v in figs.items()))
+        assert figs["out"] <= 2e-6 and figs["dW_e"] <= 4e-6 and figs["dx"] <= 4e-6, figs
