@@ -409,3 +409,29 @@ class WeConvAnyFunction(torch.autograd.Function):
         gx, gwe, groot, gbias = ops.nnconv_backward_edgeweights_any_raw(x, ctx.csr, we, root, ctx.aggr, grad_out,
                                                                         need_root=root is not None, need_bias=ctx.has_bias)
         return gx, gwe, None, groot, gbias if ctx.has_bias else None, None
+
+
+class HiddenAnyFunction(torch.autograd.Function):
+    """The RE-ASSOCIATED operator at any width 1 .. 256 (gpde_nnconv_fwd_hidden_any: aggregation of x_j (x) h_e per node, the last
+    Linear per node, update()), differentiable in x, the last hidden activations H [E, K], the last Linear (w_last [in * out, K],
+    b_last [in * out]), root and bias (gpde_nnconv_bwd_hidden_any).  H is the caller's own tensor - relu(L_{n-1}(...)) evaluated by
+    torch, rows in CSR slot order -, so dL/dH flows on through the caller's earlier layers by ordinary autograd; [E, in * out] is
+    never formed."""
+
+    @staticmethod
+    def forward(ctx, x, hidden, w_last, b_last, csr, root, bias, aggr):
+        out = ops.nnconv_forward_hidden_any_raw(x.detach(), csr, hidden.detach(), w_last, b_last, root, bias, aggr)
+        ctx.csr, ctx.aggr, ctx.has_bias = csr, aggr, bias is not None
+        ctx.has_b_last, ctx.has_root = b_last is not None, root is not None
+        ctx.save_for_backward(x, hidden, w_last, b_last, root)
+        return out
+
+    @staticmethod
+    @once_differentiable        # the native backward is not itself differentiable: create_graph=True raises
+    def backward(ctx, grad_out):
+        x, hidden, w_last, b_last, root = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gx, gh, gwl, gbl, groot, gbias = ops.nnconv_backward_hidden_any_raw(
+            x, ctx.csr, hidden, w_last, b_last, root, ctx.aggr, grad_out, need_x=need[0], need_w_last=need[2],
+            need_b_last=ctx.has_b_last and need[3], need_root=ctx.has_root and need[5], need_bias=ctx.has_bias and need[6])
+        return gx, (gh if need[1] else None), gwl, gbl, None, groot, gbias, None

@@ -382,3 +382,13 @@ int gpde_launch_tile_list(const int32_t* rowptr, int na, int nn, int e0, int32_t
 // split tile image of a row-major [n][k] matrix (ld = k): the W2 layout of gpde_mlp_pack for any operand
 int gpde_pack_split_nk(const float* Wnk, int n, int k, int NP, int KP, void* out, float* ucol, hipStream_t stream);
 int gpde_num_cus();
+
+// Node-side halves of the any-width backward (gpde_weconv_any.hip), shared with the re-associated form (gpde_reassoc_any.hip):
+//   dx finish    grad_x[j][c] = (ordered: sum over j's out-edges, ascending CSR slot, of dxe[slot][c]; else what grad_x holds)
+//                               + sum_o root[c][o] g_j[o]                 (root nullable)
+//   node grads   droot = X^T g, dbias = colsum g (either nullable) through `part`, gpde_any_node_grads_ws_bytes() bytes
+size_t gpde_any_node_grads_ws_bytes(int cin, int cout);
+int gpde_launch_any_dx_finish(const float* dxe, const int32_t* src_rowptr, const int32_t* src_slots, const float* root, const float* g,
+                              float* dx, int64_t n_nodes, int cin, int cout, int ordered, hipStream_t stream);
+int gpde_launch_any_node_grads(const float* x, const float* g, float* part, int64_t n_nodes, int cin, int cout, float* droot,
+                               float* dbias, hipStream_t stream);

@@ -349,6 +349,34 @@ int any_check_widths(const char* who, int cin, int cout) {
 
 }  // namespace
 
+size_t gpde_any_node_grads_ws_bytes(int cin, int cout) {
+    return any_al((size_t)ANY_MAX_STRIPS * ((size_t)cin * cout + cout) * 4);
+}
+
+int gpde_launch_any_dx_finish(const float* dxe, const int32_t* src_rowptr, const int32_t* src_slots, const float* root, const float* g,
+                              float* dx, int64_t n_nodes, int cin, int cout, int ordered, hipStream_t st) {
+    const size_t n = (size_t)n_nodes * cin;
+    hipLaunchKernelGGL(k_any_dx_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dxe, src_rowptr, src_slots, root, g, dx,
+                       n_nodes, cin, cout, ordered);
+    GP_LAUNCH_CHECK("k_any_dx_finish");
+    return GPDE_OK;
+}
+
+int gpde_launch_any_node_grads(const float* x, const float* g, float* part, int64_t n_nodes, int cin, int cout, float* droot,
+                               float* dbias, hipStream_t st) {
+    const int nrec = cin * cout + cout;
+    int64_t nstrips = (n_nodes + 63) / 64;
+    if (nstrips > ANY_MAX_STRIPS) nstrips = ANY_MAX_STRIPS;
+    const int64_t strip = (n_nodes + nstrips - 1) / nstrips;
+    nstrips = (n_nodes + strip - 1) / strip;
+    const unsigned gx = (unsigned)((nrec + 255) / 256);
+    hipLaunchKernelGGL(k_any_node_grads, dim3(gx, (unsigned)nstrips), dim3(256), 0, st, x, g, part, n_nodes, strip, cin, cout,
+                       droot ? 1 : 0, dbias ? 1 : 0);
+    hipLaunchKernelGGL(k_any_node_grads_reduce, dim3(gx), dim3(256), 0, st, part, (int)nstrips, cin, cout, droot, dbias);
+    GP_LAUNCH_CHECK("k_any_node_grads");
+    return GPDE_OK;
+}
+
 extern "C" int gpde_nnconv_fwd_edgeweights_any(const float* x, int64_t n_nodes, const float* edge_weights, int64_t n_edges,
                                                const int32_t* rowptr, const int32_t* src, const float* root, const float* bias,
                                                const float* residual, int relu, int aggr, int in_channels, int out_channels,
@@ -384,7 +412,7 @@ extern "C" int gpde_nnconv_fwd_edgeweights_any(const float* x, int64_t n_nodes, 
 extern "C" size_t gpde_nnconv_bwd_edgeweights_any_workspace_bytes(int64_t n_nodes, int64_t n_edges, int in_channels, int out_channels) {
     if (n_nodes < 0 || n_edges < 0 || in_channels < 1 || out_channels < 1 || in_channels > ANY_MAXW || out_channels > ANY_MAXW) return 0;
     return any_al((size_t)(n_edges > 0 ? n_edges : 1) * in_channels * 4) +                                   // dxe [E][cin]
-           any_al((size_t)ANY_MAX_STRIPS * ((size_t)in_channels * out_channels + out_channels) * 4) + 1024;  // droot / dbias partials
+           gpde_any_node_grads_ws_bytes(in_channels, out_channels) + 1024;                                   // droot / dbias partials
 }
 
 extern "C" int gpde_nnconv_edgeweights_any_plan(int in_channels, int out_channels, int vec4, int aggr, int32_t* out) {
@@ -442,23 +470,13 @@ extern "C" int gpde_nnconv_bwd_edgeweights_any(const float* x, int64_t n_nodes, 
         GP_LAUNCH_CHECK("gpde_weconv_any_bwd_kernel");
     }
     if (grad_x) {
-        const size_t n = (size_t)n_nodes * cin;
-        if (n_edges == 0) GP_HIP_CHECK(gpde_zero_async(grad_x, n * 4, st));      // no edge: the root term alone, added to 0
-        hipLaunchKernelGGL(k_any_dx_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dxe, src_rowptr, src_slots, root, grad_out,
-                           grad_x, n_nodes, cin, cout, (ordered && n_edges > 0) ? 1 : 0);
-        GP_LAUNCH_CHECK("k_any_dx_finish");
+        if (n_edges == 0) GP_HIP_CHECK(gpde_zero_async(grad_x, (size_t)n_nodes * cin * 4, st));      // no edge: the root term alone, added to 0
+        rc = gpde_launch_any_dx_finish(dxe, src_rowptr, src_slots, root, grad_out, grad_x, n_nodes, cin, cout, (ordered && n_edges > 0) ? 1 : 0, st);
+        if (rc != GPDE_OK) return rc;
     }
     if (grad_root || grad_bias) {
-        const int nrec = cin * cout + cout;
-        int64_t nstrips = (n_nodes + 63) / 64;
-        if (nstrips > ANY_MAX_STRIPS) nstrips = ANY_MAX_STRIPS;
-        const int64_t strip = (n_nodes + nstrips - 1) / nstrips;
-        nstrips = (n_nodes + strip - 1) / strip;
-        const unsigned gx = (unsigned)((nrec + 255) / 256);
-        hipLaunchKernelGGL(k_any_node_grads, dim3(gx, (unsigned)nstrips), dim3(256), 0, st, x, grad_out, part, n_nodes, strip, cin, cout,
-                           grad_root ? 1 : 0, grad_bias ? 1 : 0);
-        hipLaunchKernelGGL(k_any_node_grads_reduce, dim3(gx), dim3(256), 0, st, part, (int)nstrips, cin, cout, grad_root, grad_bias);
-        GP_LAUNCH_CHECK("k_any_node_grads");
+        rc = gpde_launch_any_node_grads(x, grad_out, part, n_nodes, cin, cout, grad_root, grad_bias, st);
+        if (rc != GPDE_OK) return rc;
     }
     return GPDE_OK;
 }

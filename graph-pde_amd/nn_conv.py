@@ -23,7 +23,8 @@ from torch.nn import Parameter
 
 from . import hidden_cache, ops
 from . import autograd as _ag
-from .autograd import NNConvDeferredFunction, NNConvFunction, NNConvHiddenFunction, SharedParamFunction, WeConvAnyFunction, WeConvFunction
+from .autograd import (HiddenAnyFunction, NNConvDeferredFunction, NNConvFunction, NNConvHiddenFunction, SharedParamFunction, WeConvAnyFunction,
+                       WeConvFunction)
 from .message_passing import MessagePassing
 
 
@@ -270,7 +271,9 @@ class NNConv_old(MessagePassing):
         gpde_nnconv_bwd_edgeweights_any, whose dL/dW_e autograd carries back into `nn`).  CPU tensors are staged to the HIP
         device around the operator (`.to()` is differentiable) and the result returns to the caller's device.  `residual` /
         `relu`: fused into the kernel's epilogue; callers pass them only when no gradient is needed.  aggr='max': the native
-        kernel when no gradient is needed, else PyG's chain over the native `message()` / `update()`, as at 64."""
+        kernel when no gradient is needed, else PyG's chain over the native `message()` / `update()`, as at 64.
+        A Linear / ReLU chain under add / mean whose per-edge weights do not fit (GPDE_ANY_REASSOC=auto), or every such call (=on),
+        takes `_propagate_any_reassociated` instead (ops.any_width_route states the rule)."""
         self._check_width()
         cin, cout = int(self.in_channels), int(self.out_channels)
         if x.dim() != 2 or x.size(1) != cin:
@@ -287,10 +290,22 @@ class NNConv_old(MessagePassing):
             csr = ops.csr_for(edge_index if edge_index.device == dev else ops.stage_const(edge_index, dev), x.size(0))
         need = csr.n_edges * cin * cout * 4
         free, _ = ops.device_free_bytes(dev)
-        if 2 * need > free:
+        # the route (ops.any_width_route; GPDE_ANY_REASSOC = auto | on | off): a call whose per-edge weights fit runs on them exactly
+        # as before; a Linear / ReLU chain under add / mean that does not fit (auto), or every such call (on), re-associates the
+        # last Linear and never forms [E, in * out]
+        lin = ops.mlp_linears(self.nn) if self._nn_is_linear_relu_chain() else None
+        chain = lin is not None and lin[-1].out_features == cin * cout
+        route = ops.any_width_route(csr.n_nodes, csr.n_edges, cin, cout, lin[-1].in_features if chain else None, self.aggr, chain, free)
+        if route["route"] == "reassociated":
+            return self._propagate_any_reassociated(x, csr, pseudo, lin, dev, needs_grad, residual, relu)
+        if route["route"] == "refused":
+            other = ""
+            if route["eligible"] and ops.ANY_REASSOC != "off":
+                other = (f"; re-associated (GPDE_ANY_REASSOC={ops.ANY_REASSOC}): hidden activations and one node block of Z' = "
+                         f"{route['bytes_reassociated'] / 2**30:.2f} GiB (twice that with gradients)")
             raise RuntimeError(f"{self!r}: at widths other than {ops.WIDTH} -> {ops.WIDTH} the per-edge weights are materialised as in the reference "
                                f"(nn_conv.py:274) - {csr.n_edges} edges x {cin} x {cout} x 4 B = {need / 2**30:.2f} GiB (twice that with "
-                               f"gradients), {free / 2**30:.2f} GiB free")
+                               f"gradients), {free / 2**30:.2f} GiB free{other}")
         # rows in CSR slot order (the order the kernels address W_e in); `nn` acts row by row, batch statistics are order-free
         pseudo_s = pseudo if bool(getattr(csr, "_perm_is_identity", False)) else pseudo.index_select(0, csr.perm.long().to(pseudo.device))
         weight = self.nn(pseudo_s)
@@ -312,6 +327,35 @@ class NNConv_old(MessagePassing):
         else:
             out = ops.nnconv_forward_edgeweights_any_raw(x.detach().to(dev), csr, weight.detach(), root, bias, self.aggr,
                                                          residual=None if residual is None else residual.to(dev), relu=relu)
+        return out.to(x.device)
+
+    def _propagate_any_reassociated(self, x, csr, pseudo, lin, dev, needs_grad, residual, relu):
+        """The re-associated route of `_propagate_any_width` (a Linear / ReLU chain, add / mean): H = relu(L_{n-1}(... pseudo)) by
+        torch where the module lives, rows in CSR slot order, [E, K] - staged like the per-edge weights of the other route - then
+        aggregation, the LAST Linear per node and update() as ONE native call (gpde_nnconv_fwd_hidden_any; backward
+        gpde_nnconv_bwd_hidden_any, whose dL/dH autograd carries back into the earlier layers).  `residual` / `relu` are torch
+        ops after the call: the fused epilogue is a property of the materialised route."""
+        pseudo_s = pseudo if bool(getattr(csr, "_perm_is_identity", False)) else pseudo.index_select(0, csr.perm.long().to(pseudo.device))
+        h = pseudo_s
+        for l in lin[:-1]:
+            h = torch.relu(torch.nn.functional.linear(h, l.weight, l.bias))
+        hidden = h.float().to(dev).contiguous()
+
+        def on_dev(t):
+            if t is None or t.device == dev:
+                return t
+            return t.to(dev) if needs_grad and t.requires_grad else ops.stage_const(t, dev)
+        # (.float(): a float64 kernel network runs with float32 x on the other route too, through `weight.float()`)
+        w_last, b_last = on_dev(lin[-1].weight).float(), None if lin[-1].bias is None else on_dev(lin[-1].bias).float()
+        root, bias = on_dev(self.root), on_dev(self.bias)
+        if needs_grad:
+            out = HiddenAnyFunction.apply(x.to(dev), hidden, w_last, b_last, csr, root, bias, self.aggr)
+        else:
+            out = ops.nnconv_forward_hidden_any_raw(x.detach().to(dev), csr, hidden.detach(), w_last, b_last, root, bias, self.aggr)
+        if residual is not None:
+            out = residual.to(dev) + out
+        if relu:
+            out = torch.relu(out)
         return out.to(x.device)
 
     def _propagate(self, x, edge_index, pseudo, weights, biases, root, bias, use_hidden_cache):

@@ -1425,6 +1425,157 @@ def nnconv_backward_edgeweights_any_raw(x: torch.Tensor, csr: Csr, edge_weights:
     return gx, gwe, groot, gbias
 
 
+# ... re-associated at any width (include/gpde.h gpde_nnconv_fwd_hidden_any / gpde_nnconv_bwd_hidden_any; csrc/gpde_reassoc_any.hip):
+# the last hidden activations [E, K] instead of the per-edge weights [E, in * out]
+ANY_MAX_HIDDEN = _lib.GPDE_REASSOC_ANY_MAX_HIDDEN
+ANY_REASSOC = os.environ.get("GPDE_ANY_REASSOC", "auto")      # auto | on | off: which any-width calls take the re-associated route
+_ANY_PREF_Z_BYTES = 512 << 20        # Z' of the library's preferred node block (RA_PREF_Z_BYTES of gpde_reassoc_any.hip; tests/test_reassoc_host.py
+#                                      holds the two together through the workspace query)
+ANY_WS_FRACTION = 0.5                # a call of the re-associated route takes at most this share of the free memory as workspace
+
+
+def _hidden_any_ws_bytes(query, n: int, e: int, cin: int, cout: int, k: int, dev) -> int:
+    """Workspace of a re-associated any-width call: the library's preferred size when ANY_WS_FRACTION of the free memory holds it,
+    else that share (more node blocks of fewer nodes), never less than one node's worth.  `auto` takes this route only when memory
+    is short, and the backward's workspace holds more than any_width_route's `bytes_reassociated` counts: P and dP (the last Linear,
+    in * KP * out floats each) and the per-edge dx rows [E, in] next to Z' and dZ' of the node block."""
+    pref, one = int(query(n, e, cin, cout, k)), int(query(1, e, cin, cout, k))
+    free, _ = device_free_bytes(dev)
+    return max(one, min(pref, int(free * ANY_WS_FRACTION)))
+
+
+def any_width_route(n_nodes: int, n_edges: int, in_channels: int, out_channels: int, k_hidden: Optional[int], aggr: str, chain: bool,
+                    free_bytes: int, mode: Optional[str] = None) -> dict:
+    """Which route a call of a module whose widths are not (64, 64) takes.  Host arithmetic only.
+
+    `materialised`: the reference's order, `nn(pseudo)` as [E, in * out] (E in out 4 bytes; the last Linear costs 2 E K in out
+    FLOP).  `reassociated`: the last Linear after the aggregation (E K 4 bytes of hidden activations plus one node block of
+    Z' = [in][K + 1 padded to 4] floats per node; 2 E in K + 2 N in K out FLOP).  A route fits when
+    twice its bytes are free (the gradient is as large again; the re-associated backward's workspace also holds the permuted last
+    Linear and its gradient and the per-edge dx rows, which `bytes_reassociated` does not count - the call shrinks its node block
+    to the free memory instead, `_hidden_any_ws_bytes`).  Eligible for re-association: `chain` (a Linear / ReLU chain),
+    aggr add / mean, 1 <= k_hidden <= ANY_MAX_HIDDEN.
+        off    materialised, or refused when it does not fit           (the behaviour before the re-associated kernels)
+        auto   materialised whenever it fits - exactly the calls of `off`; only a call that `off` refuses takes the re-associated
+               route, if it is eligible and fits; else refused
+        on     every eligible call is re-associated (refused when it does not fit); the others as `off`"""
+    mode = ANY_REASSOC if mode is None else mode
+    if mode not in ("auto", "on", "off"):
+        raise ValueError(f"GPDE_ANY_REASSOC must be auto, on or off, got {mode!r}")
+    n, e, cin, cout = int(n_nodes), int(n_edges), int(in_channels), int(out_channels)
+    k = None if k_hidden is None else int(k_hidden)
+    eligible = bool(chain) and aggr in ("add", "mean") and k is not None and 1 <= k <= ANY_MAX_HIDDEN
+    bytes_m = e * cin * cout * 4
+    out = {"eligible": eligible, "bytes_materialised": bytes_m, "bytes_reassociated": None, "node_block": None,
+           "flops_materialised": None if k is None else 2 * e * k * cin * cout, "flops_reassociated": None}
+    fits_m = 2 * bytes_m <= free_bytes
+    fits_r = False
+    if eligible:
+        zrow = cin * ((k + 1 + 3) // 4 * 4) * 4
+        block = max(1, min(n, _ANY_PREF_Z_BYTES // zrow))
+        out["node_block"] = block
+        out["bytes_reassociated"] = e * k * 4 + block * zrow
+        out["flops_reassociated"] = 2 * e * cin * k + 2 * n * cin * k * cout
+        fits_r = 2 * out["bytes_reassociated"] <= free_bytes
+    if mode == "on" and eligible:
+        out["route"] = "reassociated" if fits_r else "refused"
+    elif fits_m:
+        out["route"] = "materialised"
+    elif mode == "auto" and fits_r:
+        out["route"] = "reassociated"
+    else:
+        out["route"] = "refused"
+    return out
+
+
+def _hidden_any_args(x, csr: Csr, hidden, w_last, b_last, root):
+    """Shapes of a call of the re-associated any-width operator checked; (in_channels, out_channels, k_hidden)."""
+    n, e = csr.n_nodes, csr.n_edges
+    if x.dtype != torch.float32 or x.dim() != 2 or x.size(0) != n or x.size(1) < 1:
+        raise ValueError(f"x must be float32 [{n}, in_channels], got {x.dtype} {tuple(x.shape)}")
+    cin, dev = int(x.size(1)), x.device
+    if hidden.dtype != torch.float32 or hidden.dim() != 2 or hidden.size(0) != e or hidden.size(1) < 1 or not hidden.is_contiguous() or \
+            hidden.device != dev:
+        raise ValueError(f"hidden must be contiguous float32 [{e}, k_hidden] on {dev}, got {hidden.dtype} {tuple(hidden.shape)}")
+    k = int(hidden.size(1))
+    if w_last.dtype != torch.float32 or w_last.dim() != 2 or w_last.size(1) != k or w_last.size(0) % cin != 0 or w_last.size(0) == 0 or \
+            w_last.device != dev:
+        raise ValueError(f"w_last must be float32 [{cin} * out_channels, {k}] on {dev}, got {w_last.dtype} {tuple(w_last.shape)}")
+    cout = int(w_last.size(0)) // cin
+    if b_last is not None and (b_last.dtype != torch.float32 or tuple(b_last.shape) != (cin * cout,) or b_last.device != dev):
+        raise ValueError(f"b_last must be float32 [{cin * cout}] on {dev}, got {b_last.dtype} {tuple(b_last.shape)}")
+    if root is not None and (root.dtype != torch.float32 or tuple(root.shape) != (cin, cout) or root.device != dev):
+        raise ValueError(f"root must be float32 [{cin},{cout}] on {dev}, got {root.dtype} {tuple(root.shape)}")
+    if not width_supported(cin, cout):
+        raise NotImplementedError(f"in_channels {cin} -> out_channels {cout}: the native operator is built for widths 1 .. {ANY_MAX_WIDTH}")
+    if k > ANY_MAX_HIDDEN:
+        raise NotImplementedError(f"last hidden width {k}: the re-associated any-width operator is built for 1 .. {ANY_MAX_HIDDEN}")
+    return cin, cout, k
+
+
+def nnconv_forward_hidden_any_raw(x, csr: Csr, hidden, w_last, b_last, root, bias, aggr: str, ws_bytes: Optional[int] = None) -> torch.Tensor:
+    """gpde_nnconv_fwd_hidden_any: the any-width operator given the last hidden activations [E, K] (CSR slot order) and the last
+    Linear (w_last [in * out, K], b_last [in * out] or None) - aggregation, last Linear per node, update().  'add' / 'mean'.
+    `ws_bytes`: the workspace to run in (default: the library's preferred size); less gives more node blocks."""
+    lib = _lib.lib()
+    for t, nm in ((x, "x"), (hidden, "hidden"), (w_last, "w_last")):
+        _require_cuda(t, nm)
+    if aggr not in _AGGR:
+        raise NotImplementedError(f"aggr={aggr!r}: the re-associated operator is built for 'add' and 'mean'")
+    x_c, hid = x.detach().contiguous(), hidden.detach()
+    wl = w_last.detach().contiguous()
+    bl, root_c, bias_c = (None if t is None else t.detach().contiguous() for t in (b_last, root, bias))
+    cin, cout, k = _hidden_any_args(x_c, csr, hid, wl, bl, root_c)
+    n, e, dev = csr.n_nodes, csr.n_edges, x.device
+    if bias_c is not None and (bias_c.dtype != torch.float32 or tuple(bias_c.shape) != (cout,) or bias_c.device != dev):
+        raise ValueError(f"bias must be float32 [{cout}] on {dev}, got {bias_c.dtype} {tuple(bias_c.shape)}")
+    ws = _alloc_ws(_hidden_any_ws_bytes(lib.gpde_nnconv_fwd_hidden_any_workspace_bytes, n, e, cin, cout, k, dev) if ws_bytes is None else int(ws_bytes), dev)
+    out = torch.empty(n, cout, dtype=torch.float32, device=dev)
+    p = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        rc = lib.gpde_nnconv_fwd_hidden_any(x_c.data_ptr(), n, hid.data_ptr(), e, k, csr.rowptr.data_ptr(), csr.src.data_ptr(), wl.data_ptr(),
+                                            p(bl), p(root_c), p(bias_c), _AGGR[aggr], cin, cout, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                            _stream_ptr(dev))
+    _lib.check(rc, "gpde_nnconv_fwd_hidden_any")
+    _lib.n_native_calls += 1
+    return out
+
+
+def nnconv_backward_hidden_any_raw(x, csr: Csr, hidden, w_last, b_last, root, aggr: str, grad_out, need_x: bool = True,
+                                   need_w_last: bool = True, need_b_last: bool = True, need_root: bool = True, need_bias: bool = True,
+                                   ws_bytes: Optional[int] = None):
+    """gpde_nnconv_bwd_hidden_any: backward of the re-associated any-width operator.  Returns (grad_x [N, in], grad_hidden [E, K] -
+    dL/d hidden, the caller's ReLU not applied -, grad_w_last [in * out, K], grad_b_last [in * out], grad_root [in, out], grad_bias
+    [out]); an output that is not needed (or has no input: b_last / root None) is None."""
+    lib = _lib.lib()
+    for t, nm in ((x, "x"), (hidden, "hidden"), (w_last, "w_last"), (grad_out, "grad_out")):
+        _require_cuda(t, nm)
+    if aggr not in _AGGR:
+        raise NotImplementedError(f"aggr={aggr!r}: the re-associated operator is built for 'add' and 'mean'")
+    x_c, hid = x.detach().contiguous(), hidden.detach()
+    wl = w_last.detach().contiguous()
+    bl, root_c = (None if t is None else t.detach().contiguous() for t in (b_last, root))
+    cin, cout, k = _hidden_any_args(x_c, csr, hid, wl, bl, root_c)
+    n, e, dev = csr.n_nodes, csr.n_edges, x.device
+    grad_out = grad_out.detach().contiguous().float()
+    if tuple(grad_out.shape) != (n, cout):
+        raise ValueError(f"grad_out must be [{n},{cout}], got {tuple(grad_out.shape)}")
+    new = lambda want, *shape: torch.empty(*shape, dtype=torch.float32, device=dev) if want else None
+    gx, gh = new(need_x, n, cin), new(True, e, k)
+    gwl, gbl = new(need_w_last, cin * cout, k), new(need_b_last and b_last is not None, cin * cout)
+    groot, gbias = new(need_root and root is not None, cin, cout), new(need_bias, cout)
+    ws = _alloc_ws(_hidden_any_ws_bytes(lib.gpde_nnconv_bwd_hidden_any_workspace_bytes, n, e, cin, cout, k, dev) if ws_bytes is None else int(ws_bytes), dev)
+    srp, ssl = csr.src_order if (need_x and e > 0) else (None, None)
+    p = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        rc = lib.gpde_nnconv_bwd_hidden_any(x_c.data_ptr(), n, hid.data_ptr(), e, k, csr.rowptr.data_ptr(), csr.src.data_ptr(), wl.data_ptr(),
+                                            p(bl), p(root_c), _AGGR[aggr], cin, cout, grad_out.data_ptr(), p(gx), gh.data_ptr(), p(gwl), p(gbl),
+                                            p(groot), p(gbias), p(srp), p(ssl), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+    _lib.check(rc, "gpde_nnconv_bwd_hidden_any")
+    _lib.n_native_calls += 1
+    return gx, gh, gwl, gbl, groot, gbias
+
+
 def edge_weights_backward_raw(grad_we: torch.Tensor, hidden: torch.Tensor, dims: Sequence[int], w_last: torch.Tensor,
                               need_b: bool = True):
     """gpde_edge_weights_bwd: (grad_hidden [E, K2P] already masked by hidden > 0, grad_w_last, grad_b_last or None) from the

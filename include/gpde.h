@@ -472,6 +472,44 @@ GPDE_API int gpde_nnconv_bwd_edgeweights_any(const float* x, int64_t n_nodes, co
                                     int out_channels, const float* grad_out, float* grad_x, float* grad_edge_weights,
                                     float* grad_root, float* grad_bias, void* ws, size_t ws_bytes, void* stream);
 
+/* The RE-ASSOCIATED operator at any width (gpde_reassoc_any.hip): for a Linear / ReLU chain `nn` and aggr add / mean the last
+ * Linear commutes with the aggregation, so [E][in * out] need not be formed (what the 64-wide entry points have always done,
+ * DESIGN.md §2).  The caller gives the LAST HIDDEN ACTIVATIONS instead of the per-edge weights:
+ *   x [N][in], hidden [E][k_hidden] = relu(L_{n-1}(... pseudo)) with rows in CSR slot order (no padding), w_last [in * out][k_hidden]
+ *   and b_last [in * out] (nullable) in torch's layouts, root [in][out] or NULL, bias [out] or NULL, out [N][out]:
+ *     Z'_d = [sum_{e -> d} x_src(e) (x) hidden_e | sum_{e -> d} x_src(e)]        per destination node, [in][k_hidden + 1]
+ *     out_d = Z'_d . [W_last | b_last] (/ clamp(count_d, 1) for mean) + x_d . root + bias
+ *   1 <= in_channels, out_channels <= GPDE_WECONV_ANY_MAX_WIDTH, 1 <= k_hidden <= GPDE_REASSOC_ANY_MAX_HIDDEN; anything else and
+ *   GPDE_AGGR_MAX (not linear in the last Linear): GPDE_EUNSUPPORTED.  Zero nodes / zero edges are valid calls.
+ *   Backward outputs (overwritten): grad_x [N][in], grad_hidden [E][k_hidden] = dL/d hidden (NOT masked by hidden > 0: the
+ *   caller's autograd differentiates its own ReLU; required when n_edges > 0), grad_w_last [in * out][k_hidden], grad_b_last
+ *   [in * out], grad_root [in][out], grad_bias [out]; NULL skips any of the others.  grad_x is summed over each source's out-edges
+ *   in ascending slot order: src_rowptr / src_slots (gpde_csr_source_order) are required with grad_x when n_edges > 0.
+ * Workspace: Z' is in * (k_hidden + 1) * 4 bytes per node (1 MiB at 256 x 1024), so both calls walk blocks of destination nodes
+ * sized to the workspace they are given.  *_workspace_bytes returns the preferred size; a smaller workspace gives more blocks of
+ * fewer nodes, down to one node; less than one node's worth: GPDE_EINVAL (the message names the size).  Calls without edges use no
+ * node block: the forward and a zero-node backward take ws = NULL, a zero-edge backward needs a workspace only for grad_root /
+ * grad_bias (their strip partials; any size the query returns is enough).
+ * Plain fp32 (fmaf; fp32 MFMA in the node-side GEMMs), no atomics, in-edges in ascending slot order, long rows summed two-level
+ * (DESIGN.md §3).  The summation order is fixed by the shapes and the workspace size: two identical calls give identical bits,
+ * and out / grad_x / grad_hidden do not depend on the number of node blocks (grad_w_last / grad_b_last are summed over the
+ * blocks in order).  Additions to the ABI like the block above: GPDE_VERSION is unchanged. */
+#define GPDE_REASSOC_ANY_MAX_HIDDEN 4096
+GPDE_API size_t gpde_nnconv_fwd_hidden_any_workspace_bytes(int64_t n_nodes, int64_t n_edges, int in_channels, int out_channels,
+                                                  int k_hidden);
+GPDE_API int gpde_nnconv_fwd_hidden_any(const float* x, int64_t n_nodes, const float* hidden, int64_t n_edges, int k_hidden,
+                               const int32_t* rowptr, const int32_t* src, const float* w_last, const float* b_last,
+                               const float* root, const float* bias, int aggr, int in_channels, int out_channels, float* out,
+                               void* ws, size_t ws_bytes, void* stream);
+GPDE_API size_t gpde_nnconv_bwd_hidden_any_workspace_bytes(int64_t n_nodes, int64_t n_edges, int in_channels, int out_channels,
+                                                  int k_hidden);
+GPDE_API int gpde_nnconv_bwd_hidden_any(const float* x, int64_t n_nodes, const float* hidden, int64_t n_edges, int k_hidden,
+                               const int32_t* rowptr, const int32_t* src, const float* w_last, const float* b_last,
+                               const float* root, int aggr, int in_channels, int out_channels, const float* grad_out,
+                               float* grad_x, float* grad_hidden, float* grad_w_last, float* grad_b_last, float* grad_root,
+                               float* grad_bias, const int32_t* src_rowptr, const int32_t* src_slots, void* ws, size_t ws_bytes,
+                               void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Edge attributes on the fly (opt-in): the `node_attr` argument (GpdeNodeAttr, declared at the top).
  * The reference materialises edge_attr[e] = [pos_src(2), pos_dst(2), a_src, a_dst] from node data
