@@ -435,3 +435,56 @@ class HiddenAnyFunction(torch.autograd.Function):
             x, ctx.csr, hidden, w_last, b_last, root, ctx.aggr, grad_out, need_x=need[0], need_w_last=need[2],
             need_b_last=ctx.has_b_last and need[3], need_root=ctx.has_root and need[5], need_bias=ctx.has_bias and need[6])
         return gx, (gh if need[1] else None), gwl, gbl, None, groot, gbias, None
+
+
+class WeConvBipFunction(torch.autograd.Function):
+    """WeConvAnyFunction BETWEEN TWO NODE SETS (gpde_nnconv_fwd_edgeweights_bip / gpde_nnconv_bwd_edgeweights_bip): x_src
+    [n_src, in_src] is gathered along the edges of the rectangular `csr`, x_dst [n_dst, in_dst] (or None: no root term) enters
+    `x_dst . root`, out is [n_dst, out].  Differentiable in x_src, x_dst, W_e [E, in_src * out], root [in_dst, out] and bias."""
+
+    @staticmethod
+    def forward(ctx, x_src, x_dst, we, csr, root, bias, aggr):
+        if x_dst is None:
+            root = None                 # PyG: `if x_r is not None and root_weight: out += lin(x_r)`
+        out = ops.nnconv_forward_edgeweights_bip_raw(x_src.detach(), None if x_dst is None else x_dst.detach(), csr, we.detach(), root, bias, aggr)
+        ctx.csr, ctx.aggr, ctx.has_bias, ctx.has_dst, ctx.has_root = csr, aggr, bias is not None, x_dst is not None, root is not None
+        ctx.save_for_backward(x_src, x_dst, we, root)
+        return out
+
+    @staticmethod
+    @once_differentiable        # the native backward is not itself differentiable: create_graph=True raises
+    def backward(ctx, grad_out):
+        x_src, x_dst, we, root = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gxs, gxd, gwe, groot, gbias = ops.nnconv_backward_edgeweights_bip_raw(
+            x_src, x_dst, ctx.csr, we, root, ctx.aggr, grad_out, need_x_src=need[0], need_x_dst=ctx.has_dst and need[1],
+            need_root=ctx.has_root and need[4], need_bias=ctx.has_bias and need[5])
+        return gxs, gxd, (gwe if need[2] else None), None, groot, gbias, None
+
+
+class HiddenBipFunction(torch.autograd.Function):
+    """HiddenAnyFunction BETWEEN TWO NODE SETS (gpde_nnconv_fwd_hidden_bip / gpde_nnconv_bwd_hidden_bip): Z' is aggregated per
+    destination from x_src, the last Linear runs per destination, x_dst [n_dst, in_dst] (or None) enters the root term.
+    Differentiable in x_src, x_dst, H [E, K], the last Linear (w_last [in_src * out, K], b_last), root [in_dst, out] and bias."""
+
+    @staticmethod
+    def forward(ctx, x_src, x_dst, hidden, w_last, b_last, csr, root, bias, aggr):
+        if x_dst is None:
+            root = None
+        out = ops.nnconv_forward_hidden_bip_raw(x_src.detach(), None if x_dst is None else x_dst.detach(), csr, hidden.detach(), w_last, b_last,
+                                                root, bias, aggr)
+        ctx.csr, ctx.aggr, ctx.has_bias, ctx.has_dst = csr, aggr, bias is not None, x_dst is not None
+        ctx.has_b_last, ctx.has_root = b_last is not None, root is not None
+        ctx.save_for_backward(x_src, x_dst, hidden, w_last, b_last, root)
+        return out
+
+    @staticmethod
+    @once_differentiable        # the native backward is not itself differentiable: create_graph=True raises
+    def backward(ctx, grad_out):
+        x_src, x_dst, hidden, w_last, b_last, root = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gxs, gxd, gh, gwl, gbl, groot, gbias = ops.nnconv_backward_hidden_bip_raw(
+            x_src, x_dst, ctx.csr, hidden, w_last, b_last, root, ctx.aggr, grad_out, need_x_src=need[0], need_x_dst=ctx.has_dst and need[1],
+            need_w_last=need[3], need_b_last=ctx.has_b_last and need[4], need_root=ctx.has_root and need[6],
+            need_bias=ctx.has_bias and need[7])
+        return gxs, gxd, (gh if need[2] else None), gwl, gbl, None, groot, gbias, None

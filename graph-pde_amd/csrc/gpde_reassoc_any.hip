@@ -26,6 +26,8 @@
 //                                 coalesced, the 8 x_j rows in LDS), dxe with one wave per row i and an xor-shuffle tree over k
 //   k_ra_permute / k_ra_unpermute the last Linear into P and dP back into torch's layouts: 32 x 32 tiles through LDS
 //   k_ra_scale_g / k_ra_epilogue  g / deg of a node block;  split-K sum, mean, x . root + bias
+// Two node sets (gpde_nnconv_*_hidden_bip): the aggregation and the per-edge backward gather x_src [n_src][in], the node blocks walk the
+// n_dst destinations, the epilogue's root term and grad_root read x_dst [n_dst][in_dst]; the square entry points hand x for both.
 #include "gpde_common.h"
 
 namespace {
@@ -212,6 +214,7 @@ __global__ __launch_bounds__(256) void k_ra_scale_g(const float* __restrict__ g,
 }
 
 // out[node0 + d][o] = (sum of the split-K partials, in order) (/ in-degree) + x . root + bias
+// `x` is the DESTINATION node table and `cin` its width (in_dst; root is [in_dst][out]): a square call hands its one table
 __global__ __launch_bounds__(256) void k_ra_epilogue(const float* __restrict__ part, int splits, size_t split_stride,
                                                      const float* __restrict__ x, const int32_t* __restrict__ rowptr,
                                                      const float* __restrict__ root, const float* __restrict__ bias, float* __restrict__ out,
@@ -257,8 +260,9 @@ constexpr size_t RA_SLACK = 256 + 3 * 256;       // alignment of the workspace b
 
 size_t ra_fwd_fixed(const RaShape& s) { return s.p_bytes + RA_SLACK; }
 size_t ra_fwd_per_node(const RaShape& s) { return s.zrow * 4 + (size_t)s.splits * s.cout * 4; }
-size_t ra_bwd_fixed(const RaShape& s, int64_t n_edges) {
-    return 2 * s.p_bytes + ra_al((size_t)(n_edges > 0 ? n_edges : 1) * s.cin * 4) + gpde_any_node_grads_ws_bytes(s.cin, s.cout) + RA_SLACK;
+// `cind`: the width of the destination table, whose droot partials [in_dst][out] the workspace holds (a square call: cin)
+size_t ra_bwd_fixed(const RaShape& s, int64_t n_edges, int cind) {
+    return 2 * s.p_bytes + ra_al((size_t)(n_edges > 0 ? n_edges : 1) * s.cin * 4) + gpde_any_node_grads_ws_bytes(cind, s.cout) + RA_SLACK;
 }
 size_t ra_bwd_per_node(const RaShape& s) { return 2 * s.zrow * 4 + (size_t)s.coutP * 4; }
 
@@ -324,35 +328,20 @@ inline char* ra_base(void* ws) { return (char*)(((uintptr_t)ws + 255) / 256 * 25
 
 }  // namespace
 
-extern "C" size_t gpde_nnconv_fwd_hidden_any_workspace_bytes(int64_t n_nodes, int64_t n_edges, int in_channels, int out_channels,
-                                                             int k_hidden) {
-    if (n_nodes < 0 || n_edges < 0 || in_channels < 1 || out_channels < 1 || in_channels > RA_MAXW || out_channels > RA_MAXW ||
-        k_hidden < 1 || k_hidden > RA_MAXK)
-        return 0;
-    const RaShape s = ra_shape(in_channels, out_channels, k_hidden);
-    return ra_fwd_fixed(s) + (size_t)ra_pref_block(s, n_nodes) * ra_fwd_per_node(s);
-}
+namespace {
 
-extern "C" int gpde_nnconv_fwd_hidden_any(const float* x, int64_t n_nodes, const float* hidden, int64_t n_edges, int k_hidden,
-                                          const int32_t* rowptr, const int32_t* src, const float* w_last, const float* b_last,
-                                          const float* root, const float* bias, int aggr, int in_channels, int out_channels, float* out,
-                                          void* ws, size_t ws_bytes, void* stream_) {
-    hipStream_t st = (hipStream_t)stream_;
-    const char* who = "gpde_nnconv_fwd_hidden_any";
-    if (n_nodes < 0 || n_edges < 0 || !rowptr || (n_nodes > 0 && (!x || !out)) || (n_edges > 0 && (!hidden || !src || !w_last || !ws)) ||
-        n_nodes >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31)) {
-        gpde_set_error("%s: null/negative argument", who);
-        return GPDE_EINVAL;
-    }
-    int rc = ra_check(who, in_channels, out_channels, k_hidden, aggr);
-    if (rc != GPDE_OK) return rc;
-    if (n_nodes == 0) return GPDE_OK;
+// Both forwards after their argument checks.  x_src [n_src][cin] is gathered by `src`; x_dst [n_dst][cind] (nullable with root
+// == NULL) enters the epilogue's root term only; the node blocks walk the n_dst destinations.  A square call hands x twice.
+int ra_fwd_run(const char* who, const float* x_src, const float* x_dst, int64_t n_nodes, const float* hidden, int64_t n_edges, int k_hidden,
+               const int32_t* rowptr, const int32_t* src, const float* w_last, const float* b_last, const float* root, const float* bias,
+               int aggr, int in_channels, int in_dst, int out_channels, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
+    int rc;
     const RaShape s = ra_shape(in_channels, out_channels, k_hidden);
-    const int cin = s.cin, cout = s.cout;
+    const int cout = s.cout;
     if (n_edges == 0) {                                          // no edge: update() alone
         const size_t n = (size_t)n_nodes * cout;
-        hipLaunchKernelGGL(k_ra_epilogue, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)nullptr, 0, (size_t)0, x, rowptr,
-                           root, bias, out, 0, (int)n_nodes, cin, cout, aggr);
+        hipLaunchKernelGGL(k_ra_epilogue, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)nullptr, 0, (size_t)0, x_dst, rowptr,
+                           root, bias, out, 0, (int)n_nodes, in_dst, cout, aggr);
         GP_LAUNCH_CHECK("k_ra_epilogue");
         return GPDE_OK;
     }
@@ -372,7 +361,7 @@ extern "C" int gpde_nnconv_fwd_hidden_any(const float* x, int64_t n_nodes, const
     if (rc != GPDE_OK) return rc;
     for (int64_t na = 0; na < n_nodes; na += blk) {
         const int nb = (int)(n_nodes - na < blk ? n_nodes - na : blk);
-        rc = ra_launch_zagg(s, x, hidden, rowptr, src, Z, (int)na, nb, st);
+        rc = ra_launch_zagg(s, x_src, hidden, rowptr, src, Z, (int)na, nb, st);
         if (rc != GPDE_OK) return rc;
         GpdeGemmArgs g = ra_gemm(Z, P, part, nb, cout, (int)s.zrow, (int)s.zrow, s.coutP, cout, 1, 0);     // NN: Z' . P
         g.splits = s.splits;
@@ -380,11 +369,189 @@ extern "C" int gpde_nnconv_fwd_hidden_any(const float* x, int64_t n_nodes, const
         rc = gpde_launch_gemm(g, st);
         if (rc != GPDE_OK) return rc;
         const size_t n = (size_t)nb * cout;
-        hipLaunchKernelGGL(k_ra_epilogue, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, s.splits, (size_t)nb * cout, x, rowptr,
-                           root, bias, out, (int)na, nb, cin, cout, aggr);
+        hipLaunchKernelGGL(k_ra_epilogue, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, s.splits, (size_t)nb * cout, x_dst, rowptr,
+                           root, bias, out, (int)na, nb, in_dst, cout, aggr);
         GP_LAUNCH_CHECK("k_ra_epilogue");
     }
     return GPDE_OK;
+}
+
+// Both backwards after their argument checks; n_nodes = the destinations (> 0).  `square`: one node set - grad_x_src [n_src = n_nodes]
+// receives the root term in the same k_any_dx_finish launch as the source sum, grad_x_dst is unused.  Otherwise grad_x_src [n_src][cin]
+// is the source sum alone and grad_x_dst [n_nodes][cind] = g . root^T.
+int ra_bwd_run(const char* who, const float* x_src, int64_t n_src, const float* x_dst, int64_t n_nodes, const float* hidden, int64_t n_edges,
+               int k_hidden, const int32_t* rowptr, const int32_t* src, const float* w_last, const float* b_last, const float* root, int aggr,
+               int in_channels, int in_dst, int out_channels, const float* grad_out, float* grad_x_src, float* grad_x_dst, float* grad_hidden,
+               float* grad_w_last, float* grad_b_last, float* grad_root, float* grad_bias, const int32_t* src_rowptr, const int32_t* src_slots,
+               void* ws, size_t ws_bytes, bool square, hipStream_t st) {
+    int rc;
+    const RaShape s = ra_shape(in_channels, out_channels, k_hidden);
+    const int cin = s.cin, cout = s.cout, cind = in_dst;
+    if (n_edges == 0) {                                          // no edge: the node-side terms alone; only grad_root / grad_bias use the workspace
+        if (square) {
+            if (grad_x_src) {
+                GP_HIP_CHECK(gpde_zero_async(grad_x_src, (size_t)n_nodes * cin * 4, st));          // the root term alone, added to 0
+                rc = gpde_launch_any_dx_finish(nullptr, nullptr, nullptr, root, grad_out, grad_x_src, n_nodes, cin, cout, 0, st);
+                if (rc != GPDE_OK) return rc;
+            }
+        } else {
+            if (grad_x_src && n_src > 0) GP_HIP_CHECK(gpde_zero_async(grad_x_src, (size_t)n_src * cin * 4, st));
+            if (grad_x_dst) {
+                if (!root) GP_HIP_CHECK(gpde_zero_async(grad_x_dst, (size_t)n_nodes * cind * 4, st));
+                else {
+                    rc = gpde_launch_any_dx_finish(nullptr, nullptr, nullptr, root, grad_out, grad_x_dst, n_nodes, cind, cout, 2, st);
+                    if (rc != GPDE_OK) return rc;
+                }
+            }
+        }
+        if (grad_root || grad_bias) {
+            if (!ws || ws_bytes < gpde_any_node_grads_ws_bytes(cind, cout) + 256) {
+                gpde_set_error("%s: grad_root / grad_bias need %zu bytes of workspace", who, gpde_any_node_grads_ws_bytes(cind, cout) + 256);
+                return GPDE_EINVAL;
+            }
+            rc = gpde_launch_any_node_grads(x_dst, grad_out, (float*)ra_base(ws), n_nodes, cind, cout, grad_root, grad_bias, st);
+            if (rc != GPDE_OK) return rc;
+        }
+        return GPDE_OK;
+    }
+    if (ws_bytes < ra_bwd_fixed(s, n_edges, cind) + ra_bwd_per_node(s)) {
+        gpde_set_error("%s: workspace of %zu bytes holds less than one node's Z' and dZ' (%zu bytes needed; %zu preferred)", who, ws_bytes,
+                       ra_bwd_fixed(s, n_edges, cind) + ra_bwd_per_node(s),
+                       gpde_nnconv_bwd_hidden_bip_workspace_bytes(n_nodes, n_edges, in_channels, cind, out_channels, k_hidden));
+        return GPDE_EINVAL;
+    }
+    char* w = ra_base(ws);
+    float* P = (float*)w;
+    float* dP = (float*)(w + s.p_bytes);
+    float* dxe = (float*)(w + 2 * s.p_bytes);
+    float* ngp = (float*)((char*)dxe + ra_al((size_t)n_edges * cin * 4));
+    char* blkbuf = (char*)ngp + gpde_any_node_grads_ws_bytes(cind, cout);
+    {
+        int64_t blk = (int64_t)((ws_bytes - ra_bwd_fixed(s, n_edges, cind)) / ra_bwd_per_node(s));
+        if (blk > n_nodes) blk = n_nodes;
+        float* dZ = (float*)blkbuf;
+        float* Z = (float*)((char*)dZ + ra_al((size_t)blk * s.zrow * 4));
+        float* gs = (float*)((char*)Z + ra_al((size_t)blk * s.zrow * 4));
+        const bool want_dp = grad_w_last || grad_b_last;
+        rc = ra_launch_permute(s, w_last, b_last, P, st);
+        if (rc != GPDE_OK) return rc;
+        for (int64_t na = 0; na < n_nodes; na += blk) {
+            const int nb = (int)(n_nodes - na < blk ? n_nodes - na : blk);
+            const size_t ng = (size_t)nb * s.coutP;
+            hipLaunchKernelGGL(k_ra_scale_g, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, st, grad_out, rowptr, gs, (int)na, nb, cout,
+                               s.coutP, aggr);
+            GP_LAUNCH_CHECK("k_ra_scale_g");
+            // NT: dZ' = g . P^T
+            rc = gpde_launch_gemm(ra_gemm(gs, P, dZ, nb, (int)s.zrow, s.coutP, s.coutP, s.coutP, (int)s.zrow, 1, 1), st);
+            if (rc != GPDE_OK) return rc;
+            if (want_dp) {                                       // TN: dP (+)= Z'^T . g, Z' of the block recomputed
+                rc = ra_launch_zagg(s, x_src, hidden, rowptr, src, Z, (int)na, nb, st);
+                if (rc != GPDE_OK) return rc;
+                GpdeGemmArgs g = ra_gemm(Z, gs, dP, (int)s.zrow, cout, nb, (int)s.zrow, s.coutP, s.coutP, 0, 0);
+                g.accumulate = na > 0 ? 1 : 0;
+                rc = gpde_launch_gemm(g, st);
+                if (rc != GPDE_OK) return rc;
+            }
+            hipLaunchKernelGGL(gpde_reassoc_edge_bwd_kernel, dim3((unsigned)nb, RB_SEGS), dim3(256), 0, st, x_src, hidden, rowptr, src, dZ,
+                               grad_hidden, grad_x_src ? dxe : (float*)nullptr, (int)na, cin, s.K, s.KP);
+            GP_LAUNCH_CHECK("gpde_reassoc_edge_bwd_kernel");
+        }
+        if (want_dp) {
+            hipLaunchKernelGGL(k_ra_unpermute, dim3((s.KP + 31) / 32, (s.coutP + 31) / 32, cin), dim3(256), 0, st, dP, grad_w_last,
+                               grad_b_last, cout, s.coutP, s.K, s.KP);
+            GP_LAUNCH_CHECK("k_ra_unpermute");
+        }
+    }
+    if (square) {
+        if (grad_x_src) {
+            rc = gpde_launch_any_dx_finish(dxe, src_rowptr, src_slots, root, grad_out, grad_x_src, n_nodes, cin, cout, 1, st);
+            if (rc != GPDE_OK) return rc;
+        }
+    } else {
+        if (grad_x_src) {                                        // the sources: the sum over their out-edges, no root term
+            rc = gpde_launch_any_dx_finish(dxe, src_rowptr, src_slots, nullptr, nullptr, grad_x_src, n_src, cin, cout, 1, st);
+            if (rc != GPDE_OK) return rc;
+        }
+        if (grad_x_dst) {                                        // the destinations: g . root^T
+            if (!root) GP_HIP_CHECK(gpde_zero_async(grad_x_dst, (size_t)n_nodes * cind * 4, st));
+            else {
+                rc = gpde_launch_any_dx_finish(nullptr, nullptr, nullptr, root, grad_out, grad_x_dst, n_nodes, cind, cout, 2, st);
+                if (rc != GPDE_OK) return rc;
+            }
+        }
+    }
+    if (grad_root || grad_bias) {
+        rc = gpde_launch_any_node_grads(x_dst, grad_out, ngp, n_nodes, cind, cout, grad_root, grad_bias, st);
+        if (rc != GPDE_OK) return rc;
+    }
+    return GPDE_OK;
+}
+
+int ra_check_in_dst(const char* who, int in_dst) {
+    if (in_dst < 1 || in_dst > RA_MAXW) {
+        gpde_set_error("%s: in_dst %d: built for 1 <= in_dst <= %d (GPDE_WECONV_ANY_MAX_WIDTH)", who, in_dst, RA_MAXW);
+        return GPDE_EUNSUPPORTED;
+    }
+    return GPDE_OK;
+}
+
+}  // namespace
+
+extern "C" size_t gpde_nnconv_fwd_hidden_any_workspace_bytes(int64_t n_nodes, int64_t n_edges, int in_channels, int out_channels,
+                                                             int k_hidden) {
+    if (n_nodes < 0 || n_edges < 0 || in_channels < 1 || out_channels < 1 || in_channels > RA_MAXW || out_channels > RA_MAXW ||
+        k_hidden < 1 || k_hidden > RA_MAXK)
+        return 0;
+    const RaShape s = ra_shape(in_channels, out_channels, k_hidden);
+    return ra_fwd_fixed(s) + (size_t)ra_pref_block(s, n_nodes) * ra_fwd_per_node(s);
+}
+
+// the forward's workspace holds P and Z' of a block of DESTINATION nodes: neither depends on the source count or on in_dst
+extern "C" size_t gpde_nnconv_fwd_hidden_bip_workspace_bytes(int64_t n_dst, int64_t n_edges, int in_src, int out_channels, int k_hidden) {
+    return gpde_nnconv_fwd_hidden_any_workspace_bytes(n_dst, n_edges, in_src, out_channels, k_hidden);
+}
+
+extern "C" int gpde_nnconv_fwd_hidden_any(const float* x, int64_t n_nodes, const float* hidden, int64_t n_edges, int k_hidden,
+                                          const int32_t* rowptr, const int32_t* src, const float* w_last, const float* b_last,
+                                          const float* root, const float* bias, int aggr, int in_channels, int out_channels, float* out,
+                                          void* ws, size_t ws_bytes, void* stream_) {
+    hipStream_t st = (hipStream_t)stream_;
+    const char* who = "gpde_nnconv_fwd_hidden_any";
+    if (n_nodes < 0 || n_edges < 0 || !rowptr || (n_nodes > 0 && (!x || !out)) || (n_edges > 0 && (!hidden || !src || !w_last || !ws)) ||
+        n_nodes >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31)) {
+        gpde_set_error("%s: null/negative argument", who);
+        return GPDE_EINVAL;
+    }
+    int rc = ra_check(who, in_channels, out_channels, k_hidden, aggr);
+    if (rc != GPDE_OK) return rc;
+    if (n_nodes == 0) return GPDE_OK;
+    return ra_fwd_run(who, x, x, n_nodes, hidden, n_edges, k_hidden, rowptr, src, w_last, b_last, root, bias, aggr, in_channels, in_channels,
+                      out_channels, out, ws, ws_bytes, st);
+}
+
+extern "C" int gpde_nnconv_fwd_hidden_bip(const float* x_src, int64_t n_src, const float* x_dst, int64_t n_dst, const float* hidden,
+                                          int64_t n_edges, int k_hidden, const int32_t* rowptr, const int32_t* src, const float* w_last,
+                                          const float* b_last, const float* root, const float* bias, int aggr, int in_src, int in_dst,
+                                          int out_channels, float* out, void* ws, size_t ws_bytes, void* stream_) {
+    hipStream_t st = (hipStream_t)stream_;
+    const char* who = "gpde_nnconv_fwd_hidden_bip";
+    if (n_src < 0 || n_dst < 0 || n_edges < 0 || !rowptr || (n_dst > 0 && !out) ||
+        (n_edges > 0 && (!hidden || !src || !w_last || !ws || !x_src || n_src == 0 || n_dst == 0)) ||
+        n_src >= ((int64_t)1 << 31) || n_dst >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31)) {
+        gpde_set_error("%s: null/negative argument or edges without sources or destinations", who);
+        return GPDE_EINVAL;
+    }
+    if (n_dst > 0 && root && !x_dst) {                           // (no destination: an empty table has no address)
+        gpde_set_error("%s: root without x_dst: the root term is x_dst . root (pass root = NULL for a call without destination features)", who);
+        return GPDE_EINVAL;
+    }
+    int rc = ra_check(who, in_src, out_channels, k_hidden, aggr);
+    if (rc != GPDE_OK) return rc;
+    rc = ra_check_in_dst(who, in_dst);
+    if (rc != GPDE_OK) return rc;
+    if (n_dst == 0) return GPDE_OK;
+    return ra_fwd_run(who, x_src, x_dst, n_dst, hidden, n_edges, k_hidden, rowptr, src, w_last, b_last, root, bias, aggr, in_src, in_dst,
+                      out_channels, out, ws, ws_bytes, st);
 }
 
 extern "C" size_t gpde_nnconv_bwd_hidden_any_workspace_bytes(int64_t n_nodes, int64_t n_edges, int in_channels, int out_channels,
@@ -393,7 +560,16 @@ extern "C" size_t gpde_nnconv_bwd_hidden_any_workspace_bytes(int64_t n_nodes, in
         k_hidden < 1 || k_hidden > RA_MAXK)
         return 0;
     const RaShape s = ra_shape(in_channels, out_channels, k_hidden);
-    return ra_bwd_fixed(s, n_edges) + (size_t)ra_pref_block(s, n_nodes) * ra_bwd_per_node(s);
+    return ra_bwd_fixed(s, n_edges, in_channels) + (size_t)ra_pref_block(s, n_nodes) * ra_bwd_per_node(s);
+}
+
+extern "C" size_t gpde_nnconv_bwd_hidden_bip_workspace_bytes(int64_t n_dst, int64_t n_edges, int in_src, int in_dst, int out_channels,
+                                                             int k_hidden) {
+    if (n_dst < 0 || n_edges < 0 || in_src < 1 || in_dst < 1 || out_channels < 1 || in_src > RA_MAXW || in_dst > RA_MAXW ||
+        out_channels > RA_MAXW || k_hidden < 1 || k_hidden > RA_MAXK)
+        return 0;
+    const RaShape s = ra_shape(in_src, out_channels, k_hidden);
+    return ra_bwd_fixed(s, n_edges, in_dst) + (size_t)ra_pref_block(s, n_dst) * ra_bwd_per_node(s);
 }
 
 extern "C" int gpde_nnconv_bwd_hidden_any(const float* x, int64_t n_nodes, const float* hidden, int64_t n_edges, int k_hidden,
@@ -423,77 +599,46 @@ extern "C" int gpde_nnconv_bwd_hidden_any(const float* x, int64_t n_nodes, const
         if (grad_bias) GP_HIP_CHECK(gpde_zero_async(grad_bias, (size_t)cout * 4, st));
         return GPDE_OK;
     }
-    if (n_edges == 0) {                                          // no edge: the node-side terms alone; only grad_root / grad_bias use the workspace
-        if (grad_x) {
-            GP_HIP_CHECK(gpde_zero_async(grad_x, (size_t)n_nodes * cin * 4, st));          // the root term alone, added to 0
-            rc = gpde_launch_any_dx_finish(nullptr, nullptr, nullptr, root, grad_out, grad_x, n_nodes, cin, cout, 0, st);
-            if (rc != GPDE_OK) return rc;
-        }
-        if (grad_root || grad_bias) {
-            if (!ws || ws_bytes < gpde_any_node_grads_ws_bytes(cin, cout) + 256) {
-                gpde_set_error("%s: grad_root / grad_bias need %zu bytes of workspace", who, gpde_any_node_grads_ws_bytes(cin, cout) + 256);
-                return GPDE_EINVAL;
-            }
-            rc = gpde_launch_any_node_grads(x, grad_out, (float*)ra_base(ws), n_nodes, cin, cout, grad_root, grad_bias, st);
-            if (rc != GPDE_OK) return rc;
-        }
-        return GPDE_OK;
-    }
-    if (ws_bytes < ra_bwd_fixed(s, n_edges) + ra_bwd_per_node(s)) {
-        gpde_set_error("%s: workspace of %zu bytes holds less than one node's Z' and dZ' (%zu bytes needed; %zu preferred)", who, ws_bytes,
-                       ra_bwd_fixed(s, n_edges) + ra_bwd_per_node(s),
-                       gpde_nnconv_bwd_hidden_any_workspace_bytes(n_nodes, n_edges, in_channels, out_channels, k_hidden));
+    return ra_bwd_run(who, x, n_nodes, x, n_nodes, hidden, n_edges, k_hidden, rowptr, src, w_last, b_last, root, aggr, in_channels,
+                      in_channels, out_channels, grad_out, grad_x, nullptr, grad_hidden, grad_w_last, grad_b_last, grad_root, grad_bias,
+                      src_rowptr, src_slots, ws, ws_bytes, true, st);
+}
+
+extern "C" int gpde_nnconv_bwd_hidden_bip(const float* x_src, int64_t n_src, const float* x_dst, int64_t n_dst, const float* hidden,
+                                          int64_t n_edges, int k_hidden, const int32_t* rowptr, const int32_t* src, const float* w_last,
+                                          const float* b_last, const float* root, int aggr, int in_src, int in_dst, int out_channels,
+                                          const float* grad_out, float* grad_x_src, float* grad_x_dst, float* grad_hidden,
+                                          float* grad_w_last, float* grad_b_last, float* grad_root, float* grad_bias,
+                                          const int32_t* src_rowptr, const int32_t* src_slots, void* ws, size_t ws_bytes, void* stream_) {
+    hipStream_t st = (hipStream_t)stream_;
+    const char* who = "gpde_nnconv_bwd_hidden_bip";
+    if (n_src < 0 || n_dst < 0 || n_edges < 0 || !rowptr || (n_dst > 0 && !grad_out) ||
+        (n_edges > 0 && (!ws || !hidden || !src || !w_last || !grad_hidden || !x_src || n_src == 0 || n_dst == 0 ||
+                         (grad_x_src && (!src_rowptr || !src_slots)))) ||
+        n_src >= ((int64_t)1 << 31) || n_dst >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31)) {
+        gpde_set_error("%s: null/negative argument (grad_hidden is required with edges, src_rowptr / src_slots over n_src with grad_x_src)", who);
         return GPDE_EINVAL;
     }
-    char* w = ra_base(ws);
-    float* P = (float*)w;
-    float* dP = (float*)(w + s.p_bytes);
-    float* dxe = (float*)(w + 2 * s.p_bytes);
-    float* ngp = (float*)((char*)dxe + ra_al((size_t)n_edges * cin * 4));
-    char* blkbuf = (char*)ngp + gpde_any_node_grads_ws_bytes(cin, cout);
-    if (n_edges > 0) {
-        int64_t blk = (int64_t)((ws_bytes - ra_bwd_fixed(s, n_edges)) / ra_bwd_per_node(s));
-        if (blk > n_nodes) blk = n_nodes;
-        float* dZ = (float*)blkbuf;
-        float* Z = (float*)((char*)dZ + ra_al((size_t)blk * s.zrow * 4));
-        float* gs = (float*)((char*)Z + ra_al((size_t)blk * s.zrow * 4));
-        const bool want_dp = grad_w_last || grad_b_last;
-        rc = ra_launch_permute(s, w_last, b_last, P, st);
-        if (rc != GPDE_OK) return rc;
-        for (int64_t na = 0; na < n_nodes; na += blk) {
-            const int nb = (int)(n_nodes - na < blk ? n_nodes - na : blk);
-            const size_t ng = (size_t)nb * s.coutP;
-            hipLaunchKernelGGL(k_ra_scale_g, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, st, grad_out, rowptr, gs, (int)na, nb, cout,
-                               s.coutP, aggr);
-            GP_LAUNCH_CHECK("k_ra_scale_g");
-            // NT: dZ' = g . P^T
-            rc = gpde_launch_gemm(ra_gemm(gs, P, dZ, nb, (int)s.zrow, s.coutP, s.coutP, s.coutP, (int)s.zrow, 1, 1), st);
-            if (rc != GPDE_OK) return rc;
-            if (want_dp) {                                       // TN: dP (+)= Z'^T . g, Z' of the block recomputed
-                rc = ra_launch_zagg(s, x, hidden, rowptr, src, Z, (int)na, nb, st);
-                if (rc != GPDE_OK) return rc;
-                GpdeGemmArgs g = ra_gemm(Z, gs, dP, (int)s.zrow, cout, nb, (int)s.zrow, s.coutP, s.coutP, 0, 0);
-                g.accumulate = na > 0 ? 1 : 0;
-                rc = gpde_launch_gemm(g, st);
-                if (rc != GPDE_OK) return rc;
-            }
-            hipLaunchKernelGGL(gpde_reassoc_edge_bwd_kernel, dim3((unsigned)nb, RB_SEGS), dim3(256), 0, st, x, hidden, rowptr, src, dZ,
-                               grad_hidden, grad_x ? dxe : (float*)nullptr, (int)na, cin, s.K, s.KP);
-            GP_LAUNCH_CHECK("gpde_reassoc_edge_bwd_kernel");
-        }
-        if (want_dp) {
-            hipLaunchKernelGGL(k_ra_unpermute, dim3((s.KP + 31) / 32, (s.coutP + 31) / 32, cin), dim3(256), 0, st, dP, grad_w_last,
-                               grad_b_last, cout, s.coutP, s.K, s.KP);
-            GP_LAUNCH_CHECK("k_ra_unpermute");
-        }
+    if (n_dst > 0 && !x_dst && (root || grad_root || grad_x_dst)) {
+        gpde_set_error("%s: root / grad_root / grad_x_dst without x_dst: the root term is x_dst . root", who);
+        return GPDE_EINVAL;
     }
-    if (grad_x) {
-        rc = gpde_launch_any_dx_finish(dxe, src_rowptr, src_slots, root, grad_out, grad_x, n_nodes, cin, cout, 1, st);
-        if (rc != GPDE_OK) return rc;
+    int rc = ra_check(who, in_src, out_channels, k_hidden, aggr);
+    if (rc != GPDE_OK) return rc;
+    rc = ra_check_in_dst(who, in_dst);
+    if (rc != GPDE_OK) return rc;
+    const RaShape s = ra_shape(in_src, out_channels, k_hidden);
+    if (n_dst == 0 || n_edges == 0) {                            // no edge: the last Linear received nothing
+        if (grad_w_last) GP_HIP_CHECK(gpde_zero_async(grad_w_last, (size_t)s.cin * s.cout * s.K * 4, st));
+        if (grad_b_last) GP_HIP_CHECK(gpde_zero_async(grad_b_last, (size_t)s.cin * s.cout * 4, st));
     }
-    if (grad_root || grad_bias) {
-        rc = gpde_launch_any_node_grads(x, grad_out, ngp, n_nodes, cin, cout, grad_root, grad_bias, st);
-        if (rc != GPDE_OK) return rc;
+    if (n_dst == 0) {                                            // no destination: sums over nothing, no workspace
+        if (grad_x_src && n_src > 0) GP_HIP_CHECK(gpde_zero_async(grad_x_src, (size_t)n_src * in_src * 4, st));
+        if (grad_root) GP_HIP_CHECK(gpde_zero_async(grad_root, (size_t)in_dst * s.cout * 4, st));
+        if (grad_bias) GP_HIP_CHECK(gpde_zero_async(grad_bias, (size_t)s.cout * 4, st));
+        return GPDE_OK;
     }
-    return GPDE_OK;
+    return ra_bwd_run(who, x_src, n_src, x_dst, n_dst, hidden, n_edges, k_hidden, rowptr, src, w_last, b_last, root, aggr, in_src, in_dst,
+                      out_channels, grad_out, grad_x_src, grad_x_dst, grad_hidden, grad_w_last, grad_b_last, grad_root, grad_bias, src_rowptr,
+                      src_slots, ws, ws_bytes, false, st);
 }

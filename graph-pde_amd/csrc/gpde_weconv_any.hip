@@ -26,6 +26,9 @@
 // Nodes of 2-3 in-edges cost one small wave each; a few hundred in-edges per node are one wave's sequential stream, and the
 // machine is filled by the other nodes' waves (DESIGN.md §3 records the measured rates).
 // All offsets into W_e are size_t: E * cin * cout passes 2^31 at 33 k edges of 256 x 256.
+// Two node sets (gpde_nnconv_*_edgeweights_bip): x_src [n_src][cin] is what the edges gather, x_dst [n_dst][in_dst] enters the root term
+// only (root [in_dst][out]), one wave per DESTINATION; grad_x_src [n_src][cin] is the source sum without a root term, grad_x_dst = g . root^T.
+// The square entry points run the same launches with x_dst = x, in_dst = cin, n_src = n_dst: the same instructions on the same values.
 #include "gpde_common.h"
 
 namespace {
@@ -55,6 +58,7 @@ struct AnyFwdArgs {
     const float* x; const float* we; const int32_t* rowptr; const int32_t* src; const float* root; const float* bias;
     const float* residual; float* out;
     int cin, cout, aggr, relu, LC, lcs, R, ES, B;
+    const float* xd; int cind;      // the DESTINATION node table [n_dst][cind] of the root term (a square call: xd = x, cind = cin)
 };
 
 // the lane's (up to) 4 values of one row: V = 4: columns 4 lc .. 4 lc + 3; V = 1: columns lc, lc + LC, lc + 2 LC, lc + 3 LC
@@ -166,8 +170,9 @@ __global__ __launch_bounds__(64) void gpde_weconv_any_kernel(AnyFwdArgs a) {
         }
     }
     if (a.root && es == 0) {                                     // update(): + x_i . root   (nn_conv.py:279-280)
-        const float* __restrict__ xr = a.x + (size_t)i * cin;
-        for (int c = r; c < cin; c += R) {
+        const int cind = a.cind;                                 // root is [in_dst][out], x_i a row of the destination table
+        const float* __restrict__ xr = a.xd + (size_t)i * cind;
+        for (int c = r; c < cind; c += R) {
             float v[4];
             row_load<V>(v, a.root + (size_t)c * cout, lc, LC, cout, true);
             const float xv = xr[c];
@@ -274,8 +279,10 @@ __global__ __launch_bounds__(64) void gpde_weconv_any_bwd_kernel(AnyBwdArgs a) {
     }
 }
 
-// grad_x[j][c] = (ordered: sum over j's out-edges, ascending CSR slot, of dxe[slot][c]; else what the atomics left in grad_x)
-//                + sum_o root[c][o] g_j[o]                                          one owner per element, sequential sums
+// grad_x[j][c] = (ordered == 1: sum over j's out-edges, ascending CSR slot, of dxe[slot][c]; 0: what the atomics left in grad_x;
+//                 2: nothing) + sum_o root[c][o] g_j[o]                             one owner per element, sequential sums
+// A square call has both terms on one node set.  A rectangular call runs it twice: over the n_src sources with root = NULL
+// (grad_x_src has no root term) and over the n_dst destinations with ordered = 2 (grad_x_dst = g . root^T, cin = in_dst).
 __global__ __launch_bounds__(256) void k_any_dx_finish(const float* __restrict__ dxe, const int32_t* __restrict__ srp,
                                                        const int32_t* __restrict__ ssl, const float* __restrict__ root,
                                                        const float* __restrict__ g, float* __restrict__ dx, int64_t n_nodes,
@@ -285,10 +292,10 @@ __global__ __launch_bounds__(256) void k_any_dx_finish(const float* __restrict__
     const size_t j = idx / cin;
     const int c = (int)(idx - j * cin);
     float s = 0.f;
-    if (ordered) {
+    if (ordered == 1) {
         const int p1 = srp[j + 1];
         for (int p = srp[j]; p < p1; ++p) s += dxe[(size_t)ssl[p] * cin + c];
-    } else {
+    } else if (ordered == 0) {
         s = dx[idx];
     }
     if (root) {
@@ -301,7 +308,7 @@ __global__ __launch_bounds__(256) void k_any_dx_finish(const float* __restrict__
     dx[idx] = s;
 }
 
-// droot = X^T g, dbias = colsum g: strip s of the nodes -> part[s][cin * cout + cout] (one thread per element, nodes in order),
+// droot = X^T g, dbias = colsum g (X the DESTINATION table, cin = in_dst, for a rectangular call): strip s of the nodes -> part[s][cin * cout + cout] (one thread per element, nodes in order),
 // then the strips in order
 __global__ __launch_bounds__(256) void k_any_node_grads(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ part,
                                                         int64_t n_nodes, int64_t strip, int cin, int cout, int do_root, int do_bias) {
@@ -377,6 +384,82 @@ int gpde_launch_any_node_grads(const float* x, const float* g, float* part, int6
     return GPDE_OK;
 }
 
+namespace {
+
+// the launch of both forwards: the square call hands x for both tables
+int any_fwd_launch(const float* x_src, const float* x_dst, int64_t n_dst, const float* edge_weights, const int32_t* rowptr,
+                   const int32_t* src, const float* root, const float* bias, const float* residual, int relu, int aggr, int in_src,
+                   int in_dst, int out_channels, float* out, hipStream_t st) {
+    const bool vec4 = out_channels % 4 == 0 && any_aligned16(edge_weights) && any_aligned16(root) && any_aligned16(bias) &&
+                      any_aligned16(residual) && any_aligned16(out);
+    const bool is_max = aggr == GPDE_AGGR_MAX;
+    const AnyPlan p = any_plan(in_src, out_channels, vec4, is_max);
+    AnyFwdArgs a{x_src, edge_weights, rowptr, src, root, bias, residual, out,
+                 in_src, out_channels, aggr, relu ? 1 : 0, p.LC, p.lcs, p.R, p.ES, p.B, x_dst, in_dst};
+    const dim3 grid((unsigned)n_dst), block(64);
+    if (vec4) {
+        if (is_max) hipLaunchKernelGGL((gpde_weconv_any_kernel<4, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((gpde_weconv_any_kernel<4, false>), grid, block, 0, st, a);
+    } else {
+        if (is_max) hipLaunchKernelGGL((gpde_weconv_any_kernel<1, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((gpde_weconv_any_kernel<1, false>), grid, block, 0, st, a);
+    }
+    GP_LAUNCH_CHECK("gpde_weconv_any_kernel");
+    return GPDE_OK;
+}
+
+// the launches of both backwards after their argument checks.  `square`: one node set - grad_x_src receives the root term in the
+// same k_any_dx_finish launch as the source sum (the order of additions of the square call), grad_x_dst is unused.
+int any_bwd_launch(const float* x_src, int64_t n_src, const float* x_dst, int64_t n_dst, const float* edge_weights, int64_t n_edges,
+                   const int32_t* rowptr, const int32_t* src, const int32_t* src_rowptr, const int32_t* src_slots, const float* root,
+                   int aggr, int cin, int cind, int cout, const float* grad_out, float* grad_x_src, float* grad_x_dst,
+                   float* grad_edge_weights, float* grad_root, float* grad_bias, void* ws, bool square, hipStream_t st) {
+    int rc;
+    char* w = (char*)(((uintptr_t)ws + 255) / 256 * 256);
+    float* dxe = (float*)w;
+    float* part = (float*)(w + any_al((size_t)(n_edges > 0 ? n_edges : 1) * cin * 4));
+    const bool ordered = src_rowptr && src_slots;
+    if (n_edges > 0) {
+        const bool vec4 = cout % 4 == 0 && any_aligned16(edge_weights) && any_aligned16(grad_edge_weights) && any_aligned16(grad_out);
+        const AnyPlan p = any_plan(cin, cout, vec4, false);
+        if (grad_x_src && !ordered) GP_HIP_CHECK(gpde_zero_async(grad_x_src, (size_t)n_src * cin * 4, st));
+        AnyBwdArgs a{x_src, edge_weights, rowptr, src, grad_out, grad_edge_weights, ordered ? dxe : nullptr, grad_x_src, cin, cout, aggr, p.LC, p.lcs, p.R, p.ES};
+        if (!ordered && !grad_x_src) a.dxe = dxe;                // grad_x not wanted: the per-edge rows go to the workspace and are dropped
+        if (vec4) hipLaunchKernelGGL(gpde_weconv_any_bwd_kernel<4>, dim3((unsigned)n_dst), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL(gpde_weconv_any_bwd_kernel<1>, dim3((unsigned)n_dst), dim3(64), 0, st, a);
+        GP_LAUNCH_CHECK("gpde_weconv_any_bwd_kernel");
+    }
+    if (square) {
+        if (grad_x_src) {
+            if (n_edges == 0) GP_HIP_CHECK(gpde_zero_async(grad_x_src, (size_t)n_src * cin * 4, st));      // no edge: the root term alone, added to 0
+            rc = gpde_launch_any_dx_finish(dxe, src_rowptr, src_slots, root, grad_out, grad_x_src, n_src, cin, cout, (ordered && n_edges > 0) ? 1 : 0, st);
+            if (rc != GPDE_OK) return rc;
+        }
+    } else {
+        if (grad_x_src && n_src > 0) {                           // the sources: the sum over their out-edges, no root term
+            if (n_edges == 0) GP_HIP_CHECK(gpde_zero_async(grad_x_src, (size_t)n_src * cin * 4, st));
+            else if (ordered) {
+                rc = gpde_launch_any_dx_finish(dxe, src_rowptr, src_slots, nullptr, nullptr, grad_x_src, n_src, cin, cout, 1, st);
+                if (rc != GPDE_OK) return rc;
+            }                                                    // (atomics: grad_x_src is complete)
+        }
+        if (grad_x_dst) {                                        // the destinations: g . root^T
+            if (!root) GP_HIP_CHECK(gpde_zero_async(grad_x_dst, (size_t)n_dst * cind * 4, st));
+            else {
+                rc = gpde_launch_any_dx_finish(nullptr, nullptr, nullptr, root, grad_out, grad_x_dst, n_dst, cind, cout, 2, st);
+                if (rc != GPDE_OK) return rc;
+            }
+        }
+    }
+    if (grad_root || grad_bias) {
+        rc = gpde_launch_any_node_grads(x_dst, grad_out, part, n_dst, cind, cout, grad_root, grad_bias, st);
+        if (rc != GPDE_OK) return rc;
+    }
+    return GPDE_OK;
+}
+
+}  // namespace
+
 extern "C" int gpde_nnconv_fwd_edgeweights_any(const float* x, int64_t n_nodes, const float* edge_weights, int64_t n_edges,
                                                const int32_t* rowptr, const int32_t* src, const float* root, const float* bias,
                                                const float* residual, int relu, int aggr, int in_channels, int out_channels,
@@ -391,28 +474,51 @@ extern "C" int gpde_nnconv_fwd_edgeweights_any(const float* x, int64_t n_nodes, 
     int rc = any_check_widths("gpde_nnconv_fwd_edgeweights_any", in_channels, out_channels);
     if (rc != GPDE_OK) return rc;
     if (n_nodes == 0) return GPDE_OK;
-    const bool vec4 = out_channels % 4 == 0 && any_aligned16(edge_weights) && any_aligned16(root) && any_aligned16(bias) &&
-                      any_aligned16(residual) && any_aligned16(out);
-    const bool is_max = aggr == GPDE_AGGR_MAX;
-    const AnyPlan p = any_plan(in_channels, out_channels, vec4, is_max);
-    AnyFwdArgs a{x, edge_weights, rowptr, src, root, bias, residual, out,
-                 in_channels, out_channels, aggr, relu ? 1 : 0, p.LC, p.lcs, p.R, p.ES, p.B};
-    const dim3 grid((unsigned)n_nodes), block(64);
-    if (vec4) {
-        if (is_max) hipLaunchKernelGGL((gpde_weconv_any_kernel<4, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((gpde_weconv_any_kernel<4, false>), grid, block, 0, st, a);
-    } else {
-        if (is_max) hipLaunchKernelGGL((gpde_weconv_any_kernel<1, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((gpde_weconv_any_kernel<1, false>), grid, block, 0, st, a);
+    return any_fwd_launch(x, x, n_nodes, edge_weights, rowptr, src, root, bias, residual, relu, aggr, in_channels, in_channels,
+                          out_channels, out, st);
+}
+
+extern "C" int gpde_nnconv_fwd_edgeweights_bip(const float* x_src, int64_t n_src, const float* x_dst, int64_t n_dst,
+                                               const float* edge_weights, int64_t n_edges, const int32_t* rowptr, const int32_t* src,
+                                               const float* root, const float* bias, const float* residual, int relu, int aggr,
+                                               int in_src, int in_dst, int out_channels, float* out, void* stream_) {
+    hipStream_t st = (hipStream_t)stream_;
+    const char* who = "gpde_nnconv_fwd_edgeweights_bip";
+    if (n_src < 0 || n_dst < 0 || n_edges < 0 || !rowptr || (n_dst > 0 && !out) || (n_edges > 0 && (!edge_weights || !src || !x_src)) ||
+        (n_edges > 0 && (n_src == 0 || n_dst == 0)) ||
+        (aggr != GPDE_AGGR_ADD && aggr != GPDE_AGGR_MEAN && aggr != GPDE_AGGR_MAX) || (residual && residual == out) ||
+        n_src >= ((int64_t)1 << 31) || n_dst >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31)) {
+        gpde_set_error("%s: null/negative argument, edges without sources or destinations, unknown aggr or residual aliases out", who);
+        return GPDE_EINVAL;
     }
-    GP_LAUNCH_CHECK("gpde_weconv_any_kernel");
-    return GPDE_OK;
+    if (n_dst > 0 && root && !x_dst) {                           // (no destination: an empty table has no address)
+        gpde_set_error("%s: root without x_dst: the root term is x_dst . root (pass root = NULL for a call without destination features)", who);
+        return GPDE_EINVAL;
+    }
+    int rc = any_check_widths(who, in_src, out_channels);
+    if (rc != GPDE_OK) return rc;
+    if (in_dst < 1 || in_dst > ANY_MAXW) {
+        gpde_set_error("%s: in_dst %d: built for 1 <= in_dst <= %d (GPDE_WECONV_ANY_MAX_WIDTH)", who, in_dst, ANY_MAXW);
+        return GPDE_EUNSUPPORTED;
+    }
+    if (n_dst == 0) return GPDE_OK;
+    return any_fwd_launch(x_src, x_dst, n_dst, edge_weights, rowptr, src, root, bias, residual, relu, aggr, in_src, in_dst, out_channels,
+                          out, st);
 }
 
 extern "C" size_t gpde_nnconv_bwd_edgeweights_any_workspace_bytes(int64_t n_nodes, int64_t n_edges, int in_channels, int out_channels) {
     if (n_nodes < 0 || n_edges < 0 || in_channels < 1 || out_channels < 1 || in_channels > ANY_MAXW || out_channels > ANY_MAXW) return 0;
     return any_al((size_t)(n_edges > 0 ? n_edges : 1) * in_channels * 4) +                                   // dxe [E][cin]
            gpde_any_node_grads_ws_bytes(in_channels, out_channels) + 1024;                                   // droot / dbias partials
+}
+
+extern "C" size_t gpde_nnconv_bwd_edgeweights_bip_workspace_bytes(int64_t n_src, int64_t n_dst, int64_t n_edges, int in_src, int in_dst,
+                                                                  int out_channels) {
+    if (n_src < 0 || n_dst < 0 || n_edges < 0 || in_src < 1 || in_dst < 1 || out_channels < 1 || in_src > ANY_MAXW || in_dst > ANY_MAXW ||
+        out_channels > ANY_MAXW)
+        return 0;
+    return any_al((size_t)(n_edges > 0 ? n_edges : 1) * in_src * 4) +                                        // dxe [E][in_src]
+           gpde_any_node_grads_ws_bytes(in_dst, out_channels) + 1024;                                        // droot [in_dst][out] / dbias partials
 }
 
 extern "C" int gpde_nnconv_edgeweights_any_plan(int in_channels, int out_channels, int vec4, int aggr, int32_t* out) {
@@ -454,29 +560,49 @@ extern "C" int gpde_nnconv_bwd_edgeweights_any(const float* x, int64_t n_nodes, 
         if (grad_bias) GP_HIP_CHECK(gpde_zero_async(grad_bias, (size_t)out_channels * 4, st));
         return GPDE_OK;
     }
-    const int cin = in_channels, cout = out_channels;
-    char* w = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    float* dxe = (float*)w;
-    float* part = (float*)(w + any_al((size_t)(n_edges > 0 ? n_edges : 1) * cin * 4));
-    const bool ordered = src_rowptr && src_slots;
-    if (n_edges > 0) {
-        const bool vec4 = cout % 4 == 0 && any_aligned16(edge_weights) && any_aligned16(grad_edge_weights) && any_aligned16(grad_out);
-        const AnyPlan p = any_plan(cin, cout, vec4, false);
-        if (grad_x && !ordered) GP_HIP_CHECK(gpde_zero_async(grad_x, (size_t)n_nodes * cin * 4, st));
-        AnyBwdArgs a{x, edge_weights, rowptr, src, grad_out, grad_edge_weights, ordered ? dxe : nullptr, grad_x, cin, cout, aggr, p.LC, p.lcs, p.R, p.ES};
-        if (!ordered && !grad_x) a.dxe = dxe;                    // grad_x not wanted: the per-edge rows go to the workspace and are dropped
-        if (vec4) hipLaunchKernelGGL(gpde_weconv_any_bwd_kernel<4>, dim3((unsigned)n_nodes), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL(gpde_weconv_any_bwd_kernel<1>, dim3((unsigned)n_nodes), dim3(64), 0, st, a);
-        GP_LAUNCH_CHECK("gpde_weconv_any_bwd_kernel");
+    return any_bwd_launch(x, n_nodes, x, n_nodes, edge_weights, n_edges, rowptr, src, src_rowptr, src_slots, root, aggr, in_channels,
+                          in_channels, out_channels, grad_out, grad_x, nullptr, grad_edge_weights, grad_root, grad_bias, ws, true, st);
+}
+
+extern "C" int gpde_nnconv_bwd_edgeweights_bip(const float* x_src, int64_t n_src, const float* x_dst, int64_t n_dst,
+                                               const float* edge_weights, int64_t n_edges, const int32_t* rowptr, const int32_t* src,
+                                               const int32_t* src_rowptr, const int32_t* src_slots, const float* root, int aggr,
+                                               int in_src, int in_dst, int out_channels, const float* grad_out, float* grad_x_src,
+                                               float* grad_x_dst, float* grad_edge_weights, float* grad_root, float* grad_bias,
+                                               void* ws, size_t ws_bytes, void* stream_) {
+    hipStream_t st = (hipStream_t)stream_;
+    const char* who = "gpde_nnconv_bwd_edgeweights_bip";
+    if (n_src < 0 || n_dst < 0 || n_edges < 0 || !rowptr || !ws || (n_dst > 0 && !grad_out) ||
+        (n_edges > 0 && (!edge_weights || !src || !grad_edge_weights || !x_src || n_src == 0 || n_dst == 0)) ||
+        n_src >= ((int64_t)1 << 31) || n_dst >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31)) {
+        gpde_set_error("%s: null/negative argument or edges without sources or destinations", who);
+        return GPDE_EINVAL;
     }
-    if (grad_x) {
-        if (n_edges == 0) GP_HIP_CHECK(gpde_zero_async(grad_x, (size_t)n_nodes * cin * 4, st));      // no edge: the root term alone, added to 0
-        rc = gpde_launch_any_dx_finish(dxe, src_rowptr, src_slots, root, grad_out, grad_x, n_nodes, cin, cout, (ordered && n_edges > 0) ? 1 : 0, st);
-        if (rc != GPDE_OK) return rc;
+    if (n_dst > 0 && !x_dst && (root || grad_root || grad_x_dst)) {
+        gpde_set_error("%s: root / grad_root / grad_x_dst without x_dst: the root term is x_dst . root", who);
+        return GPDE_EINVAL;
     }
-    if (grad_root || grad_bias) {
-        rc = gpde_launch_any_node_grads(x, grad_out, part, n_nodes, cin, cout, grad_root, grad_bias, st);
-        if (rc != GPDE_OK) return rc;
+    if (aggr != GPDE_AGGR_ADD && aggr != GPDE_AGGR_MEAN) {
+        gpde_set_error("%s: aggr %d: built for GPDE_AGGR_ADD and GPDE_AGGR_MEAN (the gradient of 'max' is composed by the caller)", who, aggr);
+        return GPDE_EUNSUPPORTED;
     }
-    return GPDE_OK;
+    int rc = any_check_widths(who, in_src, out_channels);
+    if (rc != GPDE_OK) return rc;
+    if (in_dst < 1 || in_dst > ANY_MAXW) {
+        gpde_set_error("%s: in_dst %d: built for 1 <= in_dst <= %d (GPDE_WECONV_ANY_MAX_WIDTH)", who, in_dst, ANY_MAXW);
+        return GPDE_EUNSUPPORTED;
+    }
+    if (ws_bytes < gpde_nnconv_bwd_edgeweights_bip_workspace_bytes(n_src, n_dst, n_edges, in_src, in_dst, out_channels)) {
+        gpde_set_error("%s: workspace too small", who);
+        return GPDE_EWORKSPACE;
+    }
+    if (n_dst == 0) {
+        // no destination: no edge either - every gradient is a sum over nothing
+        if (grad_x_src && n_src > 0) GP_HIP_CHECK(gpde_zero_async(grad_x_src, (size_t)n_src * in_src * 4, st));
+        if (grad_root) GP_HIP_CHECK(gpde_zero_async(grad_root, (size_t)in_dst * out_channels * 4, st));
+        if (grad_bias) GP_HIP_CHECK(gpde_zero_async(grad_bias, (size_t)out_channels * 4, st));
+        return GPDE_OK;
+    }
+    return any_bwd_launch(x_src, n_src, x_dst, n_dst, edge_weights, n_edges, rowptr, src, src_rowptr, src_slots, root, aggr, in_src,
+                          in_dst, out_channels, grad_out, grad_x_src, grad_x_dst, grad_edge_weights, grad_root, grad_bias, ws, false, st);
 }

@@ -23,8 +23,8 @@ from torch.nn import Parameter
 
 from . import hidden_cache, ops
 from . import autograd as _ag
-from .autograd import (HiddenAnyFunction, NNConvDeferredFunction, NNConvFunction, NNConvHiddenFunction, SharedParamFunction, WeConvAnyFunction,
-                       WeConvFunction)
+from .autograd import (HiddenAnyFunction, HiddenBipFunction, NNConvDeferredFunction, NNConvFunction, NNConvHiddenFunction, SharedParamFunction,
+                       WeConvAnyFunction, WeConvBipFunction, WeConvFunction)
 from .message_passing import MessagePassing
 
 
@@ -62,23 +62,36 @@ class NNConv_old(MessagePassing):
     1 <= in_channels, out_channels <= 256 takes the reference's own order for every kernel network: `weight =
     self.nn(pseudo)` by the caller's module ([E, in * out], as nn_conv.py:274 materialises it), then message / aggregate /
     update as ONE native kernel over it (`_propagate_any_width`, csrc/gpde_weconv_any.hip).  Wider raises
-    NotImplementedError."""
+    NotImplementedError.
+
+    Two node sets (torch_geometric.nn.NNConv's bipartite form): `in_channels` may be a pair `(in_src, in_dst)` - `nn` emits
+    in_src * out values per edge, `root` is [in_dst, out] -, `forward` takes `x = (x_src, x_dst)` (x_dst may be None: no root
+    term) and `size = (n_src, n_dst)`, and `edge_index[0]` then indexes the sources, `edge_index[1]` the destinations:
+        out_i = aggr_{e: j -> i} x_src[j] . W_e  (+ x_dst[i] . root)  + bias                          out [n_dst, out_channels]
+    Such a call runs the any-width kernels at every width (`_propagate_rect`; 64 -> 64 included).  Not built for it: a gradient
+    through aggr='max', `ops.NodeAttr` attributes, the hidden / edge-weight caches and the shared launch of `nnconv_group`.
+    `flow='target_to_source'` swaps the two rows of `edge_index` (read in place through a negative row stride, no copy) at every
+    width."""
 
     def __init__(self, in_channels, out_channels, nn, aggr="add", root_weight=True, bias=True,
                  **kwargs):
         flow = kwargs.pop("flow", "source_to_target")
-        if flow != "source_to_target":
-            raise NotImplementedError("only flow='source_to_target' (the reference default) is built")
+        if flow not in ("source_to_target", "target_to_source"):
+            raise ValueError(f"flow must be 'source_to_target' or 'target_to_source', got {flow!r}")
         if kwargs:
             raise TypeError(f"unexpected arguments {sorted(kwargs)}")
         if aggr not in ("add", "mean", "max"):
             raise ValueError(f"aggr must be 'add', 'mean' or 'max' (nn_conv.py:222-224), got {aggr!r}")
         super().__init__(aggr=aggr, flow=flow)                     # nn_conv.py:242
+        if isinstance(in_channels, (tuple, list)):
+            if len(in_channels) != 2:
+                raise ValueError(f"in_channels must be an int or a pair (in_src, in_dst), got {in_channels!r}")
+            in_channels = (in_channels[0], in_channels[1])
         self.in_channels = in_channels
         self.out_channels = out_channels
         self.nn = nn
         if root_weight:
-            self.root = Parameter(torch.Tensor(in_channels, out_channels))
+            self.root = Parameter(torch.Tensor(self._in_dst(), out_channels))
         else:
             self.register_parameter("root", None)
         if bias:
@@ -97,22 +110,115 @@ class NNConv_old(MessagePassing):
 
     def reset_parameters(self):                       # nn_conv.py:261-265
         _reset(self.nn)
-        size = self.in_channels
+        size = self._in_src()
         _uniform(size, self.root)
         _uniform(size, self.bias)
 
-    def forward(self, x, edge_index, edge_attr, *, residual=None, activation=None):      # nn_conv.py:267-271
-        """The reference signature `forward(x, edge_index, edge_attr)`.  Two keyword-only, opt-in extras fuse the
+    def _in_src(self):
+        return self.in_channels[0] if isinstance(self.in_channels, tuple) else self.in_channels
+
+    def _in_dst(self):
+        return self.in_channels[1] if isinstance(self.in_channels, tuple) else self.in_channels
+
+    def _flipped(self) -> bool:
+        return self.flow == "target_to_source"
+
+    def _rect_call(self, x, size, residual=None):
+        """Whether `forward(x, ..., size)` / `propagate(..., size=, x=)` is a call between two node sets, validated without a device:
+        None for today's square call (a tensor, or a pair of the SAME tensor, with `size` square or None, on a module of one
+        width), else (x_src, x_dst, n_src, n_dst)."""
+        pair = isinstance(x, (tuple, list))
+        if pair and len(x) != 2:
+            raise ValueError(f"x must be a tensor or a pair (x_src, x_dst), got {len(x)} entries")
+        x_src, x_dst = (x[0], x[1]) if pair else (x, x)
+        if not torch.is_tensor(x_src) or not (x_dst is None or torch.is_tensor(x_dst)):
+            raise ValueError("x must be a tensor or a pair (x_src tensor, x_dst tensor or None)")
+        if size is not None:
+            sz = list(size) if isinstance(size, (list, tuple)) else [size, size]
+            if len(sz) != 2:
+                raise ValueError(f"size must be (n_src, n_dst), got {size!r}")
+            sz = [None if v is None else int(v) for v in sz]
+        else:
+            sz = [None, None]
+        x_src = x_src.unsqueeze(-1) if x_src.dim() == 1 else x_src
+        if x_dst is not None and x_dst.dim() == 1:
+            x_dst = x_dst.unsqueeze(-1)
+        n = int(x_src.size(0))
+        same = (not pair) or (x[1] is x[0])
+        if same and not isinstance(self.in_channels, tuple) and all(v is None or v == n for v in sz):
+            return None
+        if sz[0] is not None and sz[0] != n:
+            raise ValueError(f"size[0] = {sz[0]} but x_src has {n} rows")
+        if x_dst is not None and sz[1] is not None and sz[1] != int(x_dst.size(0)):
+            raise ValueError(f"size[1] = {sz[1]} but x_dst has {int(x_dst.size(0))} rows")
+        if sz[1] is not None:
+            n_dst = sz[1]
+        elif x_dst is not None:
+            n_dst = int(x_dst.size(0))
+        else:
+            raise ValueError("the number of destination nodes is unknown: give size=(n_src, n_dst) or x_dst (it is not guessed from the "
+                             "largest index of edge_index)")
+        if n < 0 or n_dst < 0:
+            raise ValueError(f"size must be non-negative, got ({n}, {n_dst})")
+        cs, cd, co = self._in_src(), self._in_dst(), self.out_channels
+        if x_src.dim() != 2 or x_src.size(1) != cs:
+            raise ValueError(f"x_src must be [n_src, {cs}] (in_channels of the sources), got {tuple(x_src.shape)}")
+        if x_dst is not None and (x_dst.dim() != 2 or x_dst.size(1) != cd):
+            raise ValueError(f"x_dst must be [n_dst, {cd}] (in_channels of the destinations), got {tuple(x_dst.shape)}")
+        if residual is not None and tuple(residual.shape) != (n_dst, co):
+            raise ValueError(f"residual must be [n_dst, out_channels] = [{n_dst}, {co}], got {tuple(residual.shape)}")
+        return x_src, x_dst, n, n_dst
+
+    def _flow_csr(self, edge_index, x):
+        """flow='target_to_source': the operator runs on `edge_index` with its rows swapped.  The destination CSR of the swapped
+        list, built (and cached) from the caller's tensor in place; every square path takes a `Csr` where it takes edge_index."""
+        if isinstance(edge_index, ops.Csr):
+            if edge_index._flow_flipped:
+                return edge_index
+            raise NotImplementedError("flow='target_to_source' with a destination CSR (ops.Csr): a CSR has its direction built in - "
+                                      "pass the edge_index tensor")
+        dev = x.device if x.is_cuda else ops.staging_device()
+        return ops.csr_for(edge_index if edge_index.device == dev else ops.stage_const(edge_index, dev), x.size(0), flip=True)
+
+    def _generic_propagate(self, edge_index, x, pseudo):
+        """PyG's own chain (MessagePassing.propagate) for a gradient through aggr='max'.  It applies `flow` itself: a CSR built
+        with the rows swapped is handed back as the caller's list, its per-edge rows in slot order."""
+        if isinstance(edge_index, ops.Csr):
+            csr = edge_index
+            edge_index = csr.edge_index
+            if csr._flow_flipped:
+                edge_index = edge_index.flip(0)
+                pseudo = pseudo.index_select(0, csr.perm.long().to(pseudo.device))
+        return MessagePassing.propagate(self, edge_index.to(x.device), x=x, pseudo=pseudo)
+
+    def forward(self, x, edge_index, edge_attr, *, size=None, residual=None, activation=None):      # nn_conv.py:267-271
+        """The reference signature `forward(x, edge_index, edge_attr)`; `x` may be a pair `(x_src, x_dst)` and `size=` the pair
+        `(n_src, n_dst)` (torch_geometric.nn.NNConv: a graph between two node sets, class docstring; `size` is keyword-only here:
+        the positional parameters are the reference's three).  Two more keyword-only, opt-in extras fuse the
         callers' elementwise glue into the operator's last kernel: `residual` (a [N, 64] tensor
         added to the result) and `activation="relu"` - `conv(x, ei, ea, residual=x, activation="relu")` equals
         `F.relu(x + conv(x, ei, ea))` (MGKN_general_darcy2d.py:79-80).  Fused for inference on device tensors;
         when a gradient is needed the same value is composed from the unfused operator and torch ops."""
         if activation not in (None, "relu"):
             raise ValueError(f"activation must be None or 'relu', got {activation!r}")
+        rect = self._rect_call(x, size, residual)
+        if rect is not None:
+            if isinstance(edge_attr, ops.NodeAttr):
+                raise NotImplementedError("ops.NodeAttr attributes on a call between two node sets are not built: a node table addresses ONE "
+                                          "node set - pass the edge_attr tensor")
+            pseudo = edge_attr.unsqueeze(-1) if edge_attr.dim() == 1 else edge_attr
+            with ops.ver_scope():
+                return self._propagate_rect(rect[0], rect[1], rect[2], rect[3], edge_index, pseudo, residual, activation == "relu")
+        if isinstance(x, (tuple, list)):
+            x = x[0]
         with ops.ver_scope():        # (inference tensors: one content checksum per tensor and call, shared by all cache keys)
             return self._forward(x, edge_index, edge_attr, residual, activation)
 
     def _forward(self, x, edge_index, edge_attr, residual, activation):
+        if self._flipped() and not (isinstance(edge_index, ops.Csr) and edge_index._flow_flipped):
+            if isinstance(edge_attr, ops.NodeAttr):
+                raise NotImplementedError("ops.NodeAttr attributes with flow='target_to_source' are not built - pass the edge_attr tensor")
+            edge_index = self._flow_csr(edge_index, x.unsqueeze(-1) if x.dim() == 1 else x)
         if residual is not None or activation is not None:
             return self._forward_act(x, edge_index, edge_attr, residual, activation == "relu")
         x = x.unsqueeze(-1) if x.dim() == 1 else x
@@ -160,12 +266,22 @@ class NNConv_old(MessagePassing):
         if set(kwargs) != {"x", "pseudo"}:
             raise TypeError(f"propagate() takes x= and pseudo= (nn_conv.py:271), got {sorted(kwargs)}")
         x, pseudo = kwargs["x"], kwargs["pseudo"]
+        rect = self._rect_call(x, size)
+        if rect is not None:
+            # two node sets: `propagate(edge_index, size=(n_src, n_dst), x=(x_src, x_dst), pseudo=...)`
+            if isinstance(pseudo, ops.NodeAttr):
+                raise NotImplementedError("ops.NodeAttr attributes on a call between two node sets are not built: a node table addresses ONE "
+                                          "node set - pass the edge_attr tensor")
+            pseudo = pseudo.unsqueeze(-1) if pseudo.dim() == 1 else pseudo
+            return self._propagate_rect(rect[0], rect[1], rect[2], rect[3], edge_index, pseudo, None, False)
+        if isinstance(x, (tuple, list)):
+            x = x[0]
         x = x.unsqueeze(-1) if x.dim() == 1 else x
         pseudo = pseudo.unsqueeze(-1) if pseudo.dim() == 1 else pseudo
-        if size is not None:
-            sz = list(size) if isinstance(size, (list, tuple)) else [size, size]
-            if any(v is not None and int(v) != x.size(0) for v in sz):
-                raise NotImplementedError("bipartite propagate (size != [N, N]) is not built: no graph-pde script uses it")
+        if self._flipped() and not (isinstance(edge_index, ops.Csr) and edge_index._flow_flipped):
+            if isinstance(pseudo, ops.NodeAttr):
+                raise NotImplementedError("ops.NodeAttr attributes with flow='target_to_source' are not built - pass the edge_attr tensor")
+            edge_index = self._flow_csr(edge_index, x)
         if not self._is_width_64():
             return self._propagate_any_width(x, edge_index, pseudo)
         if not x.is_cuda:
@@ -194,6 +310,8 @@ class NNConv_old(MessagePassing):
         carries back into `nn`).  The operator itself never leaves libgpde.so; what cannot be fused is the caller's network."""
         self._check_width()
         if self.aggr not in ("add", "mean"):
+            if self._flipped():
+                return self._generic_propagate(edge_index, x, pseudo)
             return MessagePassing.propagate(self, edge_index.edge_index if isinstance(edge_index, ops.Csr) else edge_index, x=x, pseudo=pseudo)
         if x.dtype != torch.float32:
             raise NotImplementedError(f"a kernel network outside the Linear / ReLU chain: float32 only (x is {x.dtype})")
@@ -282,6 +400,8 @@ class NNConv_old(MessagePassing):
             raise NotImplementedError(f"widths other than {ops.WIDTH} -> {ops.WIDTH}: float32 only (x is {x.dtype})")
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or pseudo.requires_grad or any(p.requires_grad for p in self.parameters()))
         if self.aggr == "max" and needs_grad:
+            if self._flipped():
+                return self._generic_propagate(edge_index, x, pseudo)
             return MessagePassing.propagate(self, edge_index.edge_index if isinstance(edge_index, ops.Csr) else edge_index, x=x, pseudo=pseudo)
         dev = x.device if x.is_cuda else ops.staging_device()
         if isinstance(edge_index, ops.Csr):
@@ -358,6 +478,86 @@ class NNConv_old(MessagePassing):
             out = torch.relu(out)
         return out.to(x.device)
 
+    def _propagate_rect(self, x_src, x_dst, n_src, n_dst, edge_index, pseudo, residual, relu):
+        """propagate() BETWEEN TWO NODE SETS: sources x_src [n_src, in_src], destinations x_dst [n_dst, in_dst] or None, edges
+        (edge_index[0] in [0, n_src)) -> (edge_index[1] in [0, n_dst)) (rows swapped under flow='target_to_source'), out
+        [n_dst, out].  The two routes of `_propagate_any_width` at EVERY width, 64 -> 64 included, on the rectangular entry points
+        (gpde_nnconv_*_edgeweights_bip / gpde_nnconv_*_hidden_bip; ops.any_width_route decides with n_dst as its node count):
+        `nn(pseudo)` or the hidden layers by the caller's module on rows in CSR slot order, CPU tensors staged around the
+        operator, `residual` [n_dst, out] / `relu` fused into the materialised inference call and composed from torch ops
+        otherwise.  x_dst None: no root term although the module may have a root (PyG's rule)."""
+        cin, cind, cout = self._in_src(), self._in_dst(), self.out_channels
+        if not (ops.width_supported(cin, cout) and ops.width_supported(cind, cout)):
+            raise NotImplementedError(f"the MI355X operator is built for 1 <= in_channels, out_channels <= {ops.ANY_MAX_WIDTH}, got "
+                                      f"{self.in_channels}->{self.out_channels}")
+        cin, cind, cout = int(cin), int(cind), int(cout)
+        tensors = [t for t in (x_src, x_dst, residual) if t is not None]
+        if any(t.dtype != torch.float32 for t in tensors):
+            raise NotImplementedError(f"a call between two node sets: float32 only (got {[str(t.dtype) for t in tensors]})")
+        needs_grad = torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or pseudo.requires_grad or
+                                                  any(p.requires_grad for p in self.parameters()))
+        if self.aggr == "max" and needs_grad:
+            raise NotImplementedError("aggr='max' with a gradient on a call between two node sets is not built (inference runs natively: "
+                                      "call under torch.no_grad())")
+        dev = x_src.device if x_src.is_cuda else ops.staging_device()
+        if isinstance(edge_index, ops.Csr):
+            if self._flipped() and not edge_index._flow_flipped:
+                raise NotImplementedError("flow='target_to_source' with a destination CSR (ops.Csr): a CSR has its direction built in - "
+                                          "pass the edge_index tensor")
+            csr = ops.csr_for(edge_index, n_dst, n_src=n_src)
+        else:
+            csr = ops.csr_for(edge_index if edge_index.device == dev else ops.stage_const(edge_index, dev), n_dst, n_src=n_src,
+                              flip=self._flipped())
+        if pseudo.size(0) != csr.n_edges:
+            raise ValueError(f"edge_attr has {pseudo.size(0)} rows, edge_index {csr.n_edges} edges")
+        need = csr.n_edges * cin * cout * 4
+        free, _ = ops.device_free_bytes(dev)
+        lin = ops.mlp_linears(self.nn) if self._nn_is_linear_relu_chain() else None
+        chain = lin is not None and lin[-1].out_features == cin * cout
+        route = ops.any_width_route(n_dst, csr.n_edges, cin, cout, lin[-1].in_features if chain else None, self.aggr, chain, free)
+        if route["route"] == "refused":
+            raise RuntimeError(f"{self!r}: a call between two node sets materialises the per-edge weights as the reference does (nn_conv.py:274) - "
+                               f"{csr.n_edges} edges x {cin} x {cout} x 4 B = {need / 2**30:.2f} GiB (twice that with gradients), "
+                               f"{free / 2**30:.2f} GiB free (GPDE_ANY_REASSOC={ops.ANY_REASSOC})")
+
+        def on_dev(t):
+            if t is None or t.device == dev:
+                return t
+            return t.to(dev) if needs_grad and t.requires_grad else ops.stage_const(t, dev)
+        # rows in CSR slot order (the order the kernels address W_e / H in); `nn` acts row by row
+        pseudo_s = pseudo if bool(getattr(csr, "_perm_is_identity", False)) else pseudo.index_select(0, csr.perm.long().to(pseudo.device))
+        root, bias = (None if x_dst is None else on_dev(self.root)), on_dev(self.bias)
+        xs_d = x_src.to(dev) if needs_grad else x_src.detach().to(dev)
+        xd_d = None if x_dst is None else (x_dst.to(dev) if needs_grad else x_dst.detach().to(dev))
+        fused = False
+        if route["route"] == "reassociated":
+            h = pseudo_s
+            for l in lin[:-1]:
+                h = torch.relu(torch.nn.functional.linear(h, l.weight, l.bias))
+            hidden = h.float().to(dev).contiguous()
+            w_last, b_last = on_dev(lin[-1].weight).float(), None if lin[-1].bias is None else on_dev(lin[-1].bias).float()
+            if needs_grad:
+                out = HiddenBipFunction.apply(xs_d, xd_d, hidden, w_last, b_last, csr, root, bias, self.aggr)
+            else:
+                out = ops.nnconv_forward_hidden_bip_raw(xs_d, xd_d, csr, hidden.detach(), w_last, b_last, root, bias, self.aggr)
+        else:
+            weight = self.nn(pseudo_s)
+            if weight.dim() != 2 or weight.size(0) != csr.n_edges or weight.size(1) != cin * cout:
+                raise ValueError(f"nn(pseudo) must be [E, {cin * cout}] = [{csr.n_edges}, in_src * out_channels] (nn_conv.py:274), got {tuple(weight.shape)}")
+            weight = weight.float().to(dev).contiguous()
+            if needs_grad:
+                out = WeConvBipFunction.apply(xs_d, xd_d, weight, csr, root, bias, self.aggr)
+            else:
+                out = ops.nnconv_forward_edgeweights_bip_raw(xs_d, xd_d, csr, weight.detach(), root, bias, self.aggr,
+                                                             residual=None if residual is None else residual.detach().to(dev), relu=relu)
+                fused = True
+        if not fused:
+            if residual is not None:
+                out = residual.to(dev) + out
+            if relu:
+                out = torch.relu(out)
+        return out.to(x_src.device)
+
     def _propagate(self, x, edge_index, pseudo, weights, biases, root, bias, use_hidden_cache):
         """propagate() of the reference (gather, message, aggregate, update) as ONE native operator on device
         tensors; `weights / biases / root / bias` are the tensors to use (the module's own, or staged copies)."""
@@ -368,6 +568,8 @@ class NNConv_old(MessagePassing):
             # a gradient through 'max' (no graph-pde script uses it; a freshly built module in grad mode lands here): PyG's own
             # chain - gather, `message`, segment max, `update` - with the native `message()` / `update()`,
             # both differentiable; the fused inference kernel serves no_grad calls
+            if self._flipped():
+                return self._generic_propagate(edge_index, x, pseudo)
             if isinstance(edge_index, ops.Csr):
                 edge_index = edge_index.edge_index
             return MessagePassing.propagate(self, edge_index, x=x, pseudo=pseudo)
@@ -567,6 +769,10 @@ def nnconv_group(calls):
         if activation not in (None, "relu"):
             raise ValueError(f"activation must be None or 'relu', got {activation!r}")
         call = None
+        if isinstance(x, (tuple, list)) or isinstance(conv.in_channels, tuple) or conv.flow != "source_to_target":
+            # a call between two node sets (or with the rows swapped) runs on its own: the shared launch is built for square calls
+            outs[k] = conv(x, edge_index, edge_attr, residual=residual, activation=activation)
+            continue
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad) or
                                                   (torch.is_tensor(edge_attr) and edge_attr.requires_grad) or
                                                   any(p.requires_grad for p in conv.parameters()))

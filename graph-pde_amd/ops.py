@@ -36,6 +36,14 @@ class Csr:
     _identity: Optional[torch.Tensor] = None
     _perm_is_identity: bool = False
     _max_in_degree: Optional[int] = None
+    n_src_nodes: Optional[int] = None        # a RECTANGULAR graph: `src` indexes this many source nodes, `n_nodes` counts the destination
+    #                                          rows (rowptr has n_nodes + 1 entries); None: square, one node set
+    _flow_flipped: bool = False              # built from edge_index with its rows swapped (flow='target_to_source' of the module)
+
+    @property
+    def n_src(self) -> int:
+        """Number of SOURCE nodes: `n_src_nodes` of a rectangular graph, `n_nodes` of a square one."""
+        return self.n_nodes if self.n_src_nodes is None else int(self.n_src_nodes)
 
     @property
     def max_in_degree(self) -> int:
@@ -55,12 +63,13 @@ class Csr:
         if self._src_order is None:
             lib = _lib.lib()
             dev = self.rowptr.device
-            srp = torch.empty(self.n_nodes + 1, dtype=torch.int32, device=dev)
+            n_src = self.n_src                    # (a rectangular graph: the order runs over its source nodes)
+            srp = torch.empty(n_src + 1, dtype=torch.int32, device=dev)
             ssl = torch.empty(max(self.n_edges, 1), dtype=torch.int32, device=dev)
-            nbytes = int(lib.gpde_csr_workspace_bytes(self.n_edges, self.n_nodes))
+            nbytes = int(lib.gpde_csr_workspace_bytes(self.n_edges, n_src))
             ws = _alloc_ws(nbytes, dev)
             with torch.cuda.device(dev):
-                rc = lib.gpde_csr_source_order(self.src.data_ptr(), self.n_edges, self.n_nodes, srp.data_ptr(),
+                rc = lib.gpde_csr_source_order(self.src.data_ptr(), self.n_edges, n_src, srp.data_ptr(),
                                                ssl.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
             _lib.check(rc, "gpde_csr_source_order")
             self._src_order = (srp, ssl)
@@ -254,11 +263,16 @@ def _require_cuda(t, name: str):
             "(no CPU / composite fallback exists by design)")
 
 
-def build_csr(edge_index: torch.Tensor, n_nodes: int) -> Csr:
-    """gpde_csr_from_coo on the current stream. `edge_index` int64 [2,E], any strides."""
+def build_csr(edge_index: torch.Tensor, n_nodes: int, n_src: Optional[int] = None, flip: bool = False) -> Csr:
+    """gpde_csr_from_coo on the current stream. `edge_index` int64 [2,E], any strides.
+    `n_src`: the graph is RECTANGULAR - row 0 indexes n_src source nodes, row 1 the n_nodes destinations (gpde_csr_from_coo2).
+    `flip`: the rows swapped (row 1 = sources, row 0 = destinations: flow='target_to_source') - the library reads the same
+    memory through a negative row stride, no copy is made."""
     _require_cuda(edge_index, "edge_index")
     if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
         raise ValueError(f"edge_index must be int64 [2,E], got {edge_index.dtype} {tuple(edge_index.shape)}")
+    if n_src is not None or flip:
+        return _build_csr_general(edge_index, int(n_nodes), None if n_src is None else int(n_src), bool(flip))
     lib = _lib.lib()
     dev = edge_index.device
     e = int(edge_index.size(1))
@@ -285,13 +299,48 @@ def build_csr(edge_index: torch.Tensor, n_nodes: int) -> Csr:
     return Csr(n_nodes, e, rowptr, src, dst, perm, _max_in_degree=max_deg)
 
 
+def _build_csr_general(edge_index: torch.Tensor, n_dst: int, n_src: Optional[int], flip: bool) -> Csr:
+    """build_csr of a rectangular graph and / or of edge_index with its rows swapped (gpde_csr_from_coo2)."""
+    lib = _lib.lib()
+    dev = edge_index.device
+    e = int(edge_index.size(1))
+    ns = n_dst if n_src is None else n_src
+    if e == 0:
+        z = torch.zeros(0, dtype=torch.int32, device=dev)
+        return Csr(n_dst, 0, torch.zeros(n_dst + 1, dtype=torch.int32, device=dev), z, z.clone(), z.clone(), n_src_nodes=n_src,
+                   _flow_flipped=flip)
+    rowptr = torch.empty(n_dst + 1, dtype=torch.int32, device=dev)
+    src, dst, perm = (torch.empty(e, dtype=torch.int32, device=dev) for _ in range(3))
+    n_bad = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = int(lib.gpde_csr_workspace_bytes(e, max(ns, n_dst)))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    # rows swapped: start at row 1 and step back one row - the strides of the C call are signed
+    base, s_row = edge_index.data_ptr(), edge_index.stride(0)
+    if flip:
+        base, s_row = base + s_row * edge_index.element_size(), -s_row
+    with torch.cuda.device(dev):
+        rc = lib.gpde_csr_from_coo2(base, s_row, edge_index.stride(1), e, ns, n_dst, rowptr.data_ptr(), src.data_ptr(), dst.data_ptr(),
+                                    perm.data_ptr(), n_bad.data_ptr(), ws.data_ptr(), ws_bytes, _stream_ptr(dev))
+    _lib.check(rc, "gpde_csr_from_coo2")
+    bad, max_deg = (int(v) for v in torch.stack([n_bad[0], (rowptr[1:] - rowptr[:-1]).max() if n_dst > 0 else n_bad[0] * 0]).cpu())
+    if bad:
+        r_src, r_dst = (1, 0) if flip else (0, 1)
+        bs = int(((edge_index[r_src] < 0) | (edge_index[r_src] >= ns)).sum())
+        bd = int(((edge_index[r_dst] < 0) | (edge_index[r_dst] >= n_dst)).sum())
+        sides = ([f"{bs} edges with a source (row {r_src}) outside [0, {ns})"] if bs else []) + \
+                ([f"{bd} edges with a destination (row {r_dst}) outside [0, {n_dst})"] if bd else [])
+        raise IndexError("edge_index has " + " and ".join(sides))
+    return Csr(n_dst, e, rowptr, src, dst, perm, _max_in_degree=max_deg, n_src_nodes=n_src, _flow_flipped=flip)
+
+
 _csr_cache: "dict[tuple, tuple]" = {}      # key -> (storage kept alive, nbytes, Csr); LRU order
 _CSR_CACHE_MAX_ENTRIES = 64
 _CSR_CACHE_MAX_BYTES = 8 << 30
 
 
-def csr_for(edge_index: torch.Tensor, n_nodes: int) -> Csr:
-    """Cached CSR: the reference calls the same conv `depth` times with the same edge_index
+def csr_for(edge_index: torch.Tensor, n_nodes: int, n_src: Optional[int] = None, flip: bool = False) -> Csr:
+    """Cached CSR (`n_src`: a rectangular graph of n_src sources and n_nodes destinations; `flip`: rows swapped - build_csr;
+    both are part of the key, and a `Csr` handed in is checked against both node counts):: the reference calls the same conv `depth` times with the same edge_index
     (UAI1_full_resolution.py:29-30), and MGKN re-slices the same tensors every V-cycle
     (MGKN_general_darcy2d.py:79-89).  Key = storage pointer, offset, shape, strides, in-place
     version counter, node count.  The entry keeps the index storage alive so that its address
@@ -299,16 +348,20 @@ def csr_for(edge_index: torch.Tensor, n_nodes: int) -> Csr:
     if isinstance(edge_index, Csr):          # a graph that already is a destination CSR (radius_csr, parallel.partition_rows_by_position)
         if edge_index.n_nodes != n_nodes:
             raise ValueError(f"the CSR was built for {edge_index.n_nodes} nodes, x has {n_nodes} rows")
+        if edge_index.n_src != (n_nodes if n_src is None else int(n_src)):
+            raise ValueError(f"the CSR was built for {edge_index.n_src} source nodes, the call has {n_nodes if n_src is None else int(n_src)}")
         return edge_index
     storage = edge_index.untyped_storage()
     watch(edge_index)
     key = (str(edge_index.device), storage.data_ptr(), edge_index.storage_offset(),
            tuple(edge_index.shape), tuple(edge_index.stride()), _ver(edge_index), n_nodes)
+    if n_src is not None or flip:
+        key = key + (None if n_src is None else int(n_src), bool(flip))
     hit = _csr_cache.pop(key, None)
     if hit is not None:
         _csr_cache[key] = hit            # move to the MRU end
         return hit[2]
-    csr = build_csr(edge_index, n_nodes)
+    csr = build_csr(edge_index, n_nodes, n_src, flip)
     _csr_cache[key] = (storage, storage.nbytes(), csr)
     while len(_csr_cache) > _CSR_CACHE_MAX_ENTRIES or \
             (len(_csr_cache) > 1 and sum(v[1] for v in _csr_cache.values()) > _CSR_CACHE_MAX_BYTES):
@@ -1576,6 +1629,190 @@ def nnconv_backward_hidden_any_raw(x, csr: Csr, hidden, w_last, b_last, root, ag
     return gx, gh, gwl, gbl, groot, gbias
 
 
+# ... between two node sets (include/gpde.h gpde_nnconv_*_edgeweights_bip / gpde_nnconv_*_hidden_bip): the any-width operators on a
+# RECTANGULAR graph - x_src [n_src, in_src] gathered by the edges, x_dst [n_dst, in_dst] (or None) in the root term, out [n_dst, out]
+def _bip_args(x_src, x_dst, csr: Csr, root, per_edge, per_edge_name: str):
+    """Shapes of a rectangular call checked; (in_src, in_dst, out_channels or None).  `per_edge`: W_e [E, in_src * out] or H [E, K]."""
+    n_src, n_dst, e = csr.n_src, csr.n_nodes, csr.n_edges
+    if x_src.dtype != torch.float32 or x_src.dim() != 2 or x_src.size(0) != n_src or x_src.size(1) < 1:
+        raise ValueError(f"x_src must be float32 [{n_src}, in_src], got {x_src.dtype} {tuple(x_src.shape)}")
+    dev, cin = x_src.device, int(x_src.size(1))
+    if x_dst is not None and (x_dst.dtype != torch.float32 or x_dst.dim() != 2 or x_dst.size(0) != n_dst or x_dst.size(1) < 1 or x_dst.device != dev):
+        raise ValueError(f"x_dst must be float32 [{n_dst}, in_dst] on {dev}, got {x_dst.dtype} {tuple(x_dst.shape)}")
+    cind = cin if x_dst is None else int(x_dst.size(1))
+    if per_edge.dtype != torch.float32 or per_edge.dim() != 2 or per_edge.size(0) != e or per_edge.size(1) < 1 or not per_edge.is_contiguous() or \
+            per_edge.device != dev:
+        raise ValueError(f"{per_edge_name} must be contiguous float32 [{e}, .] on {dev}, got {per_edge.dtype} {tuple(per_edge.shape)}")
+    if root is not None and x_dst is None:
+        raise ValueError("root without x_dst: the root term is x_dst . root (pass root=None for a call without destination features)")
+    if root is not None and (root.dtype != torch.float32 or root.dim() != 2 or root.size(0) != cind or root.device != dev):
+        raise ValueError(f"root must be float32 [{cind}, out_channels] on {dev}, got {root.dtype} {tuple(root.shape)}")
+    return cin, cind
+
+
+def _bip_check_widths(cin: int, cind: int, cout: int):
+    if not (width_supported(cin, cout) and width_supported(cind, cout)):
+        raise NotImplementedError(f"(in_src {cin}, in_dst {cind}) -> out_channels {cout}: the native operator is built for widths 1 .. {ANY_MAX_WIDTH}")
+
+
+def nnconv_forward_edgeweights_bip_raw(x_src, x_dst, csr: Csr, edge_weights, root, bias, aggr: str, residual=None, relu: bool = False) -> torch.Tensor:
+    """gpde_nnconv_fwd_edgeweights_bip: the operator between two node sets given the per-edge weights [E, in_src * out] (CSR slot
+    order) - gather from x_src, message, add / mean / max over the n_dst destinations, + x_dst . root + bias (+ residual
+    [n_dst, out], ReLU) in one launch.  `x_dst` None: no root term (root must be None)."""
+    lib = _lib.lib()
+    _require_cuda(x_src, "x_src")
+    if aggr not in _AGGR_WE:
+        raise NotImplementedError(f"aggr={aggr!r}")
+    xs = x_src.detach().contiguous()
+    xd = None if x_dst is None else x_dst.detach().contiguous()
+    we = edge_weights.detach()
+    root_c = None if root is None else root.detach().contiguous()
+    bias_c = None if bias is None else bias.detach().contiguous()
+    cin, cind = _bip_args(xs, xd, csr, root_c, we, "edge_weights")
+    if we.size(1) % cin != 0:
+        raise ValueError(f"edge_weights must be [{csr.n_edges}, {cin} * out_channels], got {tuple(we.shape)}")
+    cout = int(we.size(1)) // cin
+    _bip_check_widths(cin, cind, cout)
+    n_src, n_dst, e, dev = csr.n_src, csr.n_nodes, csr.n_edges, xs.device
+    if root_c is not None and root_c.size(1) != cout:
+        raise ValueError(f"root must be [{cind},{cout}], got {tuple(root_c.shape)}")
+    if bias_c is not None and (bias_c.dtype != torch.float32 or tuple(bias_c.shape) != (cout,) or bias_c.device != dev):
+        raise ValueError(f"bias must be float32 [{cout}] on {dev}, got {bias_c.dtype} {tuple(bias_c.shape)}")
+    res = None
+    if residual is not None:
+        _require_cuda(residual, "residual")
+        if residual.dtype != torch.float32 or tuple(residual.shape) != (n_dst, cout) or residual.device != dev:
+            raise ValueError(f"residual must be float32 [{n_dst},{cout}] on {dev}, got {residual.dtype} {tuple(residual.shape)}")
+        res = residual.detach().contiguous()
+    out = torch.empty(n_dst, cout, dtype=torch.float32, device=dev)
+    p = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        rc = lib.gpde_nnconv_fwd_edgeweights_bip(xs.data_ptr(), n_src, p(xd), n_dst, we.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(),
+                                                 p(root_c), p(bias_c), p(res), 1 if relu else 0, _AGGR_WE[aggr], cin, cind, cout,
+                                                 out.data_ptr(), _stream_ptr(dev))
+    _lib.check(rc, "gpde_nnconv_fwd_edgeweights_bip")
+    _lib.n_native_calls += 1
+    return out
+
+
+def nnconv_backward_edgeweights_bip_raw(x_src, x_dst, csr: Csr, edge_weights, root, aggr: str, grad_out, need_x_src: bool = True,
+                                        need_x_dst: bool = True, need_root: bool = True, need_bias: bool = True):
+    """gpde_nnconv_bwd_edgeweights_bip ('add' / 'mean').  Returns (grad_x_src [n_src, in_src], grad_x_dst [n_dst, in_dst],
+    grad_edge_weights [E, in_src * out], grad_root [in_dst, out], grad_bias [out]); an output that is not needed or has no input
+    (x_dst / root None) is None."""
+    lib = _lib.lib()
+    for t, nm in ((x_src, "x_src"), (edge_weights, "edge_weights"), (grad_out, "grad_out")):
+        _require_cuda(t, nm)
+    if aggr not in _AGGR:
+        raise NotImplementedError(f"aggr={aggr!r}: the gradient of the per-edge weight operator is built for 'add' and 'mean'")
+    xs = x_src.detach().contiguous()
+    xd = None if x_dst is None else x_dst.detach().contiguous()
+    we = edge_weights.detach()
+    root_c = None if root is None else root.detach().contiguous()
+    cin, cind = _bip_args(xs, xd, csr, root_c, we, "edge_weights")
+    if we.size(1) % cin != 0:
+        raise ValueError(f"edge_weights must be [{csr.n_edges}, {cin} * out_channels], got {tuple(we.shape)}")
+    cout = int(we.size(1)) // cin
+    _bip_check_widths(cin, cind, cout)
+    n_src, n_dst, e, dev = csr.n_src, csr.n_nodes, csr.n_edges, xs.device
+    grad_out = grad_out.detach().contiguous().float()
+    if tuple(grad_out.shape) != (n_dst, cout):
+        raise ValueError(f"grad_out must be [{n_dst},{cout}], got {tuple(grad_out.shape)}")
+    new = lambda want, *shape: torch.empty(*shape, dtype=torch.float32, device=dev) if want else None
+    gxs, gxd = new(need_x_src, n_src, cin), new(need_x_dst and xd is not None, n_dst, cind)
+    gwe = new(True, e, cin * cout)
+    groot, gbias = new(need_root and root is not None, cind, cout), new(need_bias, cout)
+    ws = _alloc_ws(int(lib.gpde_nnconv_bwd_edgeweights_bip_workspace_bytes(n_src, n_dst, e, cin, cind, cout)), dev)
+    srp, ssl = csr.src_order if (need_x_src and e > 0) else (None, None)
+    p = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        rc = lib.gpde_nnconv_bwd_edgeweights_bip(xs.data_ptr(), n_src, p(xd), n_dst, we.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(),
+                                                 p(srp), p(ssl), p(root_c), _AGGR[aggr], cin, cind, cout, grad_out.data_ptr(), p(gxs), p(gxd),
+                                                 gwe.data_ptr(), p(groot), p(gbias), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+    _lib.check(rc, "gpde_nnconv_bwd_edgeweights_bip")
+    _lib.n_native_calls += 1
+    return gxs, gxd, gwe, groot, gbias
+
+
+def _hidden_bip_args(xs, xd, csr: Csr, hid, wl, bl, root_c):
+    cin, cind = _bip_args(xs, xd, csr, root_c, hid, "hidden")
+    k, dev = int(hid.size(1)), xs.device
+    if wl.dtype != torch.float32 or wl.dim() != 2 or wl.size(1) != k or wl.size(0) % cin != 0 or wl.size(0) == 0 or wl.device != dev:
+        raise ValueError(f"w_last must be float32 [{cin} * out_channels, {k}] on {dev}, got {wl.dtype} {tuple(wl.shape)}")
+    cout = int(wl.size(0)) // cin
+    if bl is not None and (bl.dtype != torch.float32 or tuple(bl.shape) != (cin * cout,) or bl.device != dev):
+        raise ValueError(f"b_last must be float32 [{cin * cout}] on {dev}, got {bl.dtype} {tuple(bl.shape)}")
+    if root_c is not None and root_c.size(1) != cout:
+        raise ValueError(f"root must be [{cind},{cout}], got {tuple(root_c.shape)}")
+    _bip_check_widths(cin, cind, cout)
+    if k > ANY_MAX_HIDDEN:
+        raise NotImplementedError(f"last hidden width {k}: the re-associated any-width operator is built for 1 .. {ANY_MAX_HIDDEN}")
+    return cin, cind, cout, k
+
+
+def nnconv_forward_hidden_bip_raw(x_src, x_dst, csr: Csr, hidden, w_last, b_last, root, bias, aggr: str, ws_bytes: Optional[int] = None) -> torch.Tensor:
+    """gpde_nnconv_fwd_hidden_bip: the re-associated operator between two node sets given the last hidden activations [E, K] (CSR
+    slot order) and the last Linear (w_last [in_src * out, K], b_last) - Z' per destination, last Linear per destination,
+    + x_dst . root + bias.  'add' / 'mean'."""
+    lib = _lib.lib()
+    for t, nm in ((x_src, "x_src"), (hidden, "hidden"), (w_last, "w_last")):
+        _require_cuda(t, nm)
+    if aggr not in _AGGR:
+        raise NotImplementedError(f"aggr={aggr!r}: the re-associated operator is built for 'add' and 'mean'")
+    xs, hid, wl = x_src.detach().contiguous(), hidden.detach(), w_last.detach().contiguous()
+    xd, bl, root_c, bias_c = (None if t is None else t.detach().contiguous() for t in (x_dst, b_last, root, bias))
+    cin, cind, cout, k = _hidden_bip_args(xs, xd, csr, hid, wl, bl, root_c)
+    n_src, n_dst, e, dev = csr.n_src, csr.n_nodes, csr.n_edges, xs.device
+    if bias_c is not None and (bias_c.dtype != torch.float32 or tuple(bias_c.shape) != (cout,) or bias_c.device != dev):
+        raise ValueError(f"bias must be float32 [{cout}] on {dev}, got {bias_c.dtype} {tuple(bias_c.shape)}")
+    query = lambda n, ee, ci, co, kk: lib.gpde_nnconv_fwd_hidden_bip_workspace_bytes(n, ee, ci, co, kk)
+    ws = _alloc_ws(_hidden_any_ws_bytes(query, n_dst, e, cin, cout, k, dev) if ws_bytes is None else int(ws_bytes), dev)
+    out = torch.empty(n_dst, cout, dtype=torch.float32, device=dev)
+    p = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        rc = lib.gpde_nnconv_fwd_hidden_bip(xs.data_ptr(), n_src, p(xd), n_dst, hid.data_ptr(), e, k, csr.rowptr.data_ptr(), csr.src.data_ptr(),
+                                            wl.data_ptr(), p(bl), p(root_c), p(bias_c), _AGGR[aggr], cin, cind, cout, out.data_ptr(),
+                                            ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+    _lib.check(rc, "gpde_nnconv_fwd_hidden_bip")
+    _lib.n_native_calls += 1
+    return out
+
+
+def nnconv_backward_hidden_bip_raw(x_src, x_dst, csr: Csr, hidden, w_last, b_last, root, aggr: str, grad_out, need_x_src: bool = True,
+                                   need_x_dst: bool = True, need_w_last: bool = True, need_b_last: bool = True, need_root: bool = True,
+                                   need_bias: bool = True, ws_bytes: Optional[int] = None):
+    """gpde_nnconv_bwd_hidden_bip.  Returns (grad_x_src, grad_x_dst, grad_hidden [E, K], grad_w_last, grad_b_last, grad_root
+    [in_dst, out], grad_bias); an output that is not needed or has no input is None."""
+    lib = _lib.lib()
+    for t, nm in ((x_src, "x_src"), (hidden, "hidden"), (w_last, "w_last"), (grad_out, "grad_out")):
+        _require_cuda(t, nm)
+    if aggr not in _AGGR:
+        raise NotImplementedError(f"aggr={aggr!r}: the re-associated operator is built for 'add' and 'mean'")
+    xs, hid, wl = x_src.detach().contiguous(), hidden.detach(), w_last.detach().contiguous()
+    xd, bl, root_c = (None if t is None else t.detach().contiguous() for t in (x_dst, b_last, root))
+    cin, cind, cout, k = _hidden_bip_args(xs, xd, csr, hid, wl, bl, root_c)
+    n_src, n_dst, e, dev = csr.n_src, csr.n_nodes, csr.n_edges, xs.device
+    grad_out = grad_out.detach().contiguous().float()
+    if tuple(grad_out.shape) != (n_dst, cout):
+        raise ValueError(f"grad_out must be [{n_dst},{cout}], got {tuple(grad_out.shape)}")
+    new = lambda want, *shape: torch.empty(*shape, dtype=torch.float32, device=dev) if want else None
+    gxs, gxd, gh = new(need_x_src, n_src, cin), new(need_x_dst and xd is not None, n_dst, cind), new(True, e, k)
+    gwl, gbl = new(need_w_last, cin * cout, k), new(need_b_last and b_last is not None, cin * cout)
+    groot, gbias = new(need_root and root is not None, cind, cout), new(need_bias, cout)
+    query = lambda n, ee, ci, co, kk: lib.gpde_nnconv_bwd_hidden_bip_workspace_bytes(n, ee, ci, cind, co, kk)
+    ws = _alloc_ws(_hidden_any_ws_bytes(query, n_dst, e, cin, cout, k, dev) if ws_bytes is None else int(ws_bytes), dev)
+    srp, ssl = csr.src_order if (need_x_src and e > 0) else (None, None)
+    p = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        rc = lib.gpde_nnconv_bwd_hidden_bip(xs.data_ptr(), n_src, p(xd), n_dst, hid.data_ptr(), e, k, csr.rowptr.data_ptr(), csr.src.data_ptr(),
+                                            wl.data_ptr(), p(bl), p(root_c), _AGGR[aggr], cin, cind, cout, grad_out.data_ptr(), p(gxs), p(gxd),
+                                            gh.data_ptr(), p(gwl), p(gbl), p(groot), p(gbias), p(srp), p(ssl), ws.data_ptr(), ws.numel(),
+                                            _stream_ptr(dev))
+    _lib.check(rc, "gpde_nnconv_bwd_hidden_bip")
+    _lib.n_native_calls += 1
+    return gxs, gxd, gh, gwl, gbl, groot, gbias
+
+
 def edge_weights_backward_raw(grad_we: torch.Tensor, hidden: torch.Tensor, dims: Sequence[int], w_last: torch.Tensor,
                               need_b: bool = True):
     """gpde_edge_weights_bwd: (grad_hidden [E, K2P] already masked by hidden > 0, grad_w_last, grad_b_last or None) from the
@@ -1846,13 +2083,18 @@ def radius_in_degrees(pos: torch.Tensor, r: float, reference_ties: bool = False,
     return deg
 
 
-def radius_csr(pos: torch.Tensor, r: float, reference_ties: bool = False) -> Csr:
+def radius_csr(pos: torch.Tensor, r: float, reference_ties: bool = False, pos_dst: Optional[torch.Tensor] = None) -> Csr:
     """The radius graph of one point set as the `Csr` the operator consumes (no edge_index, no sort): rowptr / src / dst
     are what `csr_for(radius_graph(pos, r), n)` builds - bit for bit - and `perm` is the identity: per-edge tensors for
     this graph are laid out by CSR slot (`csr.edge_index` is the edge list in that order), or not needed at all
     (`NodeAttr`).  Replaces ball_connectivity + the per-call index handling of PyG (utilities.py:250-255, nn_conv.py:271)."""
-    rowptr, src, dst = radius_csr_raw(pos, r, reference_ties)
+    rowptr, src, dst = radius_csr_raw(pos, r, reference_ties, pos_dst)
     e = int(src.numel())
+    if pos_dst is not None:
+        # two point sets: the RECTANGULAR Csr of edges (j in pos -> i in pos_dst) - what csr_for(radius_graph(pos, r, pos_dst=...),
+        # n_dst, n_src=n_src) builds, bit for bit; consumed by the module as conv((x_src, x_dst), csr, edge_attr)
+        return Csr(int(rowptr.numel()) - 1, e, rowptr, src, dst, torch.arange(e, dtype=torch.int32, device=src.device),
+                   n_src_nodes=int(pos.size(0)))
     return Csr(int(rowptr.numel()) - 1, e, rowptr, src, dst, torch.arange(e, dtype=torch.int32, device=src.device))
 
 

@@ -107,6 +107,14 @@ GPDE_API int gpde_csr_from_coo(const int64_t* edge_index, int64_t stride_row, in
                       int64_t n_edges, int64_t n_nodes, int32_t* rowptr, int32_t* src,
                       int32_t* dst, int32_t* perm, int32_t* n_bad, void* ws, size_t ws_bytes,
                       void* stream);
+/* The same for a RECTANGULAR edge list - sources j in [0, n_src), destinations i in [0, n_dst), two different node sets (PyG's
+ * `propagate(edge_index, size=(n_src, n_dst), x=(x_src, x_dst))`): rowptr has n_dst + 1 entries, src[] indexes the n_src sources.
+ * Row 0 of edge_index is checked against [0, n_src) and row 1 against [0, n_dst); n_bad counts the edges that violate either.
+ * The same stable order; with n_src == n_dst the four arrays are those of gpde_csr_from_coo bit for bit (one body serves both).
+ * Workspace: gpde_csr_workspace_bytes(n_edges, max(n_src, n_dst)).  An addition to the ABI: GPDE_VERSION is unchanged. */
+GPDE_API int gpde_csr_from_coo2(const int64_t* edge_index, int64_t stride_row, int64_t stride_col, int64_t n_edges,
+                       int64_t n_src, int64_t n_dst, int32_t* rowptr, int32_t* src, int32_t* dst, int32_t* perm,
+                       int32_t* n_bad, void* ws, size_t ws_bytes, void* stream);
 /* out[s][0..k) = rows[perm[s]][0..k) for the n CSR slots: a per-edge tensor (edge_attr [E][k0], the `pseudo` of
  * nn_conv.py:271) laid out by CSR slot, once per (graph, tensor), so that the fused kernels stream it instead of chasing
  * perm (8 column slices x one cache line per edge otherwise).  Same values: results are bit-identical. */
@@ -249,7 +257,9 @@ GPDE_API int gpde_nnconv_bwd(const float* x, int64_t n_nodes, const float* edge_
  * the 1e-7 level, like the reference's index_select backward on a GPU); with it the per-edge contributions are written out
  * and summed per source in ascending slot order by one owner per element.  Weight gradients are ordered either way. */
 /* src_slots = CSR slots 0..E-1 stably sorted by their source node, src_rowptr[j] = first position of source j;
- * `src` is the array gpde_csr_from_coo wrote; workspace: gpde_csr_workspace_bytes(n_edges, n_nodes). */
+ * `src` is the array gpde_csr_from_coo wrote; workspace: gpde_csr_workspace_bytes(n_edges, n_nodes).
+ * `n_nodes` counts the SOURCE nodes: for a rectangular graph (gpde_csr_from_coo2) pass n_src - src_rowptr then has n_src + 1
+ * entries, which is what the *_bip backward entry points take. */
 GPDE_API int gpde_csr_source_order(const int32_t* src, int64_t n_edges, int64_t n_nodes, int32_t* src_rowptr,
                           int32_t* src_slots, void* ws, size_t ws_bytes, void* stream);
 
@@ -509,6 +519,55 @@ GPDE_API int gpde_nnconv_bwd_hidden_any(const float* x, int64_t n_nodes, const f
                                float* grad_x, float* grad_hidden, float* grad_w_last, float* grad_b_last, float* grad_root,
                                float* grad_bias, const int32_t* src_rowptr, const int32_t* src_slots, void* ws, size_t ws_bytes,
                                void* stream);
+
+/* The two any-width operators BETWEEN TWO NODE SETS (bipartite graphs; torch_geometric.nn.NNConv's `x = (x_src, x_dst)`,
+ * `size = (n_src, n_dst)`, `in_channels = (in_src, in_dst)`): evaluation of the kernel integral at query points, restriction /
+ * prolongation between the levels of a V-cycle.  Edges (j in [0, n_src)) -> (i in [0, n_dst)), the CSR of gpde_csr_from_coo2:
+ *     out_i = aggr_{e: j -> i} x_src[j] . W_e  (+ x_dst[i] . root when x_dst and root are given)  + bias        out [n_dst][out]
+ *   x_src [n_src][in_src], x_dst [n_dst][in_dst] or NULL (PyG: `x_r = x[1]; if x_r is not None and root_weight: out += lin(x_r)`),
+ *   W_e [in_src][out] per edge, root [in_dst][out] or NULL, residual [n_dst][out] or NULL.  The arguments are those of the `_any`
+ *   entry points above with the node table split in two; the SAME kernels run (the square entry points hand x_dst = x, in_dst =
+ *   in_src, n_src = n_dst to them), so a rectangular call on a graph that happens to be square gives the square call's bits.
+ *   Backward outputs: grad_x_src [n_src][in_src] - the sum over each source's out-edges, ascending slot order when src_rowptr /
+ *   src_slots OVER n_src (gpde_csr_source_order(src, n_edges, n_src, ...)) are given, else fp32 atomics (edge-weight form; the
+ *   hidden form requires them with grad_x_src when n_edges > 0); it has NO root term - grad_x_dst [n_dst][in_dst] = g . root^T
+ *   (zero without root), grad_root [in_dst][out] = x_dst^T g, grad_bias = colsum g; the others as in `_any`.  Any of grad_x_src /
+ *   grad_x_dst / grad_root / grad_bias may be NULL.
+ *   Errors: root, grad_root or grad_x_dst != NULL with x_dst == NULL and n_dst > 0: GPDE_EINVAL; in_dst outside 1 .. GPDE_WECONV_ANY_MAX_WIDTH
+ *   (also when x_dst == NULL: pass in_src): GPDE_EUNSUPPORTED; GPDE_AGGR_MAX in a backward (and in the hidden form): GPDE_EUNSUPPORTED.
+ *   n_src == 0, n_dst == 0 and n_edges == 0 are valid calls (edges need both sets non-empty: GPDE_EINVAL otherwise).
+ *   Workspaces: the *_bip_workspace_bytes queries (the forward of the hidden form depends on n_dst and in_src only); the node
+ *   blocks of the hidden form walk the n_dst destinations, Z' is [in_src][k_hidden + 1] per destination.
+ * The same documented properties: plain fp32 fmaf, two-level sums, no atomics except an un-ordered grad_x_src, a summation order
+ * fixed by the shapes.  Additions to the ABI: GPDE_VERSION is unchanged. */
+GPDE_API int gpde_nnconv_fwd_edgeweights_bip(const float* x_src, int64_t n_src, const float* x_dst, int64_t n_dst,
+                                    const float* edge_weights, int64_t n_edges, const int32_t* rowptr, const int32_t* src,
+                                    const float* root, const float* bias, const float* residual, int relu, int aggr,
+                                    int in_src, int in_dst, int out_channels, float* out, void* stream);
+GPDE_API size_t gpde_nnconv_bwd_edgeweights_bip_workspace_bytes(int64_t n_src, int64_t n_dst, int64_t n_edges, int in_src,
+                                                       int in_dst, int out_channels);
+GPDE_API int gpde_nnconv_bwd_edgeweights_bip(const float* x_src, int64_t n_src, const float* x_dst, int64_t n_dst,
+                                    const float* edge_weights, int64_t n_edges, const int32_t* rowptr, const int32_t* src,
+                                    const int32_t* src_rowptr, const int32_t* src_slots, const float* root, int aggr,
+                                    int in_src, int in_dst, int out_channels, const float* grad_out, float* grad_x_src,
+                                    float* grad_x_dst, float* grad_edge_weights, float* grad_root, float* grad_bias,
+                                    void* ws, size_t ws_bytes, void* stream);
+GPDE_API size_t gpde_nnconv_fwd_hidden_bip_workspace_bytes(int64_t n_dst, int64_t n_edges, int in_src, int out_channels,
+                                                  int k_hidden);
+GPDE_API int gpde_nnconv_fwd_hidden_bip(const float* x_src, int64_t n_src, const float* x_dst, int64_t n_dst,
+                               const float* hidden, int64_t n_edges, int k_hidden, const int32_t* rowptr,
+                               const int32_t* src, const float* w_last, const float* b_last, const float* root,
+                               const float* bias, int aggr, int in_src, int in_dst, int out_channels, float* out,
+                               void* ws, size_t ws_bytes, void* stream);
+GPDE_API size_t gpde_nnconv_bwd_hidden_bip_workspace_bytes(int64_t n_dst, int64_t n_edges, int in_src, int in_dst,
+                                                  int out_channels, int k_hidden);
+GPDE_API int gpde_nnconv_bwd_hidden_bip(const float* x_src, int64_t n_src, const float* x_dst, int64_t n_dst,
+                               const float* hidden, int64_t n_edges, int k_hidden, const int32_t* rowptr,
+                               const int32_t* src, const float* w_last, const float* b_last, const float* root, int aggr,
+                               int in_src, int in_dst, int out_channels, const float* grad_out, float* grad_x_src,
+                               float* grad_x_dst, float* grad_hidden, float* grad_w_last, float* grad_b_last,
+                               float* grad_root, float* grad_bias, const int32_t* src_rowptr, const int32_t* src_slots,
+                               void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Edge attributes on the fly (opt-in): the `node_attr` argument (GpdeNodeAttr, declared at the top).
