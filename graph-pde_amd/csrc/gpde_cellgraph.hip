@@ -65,6 +65,28 @@ __global__ void k_cell_start(const uint32_t* __restrict__ sorted_cell, int n, in
     start[c] = lo;
 }
 
+// One wave's row in LDS, sorted by source id (distinct keys): bitonic, padded with sentinels to a power of two.
+__device__ __forceinline__ void sort_row_by_source(uint32_t* row, int n_row, int lane) {
+    int np2 = 64;
+    while (np2 < n_row) np2 <<= 1;
+    for (int t = n_row + lane; t < np2; t += 64) row[t] = 0xffffffffu;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // LDS operations of one wave execute in order: a
+    __builtin_amdgcn_wave_barrier();                             // compiler fence is all the exchange between lanes needs
+    for (int k = 2; k <= np2; k <<= 1)
+        for (int jj = k >> 1; jj > 0; jj >>= 1) {
+            for (int t = lane; t < np2; t += 64) {
+                const int p = t ^ jj;
+                if (p > t) {
+                    const uint32_t a = row[t], b = row[p];
+                    const bool up = (t & k) == 0;
+                    if ((a > b) == up) { row[t] = b; row[p] = a; }
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+}
+
 template <bool FILL, bool TIES>
 __global__ __launch_bounds__(256) void k_cell_neighbors(const double* __restrict__ ps, const double* __restrict__ pd, int nd,
                                                         CellGrid g, double r2, double d2_max, int same_set,
@@ -140,26 +162,179 @@ __global__ __launch_bounds__(256) void k_cell_neighbors(const double* __restrict
         return;
     }
     if (in_lds) {
-        // bitonic sort of the row by source id (distinct keys), padded with sentinels to a power of two
-        int np2 = 64;
-        while (np2 < n_row) np2 <<= 1;
-        for (int t = n_row + lane; t < np2; t += 64) row[t] = 0xffffffffu;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // LDS operations of one wave execute in order: a
-        __builtin_amdgcn_wave_barrier();                             // compiler fence is all the exchange between lanes needs
-        for (int k = 2; k <= np2; k <<= 1)
-            for (int jj = k >> 1; jj > 0; jj >>= 1) {
-                for (int t = lane; t < np2; t += 64) {
-                    const int p = t ^ jj;
-                    if (p > t) {
-                        const uint32_t a = row[t], b = row[p];
-                        const bool up = (t & k) == 0;
-                        if ((a > b) == up) { row[t] = b; row[p] = a; }
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
+        sort_row_by_source(row, n_row, lane);
         for (int t = lane; t < n_row; t += 64) src[r0 + t] = (int32_t)row[t];
+    }
+    for (int t = lane; t < n_row; t += 64) dst[r0 + t] = i;
+}
+
+// ---- periodic (torus) arm: gpde_radius_csr_periodic_* ---------------------------------------------------------------------
+// The same cell list on a box whose axes may wrap: the reference's torus problems (TorusGridSplitter.torus_connectivity,
+// torus1d_connectivity, Burgers with is_periodic) join points across the seam and feed the kernel network the WRAPPED
+// displacement.  Axis k with period[k] = L > 0 is periodic from origin[k]; period[k] = 0 is an open axis (the arithmetic of
+// the open kernel).  Sibling kernels: the open ones above keep their code.
+//   binning   a point is reduced into [origin, origin + L) (x - L floor((x - o) / L), float64) and the reduced sources are
+//             kept in the workspace; nc = floor(L / r) cells of edge L / nc >= r tile the period exactly;
+//   walk      the distinct members of {c - 1, c, c + 1} mod nc, each once.  From 3 cells on, the cell across the seam is a
+//             whole period away: its image shift is the same for every candidate of the cell - it moves the DESTINATION
+//             (one wave-uniform value per neighbour cell) and the lanes subtract as in the open kernel.  With nc <= 2 the
+//             cells c - 1 and c + 1 are one cell that holds points on both sides: visited once, nearest image per candidate;
+//   distance  exact float64 sum of squares of the minimum-image differences against r^2; 2 r < L (checked on the host)
+//             makes the nearest image unique, so a pair gives at most one edge;
+//   geometry  optional, fill pass: geom[slot] = (pos_src[j] - image(pos_dst[i])) per axis and its norm, float64 rounded
+//             once to float32 - the [dx, dy, |d|] columns of TorusGridSplitter.get_data, in slot order.
+struct PeriodicGrid {
+    CellGrid cells;             // lo = origin on periodic axes
+    double per[3], half[3];     // period (0: open axis) and period / 2
+    int wrap[3];                // 0 open, 1 periodic with >= 3 cells (one shift per neighbour cell), 2 periodic with <= 2 (per candidate)
+};
+
+__device__ __forceinline__ double reduce_into_period(double x, double o, double L) {
+    return L > 0.0 ? x - L * floor((x - o) / L) : x;
+}
+
+// x_src - (the image of x_dst nearest to x_src): the image is chosen by comparison, the difference is taken once - the same
+// operation the walk performs with the shift of a neighbour cell, so both give the same bits for an edge
+__device__ __forceinline__ double nearest_image_diff(double xs, double xd, double L, double half) {
+    const double raw = xs - xd;
+    const double xim = raw > half ? xd + L : (raw < -half ? xd - L : xd);
+    return xs - xim;
+}
+
+__global__ void k_cell_ids_periodic(const double* __restrict__ pos, int n, PeriodicGrid g, double* __restrict__ reduced,
+                                    uint32_t* __restrict__ cell, uint32_t* __restrict__ id) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int dim = g.cells.dim;
+    double p[3] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < dim; ++k) {
+        p[k] = reduce_into_period(pos[(size_t)j * dim + k], g.cells.lo[k], g.per[k]);
+        reduced[(size_t)j * dim + k] = p[k];
+    }
+    int c[3];
+    cell_of(g.cells, p, c);
+    cell[j] = (uint32_t)((c[2] * g.cells.nc[1] + c[1]) * g.cells.nc[0] + c[0]);
+    id[j] = (uint32_t)j;
+}
+
+// The cells one axis contributes to the walk of a destination in cell c: a0 .. a1 as they lie, then (extra >= 0) the one
+// cell across the seam, whose points are nearest after moving by `shift`.
+struct AxisWalk { int a0, a1, extra; double shift; };
+
+__device__ __forceinline__ AxisWalk axis_walk(const PeriodicGrid& g, int k, int c) {
+    const int nc = g.cells.nc[k];
+    AxisWalk w;
+    w.extra = -1;
+    w.shift = 0.0;
+    if (g.wrap[k] == 2) { w.a0 = 0; w.a1 = nc - 1; return w; }         // 1 or 2 cells: all of them, once
+    w.a0 = max(c - 1, 0);
+    w.a1 = min(c + 1, nc - 1);
+    if (g.wrap[k] == 1) {
+        if (c == 0) { w.extra = nc - 1; w.shift = -g.per[k]; }         // its sources are nearest one period down
+        else if (c == nc - 1) { w.extra = 0; w.shift = g.per[k]; }
+    }
+    return w;
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_cell_neighbors_periodic(const double* __restrict__ ps /* reduced sources */,
+                                                                 const double* __restrict__ pd, int nd, PeriodicGrid g, double r2,
+                                                                 const int32_t* __restrict__ cell_start, const uint32_t* __restrict__ order,
+                                                                 int32_t* __restrict__ deg, const int32_t* __restrict__ rowptr,
+                                                                 int32_t* __restrict__ src, int32_t* __restrict__ dst, float* __restrict__ geom) {
+    extern __shared__ uint32_t sbuf[];                  // FILL: [4 waves][CG_SORT_MAX]
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // provably wave-uniform: the destination, its cell and the
+    const int i = blockIdx.x * 4 + wave;                                  // image shifts below live in scalar registers
+    if (i >= nd) return;
+    const int dim = g.cells.dim;
+    double pi[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (k < dim) pi[k] = reduce_into_period(pd[(size_t)i * dim + k], g.cells.lo[k], g.per[k]);
+    int ci[3];
+    cell_of(g.cells, pi, ci);
+    const int r0 = FILL ? rowptr[i] : 0;
+    const int n_row = FILL ? rowptr[i + 1] - r0 : 0;
+    const bool in_lds = FILL && n_row <= CG_SORT_MAX;
+    const bool want_geom = FILL && geom != nullptr;
+    uint32_t* row = sbuf + wave * CG_SORT_MAX;
+    const AxisWalk wx = axis_walk(g, 0, ci[0]), wy = axis_walk(g, 1, ci[1]), wz = axis_walk(g, 2, ci[2]);
+    double pim[3];                                      // the destination's image for the cells being walked
+    int count = 0;
+    for (int tz = wz.a0; tz <= wz.a1 + (wz.extra >= 0 ? 1 : 0); ++tz) {
+        const int cz = tz > wz.a1 ? wz.extra : tz;
+        pim[2] = tz > wz.a1 ? pi[2] - wz.shift : pi[2];
+        for (int ty = wy.a0; ty <= wy.a1 + (wy.extra >= 0 ? 1 : 0); ++ty) {
+            const int cy = ty > wy.a1 ? wy.extra : ty;
+            pim[1] = ty > wy.a1 ? pi[1] - wy.shift : pi[1];
+            const int base = (cz * g.cells.nc[1] + cy) * g.cells.nc[0];
+            // the x-neighbours that lie as they are form one range of the sorted list; the cell across the seam is a second one
+            for (int tx = 0; tx <= (wx.extra >= 0 ? 1 : 0); ++tx) {
+                const int cx0 = tx ? wx.extra : wx.a0, cx1 = tx ? wx.extra : wx.a1;
+                pim[0] = tx ? pi[0] - wx.shift : pi[0];
+                const int p0 = cell_start[base + cx0], p1 = cell_start[base + cx1 + 1];
+                for (int q0 = p0; q0 < p1; q0 += 64) {
+                    const int q = q0 + lane;
+                    bool hit = false;
+                    int j = 0;
+                    double d[3] = {0.0, 0.0, 0.0}, d2 = 0.0;
+                    if (q < p1) {
+                        j = (int)order[q];
+#pragma unroll
+                        for (int k = 0; k < 3; ++k)
+                            if (k < dim) {
+                                const double x = ps[(size_t)j * dim + k];
+                                d[k] = g.wrap[k] == 2 ? nearest_image_diff(x, pi[k], g.per[k], g.half[k]) : x - pim[k];
+                                d2 += d[k] * d[k];
+                            }
+                        hit = d2 <= r2;
+                    }
+                    const unsigned long long m = __ballot(hit);
+                    if (FILL && hit) {
+                        const int slot = count + __popcll(m & ((1ull << lane) - 1ull));
+                        if (slot < n_row) {
+                            if (in_lds) row[slot] = (uint32_t)j;
+                            else {                            // very long rows: cell order (deterministic, not ascending)
+                                src[r0 + slot] = j;
+                                if (want_geom) {
+                                    float* gs = geom + (size_t)(r0 + slot) * (dim + 1);
+#pragma unroll
+                                    for (int k = 0; k < 3; ++k)
+                                        if (k < dim) gs[k] = (float)d[k];
+                                    gs[dim] = (float)sqrt(d2);
+                                }
+                            }
+                        }
+                    }
+                    count += __popcll(m);
+                }
+            }
+        }
+    }
+    if (!FILL) {
+        if (lane == 0) deg[i] = count;
+        return;
+    }
+    if (in_lds) {
+        sort_row_by_source(row, n_row, lane);
+        for (int t = lane; t < n_row; t += 64) {
+            const int j = (int)row[t];
+            src[r0 + t] = j;
+            if (want_geom) {                                  // the slot of an edge is known only now: its difference again
+                float* gs = geom + (size_t)(r0 + t) * (dim + 1);
+                double d2 = 0.0;
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    if (k < dim) {
+                        const double x = ps[(size_t)j * dim + k];
+                        const double dk = g.wrap[k] ? nearest_image_diff(x, pi[k], g.per[k], g.half[k]) : x - pi[k];
+                        gs[k] = (float)dk;
+                        d2 += dk * dk;
+                    }
+                gs[dim] = (float)sqrt(d2);
+            }
+        }
     }
     for (int t = lane; t < n_row; t += 64) dst[r0 + t] = i;
 }
@@ -203,9 +378,10 @@ int sort_bits_for(int64_t ncells) {
     return bits;
 }
 
-struct CellWs { uint32_t *cell, *id, *cell_sorted, *order; int32_t* start; void* temp; size_t temp_bytes; size_t total; };
+struct CellWs { uint32_t *cell, *id, *cell_sorted, *order; int32_t* start; void* temp; size_t temp_bytes; size_t total;
+                double* reduced; /* periodic arm: the sources reduced into the period, [n_src][dim] */ };
 
-CellWs carve(void* ws, int64_t n_src, int64_t ncells) {
+CellWs carve(void* ws, int64_t n_src, int64_t ncells, size_t reduced_bytes = 0) {
     CellWs w{};
     size_t tb = 0;
     (void)rocprim::radix_sort_pairs(nullptr, tb, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
@@ -218,6 +394,7 @@ CellWs carve(void* ws, int64_t n_src, int64_t ncells) {
     w.order = (uint32_t*)p; p += a;
     w.start = (int32_t*)p; p += al256((size_t)(ncells + 1) * 4);
     w.temp = p; w.temp_bytes = tb; p += al256(tb);
+    w.reduced = (double*)p; p += al256(reduced_bytes);
     w.total = (size_t)(p - (char*)ws) + 256;
     return w;
 }
@@ -295,5 +472,136 @@ extern "C" int gpde_radius_csr_fill(const double* pos_src, int64_t n_src, const 
         hipLaunchKernelGGL((k_cell_neighbors<true, false>), grid, block, lds, st, pos_src, pos_dst, (int)n_dst, g, r * r, sqrt_threshold(r),
                            same, w.start, w.order, (int32_t*)nullptr, rowptr, src, dst);
     GP_LAUNCH_CHECK("gpde_radius_csr_fill kernels");
+    return GPDE_OK;
+}
+
+// ---- periodic arm: host side ------------------------------------------------------------------------------------------------
+namespace {
+
+// Every argument error of the periodic entry points that the scalars and the two host arrays show, before anything else is looked at.
+int check_periodic(const char* what, int dim, double r, const double* origin, const double* period) {
+    if (dim < 1 || dim > 3) { gpde_set_error("%s: dim must be 1..3 (got %d)", what, dim); return GPDE_EINVAL; }
+    if (!origin || !period) { gpde_set_error("%s: host arrays origin[dim] / period[dim] required", what); return GPDE_EINVAL; }
+    if (!(r > 0.0) || !isfinite(r)) { gpde_set_error("%s: r must be positive and finite", what); return GPDE_EINVAL; }
+    for (int k = 0; k < dim; ++k) {
+        if (!(period[k] >= 0.0) || !isfinite(period[k]) || !isfinite(origin[k])) {
+            gpde_set_error("%s: period[%d] must be >= 0 (0 = open axis) and origin[%d] finite", what, k, k);
+            return GPDE_EINVAL;
+        }
+        if (period[k] > 0.0 && !(2.0 * r < period[k])) {
+            gpde_set_error("%s: 2 r = %g >= period[%d] = %g: a pair would have more than one image within r", what, 2.0 * r, k, period[k]);
+            return GPDE_EINVAL;
+        }
+    }
+    return GPDE_OK;
+}
+
+// Cells of a periodic axis tile the period exactly: nc = floor(L / r) of edge L / nc >= r.  Where that edge is within 2^-20 of r
+// (L / r an integer, or next to one) one cell fewer is taken: the cell index is a rounded product, and with an edge of exactly r
+// a pair at distance r(1 - 1e-16) could land two cells apart.  Open axes are those of make_grid.  Too many cells: coarser ones.
+int make_periodic_grid(const char* what, int dim, double r, const double* lo, const double* hi, const double* origin,
+                       const double* period, PeriodicGrid* g, int64_t* ncells) {
+    for (double scale = 1.0;; scale *= 2.0) {
+        int64_t tot = 1;
+        for (int k = 0; k < 3; ++k) {
+            g->cells.lo[k] = 0.0; g->cells.inv[k] = 0.0; g->cells.nc[k] = 1;
+            g->per[k] = 0.0; g->half[k] = 0.0; g->wrap[k] = 0;
+            if (k >= dim) continue;
+            int64_t nc;
+            if (period[k] > 0.0) {
+                const double L = period[k], edge_min = r * scale * (1.0 + 0x1p-20);
+                nc = (int64_t)fmin(floor(L / (r * scale)), (double)((1 << 20) + 1));
+                while (nc > 1 && L / (double)nc < edge_min) --nc;
+                if (nc < 1) nc = 1;
+                g->cells.lo[k] = origin[k]; g->cells.inv[k] = (double)nc / L;
+                g->per[k] = L; g->half[k] = 0.5 * L; g->wrap[k] = nc >= 3 ? 1 : 2;
+            } else {
+                if (!lo || !hi) { gpde_set_error("%s: an open axis needs the host bounds lo / hi", what); return GPDE_EINVAL; }
+                const double ext = hi[k] - lo[k], cs = r * 1.0001 * scale;
+                if (!(ext >= 0.0) || !isfinite(ext)) { gpde_set_error("%s: bad bounds in dimension %d", what, k); return GPDE_EINVAL; }
+                nc = (int64_t)fmin(floor(ext / cs), (double)(1 << 20)) + 1;
+                g->cells.lo[k] = lo[k]; g->cells.inv[k] = 1.0 / cs;
+            }
+            g->cells.nc[k] = (int)nc;
+            tot *= nc;
+        }
+        if (tot <= ((int64_t)1 << 24)) { *ncells = tot; break; }
+    }
+    g->cells.dim = dim;
+    return GPDE_OK;
+}
+
+int check_periodic_points(const char* what, const double* ps, int64_t ns, const double* pd, int64_t nd, uint32_t flags) {
+    if (flags & GPDE_RADIUS_REFERENCE_TIES) {
+        gpde_set_error("%s: GPDE_RADIUS_REFERENCE_TIES has no periodic form (the reference's torus code never wraps: nothing to reproduce)", what);
+        return GPDE_EINVAL;
+    }
+    if (flags || !ps || !pd || ns < 0 || nd < 0 || ns > 0x7fffffff || nd > 0x7fffffff) {
+        gpde_set_error("%s: bad argument (flags must be 0, positions non-null, 0 <= n <= 2^31 - 1)", what);
+        return GPDE_EINVAL;
+    }
+    return GPDE_OK;
+}
+
+}  // namespace
+
+extern "C" size_t gpde_radius_csr_periodic_workspace_bytes(int64_t n_src, int dim, double r, const double* lo, const double* hi,
+                                                           const double* origin, const double* period) {
+    const char* what = "gpde_radius_csr_periodic_workspace_bytes";
+    PeriodicGrid g;
+    int64_t ncells = 0;
+    if (check_periodic(what, dim, r, origin, period) != GPDE_OK) return 0;
+    if (n_src < 0 || n_src > 0x7fffffff) { gpde_set_error("%s: n_src out of range", what); return 0; }
+    if (make_periodic_grid(what, dim, r, lo, hi, origin, period, &g, &ncells) != GPDE_OK) return 0;
+    return carve(nullptr, n_src, ncells, (size_t)(n_src > 0 ? n_src : 1) * dim * sizeof(double)).total + 256;
+}
+
+extern "C" int gpde_radius_csr_periodic_count(const double* pos_src, int64_t n_src, const double* pos_dst, int64_t n_dst, int dim,
+                                              double r, uint32_t flags, const double* lo, const double* hi, const double* origin,
+                                              const double* period, int32_t* deg, void* ws, size_t ws_bytes, void* stream_) {
+    const char* what = "gpde_radius_csr_periodic_count";
+    hipStream_t st = (hipStream_t)stream_;
+    if (int rc = check_periodic(what, dim, r, origin, period)) return rc;
+    if (int rc = check_periodic_points(what, pos_src, n_src, pos_dst, n_dst, flags)) return rc;
+    if (!deg || !ws) { gpde_set_error("%s: deg / ws is null", what); return GPDE_EINVAL; }
+    PeriodicGrid g;
+    int64_t ncells = 0;
+    if (int rc = make_periodic_grid(what, dim, r, lo, hi, origin, period, &g, &ncells)) return rc;
+    CellWs w = carve(ws, n_src, ncells, (size_t)(n_src > 0 ? n_src : 1) * dim * sizeof(double));
+    if (ws_bytes < w.total) { gpde_set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, w.total); return GPDE_EWORKSPACE; }
+    if (n_dst == 0) return GPDE_OK;
+    const int T = 256;
+    if (n_src > 0) {
+        hipLaunchKernelGGL(k_cell_ids_periodic, dim3((unsigned)((n_src + T - 1) / T)), dim3(T), 0, st, pos_src, (int)n_src, g, w.reduced,
+                           w.cell, w.id);
+        GP_HIP_CHECK(rocprim::radix_sort_pairs(w.temp, w.temp_bytes, w.cell, w.cell_sorted, w.id, w.order, (size_t)n_src, 0,
+                                               sort_bits_for(ncells), st));
+    }
+    hipLaunchKernelGGL(k_cell_start, dim3((unsigned)((ncells + 1 + T - 1) / T)), dim3(T), 0, st, w.cell_sorted, (int)n_src, (int)ncells, w.start);
+    hipLaunchKernelGGL((k_cell_neighbors_periodic<false>), dim3((unsigned)((n_dst + 3) / 4)), dim3(256), 0, st, w.reduced, pos_dst, (int)n_dst,
+                       g, r * r, w.start, w.order, deg, (const int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (float*)nullptr);
+    GP_LAUNCH_CHECK("gpde_radius_csr_periodic_count kernels");
+    return GPDE_OK;
+}
+
+// `ws` must still hold what gpde_radius_csr_periodic_count left there (same arguments); rowptr = exclusive scan of its `deg`.
+extern "C" int gpde_radius_csr_periodic_fill(const double* pos_src, int64_t n_src, const double* pos_dst, int64_t n_dst, int dim,
+                                             double r, uint32_t flags, const double* lo, const double* hi, const double* origin,
+                                             const double* period, const int32_t* rowptr, int32_t* src, int32_t* dst, float* geom,
+                                             int64_t n_edges, void* ws, size_t ws_bytes, void* stream_) {
+    const char* what = "gpde_radius_csr_periodic_fill";
+    hipStream_t st = (hipStream_t)stream_;
+    if (int rc = check_periodic(what, dim, r, origin, period)) return rc;
+    if (int rc = check_periodic_points(what, pos_src, n_src, pos_dst, n_dst, flags)) return rc;
+    if (!rowptr || !ws || n_edges < 0 || (n_edges > 0 && (!src || !dst))) { gpde_set_error("%s: null rowptr / src / dst / ws", what); return GPDE_EINVAL; }
+    PeriodicGrid g;
+    int64_t ncells = 0;
+    if (int rc = make_periodic_grid(what, dim, r, lo, hi, origin, period, &g, &ncells)) return rc;
+    CellWs w = carve(ws, n_src, ncells, (size_t)(n_src > 0 ? n_src : 1) * dim * sizeof(double));
+    if (ws_bytes < w.total) { gpde_set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, w.total); return GPDE_EWORKSPACE; }
+    if (n_dst == 0 || n_edges == 0) return GPDE_OK;
+    hipLaunchKernelGGL((k_cell_neighbors_periodic<true>), dim3((unsigned)((n_dst + 3) / 4)), dim3(256), (size_t)4 * CG_SORT_MAX * 4, st, w.reduced,
+                       pos_dst, (int)n_dst, g, r * r, w.start, w.order, (int32_t*)nullptr, rowptr, src, dst, geom);
+    GP_LAUNCH_CHECK("gpde_radius_csr_periodic_fill kernels");
     return GPDE_OK;
 }

@@ -1970,7 +1970,7 @@ def hidden_backward_raw(csr: Csr, edge_attr: torch.Tensor, dims: Sequence[int],
 # radius graph
 # ----------------------------------------------------------------------------------------------
 def radius_graph(pos: torch.Tensor, r: float, reference_ties: bool = False,
-                 pos_dst: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 pos_dst: Optional[torch.Tensor] = None, period=None, origin=None) -> torch.Tensor:
     """edge_index int64 [2,E] of the radius graph of `pos` [n,dim] (dim 1..3), in the reference's
     order (sorted by source, then target; self-loops included) - the GPU replacement of
     `ball_connectivity` (utilities.py:250-255).  One sync (the edge count) per graph.
@@ -1979,7 +1979,13 @@ def radius_graph(pos: torch.Tensor, r: float, reference_ties: bool = False,
     RandomMultiMeshGenerator (multipole-graph-neural-operator/utilities.py:617-632).
     `reference_ties=True`: scikit-learn's dot-product-expansion arithmetic, so that pairs at exactly distance r
     are kept / dropped exactly as by the reference (gpde_radius_graph2_*, GPDE_RADIUS_REFERENCE_TIES); the default
-    tests the exact float64 sum of squares (symmetric graph)."""
+    tests the exact float64 sum of squares (symmetric graph).
+    `period` / `origin`: the graph on a periodic box (see radius_csr_raw), in the same source-major order - the periodic
+    CSR stably sorted by source (there is no periodic brute-force kernel)."""
+    if period is not None:
+        _, src, dst = radius_csr_raw(pos, r, reference_ties, pos_dst, period=period, origin=origin)
+        order = torch.sort(src, stable=True).indices          # rows are destination-major: targets stay ascending per source
+        return torch.stack([src[order].long(), dst[order].long()])
     lib = _lib.lib()
     _require_cuda(pos, "pos")
     if pos.dim() == 1:
@@ -2010,10 +2016,112 @@ def radius_graph(pos: torch.Tensor, r: float, reference_ties: bool = False,
     return ei
 
 
-def radius_csr_raw(pos: torch.Tensor, r: float, reference_ties: bool = False, pos_dst: Optional[torch.Tensor] = None):
+def _positions(pos: torch.Tensor, pos_dst: Optional[torch.Tensor]):
+    """(pos, pos_dst or pos) as contiguous float64 [n, dim] device tensors of one dimension."""
+    _require_cuda(pos, "pos")
+    pos = (pos.unsqueeze(1) if pos.dim() == 1 else pos).detach().to(torch.float64).contiguous()
+    if pos_dst is None:
+        return pos, pos
+    _require_cuda(pos_dst, "pos_dst")
+    pd = (pos_dst.unsqueeze(1) if pos_dst.dim() == 1 else pos_dst).detach().to(torch.float64).contiguous()
+    if pd.size(1) != pos.size(1):
+        raise ValueError("pos and pos_dst must have the same dimension")
+    return pos, pd
+
+
+def _host_bounds(pos: torch.Tensor, pd: torch.Tensor):
+    """Host arrays lo / hi [dim]: a bounding box of both point sets (one small copy)."""
+    dim = int(pos.size(1))
+    both = pos if pd is pos else torch.cat([pos, pd])
+    lo_t, hi_t = both.min(dim=0).values.cpu(), both.max(dim=0).values.cpu()
+    return (ctypes.c_double * dim)(*[float(v) for v in lo_t]), (ctypes.c_double * dim)(*[float(v) for v in hi_t])
+
+
+def periodic_box(period, origin, dim: int, r: float, reference_ties: bool = False):
+    """`period` / `origin` of the radius-graph builders as two lists of `dim` floats (host only; raises ValueError).
+    period: a scalar (every axis) or one entry per axis, 0 / None = an open axis; origin: likewise, default 0."""
+    def per_axis(v, name):
+        if v is None or isinstance(v, (int, float)):
+            return [0.0 if v is None else float(v)] * dim
+        v = [0.0 if t is None else float(t) for t in (v.tolist() if isinstance(v, torch.Tensor) else v)]
+        if len(v) != dim:
+            raise ValueError(f"{name} has {len(v)} entries for positions of dimension {dim}")
+        return v
+    if not 1 <= dim <= 3:
+        raise ValueError(f"positions of dimension {dim}: the radius graphs are built in 1..3 dimensions")
+    if reference_ties:
+        raise ValueError("reference_ties=True has no periodic form: the reference's torus_connectivity / torus1d_connectivity shift an "
+                         "ALIAS of the grid (grid1 = grid), so its graphs never wrap and there are no reference ties to reproduce")
+    per, org = per_axis(period, "period"), per_axis(origin, "origin")
+    if not float(r) > 0.0:
+        raise ValueError(f"r = {r} must be positive")
+    for k, L in enumerate(per):
+        if L < 0.0 or L != L:
+            raise ValueError(f"period[{k}] = {L} must be >= 0 (0 = open axis)")
+        if L > 0.0 and not 2.0 * float(r) < L:
+            raise ValueError(f"2 r = {2.0 * float(r)} >= period[{k}] = {L}: a pair would have more than one image within r")
+    return per, org
+
+
+def _radius_csr_periodic(pos, r, pos_dst, period, origin, reference_ties, fill: bool, geometry: bool):
+    """gpde_radius_csr_periodic_count (+ _fill): (deg,) or (rowptr, src, dst, geom | None)."""
+    dim_in = 1 if pos.dim() == 1 else int(pos.size(1))
+    per, org = periodic_box(period, origin, dim_in, r, reference_ties)          # host checks first: no device is needed to be refused
+    lib = _lib.lib()
+    pos, pd = _positions(pos, pos_dst)
+    n, nd, dim = int(pos.size(0)), int(pd.size(0)), int(pos.size(1))
+    dev = pos.device
+    if n == 0 or nd == 0:
+        if not fill:
+            return (torch.zeros(nd, dtype=torch.int32, device=dev),)
+        z = torch.zeros(0, dtype=torch.int32, device=dev)
+        return (torch.zeros(nd + 1, dtype=torch.int32, device=dev), z, z.clone(),
+                torch.zeros(0, dim + 1, dtype=torch.float32, device=dev) if geometry else None)
+    lo, hi = _host_bounds(pos, pd)
+    org_c, per_c = (ctypes.c_double * dim)(*org), (ctypes.c_double * dim)(*per)
+    nbytes = int(lib.gpde_radius_csr_periodic_workspace_bytes(n, dim, float(r), lo, hi, org_c, per_c))
+    if nbytes == 0:
+        _lib.check(-1, "gpde_radius_csr_periodic_workspace_bytes")
+    ws = _alloc_ws(nbytes, dev)
+    deg = torch.empty(nd, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.gpde_radius_csr_periodic_count(pos.data_ptr(), n, pd.data_ptr(), nd, dim, float(r), 0, lo, hi, org_c, per_c,
+                                                      deg.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev)),
+                   "gpde_radius_csr_periodic_count")
+    if not fill:
+        return (deg,)
+    rowptr64 = torch.zeros(nd + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(deg, 0, out=rowptr64[1:])
+    e = int(rowptr64[-1].item())
+    if e >= (1 << 31) - 64:
+        raise NotImplementedError(f"{e} edges exceed the int32 CSR")
+    rowptr = rowptr64.to(torch.int32)
+    src = torch.empty(e, dtype=torch.int32, device=dev)
+    dst = torch.empty(e, dtype=torch.int32, device=dev)
+    geom = torch.empty(e, dim + 1, dtype=torch.float32, device=dev) if geometry else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.gpde_radius_csr_periodic_fill(pos.data_ptr(), n, pd.data_ptr(), nd, dim, float(r), 0, lo, hi, org_c, per_c,
+                                                     rowptr.data_ptr(), src.data_ptr(), dst.data_ptr(),
+                                                     None if geom is None else geom.data_ptr(), e, ws.data_ptr(), ws.numel(),
+                                                     _stream_ptr(dev)), "gpde_radius_csr_periodic_fill")
+    return rowptr, src, dst, geom
+
+
+def radius_csr_raw(pos: torch.Tensor, r: float, reference_ties: bool = False, pos_dst: Optional[torch.Tensor] = None,
+                   period=None, origin=None, return_geometry: bool = False):
     """Cell-list radius graph emitted directly as a destination CSR (gpde_radius_csr_count / _fill): returns
     (rowptr int32 [n_dst + 1], src int32 [E], dst int32 [E]) - edge (src[s] in pos -> dst[s] in pos_dst), rows in
-    ascending source order.  One sync (the edge count) per graph."""
+    ascending source order.  One sync (the edge count) per graph.
+
+    `period` (a scalar or one entry per axis; 0 / None = open axis) with `origin` (default 0): the graph on a periodic box by
+    minimum-image distance (gpde_radius_csr_periodic_*; 2 r < period).  `return_geometry=True` adds a fourth result, `geom`
+    float32 [E, dim + 1] by CSR slot: the minimum-image displacement pos[src] - image(pos_dst[dst]) and its norm (on open
+    axes, and with period=None, the plain difference)."""
+    if period is None and return_geometry and reference_ties:
+        raise ValueError("return_geometry=True is built on the exact distance arithmetic: reference_ties must be False")
+    if period is not None or return_geometry:
+        rowptr, src, dst, geom = _radius_csr_periodic(pos, r, pos_dst, period, origin, reference_ties, True, return_geometry)
+        return (rowptr, src, dst, geom) if return_geometry else (rowptr, src, dst)
     lib = _lib.lib()
     _require_cuda(pos, "pos")
     pos = (pos.unsqueeze(1) if pos.dim() == 1 else pos).detach().to(torch.float64).contiguous()
@@ -2057,9 +2165,13 @@ def radius_csr_raw(pos: torch.Tensor, r: float, reference_ties: bool = False, po
     return rowptr, src, dst
 
 
-def radius_in_degrees(pos: torch.Tensor, r: float, reference_ties: bool = False, pos_dst: Optional[torch.Tensor] = None) -> torch.Tensor:
+def radius_in_degrees(pos: torch.Tensor, r: float, reference_ties: bool = False, pos_dst: Optional[torch.Tensor] = None,
+                      period=None, origin=None) -> torch.Tensor:
     """int32 [n_dst]: in-degree of every destination of the radius graph - the COUNT pass of the cell-list builder alone
-    (gpde_radius_csr_count; no edge is written).  parallel.partition_rows_by_position balances its row blocks on it."""
+    (gpde_radius_csr_count; no edge is written).  parallel.partition_rows_by_position balances its row blocks on it.
+    `period` / `origin`: on a periodic box (see radius_csr_raw)."""
+    if period is not None:
+        return _radius_csr_periodic(pos, r, pos_dst, period, origin, reference_ties, False, False)[0]
     lib = _lib.lib()
     _require_cuda(pos, "pos")
     pos = (pos.unsqueeze(1) if pos.dim() == 1 else pos).detach().to(torch.float64).contiguous()
@@ -2083,30 +2195,41 @@ def radius_in_degrees(pos: torch.Tensor, r: float, reference_ties: bool = False,
     return deg
 
 
-def radius_csr(pos: torch.Tensor, r: float, reference_ties: bool = False, pos_dst: Optional[torch.Tensor] = None) -> Csr:
+def radius_csr(pos: torch.Tensor, r: float, reference_ties: bool = False, pos_dst: Optional[torch.Tensor] = None,
+               period=None, origin=None, return_geometry: bool = False):
     """The radius graph of one point set as the `Csr` the operator consumes (no edge_index, no sort): rowptr / src / dst
     are what `csr_for(radius_graph(pos, r), n)` builds - bit for bit - and `perm` is the identity: per-edge tensors for
     this graph are laid out by CSR slot (`csr.edge_index` is the edge list in that order), or not needed at all
-    (`NodeAttr`).  Replaces ball_connectivity + the per-call index handling of PyG (utilities.py:250-255, nn_conv.py:271)."""
-    rowptr, src, dst = radius_csr_raw(pos, r, reference_ties, pos_dst)
+    (`NodeAttr`).  Replaces ball_connectivity + the per-call index handling of PyG (utilities.py:250-255, nn_conv.py:271).
+
+    `period` / `origin`: the graph on a periodic box (torus; see radius_csr_raw) - what TorusGridSplitter.torus_connectivity and
+    torus1d_connectivity (multipole utilities.py:1190-1266, 404-417) are meant to build.  `return_geometry=True` returns
+    (Csr, geom): geom float32 [E, dim + 1] = the minimum-image displacement pos[src] - image(pos[dst]) and its norm, already in
+    the slot order the operator reads (perm is the identity) - the first columns of the reference's torus edge attributes
+    [dx, dy, |d|, a_i, a_j] (utilities.py:1251-1257), which endpoint coordinates (`NodeAttr`) cannot give across the seam."""
+    out = radius_csr_raw(pos, r, reference_ties, pos_dst, period=period, origin=origin, return_geometry=return_geometry)
+    rowptr, src, dst = out[:3]
     e = int(src.numel())
-    if pos_dst is not None:
-        # two point sets: the RECTANGULAR Csr of edges (j in pos -> i in pos_dst) - what csr_for(radius_graph(pos, r, pos_dst=...),
-        # n_dst, n_src=n_src) builds, bit for bit; consumed by the module as conv((x_src, x_dst), csr, edge_attr)
-        return Csr(int(rowptr.numel()) - 1, e, rowptr, src, dst, torch.arange(e, dtype=torch.int32, device=src.device),
-                   n_src_nodes=int(pos.size(0)))
-    return Csr(int(rowptr.numel()) - 1, e, rowptr, src, dst, torch.arange(e, dtype=torch.int32, device=src.device))
+    # two point sets: the RECTANGULAR Csr of edges (j in pos -> i in pos_dst) - what csr_for(radius_graph(pos, r, pos_dst=...),
+    # n_dst, n_src=n_src) builds, bit for bit; consumed by the module as conv((x_src, x_dst), csr, edge_attr)
+    csr = Csr(int(rowptr.numel()) - 1, e, rowptr, src, dst, torch.arange(e, dtype=torch.int32, device=src.device),
+              n_src_nodes=None if pos_dst is None else int(pos.size(0)))
+    return (csr, out[3]) if return_geometry else csr
 
 
 def multilevel_radius_graphs(pos_levels: Sequence[torch.Tensor], radii_inner: Sequence[float],
-                             radii_inter: Sequence[float], reference_ties: bool = True):
+                             radii_inter: Sequence[float], reference_ties: Optional[bool] = None, period=None, origin=None):
     """The inner / down / up graphs of RandomMultiMeshGenerator.ball_connectivity
     (multipole-graph-neural-operator/utilities.py:602-640) built on the GPU from the per-level point sets:
     inner[l] = radius graph of level l (local node ids), down[l] = edges (level l -> level l + 1) within
     radii_inter[l], up[l] = down[l] with the rows swapped (utilities.py:631: the SAME edge order).  Returns
-    {"inner": [...], "down": [...], "up": [...]} of int64 [2, E] tensors with level-local node ids."""
-    inner = [radius_graph(p, r, reference_ties=reference_ties) for p, r in zip(pos_levels, radii_inner)]
-    down = [radius_graph(pos_levels[l], radii_inter[l], reference_ties=reference_ties, pos_dst=pos_levels[l + 1])
-            for l in range(len(pos_levels) - 1)]
+    {"inner": [...], "down": [...], "up": [...]} of int64 [2, E] tensors with level-local node ids.
+    `reference_ties` defaults to the reference's arithmetic on an open box; with `period` (every level on the same periodic
+    box, see radius_csr_raw) it defaults to the exact arithmetic, the only one a periodic graph has."""
+    if reference_ties is None:
+        reference_ties = period is None
+    inner = [radius_graph(p, r, reference_ties=reference_ties, period=period, origin=origin) for p, r in zip(pos_levels, radii_inner)]
+    down = [radius_graph(pos_levels[l], radii_inter[l], reference_ties=reference_ties, pos_dst=pos_levels[l + 1], period=period,
+                         origin=origin) for l in range(len(pos_levels) - 1)]
     up = [d.flip(0) for d in down]
     return {"inner": inner, "down": down, "up": up}

@@ -618,6 +618,36 @@ GPDE_API int gpde_radius_csr_fill(const double* pos_src, int64_t n_src, const do
                          uint32_t flags, const double* lo, const double* hi, const int32_t* rowptr, int32_t* src,
                          int32_t* dst, int64_t n_edges, void* ws, size_t ws_bytes, void* stream);
 
+/* The cell-list builder on a PERIODIC box (torus), with the minimum-image edge geometry.  The reference's periodic problems
+ * (Burgers with is_periodic=True, MGKN_orthogonal_burgers1d.py:165; RandomMeshGenerator.torus1d_connectivity, multipole
+ * utilities.py:404-417; TorusGridSplitter.torus_connectivity / get_data, utilities.py:1190-1266) join points across the seam
+ * and give the kernel network the WRAPPED displacement [dx, dy, |d|, a_i, a_j] - which endpoint coordinates cannot reproduce.
+ * The arguments of the open twins plus
+ *   origin[dim], period[dim]  HOST arrays: period[k] > 0 - axis k wraps with that length, measured from origin[k];
+ *                             period[k] == 0 - an open axis, as in gpde_radius_csr_* (lo / hi are read on open axes only and
+ *                             may be NULL when every axis is periodic);
+ *   geom (fill, nullable)     float32 [E][dim + 1] by CSR slot: pos_src[j] - image(pos_dst[i]) per axis (source minus target, the
+ *                             sign of the reference's X_difference with rows indexed by edge_index[0]; the plain difference on
+ *                             open axes), then its Euclidean norm - float64 arithmetic, rounded to float32 once.
+ * Points outside [origin, origin + period) are legal: they are reduced into it (x - L floor((x - o) / L), float64).  The test is
+ * the exact float64 sum of squares of the minimum-image differences against r^2 (flags = 0; GPDE_RADIUS_REFERENCE_TIES has no
+ * periodic form: the reference's torus code aliases its shifted grids and never wraps, so there is no tie behaviour to
+ * reproduce).  2 r < period[k] is required on every periodic axis: each (source, destination) pair then has one nearest image
+ * and gives at most one edge.  Rows as in the open builder: ascending source id (rows longer than 4096 edges keep cell order);
+ * self-loops included.  Two passes with the caller's scan between them, `ws` untouched in between, like the open twins.
+ * GPDE_EINVAL (before any device call) for dim outside 1..3, a negative period, 2 r >= period[k], r <= 0 and
+ * GPDE_RADIUS_REFERENCE_TIES; the workspace query returns 0 for the ones it can see (gpde_last_error() names the argument).
+ * Additions to the ABI: GPDE_VERSION is unchanged. */
+GPDE_API size_t gpde_radius_csr_periodic_workspace_bytes(int64_t n_src, int dim, double r, const double* lo, const double* hi,
+                                                const double* origin, const double* period);
+GPDE_API int gpde_radius_csr_periodic_count(const double* pos_src, int64_t n_src, const double* pos_dst, int64_t n_dst, int dim,
+                                   double r, uint32_t flags, const double* lo, const double* hi, const double* origin,
+                                   const double* period, int32_t* deg, void* ws, size_t ws_bytes, void* stream);
+GPDE_API int gpde_radius_csr_periodic_fill(const double* pos_src, int64_t n_src, const double* pos_dst, int64_t n_dst, int dim,
+                                  double r, uint32_t flags, const double* lo, const double* hi, const double* origin,
+                                  const double* period, const int32_t* rowptr, int32_t* src, int32_t* dst, float* geom,
+                                  int64_t n_edges, void* ws, size_t ws_bytes, void* stream);
+
 /* HIP-event timing of the kernels launched by gpde_nnconv_fwd on the calling thread (used by
  * bench.py for the roofline figure; events are recorded on the same stream as the kernels).
  * gpde_profile_begin() arms it; gpde_profile_end_kinds() disarms it, SYNCHRONISES on the recorded
