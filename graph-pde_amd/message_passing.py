@@ -21,15 +21,18 @@ class MessagePassing(torch.nn.Module):
         self.__message_args__ = inspect.getfullargspec(self.message)[0][1:]
         self.__update_args__ = inspect.getfullargspec(self.update)[0][2:]
 
-    def propagate(self, edge_index, size=None, **kwargs):
+    def propagate(self, edge_index, size=None, _gather=None, **kwargs):
+        """`_gather(t, index)`: the row gather of the `_i` / `_j` message arguments (default `t.index_select(0, index)`, whose
+        backward adds rows with float atomics on the device; a subclass may hand in one with an ordered backward)."""
         i, j = (1, 0) if self.flow == "source_to_target" else (0, 1)
+        gather = _gather if _gather is not None else (lambda t, index: t.index_select(0, index))
         n = None
         margs = []
         for arg in self.__message_args__:
             if arg.endswith("_i") or arg.endswith("_j"):
                 t = kwargs[arg[:-2]]
                 n = t.size(0) if n is None else n
-                margs.append(t.index_select(0, edge_index[i if arg.endswith("_i") else j]))
+                margs.append(gather(t, edge_index[i if arg.endswith("_i") else j]))
             else:
                 margs.append(kwargs[arg])
         out = self.message(*margs)

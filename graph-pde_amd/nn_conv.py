@@ -53,6 +53,24 @@ def _uniform(size, tensor):
             tensor.uniform_(-bound, bound)
 
 
+class _GatherRows(torch.autograd.Function):
+    """x.index_select(0, idx) whose backward sums the gradient rows of one index in a FIXED order.  torch's own backward of
+    index_select adds them with float atomics on the device: a node with several out-edges then gets a grad_x whose last bits
+    differ from run to run (tests/test_gpu_layouts.py saw it on the 'max' chain, the one place a gather of x is left to torch).
+    index_put_(accumulate=True) sorts the indices and adds the rows of an index one after the other."""
+
+    @staticmethod
+    def forward(ctx, x, idx):
+        ctx.save_for_backward(idx)
+        ctx.shape = tuple(x.shape)
+        return x.index_select(0, idx)
+
+    @staticmethod
+    def backward(ctx, g):
+        (idx,) = ctx.saved_tensors
+        return torch.zeros(ctx.shape, dtype=g.dtype, device=g.device).index_put_((idx,), g.contiguous(), accumulate=True), None
+
+
 class NNConv_old(MessagePassing):
     r"""x'_i = Theta x_i + aggr_{j in N(i)} x_j . h_Theta(e_ij)   with h_Theta a kernel MLP emitting
     in_channels*out_channels values per edge (nn_conv.py:197-232).  Derives `MessagePassing` like the reference
@@ -189,7 +207,12 @@ class NNConv_old(MessagePassing):
             if csr._flow_flipped:
                 edge_index = edge_index.flip(0)
                 pseudo = pseudo.index_select(0, csr.perm.long().to(pseudo.device))
-        return MessagePassing.propagate(self, edge_index.to(x.device), x=x, pseudo=pseudo)
+        return self._max_chain(edge_index.to(x.device), x, pseudo)
+
+    def _max_chain(self, edge_index, x, pseudo):
+        """MessagePassing.propagate for a gradient through aggr='max', with x_j gathered by `_GatherRows`: grad_x is the same
+        bits on every run, like every other gradient of this package."""
+        return MessagePassing.propagate(self, edge_index, x=x, pseudo=pseudo, _gather=_GatherRows.apply)
 
     def forward(self, x, edge_index, edge_attr, *, size=None, residual=None, activation=None):      # nn_conv.py:267-271
         """The reference signature `forward(x, edge_index, edge_attr)`; `x` may be a pair `(x_src, x_dst)` and `size=` the pair
@@ -312,7 +335,7 @@ class NNConv_old(MessagePassing):
         if self.aggr not in ("add", "mean"):
             if self._flipped():
                 return self._generic_propagate(edge_index, x, pseudo)
-            return MessagePassing.propagate(self, edge_index.edge_index if isinstance(edge_index, ops.Csr) else edge_index, x=x, pseudo=pseudo)
+            return self._max_chain(edge_index.edge_index if isinstance(edge_index, ops.Csr) else edge_index, x, pseudo)
         if x.dtype != torch.float32:
             raise NotImplementedError(f"a kernel network outside the Linear / ReLU chain: float32 only (x is {x.dtype})")
         csr = ops.csr_for(edge_index, x.size(0))
@@ -402,7 +425,7 @@ class NNConv_old(MessagePassing):
         if self.aggr == "max" and needs_grad:
             if self._flipped():
                 return self._generic_propagate(edge_index, x, pseudo)
-            return MessagePassing.propagate(self, edge_index.edge_index if isinstance(edge_index, ops.Csr) else edge_index, x=x, pseudo=pseudo)
+            return self._max_chain(edge_index.edge_index if isinstance(edge_index, ops.Csr) else edge_index, x, pseudo)
         dev = x.device if x.is_cuda else ops.staging_device()
         if isinstance(edge_index, ops.Csr):
             csr = edge_index
@@ -572,7 +595,7 @@ class NNConv_old(MessagePassing):
                 return self._generic_propagate(edge_index, x, pseudo)
             if isinstance(edge_index, ops.Csr):
                 edge_index = edge_index.edge_index
-            return MessagePassing.propagate(self, edge_index, x=x, pseudo=pseudo)
+            return self._max_chain(edge_index, x, pseudo)
         if no_grad and pseudo.dtype == torch.float32 and x.dtype == torch.float32 and (use_hidden_cache or self.aggr == "max"):
             # inference on a low in-degree / small graph (or aggr='max'): one streaming kernel over the cached per-edge
             # weights (hidden_cache.lookup_edge_weights)

@@ -206,8 +206,10 @@ def gather_rows(rows: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
     (unreliable above 2^26 rows on this torch / ROCm build: synth.darcy_edge_attr)."""
     _require_cuda(rows, "rows")
     _require_cuda(perm, "perm")
-    if rows.dtype != torch.float32 or rows.dim() != 2 or not rows.is_contiguous() or perm.dtype != torch.int32:
-        raise ValueError("gather_rows: contiguous float32 [rows, k] and an int32 permutation")
+    if rows.dtype != torch.float32 or rows.dim() != 2 or perm.dtype != torch.int32:
+        raise ValueError("gather_rows: float32 [rows, k] and an int32 permutation")
+    rows = _operand(rows, "rows", (None, None), rows.device)
+    perm = _operand(perm, "perm", (None,) * perm.dim(), rows.device, dtype=torch.int32)
     n = int(perm.numel())
     out = torch.empty(n, rows.size(1), dtype=torch.float32, device=rows.device)
     with torch.cuda.device(rows.device):
@@ -261,6 +263,49 @@ def _require_cuda(t, name: str):
         raise RuntimeError(
             f"{name} is on {t.device}: the NNConv hot path runs only on an MI355X through libgpde.so "
             "(no CPU / composite fallback exists by design)")
+
+
+def _dense16(t: torch.Tensor) -> torch.Tensor:
+    """`t` itself when it is dense (contiguous) and starts on a 16-byte boundary, else a fresh dense copy (the allocators of
+    torch hand out blocks aligned far beyond 16 bytes).  The 64-wide kernels read their operands with 16-byte vector accesses."""
+    if t.is_contiguous() and t.data_ptr() % 16 == 0:
+        return t
+    t = t.detach()
+    return torch.empty_like(t, memory_format=torch.contiguous_format).copy_(t)
+
+
+def _operand(t: Optional[torch.Tensor], name: str, shape, dev, *, writable: bool = False, dtype: torch.dtype = torch.float32,
+             exc=ValueError) -> Optional[torch.Tensor]:
+    """The one gate between a tensor and `data_ptr()` of a native call (DESIGN.md "Operand layouts").  `shape`: the exact
+    shape, None = any extent in that dimension; `dev`: the call's device.  A wrong dtype, shape or device raises `exc` naming
+    the operand.  A READ-ONLY operand may come in any layout: it is returned as the tensor itself when that is dense and
+    16-byte aligned (no copy, the same object and `data_ptr` for the caches), else as a detached dense aligned copy.  A WRITTEN operand
+    (`writable`: out, z_keep, acc, ws) is never copied - the caller would not see the result: it must be dense and aligned
+    as it is, or ValueError.  None passes through."""
+    if t is None:
+        return None
+    want = tuple(shape)
+    ok_shape = t.dim() == len(want) and all(w is None or int(w) == int(s) for w, s in zip(want, t.shape))
+    if t.dtype != dtype or not ok_shape or t.device != dev:
+        dims = ",".join("*" if w is None else str(int(w)) for w in want)
+        raise exc(f"{name} must be {str(dtype).replace('torch.', '')} [{dims}] on {dev}, got {str(t.dtype).replace('torch.', '')} "
+                  f"{tuple(t.shape)} on {t.device}")
+    if writable:
+        if not t.is_contiguous() or t.data_ptr() % 16 != 0:
+            raise ValueError(f"{name} is written by the kernels in place: it must be contiguous and 16-byte aligned, got strides "
+                             f"{tuple(t.stride())} at an address = {t.data_ptr() % 16} mod 16 (pass a dense tensor; views are not copied)")
+        return t
+    return _dense16(t)
+
+
+def _operands(ts, name: str, shapes, dev):
+    """`_operand` over the per-layer weights or biases of a kernel MLP (None entries pass through)."""
+    return [_operand(t, f"{name}[{l}]", s, dev) for l, (t, s) in enumerate(zip(ts, shapes))]
+
+
+def _mlp_shapes(dims: Sequence[int]):
+    """([weight shapes], [bias shapes]) of the Linear layers of widths `dims`."""
+    return [(dims[l + 1], dims[l]) for l in range(len(dims) - 1)], [(dims[l + 1],) for l in range(len(dims) - 1)]
 
 
 def build_csr(edge_index: torch.Tensor, n_nodes: int, n_src: Optional[int] = None, flip: bool = False) -> Csr:
@@ -486,8 +531,9 @@ def pack_mlp(weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Te
         _lib.check(-2, "gpde_mlp_pack_bytes")      # message was set by the failed layout query
     dev = weights[0].device
     packed = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-    ws = [w.detach().contiguous() for w in weights]
-    bs = [None if b is None else b.detach().contiguous() for b in biases]
+    w_shapes, b_shapes = _mlp_shapes(dims)
+    ws = _operands([w.detach() for w in weights], "kernel-network weight", w_shapes, dev)
+    bs = _operands([None if b is None else b.detach() for b in biases], "kernel-network bias", b_shapes, dev)
     wp = (ctypes.c_void_p * n)(*[w.data_ptr() for w in ws])
     bp = (ctypes.c_void_p * n)(*[None if b is None else b.data_ptr() for b in bs])
     with torch.cuda.device(dev):
@@ -680,7 +726,19 @@ def _check_residual(residual, x, n):
     _require_cuda(residual, "residual")
     if residual.dtype != torch.float32 or tuple(residual.shape) != (n, WIDTH):
         raise ValueError(f"residual must be float32 [{n},{WIDTH}], got {residual.dtype} {tuple(residual.shape)}")
-    return residual.contiguous()
+    return _operand(residual, "residual", (n, WIDTH), x.device)
+
+
+def _root_bias(root, bias, dev):
+    """The 64-wide update() parameters as operands: root float32 [64, 64], bias float32 [64]."""
+    return (_operand(None if root is None else root.detach(), "root", (WIDTH, WIDTH), dev),
+            _operand(None if bias is None else bias.detach(), "bias", (WIDTH,), dev))
+
+
+def _out_ws(out, ws, n, dev):
+    """A caller-given `out` [n, 64] / `ws` checked as written operands (None: the wrapper allocates)."""
+    return (_operand(out, "out", (n, WIDTH), dev, writable=True),
+            _operand(ws, "ws", (None,), dev, writable=True, dtype=torch.uint8))
 
 
 def nnconv_forward_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor, pm: PackedMlp,
@@ -716,17 +774,20 @@ def nnconv_forward_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor, pm: P
         raise ValueError(f"x has {x.size(0)} rows, CSR was built for {n} nodes")
     if edge_attr.dim() != 2 or edge_attr.size(0) != e or edge_attr.size(1) != pm.dims[0]:
         raise ValueError(f"edge_attr must be [{e},{pm.dims[0]}], got {tuple(edge_attr.shape)}")
-    x = x.contiguous()
-    edge_attr, perm = attr_in_slot_order(csr, edge_attr.contiguous())
-    root_c = None if root is None else root.detach().contiguous()
-    bias_c = None if bias is None else bias.detach().contiguous()
+    x = _operand(x, "x", (n, WIDTH), x.device)
+    if edge_attr.device != x.device:
+        raise ValueError(f"edge_attr is on {edge_attr.device}, x on {x.device}")
+    edge_attr, perm = attr_in_slot_order(csr, _dense16(edge_attr))
+    root_c, bias_c = _root_bias(root, bias, x.device)
+    out, ws = _out_ws(out, ws, n, x.device)
+    z_keep = _operand(z_keep, "z_keep", (n, WIDTH * hidden_width(pm.dims)), x.device, writable=True)
+    residual = _check_residual(residual, x, n)
+    if z_keep is not None and (residual is not None or relu):
+        raise ValueError("z_keep cannot be combined with the fused glue")
     if out is None:
         out = torch.empty(n, WIDTH, dtype=torch.float32, device=x.device)
     if ws is None:
         ws = _alloc_ws(workspace_bytes(n, e, pm), x.device)
-    residual = _check_residual(residual, x, n)
-    if z_keep is not None and (residual is not None or relu):
-        raise ValueError("z_keep cannot be combined with the fused glue")
     with torch.cuda.device(x.device):
         if z_keep is not None:
             rc = lib.gpde_nnconv_fwd_keepz(x.data_ptr(), n, edge_attr.data_ptr(), None, None, e, csr.rowptr.data_ptr(),
@@ -768,7 +829,13 @@ class NodeAttr:
         for ep, col in sel:
             if ep not in (0, 1) or not 0 <= col < table.size(1) or col > 255:
                 raise ValueError(f"slot ({ep}, {col}): endpoint 0 = source / 1 = target, column < {table.size(1)}")
-        self.table = table.contiguous()
+        if table.requires_grad and torch.is_grad_enabled():
+            # a table that wants a gradient stays in the autograd graph (the module materialises the differentiable gather from
+            # `self.table`): a view or an unaligned tensor is copied by a differentiable clone, never detached
+            dense = table.is_contiguous() and table.data_ptr() % 16 == 0
+            self.table = table if dense else table.clone(memory_format=torch.contiguous_format)
+        else:
+            self.table = _dense16(table)
         self.sel = [(int(ep), int(col)) for ep, col in sel]
 
     @staticmethod
@@ -834,10 +901,10 @@ def nnconv_forward_nodeattr_raw(x: torch.Tensor, csr: Csr, na: NodeAttr, pm: Pac
         raise ValueError(f"x must be float32 [{n},{WIDTH}]")
     if na.table.size(0) != n or na.k0 != pm.dims[0]:
         raise ValueError(f"node table must have {n} rows and {pm.dims[0]} slots, got {na.table.size(0)} / {na.k0}")
-    x = x.contiguous()
+    x = _operand(x, "x", (n, WIDTH), x.device)
     nas = na.c_struct()
-    root_c = None if root is None else root.detach().contiguous()
-    bias_c = None if bias is None else bias.detach().contiguous()
+    root_c, bias_c = _root_bias(root, bias, x.device)
+    out, ws = _out_ws(out, ws, n, x.device)
     if out is None:
         out = torch.empty(n, WIDTH, dtype=torch.float32, device=x.device)
     if ws is None:
@@ -947,18 +1014,21 @@ def nnconv_backward_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor,
     nl = len(weights)
     dims = [int(weights[0].size(1))] + [int(w.size(0)) for w in weights]
     dims_c = _lib.dims_array(dims)
-    x = x.detach().contiguous()
+    x = _operand(x.detach(), "x", (n, WIDTH), dev)
     is_na = isinstance(edge_attr, NodeAttr)
     if need_attr:
         if is_na or dims[0] > 8:
             raise NotImplementedError("the edge-attribute gradient is built for attribute tensors of <= 8 slots")
-        edge_attr, perm = edge_attr.detach().contiguous(), csr.perm      # the caller's rows: the gradient goes back by perm
+        edge_attr, perm = _dense16(edge_attr.detach()), csr.perm      # the caller's rows: the gradient goes back by perm
     elif not is_na:
-        edge_attr, perm = attr_in_slot_order(csr, edge_attr.detach().contiguous())
-    grad_out = grad_out.detach().contiguous().float()
-    ws_ = [w.detach().contiguous() for w in weights]
-    bs_ = [None if b is None else b.detach().contiguous() for b in biases]
-    root_c = None if root is None else root.detach().contiguous()
+        edge_attr, perm = attr_in_slot_order(csr, _dense16(edge_attr.detach()))
+    grad_out = _operand(grad_out.detach().float(), "grad_out", (n, WIDTH), dev)
+    w_shapes, b_shapes = _mlp_shapes(dims)
+    ws_ = _operands([w.detach() for w in weights], "weights", w_shapes, dev)
+    bs_ = _operands([None if b is None else b.detach() for b in biases], "biases", b_shapes, dev)
+    root_c, _ = _root_bias(root, None, dev)
+    ws = _operand(ws, "ws", (None,), dev, writable=True, dtype=torch.uint8)
+    z_saved = _operand(z_saved, "z_saved", (n, WIDTH * hidden_width(dims)), dev)
     gx = torch.empty(n, WIDTH, dtype=torch.float32, device=dev)
     gW = [torch.empty_like(w) for w in ws_]
     gb = [None if b is None else torch.empty_like(b) for b in bs_]
@@ -980,9 +1050,10 @@ def nnconv_backward_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor,
     p = lambda t: None if t is None else t.data_ptr()
     nas = edge_attr.c_struct() if is_na else None
     ga = torch.zeros(e, dims[0], dtype=torch.float32, device=dev) if need_attr else None
-    if hidden_saved is not None and (need_attr or hidden_saved.dtype != torch.float32 or not hidden_saved.is_contiguous() or
+    if hidden_saved is not None and (need_attr or hidden_saved.dtype != torch.float32 or
                                      tuple(hidden_saved.shape) != (e, hidden_width(dims))):
-        raise ValueError(f"hidden_saved must be contiguous float32 [{e},{hidden_width(dims)}] (and excludes need_attr)")
+        raise ValueError(f"hidden_saved must be float32 [{e},{hidden_width(dims)}] (and excludes need_attr)")
+    hidden_saved = _operand(hidden_saved, "hidden_saved", (e, hidden_width(dims)), dev)
     with torch.cuda.device(dev):
         rc = lib.gpde_nnconv_bwd(x.data_ptr(), n, None if is_na else edge_attr.data_ptr(), None if nas is None else ctypes.byref(nas),
                                  p(hidden_saved), e, csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(), None if is_na else perm.data_ptr(),
@@ -1032,14 +1103,17 @@ def nnconv_backward_light_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor
     nl = len(weights)
     dims = [int(weights[0].size(1))] + [int(w.size(0)) for w in weights]
     dims_c = _lib.dims_array(dims)
-    x = x.detach().contiguous()
+    x = _operand(x.detach(), "x", (n, WIDTH), dev)
     is_na = isinstance(edge_attr, NodeAttr)
     if not is_na:
-        edge_attr, perm = attr_in_slot_order(csr, edge_attr.detach().contiguous())
-    grad_out = grad_out.detach().contiguous().float()
-    ws_ = [w.detach().contiguous() for w in weights]
-    bs_ = [None if b is None else b.detach().contiguous() for b in biases]
-    root_c = None if root is None else root.detach().contiguous()
+        edge_attr, perm = attr_in_slot_order(csr, _dense16(edge_attr.detach()))
+    grad_out = _operand(grad_out.detach().float(), "grad_out", (n, WIDTH), dev)
+    w_shapes, b_shapes = _mlp_shapes(dims)
+    ws_ = _operands([w.detach() for w in weights], "weights", w_shapes, dev)
+    bs_ = _operands([None if b is None else b.detach() for b in biases], "biases", b_shapes, dev)
+    root_c, _ = _root_bias(root, None, dev)
+    z_saved = _operand(z_saved, "z_saved", (n, WIDTH * hidden_width(dims)), dev)
+    hidden_part = _operand(hidden_part, "hidden_part", (None, hidden_width(dims)), dev)
     gx = torch.empty(n, WIDTH, dtype=torch.float32, device=dev)
     gw = torch.empty_like(ws_[-1])
     gb = None if bs_[-1] is None else torch.empty_like(bs_[-1])
@@ -1083,13 +1157,15 @@ def nnconv_backward_deferred_raw(xs: Sequence[torch.Tensor], gs: Sequence[torch.
     x_stack = torch.zeros(Lp, n, WIDTH, dtype=torch.float32, device=dev)
     g_stack = torch.empty(L, n, WIDTH, dtype=torch.float32, device=dev)
     for l in range(L):
-        x_stack[l].copy_(xs[l].detach())
-        g_stack[l].copy_(gs[l].detach())
+        x_stack[l].copy_(_operand(xs[l].detach(), f"xs[{l}]", (n, WIDTH), dev))
+        g_stack[l].copy_(_operand(gs[l].detach().float(), f"gs[{l}]", (n, WIDTH), dev))
     is_na = isinstance(edge_attr, NodeAttr)
     if not is_na:
-        edge_attr, perm = attr_in_slot_order(csr, edge_attr.detach().contiguous())
-    ws_ = [w.detach().contiguous() for w in weights]
-    bs_ = [None if b is None else b.detach().contiguous() for b in biases]
+        edge_attr, perm = attr_in_slot_order(csr, _dense16(edge_attr.detach()))
+    w_shapes, b_shapes = _mlp_shapes(dims)
+    ws_ = _operands([w.detach() for w in weights], "weights", w_shapes, dev)
+    bs_ = _operands([None if b is None else b.detach() for b in biases], "biases", b_shapes, dev)
+    hidden_part = _operand(hidden_part, "hidden_part", (None, hidden_width(dims)), dev)
     gW = [torch.empty_like(w) for w in ws_[:-1]] + [None]
     gb = [None if b is None else torch.empty_like(b) for b in bs_[:-1]] + [None]
     nbytes = int(lib.gpde_nnconv_bwd_deferred_workspace_bytes(n, e, nl, dims_c, L))
@@ -1152,14 +1228,15 @@ def hidden_forward_raw(csr: Csr, edge_attr: torch.Tensor, pm: PackedMlp,
     if edge_attr.dtype != torch.float32 or edge_attr.dim() != 2 or edge_attr.size(0) != e or \
             edge_attr.size(1) != pm.dims[0]:
         raise ValueError(f"edge_attr must be float32 [{e},{pm.dims[0]}], got {edge_attr.dtype} {tuple(edge_attr.shape)}")
-    edge_attr, perm = attr_in_slot_order(csr, edge_attr.detach().contiguous())
+    edge_attr, perm = attr_in_slot_order(csr, _dense16(edge_attr.detach()))
     n_lim = csr.n_nodes
     if n_nodes_limit is not None:           # H of the in-edges of nodes [0, n_nodes_limit) only (mixed forward)
         n_lim = int(n_nodes_limit)
         e = int(csr.rowptr_host[n_lim])
     nl = len(pm.dims) - 1
-    ws_ = [None if w is None else w.detach().contiguous() for w in weights]    # last entry unused
-    bs_ = [None if b is None else b.detach().contiguous() for b in biases]
+    w_shapes, b_shapes = _mlp_shapes(pm.dims)
+    ws_ = _operands([None if w is None else w.detach() for w in weights], "weights", w_shapes, dev)    # last entry unused
+    bs_ = _operands([None if b is None else b.detach() for b in biases], "biases", b_shapes, dev)
     hidden = torch.empty(e, hidden_width(pm.dims), dtype=torch.float32, device=dev)
     nbytes = int(lib.gpde_hidden_workspace_bytes(e, nl, pm.dims_c))
     fast = (_PRECISION[precision] & _lib.GPDE_FWD_F16SPLIT) and nl == 3
@@ -1198,17 +1275,16 @@ def nnconv_forward_hidden_raw(x: torch.Tensor, csr: Csr, hidden: torch.Tensor, p
     n, e = csr.n_nodes, csr.n_edges
     if x.dtype != torch.float32 or x.dim() != 2 or x.size(1) != WIDTH or x.size(0) != n:
         raise ValueError(f"x must be float32 [{n},{WIDTH}], got {x.dtype} {tuple(x.shape)}")
-    if hidden.dtype != torch.float32 or tuple(hidden.shape) != (e, hidden_width(pm.dims)) or \
-            not hidden.is_contiguous():
-        raise ValueError(f"hidden must be contiguous float32 [{e},{hidden_width(pm.dims)}]")
-    x = x.contiguous()
-    root_c = None if root is None else root.detach().contiguous()
-    bias_c = None if bias is None else bias.detach().contiguous()
+    x = _operand(x, "x", (n, WIDTH), x.device)
+    hidden = _operand(hidden, "hidden", (e, hidden_width(pm.dims)), x.device)
+    root_c, bias_c = _root_bias(root, bias, x.device)
+    out, ws = _out_ws(out, ws, n, x.device)
+    z_keep = _operand(z_keep, "z_keep", (n, WIDTH * hidden_width(pm.dims)), x.device, writable=True)
+    residual = _check_residual(residual, x, n)
     if out is None:
         out = torch.empty(n, WIDTH, dtype=torch.float32, device=x.device)
     if ws is None:
         ws = _alloc_ws(workspace_bytes(n, e, pm), x.device)
-    residual = _check_residual(residual, x, n)
     if z_keep is not None:
         if residual is not None or relu:
             raise ValueError("z_keep cannot be combined with the fused glue")
@@ -1248,12 +1324,11 @@ def edge_weights_raw(hidden: torch.Tensor, pm: PackedMlp, w_last: torch.Tensor, 
     lib = _lib.lib()
     _require_cuda(hidden, "hidden")
     e, dev = int(hidden.size(0)), hidden.device
-    if hidden.dtype != torch.float32 or hidden.dim() != 2 or hidden.size(1) != hidden_width(pm.dims) or not hidden.is_contiguous():
-        raise ValueError(f"hidden must be contiguous float32 [E,{hidden_width(pm.dims)}]")
-    if tuple(w_last.shape) != (WIDTH * WIDTH, pm.dims[-2]):
-        raise ValueError(f"w_last must be [{WIDTH * WIDTH},{pm.dims[-2]}], got {tuple(w_last.shape)}")
-    w_c = w_last.detach().contiguous()
-    b_c = None if b_last is None else b_last.detach().contiguous()
+    if hidden.dim() != 2:
+        raise ValueError(f"hidden must be float32 [E,{hidden_width(pm.dims)}]")
+    hidden = _operand(hidden.detach(), "hidden", (e, hidden_width(pm.dims)), dev)
+    w_c = _operand(w_last.detach(), "w_last", (WIDTH * WIDTH, pm.dims[-2]), dev)
+    b_c = _operand(None if b_last is None else b_last.detach(), "b_last", (WIDTH * WIDTH,), dev)
     we = torch.empty(e, WIDTH * WIDTH, dtype=torch.float32, device=dev)
     nl = len(pm.dims) - 1
     ws = torch.empty(max(int(lib.gpde_edge_weights_workspace_bytes(e, nl, pm.dims_c)), 1), dtype=torch.uint8, device=dev)
@@ -1287,17 +1362,14 @@ def nnconv_forward_edgeweights_group(calls: Sequence[dict]) -> List[torch.Tensor
             raise ValueError("all calls of a group must live on one device")
         if x.dtype != torch.float32 or x.dim() != 2 or tuple(x.shape) != (n, WIDTH):
             raise ValueError(f"x must be float32 [{n},{WIDTH}], got {x.dtype} {tuple(x.shape)}")
-        if we.dtype != torch.float32 or tuple(we.shape) != (e, WIDTH * WIDTH) or not we.is_contiguous() or we.device != dev:
-            raise ValueError(f"edge_weights must be contiguous float32 [{e},{WIDTH * WIDTH}] on {dev}")
+        we = _operand(we.detach(), "edge_weights", (e, WIDTH * WIDTH), dev)
         aggr = c.get("aggr", "mean")
         if aggr not in _AGGR_WE:
             raise NotImplementedError(f"aggr={aggr!r}")
-        x_c = x.detach().contiguous()
-        root, bias = c.get("root"), c.get("bias")
-        root_c = None if root is None else root.detach().contiguous()
-        bias_c = None if bias is None else bias.detach().contiguous()
+        x_c = _operand(x.detach(), "x", (n, WIDTH), dev)
+        root_c, bias_c = _root_bias(c.get("root"), c.get("bias"), dev)
         res = _check_residual(c.get("residual"), x_c, n)
-        out = c.get("out")
+        out = _operand(c.get("out"), "out", (n, WIDTH), dev, writable=True)
         if out is None:
             out = torch.empty(n, WIDTH, dtype=torch.float32, device=dev)
         keep.append((x_c, root_c, bias_c, res, we, csr))
@@ -1332,20 +1404,20 @@ def nnconv_backward_edgeweights_raw(x: torch.Tensor, csr: Csr, edge_weights: tor
     if aggr not in _AGGR:
         raise NotImplementedError(f"aggr={aggr!r}: the gradient of the per-edge weight operator is built for 'add' and 'mean'")
     n, e, dev = csr.n_nodes, csr.n_edges, x.device
-    x = x.detach().contiguous()
-    grad_out = grad_out.detach().contiguous().float()
-    we = edge_weights.detach()
-    if we.dtype != torch.float32 or tuple(we.shape) != (e, WIDTH * WIDTH) or not we.is_contiguous():
-        raise ValueError(f"edge_weights must be contiguous float32 [{e},{WIDTH * WIDTH}]")
-    root_c = None if root is None else root.detach().contiguous()
+    x = _operand(x.detach(), "x", (n, WIDTH), dev)
+    grad_out = _operand(grad_out.detach().float(), "grad_out", (n, WIDTH), dev)
+    we = _operand(edge_weights.detach(), "edge_weights", (e, WIDTH * WIDTH), dev)
+    root_c, _ = _root_bias(root, None, dev)
     gx = torch.empty(n, WIDTH, dtype=torch.float32, device=dev)
     want_root = need_root and root is not None
     bits = 0
     if acc is not None:
         gwe, groot, gbias = acc
-        if tuple(gwe.shape) != (e, WIDTH * WIDTH) or gwe.dtype != torch.float32 or not gwe.is_contiguous() or gwe.device != dev or \
-                (groot is not None) != want_root or (gbias is not None) != bool(need_bias):
+        if (groot is not None) != want_root or (gbias is not None) != bool(need_bias):
             raise ValueError("acc: (grad_edge_weights [E,4096], grad_root, grad_bias) of an application of the same module expected")
+        gwe = _operand(gwe, "acc[0] (grad_edge_weights)", (e, WIDTH * WIDTH), dev, writable=True)
+        groot = _operand(groot, "acc[1] (grad_root)", (WIDTH, WIDTH), dev, writable=True)
+        gbias = _operand(gbias, "acc[2] (grad_bias)", (WIDTH,), dev, writable=True)
         bits = _lib.GPDE_ACC_EDGE_WEIGHTS | (_lib.GPDE_ACC_ROOT if want_root else 0) | (_lib.GPDE_ACC_BIAS if need_bias else 0)
     else:
         gwe = torch.empty(e, WIDTH * WIDTH, dtype=torch.float32, device=dev)
@@ -1396,9 +1468,8 @@ def _any_widths(x: torch.Tensor, csr: Csr, edge_weights: torch.Tensor, out_chann
         raise ValueError(f"x must be float32 [{n}, in_channels], got {x.dtype} {tuple(x.shape)}")
     cin = int(x.size(1))
     we = edge_weights
-    if we.dtype != torch.float32 or we.dim() != 2 or we.size(0) != e or we.size(1) % cin != 0 or we.size(1) == 0 or \
-            not we.is_contiguous() or we.device != x.device:
-        raise ValueError(f"edge_weights must be contiguous float32 [{e}, {cin} * out_channels] on {x.device}, got {we.dtype} {tuple(we.shape)}")
+    if we.dtype != torch.float32 or we.dim() != 2 or we.size(0) != e or we.size(1) % cin != 0 or we.size(1) == 0 or we.device != x.device:
+        raise ValueError(f"edge_weights must be float32 [{e}, {cin} * out_channels] on {x.device}, got {we.dtype} {tuple(we.shape)}")
     cout = int(we.size(1)) // cin
     if out_channels is not None and int(out_channels) != cout:
         raise ValueError(f"edge_weights has {we.size(1)} columns = {cin} x {cout}, not {cin} x {out_channels}")
@@ -1418,7 +1489,7 @@ def nnconv_forward_edgeweights_any_raw(x, csr: Csr, edge_weights, root, bias, ag
     cin, cout = _any_widths(x, csr, edge_weights, out_channels)
     n, e, dev = csr.n_nodes, csr.n_edges, x.device
     x_c = x.detach().contiguous()
-    we = edge_weights.detach()
+    we = edge_weights.detach().contiguous()     # (a dense tensor is passed as it is, aligned or not: the dword route stays)
     root_c = None if root is None else root.detach().contiguous()
     bias_c = None if bias is None else bias.detach().contiguous()
     if root_c is not None and (root_c.dtype != torch.float32 or tuple(root_c.shape) != (cin, cout) or root_c.device != dev):
@@ -1457,7 +1528,7 @@ def nnconv_backward_edgeweights_any_raw(x: torch.Tensor, csr: Csr, edge_weights:
     grad_out = grad_out.detach().contiguous().float()
     if tuple(grad_out.shape) != (n, cout):
         raise ValueError(f"grad_out must be [{n},{cout}], got {tuple(grad_out.shape)}")
-    we = edge_weights.detach()
+    we = edge_weights.detach().contiguous()     # (a dense tensor is passed as it is, aligned or not: the dword route stays)
     root_c = None if root is None else root.detach().contiguous()
     if root_c is not None and (root_c.dtype != torch.float32 or tuple(root_c.shape) != (cin, cout)):
         raise ValueError(f"root must be float32 [{cin},{cout}], got {root_c.dtype} {tuple(root_c.shape)}")
@@ -1547,9 +1618,8 @@ def _hidden_any_args(x, csr: Csr, hidden, w_last, b_last, root):
     if x.dtype != torch.float32 or x.dim() != 2 or x.size(0) != n or x.size(1) < 1:
         raise ValueError(f"x must be float32 [{n}, in_channels], got {x.dtype} {tuple(x.shape)}")
     cin, dev = int(x.size(1)), x.device
-    if hidden.dtype != torch.float32 or hidden.dim() != 2 or hidden.size(0) != e or hidden.size(1) < 1 or not hidden.is_contiguous() or \
-            hidden.device != dev:
-        raise ValueError(f"hidden must be contiguous float32 [{e}, k_hidden] on {dev}, got {hidden.dtype} {tuple(hidden.shape)}")
+    if hidden.dtype != torch.float32 or hidden.dim() != 2 or hidden.size(0) != e or hidden.size(1) < 1 or hidden.device != dev:
+        raise ValueError(f"hidden must be float32 [{e}, k_hidden] on {dev}, got {hidden.dtype} {tuple(hidden.shape)}")
     k = int(hidden.size(1))
     if w_last.dtype != torch.float32 or w_last.dim() != 2 or w_last.size(1) != k or w_last.size(0) % cin != 0 or w_last.size(0) == 0 or \
             w_last.device != dev:
@@ -1575,7 +1645,7 @@ def nnconv_forward_hidden_any_raw(x, csr: Csr, hidden, w_last, b_last, root, bia
         _require_cuda(t, nm)
     if aggr not in _AGGR:
         raise NotImplementedError(f"aggr={aggr!r}: the re-associated operator is built for 'add' and 'mean'")
-    x_c, hid = x.detach().contiguous(), hidden.detach()
+    x_c, hid = x.detach().contiguous(), hidden.detach().contiguous()
     wl = w_last.detach().contiguous()
     bl, root_c, bias_c = (None if t is None else t.detach().contiguous() for t in (b_last, root, bias))
     cin, cout, k = _hidden_any_args(x_c, csr, hid, wl, bl, root_c)
@@ -1605,7 +1675,7 @@ def nnconv_backward_hidden_any_raw(x, csr: Csr, hidden, w_last, b_last, root, ag
         _require_cuda(t, nm)
     if aggr not in _AGGR:
         raise NotImplementedError(f"aggr={aggr!r}: the re-associated operator is built for 'add' and 'mean'")
-    x_c, hid = x.detach().contiguous(), hidden.detach()
+    x_c, hid = x.detach().contiguous(), hidden.detach().contiguous()
     wl = w_last.detach().contiguous()
     bl, root_c = (None if t is None else t.detach().contiguous() for t in (b_last, root))
     cin, cout, k = _hidden_any_args(x_c, csr, hid, wl, bl, root_c)
@@ -1640,9 +1710,8 @@ def _bip_args(x_src, x_dst, csr: Csr, root, per_edge, per_edge_name: str):
     if x_dst is not None and (x_dst.dtype != torch.float32 or x_dst.dim() != 2 or x_dst.size(0) != n_dst or x_dst.size(1) < 1 or x_dst.device != dev):
         raise ValueError(f"x_dst must be float32 [{n_dst}, in_dst] on {dev}, got {x_dst.dtype} {tuple(x_dst.shape)}")
     cind = cin if x_dst is None else int(x_dst.size(1))
-    if per_edge.dtype != torch.float32 or per_edge.dim() != 2 or per_edge.size(0) != e or per_edge.size(1) < 1 or not per_edge.is_contiguous() or \
-            per_edge.device != dev:
-        raise ValueError(f"{per_edge_name} must be contiguous float32 [{e}, .] on {dev}, got {per_edge.dtype} {tuple(per_edge.shape)}")
+    if per_edge.dtype != torch.float32 or per_edge.dim() != 2 or per_edge.size(0) != e or per_edge.size(1) < 1 or per_edge.device != dev:
+        raise ValueError(f"{per_edge_name} must be float32 [{e}, .] on {dev}, got {per_edge.dtype} {tuple(per_edge.shape)}")
     if root is not None and x_dst is None:
         raise ValueError("root without x_dst: the root term is x_dst . root (pass root=None for a call without destination features)")
     if root is not None and (root.dtype != torch.float32 or root.dim() != 2 or root.size(0) != cind or root.device != dev):
@@ -1665,7 +1734,7 @@ def nnconv_forward_edgeweights_bip_raw(x_src, x_dst, csr: Csr, edge_weights, roo
         raise NotImplementedError(f"aggr={aggr!r}")
     xs = x_src.detach().contiguous()
     xd = None if x_dst is None else x_dst.detach().contiguous()
-    we = edge_weights.detach()
+    we = edge_weights.detach().contiguous()     # (a dense tensor is passed as it is, aligned or not: the dword route stays)
     root_c = None if root is None else root.detach().contiguous()
     bias_c = None if bias is None else bias.detach().contiguous()
     cin, cind = _bip_args(xs, xd, csr, root_c, we, "edge_weights")
@@ -1707,7 +1776,7 @@ def nnconv_backward_edgeweights_bip_raw(x_src, x_dst, csr: Csr, edge_weights, ro
         raise NotImplementedError(f"aggr={aggr!r}: the gradient of the per-edge weight operator is built for 'add' and 'mean'")
     xs = x_src.detach().contiguous()
     xd = None if x_dst is None else x_dst.detach().contiguous()
-    we = edge_weights.detach()
+    we = edge_weights.detach().contiguous()     # (a dense tensor is passed as it is, aligned or not: the dword route stays)
     root_c = None if root is None else root.detach().contiguous()
     cin, cind = _bip_args(xs, xd, csr, root_c, we, "edge_weights")
     if we.size(1) % cin != 0:
@@ -1759,7 +1828,7 @@ def nnconv_forward_hidden_bip_raw(x_src, x_dst, csr: Csr, hidden, w_last, b_last
         _require_cuda(t, nm)
     if aggr not in _AGGR:
         raise NotImplementedError(f"aggr={aggr!r}: the re-associated operator is built for 'add' and 'mean'")
-    xs, hid, wl = x_src.detach().contiguous(), hidden.detach(), w_last.detach().contiguous()
+    xs, hid, wl = x_src.detach().contiguous(), hidden.detach().contiguous(), w_last.detach().contiguous()
     xd, bl, root_c, bias_c = (None if t is None else t.detach().contiguous() for t in (x_dst, b_last, root, bias))
     cin, cind, cout, k = _hidden_bip_args(xs, xd, csr, hid, wl, bl, root_c)
     n_src, n_dst, e, dev = csr.n_src, csr.n_nodes, csr.n_edges, xs.device
@@ -1788,7 +1857,7 @@ def nnconv_backward_hidden_bip_raw(x_src, x_dst, csr: Csr, hidden, w_last, b_las
         _require_cuda(t, nm)
     if aggr not in _AGGR:
         raise NotImplementedError(f"aggr={aggr!r}: the re-associated operator is built for 'add' and 'mean'")
-    xs, hid, wl = x_src.detach().contiguous(), hidden.detach(), w_last.detach().contiguous()
+    xs, hid, wl = x_src.detach().contiguous(), hidden.detach().contiguous(), w_last.detach().contiguous()
     xd, bl, root_c = (None if t is None else t.detach().contiguous() for t in (x_dst, b_last, root))
     cin, cind, cout, k = _hidden_bip_args(xs, xd, csr, hid, wl, bl, root_c)
     n_src, n_dst, e, dev = csr.n_src, csr.n_nodes, csr.n_edges, xs.device
@@ -1822,11 +1891,9 @@ def edge_weights_backward_raw(grad_we: torch.Tensor, hidden: torch.Tensor, dims:
     e, dev = int(hidden.size(0)), hidden.device
     nl = len(dims) - 1
     dims_c = _lib.dims_array(dims)
-    grad_we = grad_we.detach().contiguous()
-    hidden = hidden.detach()
-    if tuple(grad_we.shape) != (e, WIDTH * WIDTH) or tuple(hidden.shape) != (e, hidden_width(dims)) or not hidden.is_contiguous():
-        raise ValueError("grad_edge_weights [E, 4096] and contiguous hidden [E, K2P] expected")
-    w_c = w_last.detach().contiguous()
+    grad_we = _operand(grad_we.detach(), "grad_edge_weights", (e, WIDTH * WIDTH), dev)
+    hidden = _operand(hidden.detach(), "hidden", (e, hidden_width(dims)), dev)
+    w_c = _operand(w_last.detach(), "w_last", (WIDTH * WIDTH, dims[-2]), dev)
     gh = torch.empty_like(hidden)
     gw = torch.empty_like(w_c)
     gb = torch.empty(WIDTH * WIDTH, dtype=torch.float32, device=dev) if need_b else None
@@ -1856,11 +1923,12 @@ def nnconv_forward_mixed_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor,
     if x.dtype != torch.float32 or x.dim() != 2 or x.size(1) != WIDTH or x.size(0) != n:
         raise ValueError(f"x must be float32 [{n},{WIDTH}]")
     eh = int(csr.rowptr_host[hidden_nodes]) if hidden_nodes > 0 else 0
-    if hidden_nodes > 0 and (tuple(hidden.shape) != (eh, hidden_width(pm.dims)) or not hidden.is_contiguous()):
-        raise ValueError(f"hidden must be contiguous float32 [{eh},{hidden_width(pm.dims)}]")
-    x = x.contiguous()
-    root_c = None if root is None else root.detach().contiguous()
-    bias_c = None if bias is None else bias.detach().contiguous()
+    if hidden_nodes > 0:
+        hidden = _operand(hidden, "hidden", (eh, hidden_width(pm.dims)), x.device)
+    x = _operand(x, "x", (n, WIDTH), x.device)
+    root_c, bias_c = _root_bias(root, bias, x.device)
+    out, ws = _out_ws(out, ws, n, x.device)
+    z_keep = _operand(z_keep, "z_keep", (n, WIDTH * hidden_width(pm.dims)), x.device, writable=True)
     if out is None:
         out = torch.empty(n, WIDTH, dtype=torch.float32, device=x.device)
     if ws is None:
@@ -1872,7 +1940,7 @@ def nnconv_forward_mixed_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor,
             raise ValueError(f"node table must have {n} rows and {pm.dims[0]} slots")
         nas = edge_attr.c_struct()
     else:
-        edge_attr, perm = attr_in_slot_order(csr, edge_attr.detach().contiguous())
+        edge_attr, perm = attr_in_slot_order(csr, _dense16(edge_attr.detach()))
     p = lambda t: None if t is None else t.data_ptr()
     with torch.cuda.device(x.device):
         rc = lib.gpde_nnconv_fwd_mixed_keepz(x.data_ptr(), n, None if is_na else edge_attr.data_ptr(), None if nas is None else ctypes.byref(nas),
@@ -1898,15 +1966,18 @@ def nnconv_backward_hidden_raw(x: torch.Tensor, csr: Csr, hidden: torch.Tensor, 
     n, e, dev = csr.n_nodes, csr.n_edges, x.device
     nl = len(dims) - 1
     dims_c = _lib.dims_array(dims)
-    x = x.detach().contiguous()
-    grad_out = grad_out.detach().contiguous().float()
-    w_last = w_last.detach().contiguous()
-    b_c = None if b_last is None else b_last.detach().contiguous()
-    root_c = None if root is None else root.detach().contiguous()
+    for t, nm in ((x, "x"), (hidden, "hidden"), (grad_out, "grad_out")):
+        _require_cuda(t, nm)
+    x = _operand(x.detach(), "x", (n, WIDTH), dev)
+    grad_out = _operand(grad_out.detach().float(), "grad_out", (n, WIDTH), dev)
+    hidden = _operand(hidden.detach(), "hidden", (e, hidden_width(dims)), dev)
+    w_last = _operand(w_last.detach(), "w_last", (WIDTH * WIDTH, dims[-2]), dev)
+    b_c = _operand(None if b_last is None else b_last.detach(), "b_last", (WIDTH * WIDTH,), dev)
+    root_c, _ = _root_bias(root, None, dev)
+    z_saved = _operand(z_saved, "z_saved", (n, WIDTH * hidden_width(dims)), dev)
     gx = torch.empty(n, WIDTH, dtype=torch.float32, device=dev)
     accumulate = grad_hidden_acc is not None
-    if accumulate and (grad_hidden_acc.shape != hidden.shape or grad_hidden_acc.dtype != torch.float32 or not grad_hidden_acc.is_contiguous()):
-        raise ValueError("grad_hidden_acc must be a contiguous float32 tensor of the shape of `hidden`")
+    grad_hidden_acc = _operand(grad_hidden_acc, "grad_hidden_acc", tuple(hidden.shape), dev, writable=True)
     gh = grad_hidden_acc if accumulate else torch.empty_like(hidden)
     gw = torch.empty_like(w_last)
     gb = None if b_c is None else torch.empty_like(b_c)
@@ -1948,10 +2019,11 @@ def hidden_backward_raw(csr: Csr, edge_attr: torch.Tensor, dims: Sequence[int],
     dims_c = _lib.dims_array(dims)
     is_na = isinstance(edge_attr, NodeAttr)
     if not is_na:
-        edge_attr, perm = attr_in_slot_order(csr, edge_attr.detach().contiguous())
-    grad_hidden = grad_hidden.detach().contiguous()
-    ws_ = [w.detach().contiguous() for w in weights] + [None]
-    bs_ = [None if b is None else b.detach().contiguous() for b in biases] + [None]
+        edge_attr, perm = attr_in_slot_order(csr, _dense16(edge_attr.detach()))
+    grad_hidden = _operand(grad_hidden.detach(), "grad_hidden", (e, hidden_width(dims)), dev)
+    w_shapes, b_shapes = _mlp_shapes(dims)
+    ws_ = _operands([w.detach() for w in weights], "weights", w_shapes, dev) + [None]
+    bs_ = _operands([None if b is None else b.detach() for b in biases], "biases", b_shapes, dev) + [None]
     gW = [torch.empty_like(w) for w in ws_[:-1]] + [None]
     gb = [None if b is None else torch.empty_like(b) for b in bs_[:-1]] + [None]
     ws = alloc_bwd_ws(lib, 0, e, nl, dims_c, dev)
