@@ -605,3 +605,300 @@ extern "C" int gpde_radius_csr_periodic_fill(const double* pos_src, int64_t n_sr
     GP_LAUNCH_CHECK("gpde_radius_csr_periodic_fill kernels");
     return GPDE_OK;
 }
+
+// ---- batched arm: gpde_radius_csr_batched_* -----------------------------------------------------------------------------------
+// The radius graphs of B independent point sets in ONE build: the block-diagonal destination CSR with global node ids.  The
+// reference's training scripts build one small graph per sample in a Python loop (UAI3_resolution.py:131-145,
+// neurips1_MGKN.py:204) and the DataLoader collates them; one call of the open builder per sample costs two host
+// synchronisations, a radix sort and four launches each.  Sibling kernels: the open and periodic ones above keep their code.
+//   table     one BatchGraph record per graph (GPDE_RADIUS_BATCHED_REC_BYTES), written on the HOST by
+//             gpde_radius_csr_batched_plan and handed to count / fill in a device buffer: the graph's own CellGrid (the rule of
+//             make_grid on its own bounds and radius), r^2 and the reference-ties threshold, its first cell `cell_base` in the
+//             batch-wide cell numbering, and its source / destination ranges of the concatenated position arrays;
+//   keys      source j of graph b sorts under cell_base[b] + (its cell in b's grid): one stable radix sort orders all sources
+//             graph-major, cell-major, ascending id inside a cell; one k_cell_start runs over the summed cell count;
+//   walk      one wave per destination: binary search of its graph in the table (wave-uniform), then the 3^dim cells of that
+//             graph only - the contiguous x-range is taken from the graph's own base, so it never runs into the next graph's
+//             cells.  Arithmetic, ballot slots, LDS row sort and the cell-order fallback are those of k_cell_neighbors;
+//   cap       the summed cell count is held to BATCH_CELL_CAP = 2^24 (make_grid's own cap for one graph, so B = 1 plans the
+//             grid of the open builder): while it is exceeded every graph's cell edge doubles (a coarser filter, same edges).
+//             A batch of more graphs than that ends at one cell per graph.
+namespace {
+
+struct BatchGraph {
+    double lo[3], inv[3];
+    double r2, d2_max;
+    int32_t nc[3];
+    int32_t cell_base;
+    int32_t src_begin, src_end, dst_begin, dst_end;
+};
+static_assert(sizeof(BatchGraph) == GPDE_RADIUS_BATCHED_REC_BYTES, "BatchGraph is the record of include/gpde.h");
+
+constexpr int64_t BATCH_CELL_CAP = (int64_t)1 << 24;
+
+// the graph that owns point `p`: the first record whose range ends after p (empty graphs in between are passed over)
+template <bool DST>
+__device__ __forceinline__ int graph_of(const BatchGraph* __restrict__ tab, int n_graphs, int p) {
+    int lo = 0, hi = n_graphs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((DST ? tab[mid].dst_end : tab[mid].src_end) <= p) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ CellGrid grid_of(const BatchGraph& t, int dim) {
+    CellGrid g;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { g.lo[k] = t.lo[k]; g.inv[k] = t.inv[k]; g.nc[k] = t.nc[k]; }
+    g.dim = dim;
+    return g;
+}
+
+__global__ void k_cell_ids_batched(const double* __restrict__ pos, int n, int dim, const BatchGraph* __restrict__ tab, int n_graphs,
+                                   uint32_t* __restrict__ cell, uint32_t* __restrict__ id) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const BatchGraph t = tab[graph_of<false>(tab, n_graphs, j)];
+    const CellGrid g = grid_of(t, dim);
+    double p[3] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < dim; ++k) p[k] = pos[(size_t)j * dim + k];
+    int c[3];
+    cell_of(g, p, c);
+    cell[j] = (uint32_t)(t.cell_base + (c[2] * g.nc[1] + c[1]) * g.nc[0] + c[0]);
+    id[j] = (uint32_t)j;
+}
+
+template <bool FILL, bool TIES>
+__global__ __launch_bounds__(256) void k_cell_neighbors_batched(const double* __restrict__ ps, const double* __restrict__ pd, int nd, int dim,
+                                                                const BatchGraph* __restrict__ tab, int n_graphs, int n_cells, int same_set,
+                                                                const int32_t* __restrict__ cell_start, const uint32_t* __restrict__ order,
+                                                                int32_t* __restrict__ deg, const int32_t* __restrict__ rowptr,
+                                                                int32_t* __restrict__ src, int32_t* __restrict__ dst) {
+    extern __shared__ uint32_t sbuf[];                  // FILL: [4 waves][CG_SORT_MAX]
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: the graph search and its record are scalar
+    const int i = blockIdx.x * 4 + wave;
+    if (i >= nd) return;
+    const BatchGraph t = tab[graph_of<true>(tab, n_graphs, i)];
+    const CellGrid g = grid_of(t, dim);
+    const double r2 = t.r2, d2_max = t.d2_max;
+    double pi[3] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < g.dim; ++k) pi[k] = pd[(size_t)i * g.dim + k];
+    double yy = 0.0;
+    if (TIES)
+        for (int k = 0; k < g.dim; ++k) yy = yy + pi[k] * pi[k];
+    int ci[3];
+    cell_of(g, pi, ci);
+    const int r0 = FILL ? rowptr[i] : 0;
+    const int n_row = FILL ? rowptr[i + 1] - r0 : 0;
+    const bool in_lds = FILL && n_row <= CG_SORT_MAX;
+    uint32_t* row = sbuf + wave * CG_SORT_MAX;
+    int count = 0;
+    for (int dz = (g.dim > 2 ? -1 : 0); dz <= (g.dim > 2 ? 1 : 0); ++dz)
+        for (int dy = (g.dim > 1 ? -1 : 0); dy <= (g.dim > 1 ? 1 : 0); ++dy) {
+            const int cz = ci[2] + dz, cy = ci[1] + dy;
+            if (cz < 0 || cz >= g.nc[2] || cy < 0 || cy >= g.nc[1]) continue;
+            // the x-neighbours of a cell row are contiguous in the sorted list: one range for dx = -1 .. 1, inside THIS graph's cells
+            const int cx0 = max(ci[0] - 1, 0), cx1 = min(ci[0] + 1, g.nc[0] - 1);
+            const int base = t.cell_base + (cz * g.nc[1] + cy) * g.nc[0];
+            if (base < 0 || base + cx1 + 1 > n_cells) continue;       // a table that does not belong to this workspace reads nothing
+            const int p0 = cell_start[base + cx0], p1 = cell_start[base + cx1 + 1];
+            for (int q0 = p0; q0 < p1; q0 += 64) {
+                const int q = q0 + lane;
+                bool hit = false;
+                int j = 0;
+                if (q < p1) {
+                    j = (int)order[q];
+                    if (TIES) {
+                        double xx = 0.0, dot = 0.0;
+                        for (int k = 0; k < g.dim; ++k) {
+                            const double x = ps[(size_t)j * g.dim + k];
+                            xx = xx + x * x;
+                            dot = fma(x, pi[k], dot);
+                        }
+                        double d2 = -2.0 * dot;
+                        d2 = d2 + xx;
+                        d2 = d2 + yy;
+                        if (d2 < 0.0) d2 = 0.0;
+                        if (same_set && i == j) d2 = 0.0;             // global ids: one point set, the diagonal of its own graph
+                        hit = d2 <= d2_max;
+                    } else {
+                        double d2 = 0.0;
+                        for (int k = 0; k < g.dim; ++k) {
+                            const double d = pi[k] - ps[(size_t)j * g.dim + k];
+                            d2 += d * d;
+                        }
+                        hit = d2 <= r2;
+                    }
+                }
+                const unsigned long long m = __ballot(hit);
+                if (FILL && hit) {
+                    const int slot = count + __popcll(m & ((1ull << lane) - 1ull));
+                    if (slot < n_row) {
+                        if (in_lds) row[slot] = (uint32_t)j;
+                        else src[r0 + slot] = j;              // very long rows: cell order (deterministic, not ascending)
+                    }
+                }
+                count += __popcll(m);
+            }
+        }
+    if (!FILL) {
+        if (lane == 0) deg[i] = count;
+        return;
+    }
+    if (in_lds) {
+        sort_row_by_source(row, n_row, lane);
+        for (int t2 = lane; t2 < n_row; t2 += 64) src[r0 + t2] = (int32_t)row[t2];
+    }
+    for (int t2 = lane; t2 < n_row; t2 += 64) dst[r0 + t2] = i;
+}
+
+// ptr[0] = 0 <= ptr[1] <= ... <= ptr[B] = n <= 2^31 - 1
+int check_ptr(const char* what, const char* name, const int64_t* ptr, int64_t n_graphs, int64_t n) {
+    if (!ptr) { gpde_set_error("%s: host array %s[n_graphs + 1] required", what, name); return GPDE_EINVAL; }
+    if (ptr[0] != 0) { gpde_set_error("%s: %s[0] = %lld, must be 0", what, name, (long long)ptr[0]); return GPDE_EINVAL; }
+    for (int64_t b = 0; b < n_graphs; ++b)
+        if (ptr[b + 1] < ptr[b]) {
+            gpde_set_error("%s: %s decreases at graph %lld (%lld -> %lld)", what, name, (long long)b, (long long)ptr[b], (long long)ptr[b + 1]);
+            return GPDE_EINVAL;
+        }
+    if (ptr[n_graphs] > 0x7fffffff) { gpde_set_error("%s: %s ends at %lld points, more than 2^31 - 1", what, name, (long long)ptr[n_graphs]); return GPDE_EINVAL; }
+    if (n >= 0 && ptr[n_graphs] != n) {
+        gpde_set_error("%s: %s ends at %lld, the position array has %lld points", what, name, (long long)ptr[n_graphs], (long long)n);
+        return GPDE_EINVAL;
+    }
+    return GPDE_OK;
+}
+
+int check_batch_scalars(const char* what, int64_t n_graphs, int dim) {
+    if (dim < 1 || dim > 3) { gpde_set_error("%s: dim must be 1..3 (got %d)", what, dim); return GPDE_EINVAL; }
+    if (n_graphs < 0 || n_graphs > 0x7ffffffe) { gpde_set_error("%s: n_graphs = %lld out of range (0 .. 2^31 - 2)", what, (long long)n_graphs); return GPDE_EINVAL; }
+    return GPDE_OK;
+}
+
+// what count and fill share: every refusal the host values show, then the workspace carved for n_cells
+int check_batched_call(const char* what, const double* ps, int64_t ns, const double* pd, int64_t nd, int dim, uint32_t flags,
+                       const int64_t* ptr_src, const int64_t* ptr_dst, int64_t n_graphs, const void* table, int64_t n_cells,
+                       void* ws, size_t ws_bytes, CellWs* w) {
+    if (int rc = check_batch_scalars(what, n_graphs, dim)) return rc;
+    if (flags & ~(uint32_t)GPDE_RADIUS_REFERENCE_TIES) { gpde_set_error("%s: flags must be 0 | GPDE_RADIUS_REFERENCE_TIES", what); return GPDE_EINVAL; }
+    if (ns < 0 || nd < 0 || ns > 0x7fffffff || nd > 0x7fffffff) { gpde_set_error("%s: point counts must be 0 .. 2^31 - 1", what); return GPDE_EINVAL; }
+    if ((ns > 0 && !ps) || (nd > 0 && !pd)) { gpde_set_error("%s: pos_src / pos_dst is null", what); return GPDE_EINVAL; }
+    if (int rc = check_ptr(what, "ptr_src", ptr_src, n_graphs, ns)) return rc;
+    if (int rc = check_ptr(what, "ptr_dst", ptr_dst, n_graphs, nd)) return rc;
+    if (ps == pd && ns == nd)                              // ONE point set: one division into graphs
+        for (int64_t b = 0; b <= n_graphs; ++b)
+            if (ptr_dst[b] != ptr_src[b]) {
+                gpde_set_error("%s: pos_dst is pos_src (one point set) but ptr_dst[%lld] = %lld differs from ptr_src[%lld] = %lld", what,
+                               (long long)b, (long long)ptr_dst[b], (long long)b, (long long)ptr_src[b]);
+                return GPDE_EINVAL;
+            }
+    if (n_graphs > 0 && !table) { gpde_set_error("%s: the device table of gpde_radius_csr_batched_plan is null", what); return GPDE_EINVAL; }
+    if (n_cells < n_graphs || n_cells > 0x7ffffffe) { gpde_set_error("%s: n_cells = %lld is not what the plan returned for %lld graphs", what, (long long)n_cells, (long long)n_graphs); return GPDE_EINVAL; }
+    if (!ws) { gpde_set_error("%s: ws is null", what); return GPDE_EINVAL; }
+    *w = carve(ws, ns, n_cells);
+    if (ws_bytes < w->total) { gpde_set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, w->total); return GPDE_EWORKSPACE; }
+    return GPDE_OK;
+}
+
+}  // namespace
+
+// HOST ONLY.  bounds [B][2][dim] (lo then hi of graph b; not read for a graph without sources), ptr_src / ptr_dst [B + 1]
+// (ptr_dst NULL: one point set), r [B].  table (nullable: a query) receives B records.
+extern "C" int gpde_radius_csr_batched_plan(const double* bounds, const int64_t* ptr_src, const int64_t* ptr_dst, const double* r,
+                                            int64_t n_graphs, int dim, void* table, int64_t* n_cells, size_t* ws_bytes) {
+    const char* what = "gpde_radius_csr_batched_plan";
+    if (int rc = check_batch_scalars(what, n_graphs, dim)) return rc;
+    if (!n_cells || !ws_bytes) { gpde_set_error("%s: n_cells / ws_bytes is null", what); return GPDE_EINVAL; }
+    if (int rc = check_ptr(what, "ptr_src", ptr_src, n_graphs, -1)) return rc;
+    if (!ptr_dst) ptr_dst = ptr_src;
+    if (int rc = check_ptr(what, "ptr_dst", ptr_dst, n_graphs, -1)) return rc;
+    if (n_graphs > 0 && (!bounds || !r)) { gpde_set_error("%s: host arrays bounds[n_graphs][2][dim] / r[n_graphs] required", what); return GPDE_EINVAL; }
+    for (int64_t b = 0; b < n_graphs; ++b)
+        if (!(r[b] > 0.0) || !isfinite(r[b])) { gpde_set_error("%s: r[%lld] = %g must be positive and finite", what, (long long)b, r[b]); return GPDE_EINVAL; }
+    BatchGraph* tab = (BatchGraph*)table;
+    int64_t total = 0;
+    for (double scale = 1.0;; scale *= 2.0) {              // a power of two: r * scale * 1.0001 is make_grid's r * 1.0001 doubled
+        total = 0;
+        for (int64_t b = 0; b < n_graphs; ++b) {
+            CellGrid g;
+            int64_t nc = 1;
+            if (ptr_src[b + 1] > ptr_src[b]) {
+                if (int rc = make_grid(dim, r[b] * scale, bounds + (size_t)b * 2 * dim, bounds + ((size_t)b * 2 + 1) * dim, &g, &nc)) return rc;
+            } else {                                       // no sources: one empty cell, whatever the bounds hold
+                for (int k = 0; k < 3; ++k) { g.lo[k] = 0.0; g.inv[k] = 0.0; g.nc[k] = 1; }
+            }
+            if (tab) {
+                BatchGraph& t = tab[b];
+                for (int k = 0; k < 3; ++k) { t.lo[k] = g.lo[k]; t.inv[k] = g.inv[k]; t.nc[k] = g.nc[k]; }
+                t.r2 = r[b] * r[b];
+                t.d2_max = sqrt_threshold(r[b]);
+                t.cell_base = (int32_t)total;
+                t.src_begin = (int32_t)ptr_src[b]; t.src_end = (int32_t)ptr_src[b + 1];
+                t.dst_begin = (int32_t)ptr_dst[b]; t.dst_end = (int32_t)ptr_dst[b + 1];
+            }
+            total += nc;
+            if (total > BATCH_CELL_CAP && total > n_graphs) break;      // over the cap already: coarsen (every graph) and start over
+        }
+        if (total <= BATCH_CELL_CAP || total <= n_graphs) break;        // one cell per graph cannot be coarsened further
+    }
+    *n_cells = total;
+    *ws_bytes = carve(nullptr, ptr_src[n_graphs], total).total + 256;
+    return GPDE_OK;
+}
+
+extern "C" int gpde_radius_csr_batched_count(const double* pos_src, int64_t n_src, const double* pos_dst, int64_t n_dst, int dim,
+                                             uint32_t flags, const int64_t* ptr_src, const int64_t* ptr_dst, int64_t n_graphs,
+                                             const void* table, int64_t n_cells, int32_t* deg, void* ws, size_t ws_bytes, void* stream_) {
+    const char* what = "gpde_radius_csr_batched_count";
+    hipStream_t st = (hipStream_t)stream_;
+    CellWs w;
+    if (int rc = check_batched_call(what, pos_src, n_src, pos_dst, n_dst, dim, flags, ptr_src, ptr_dst, n_graphs, table, n_cells, ws, ws_bytes, &w)) return rc;
+    if (n_dst > 0 && !deg) { gpde_set_error("%s: deg is null", what); return GPDE_EINVAL; }
+    if (n_dst == 0) return GPDE_OK;
+    const BatchGraph* tab = (const BatchGraph*)table;
+    const int T = 256;
+    if (n_src > 0) {
+        hipLaunchKernelGGL(k_cell_ids_batched, dim3((unsigned)((n_src + T - 1) / T)), dim3(T), 0, st, pos_src, (int)n_src, dim, tab, (int)n_graphs,
+                           w.cell, w.id);
+        GP_HIP_CHECK(rocprim::radix_sort_pairs(w.temp, w.temp_bytes, w.cell, w.cell_sorted, w.id, w.order, (size_t)n_src, 0,
+                                               sort_bits_for(n_cells), st));
+    }
+    hipLaunchKernelGGL(k_cell_start, dim3((unsigned)((n_cells + 1 + T - 1) / T)), dim3(T), 0, st, w.cell_sorted, (int)n_src, (int)n_cells, w.start);
+    const int same = pos_src == pos_dst && n_src == n_dst;
+    const dim3 grid((unsigned)((n_dst + 3) / 4)), block(256);
+    if (flags & GPDE_RADIUS_REFERENCE_TIES)
+        hipLaunchKernelGGL((k_cell_neighbors_batched<false, true>), grid, block, 0, st, pos_src, pos_dst, (int)n_dst, dim, tab, (int)n_graphs,
+                           (int)n_cells, same, w.start, w.order, deg, (const int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
+    else
+        hipLaunchKernelGGL((k_cell_neighbors_batched<false, false>), grid, block, 0, st, pos_src, pos_dst, (int)n_dst, dim, tab, (int)n_graphs,
+                           (int)n_cells, same, w.start, w.order, deg, (const int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
+    GP_LAUNCH_CHECK("gpde_radius_csr_batched_count kernels");
+    return GPDE_OK;
+}
+
+// `ws` must still hold what gpde_radius_csr_batched_count left there (same arguments); rowptr = exclusive scan of its `deg`.
+extern "C" int gpde_radius_csr_batched_fill(const double* pos_src, int64_t n_src, const double* pos_dst, int64_t n_dst, int dim,
+                                            uint32_t flags, const int64_t* ptr_src, const int64_t* ptr_dst, int64_t n_graphs,
+                                            const void* table, int64_t n_cells, const int32_t* rowptr, int32_t* src, int32_t* dst,
+                                            int64_t n_edges, void* ws, size_t ws_bytes, void* stream_) {
+    const char* what = "gpde_radius_csr_batched_fill";
+    hipStream_t st = (hipStream_t)stream_;
+    CellWs w;
+    if (int rc = check_batched_call(what, pos_src, n_src, pos_dst, n_dst, dim, flags, ptr_src, ptr_dst, n_graphs, table, n_cells, ws, ws_bytes, &w)) return rc;
+    if (!rowptr || n_edges < 0 || (n_edges > 0 && (!src || !dst))) { gpde_set_error("%s: null rowptr / src / dst", what); return GPDE_EINVAL; }
+    if (n_dst == 0 || n_edges == 0) return GPDE_OK;
+    const BatchGraph* tab = (const BatchGraph*)table;
+    const int same = pos_src == pos_dst && n_src == n_dst;
+    const dim3 grid((unsigned)((n_dst + 3) / 4)), block(256);
+    const size_t lds = (size_t)4 * CG_SORT_MAX * 4;
+    if (flags & GPDE_RADIUS_REFERENCE_TIES)
+        hipLaunchKernelGGL((k_cell_neighbors_batched<true, true>), grid, block, lds, st, pos_src, pos_dst, (int)n_dst, dim, tab, (int)n_graphs,
+                           (int)n_cells, same, w.start, w.order, (int32_t*)nullptr, rowptr, src, dst);
+    else
+        hipLaunchKernelGGL((k_cell_neighbors_batched<true, false>), grid, block, lds, st, pos_src, pos_dst, (int)n_dst, dim, tab, (int)n_graphs,
+                           (int)n_cells, same, w.start, w.order, (int32_t*)nullptr, rowptr, src, dst);
+    GP_LAUNCH_CHECK("gpde_radius_csr_batched_fill kernels");
+    return GPDE_OK;
+}

@@ -2305,3 +2305,178 @@ def multilevel_radius_graphs(pos_levels: Sequence[torch.Tensor], radii_inner: Se
                          origin=origin) for l in range(len(pos_levels) - 1)]
     up = [d.flip(0) for d in down]
     return {"inner": inner, "down": down, "up": up}
+
+
+# ----------------------------------------------------------------------------------------------
+# the radius graphs of a BATCH of point sets in one build (gpde_radius_csr_batched_*)
+# ----------------------------------------------------------------------------------------------
+def ptr_from_batch(batch: torch.Tensor, n_graphs: Optional[int] = None) -> torch.Tensor:
+    """`ptr` int64 [B + 1] of PyG's sorted graph-id vector `batch` [n]: graph b owns the points ptr[b] .. ptr[b + 1].
+    B = n_graphs, or batch.max() + 1 (graphs without points are legal anywhere when n_graphs is given).  ValueError for an
+    unsorted or negative `batch`, or an id >= n_graphs.  Runs on the device of `batch`; host tensors need no device."""
+    if batch.dim() != 1 or batch.is_floating_point() or batch.dtype == torch.bool:
+        raise ValueError(f"batch must be a 1-D integer vector of graph ids (got {batch.dtype} {tuple(batch.shape)})")
+    batch = batch.detach().to(torch.int64)
+    n = int(batch.numel())
+    if n > 0:
+        if bool((batch[1:] < batch[:-1]).any()):
+            raise ValueError("batch is not sorted: the points of a graph must be contiguous (PyG's Batch order)")
+        if int(batch[0]) < 0:
+            raise ValueError(f"batch holds the negative graph id {int(batch[0])}")
+    top = int(batch[-1]) + 1 if n > 0 else 0
+    b = top if n_graphs is None else int(n_graphs)
+    if b < top:
+        raise ValueError(f"batch holds graph id {top - 1}, n_graphs = {b}")
+    ptr = torch.zeros(b + 1, dtype=torch.int64, device=batch.device)
+    if n > 0:
+        torch.cumsum(torch.bincount(batch, minlength=b), 0, out=ptr[1:])
+    return ptr
+
+
+_BATCHED_SINGLE_ONLY = ("period", "origin", "return_geometry")
+
+
+def _host_ptr(ptr, name: str, n: int) -> torch.Tensor:
+    """`ptr` as a host int64 [B + 1] tensor that starts at 0, never decreases and ends at n (ValueError otherwise)."""
+    t = ptr.detach() if isinstance(ptr, torch.Tensor) else torch.as_tensor(ptr)
+    if t.dim() != 1 or t.numel() < 1 or t.is_floating_point() or t.dtype == torch.bool:
+        raise ValueError(f"{name} must be a 1-D integer vector [B + 1] (got {t.dtype} {tuple(t.shape)})")
+    t = t.to(device="cpu", dtype=torch.int64).contiguous()
+    if int(t[0]) != 0:
+        raise ValueError(f"{name}[0] = {int(t[0])}: {name} must start at 0")
+    if bool((t[1:] < t[:-1]).any()):
+        raise ValueError(f"{name} decreases: the points of a graph must be contiguous, graph after graph")
+    if int(t[-1]) != n:
+        raise ValueError(f"{name} ends at {int(t[-1])}, the position array has {n} points")
+    return t
+
+
+def batched_graph_args(pos, ptr, r, pos_dst=None, ptr_dst=None, unsupported=None):
+    """Every argument check of the batched radius-graph builders, on HOST values only (ValueError; no device is needed to be
+    refused): returns (dim, ptr host int64 [B + 1], ptr_dst host int64 [B + 1] or None, radii list of B floats)."""
+    for k in (unsupported or {}):
+        if k in _BATCHED_SINGLE_ONLY:
+            raise ValueError(f"{k}= has no batched form: a periodic box, return_geometry, radius_in_degrees and the rank partitioner "
+                             "keep their single-graph forms (ops.radius_csr / radius_csr_raw, one call per graph)")
+        raise TypeError(f"unexpected keyword argument {k!r}")
+    if not isinstance(pos, torch.Tensor) or pos.dim() not in (1, 2):
+        raise ValueError("pos must be a tensor [n, dim] (or [n]: one dimension)")
+    dim = 1 if pos.dim() == 1 else int(pos.size(1))
+    if not 1 <= dim <= 3:
+        raise ValueError(f"positions of dimension {dim}: the radius graphs are built in 1..3 dimensions")
+    if ptr_dst is not None and pos_dst is None:
+        raise ValueError("ptr_dst given without pos_dst: a second ptr needs the second point set it divides")
+    if pos_dst is not None:
+        if ptr_dst is None:
+            raise ValueError("pos_dst given without ptr_dst: the second point set needs its own division into graphs")
+        if not isinstance(pos_dst, torch.Tensor) or pos_dst.dim() not in (1, 2):
+            raise ValueError("pos_dst must be a tensor [n_dst, dim] (or [n_dst]: one dimension)")
+        if (1 if pos_dst.dim() == 1 else int(pos_dst.size(1))) != dim:
+            raise ValueError("pos and pos_dst must have the same dimension")
+    ptr_h = _host_ptr(ptr, "ptr", int(pos.size(0)))
+    n_graphs = int(ptr_h.numel()) - 1
+    ptr_dst_h = None
+    if pos_dst is not None:
+        ptr_dst_h = _host_ptr(ptr_dst, "ptr_dst", int(pos_dst.size(0)))
+        if int(ptr_dst_h.numel()) != n_graphs + 1:
+            raise ValueError(f"ptr_dst divides pos_dst into {int(ptr_dst_h.numel()) - 1} graphs, ptr divides pos into {n_graphs}")
+    if isinstance(r, (int, float)):
+        radii = [float(r)] * n_graphs
+        if not (float(r) > 0.0 and float(r) != float("inf")):
+            raise ValueError(f"r = {r} must be positive and finite")
+    else:
+        radii = [float(v) for v in (r.detach().reshape(-1).tolist() if isinstance(r, torch.Tensor) else list(r))]
+        if len(radii) != n_graphs:
+            raise ValueError(f"r has {len(radii)} entries for {n_graphs} graphs (a float, or one radius per graph)")
+    for b, v in enumerate(radii):
+        if not (v > 0.0 and v != float("inf")):
+            raise ValueError(f"r[{b}] = {v} must be positive and finite")
+    return dim, ptr_h, ptr_dst_h, radii
+
+
+def batched_plan(bounds, ptr_src, ptr_dst, radii, dim: int):
+    """gpde_radius_csr_batched_plan on host values: (table uint8 [B * GPDE_RADIUS_BATCHED_REC_BYTES] host tensor, n_cells,
+    workspace bytes).  bounds: [B, 2, dim] float64 (host); ptr_src / ptr_dst: host int64 [B + 1] (ptr_dst None = ptr_src)."""
+    lib = _lib.lib()
+    n_graphs = int(ptr_src.numel()) - 1
+    bounds = torch.as_tensor(bounds, dtype=torch.float64).reshape(n_graphs, 2, dim).contiguous()
+    r_c = (ctypes.c_double * max(n_graphs, 1))(*radii)
+    table = torch.zeros(max(n_graphs, 1) * _lib.GPDE_RADIUS_BATCHED_REC_BYTES, dtype=torch.uint8)
+    n_cells, nbytes = ctypes.c_int64(0), ctypes.c_size_t(0)
+    _lib.check(lib.gpde_radius_csr_batched_plan(bounds.data_ptr(), ptr_src.data_ptr(), None if ptr_dst is None else ptr_dst.data_ptr(),
+                                                r_c, n_graphs, dim, table.data_ptr(), ctypes.byref(n_cells), ctypes.byref(nbytes)),
+               "gpde_radius_csr_batched_plan")
+    return table, int(n_cells.value), int(nbytes.value)
+
+
+def _graph_ids(ptr_dev: torch.Tensor, n: int) -> torch.Tensor:
+    """int64 [n]: the graph of every point of a ptr-divided array (on the device of ptr_dev; no sync)."""
+    return torch.searchsorted(ptr_dev[1:].contiguous(), torch.arange(n, dtype=torch.int64, device=ptr_dev.device), right=True)
+
+
+def radius_csr_batched(pos: torch.Tensor, ptr, r, *, pos_dst: Optional[torch.Tensor] = None, ptr_dst=None,
+                       reference_ties: bool = False, **single_graph_only):
+    """The radius graphs of B independent point sets in ONE build (gpde_radius_csr_batched_*): PyG's
+    `radius_graph(pos, r, batch=batch)` as the block-diagonal `Csr` the operator consumes.  Graph b owns the points
+    pos[ptr[b]:ptr[b + 1]] (`ptr` int64 [B + 1], see ptr_from_batch; pass it as a host tensor - a device tensor costs one more
+    copy) and has radius r[b] (`r`: a float, or a sequence / tensor of B radii).  Returns (Csr, edge_ptr):
+      Csr        global node ids, rows in ascending source order, `perm` the identity (edge attributes by CSR slot or NodeAttr) -
+                 rowptr / src / dst are the per-graph `radius_csr` results concatenated with their offsets, bit for bit;
+      edge_ptr   int64 [B + 1] = rowptr[ptr_dst]: graph b occupies the CSR slots edge_ptr[b] .. edge_ptr[b + 1].
+    `pos_dst` with `ptr_dst`: two point sets per graph - edges (j in pos -> i in pos_dst), a rectangular Csr (`n_src_nodes`).
+    Two synchronisations per call whatever B is (the per-graph bounds [B, 2, dim] and the edge count), one radix sort, four
+    launches - against two synchronisations, a sort and four launches PER GRAPH of a loop over radius_csr.
+    A periodic box, return_geometry, radius_in_degrees and the rank partitioner keep their single-graph forms."""
+    dim, ptr_h, ptr_dst_h, radii = batched_graph_args(pos, ptr, r, pos_dst, ptr_dst, single_graph_only)
+    lib = _lib.lib()
+    pos, pd = _positions(pos, pos_dst)
+    n, nd, n_graphs = int(pos.size(0)), int(pd.size(0)), int(ptr_h.numel()) - 1
+    dev = pos.device
+    ptr_d = ptr_h.to(dev)
+    ptr_dst_d = ptr_d if ptr_dst_h is None else ptr_dst_h.to(dev)
+    # per-graph bounds of both point sets, reduced on the device: ONE small copy [B, 2, dim] (graphs without points keep +-inf;
+    # the plan does not read the bounds of a graph without sources)
+    inf = float("inf")
+    lo = torch.full((n_graphs, dim), inf, dtype=torch.float64, device=dev)
+    hi = torch.full((n_graphs, dim), -inf, dtype=torch.float64, device=dev)
+    for p, pt in ((pos, ptr_d),) if pd is pos else ((pos, ptr_d), (pd, ptr_dst_d)):
+        if p.size(0) > 0 and n_graphs > 0:
+            gid = _graph_ids(pt, int(p.size(0))).unsqueeze(1).expand(-1, dim).contiguous()
+            lo.scatter_reduce_(0, gid, p, "amin")
+            hi.scatter_reduce_(0, gid, p, "amax")
+    bounds = torch.stack([lo, hi], dim=1).cpu()
+    table_h, n_cells, nbytes = batched_plan(bounds, ptr_h, ptr_dst_h, radii, dim)
+    table = table_h.to(dev)
+    ws = _alloc_ws(nbytes, dev)
+    flags = 1 if reference_ties else 0
+    ptr_dst_c = ptr_h if ptr_dst_h is None else ptr_dst_h
+    deg = torch.zeros(nd, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.gpde_radius_csr_batched_count(pos.data_ptr(), n, pd.data_ptr(), nd, dim, flags, ptr_h.data_ptr(), ptr_dst_c.data_ptr(),
+                                                     n_graphs, table.data_ptr(), n_cells, deg.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                     _stream_ptr(dev)), "gpde_radius_csr_batched_count")
+    rowptr64 = torch.zeros(nd + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(deg, 0, out=rowptr64[1:])
+    edge_ptr = rowptr64[ptr_dst_d]
+    e = int(rowptr64[-1].item())
+    if e >= (1 << 31) - 64:
+        raise NotImplementedError(f"{e} edges exceed the int32 CSR")
+    rowptr = rowptr64.to(torch.int32)
+    src = torch.empty(e, dtype=torch.int32, device=dev)
+    dst = torch.empty(e, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.gpde_radius_csr_batched_fill(pos.data_ptr(), n, pd.data_ptr(), nd, dim, flags, ptr_h.data_ptr(), ptr_dst_c.data_ptr(),
+                                                    n_graphs, table.data_ptr(), n_cells, rowptr.data_ptr(), src.data_ptr(), dst.data_ptr(),
+                                                    e, ws.data_ptr(), ws.numel(), _stream_ptr(dev)), "gpde_radius_csr_batched_fill")
+    csr = Csr(nd, e, rowptr, src, dst, torch.arange(e, dtype=torch.int32, device=dev), n_src_nodes=None if pos_dst is None else n)
+    return csr, edge_ptr
+
+
+def radius_graph_batched(pos: torch.Tensor, ptr, r, *, pos_dst: Optional[torch.Tensor] = None, ptr_dst=None,
+                         reference_ties: bool = False, **single_graph_only):
+    """(edge_index int64 [2, E], edge_ptr int64 [B + 1]) of the same batch (arguments of radius_csr_batched): every graph in the
+    reference's source-major order, graph after graph, global node ids - exactly what collating the per-sample `radius_graph`
+    edge lists gives.  It is the batched CSR stably sorted by source (graph b's edges are edge_index[:, edge_ptr[b]:edge_ptr[b + 1]])."""
+    csr, edge_ptr = radius_csr_batched(pos, ptr, r, pos_dst=pos_dst, ptr_dst=ptr_dst, reference_ties=reference_ties, **single_graph_only)
+    order = torch.sort(csr.src, stable=True).indices            # rows are destination-major: targets stay ascending per source
+    return torch.stack([csr.src[order].long(), csr.dst[order].long()]), edge_ptr

@@ -648,6 +648,40 @@ GPDE_API int gpde_radius_csr_periodic_fill(const double* pos_src, int64_t n_src,
                                   const double* period, const int32_t* rowptr, int32_t* src, int32_t* dst, float* geom,
                                   int64_t n_edges, void* ws, size_t ws_bytes, void* stream);
 
+/* The cell-list builder for a BATCH of independent point sets: the block-diagonal destination CSR of B radius graphs in one
+ * build (what a DataLoader makes of the per-sample graphs of the reference's training scripts, UAI3_resolution.py:131-145,
+ * neurips1_MGKN.py:204 - one ball_connectivity per sample - without one build per sample).  Graph b owns the sources
+ * ptr_src[b] .. ptr_src[b + 1] and the destinations ptr_dst[b] .. ptr_dst[b + 1] of the concatenated position arrays and has
+ * its own radius r[b]; node ids in rowptr / src / dst are GLOBAL (rows of the concatenated destinations, sources of the
+ * concatenated sources).  Rows as in the open builder: ascending source id (rows longer than 4096 edges keep cell order),
+ * self-loops included, both arithmetics (flags as gpde_radius_csr_count; under GPDE_RADIUS_REFERENCE_TIES the forced zero of
+ * the diagonal compares global ids).  pos_dst == pos_src with n_dst == n_src means ONE point set (then ptr_dst = ptr_src).
+ *   gpde_radius_csr_batched_plan   HOST ONLY, no device call.  bounds [B][2][dim]: lo then hi of a box around both point sets of
+ *       graph b (not read for a graph without sources, which gets one empty cell, as does a graph of coincident points);
+ *       ptr_src / ptr_dst [B + 1] (ptr_dst NULL = ptr_src); r [B].  Writes B records of GPDE_RADIUS_BATCHED_REC_BYTES bytes
+ *       into the host array `table` (NULL: a query) - each graph's own cell grid by the rule of the open builder, its radius
+ *       terms, its first cell in the batch-wide numbering and its point ranges - and returns the summed cell count and the
+ *       workspace bytes of count / fill.  The summed cell count is held to 2^24: while it is exceeded every graph's cell edge
+ *       doubles (the grid is only a filter: the edges do not depend on it); more graphs than that end at one cell each.
+ *   gpde_radius_csr_batched_count / _fill   the two passes with the caller's scan between them, `ws` untouched in between, like
+ *       the open twins.  `table`: the planned records in a DEVICE buffer (the caller uploads them; the library copies nothing
+ *       between host and device); n_cells: what the plan returned.  ptr_src / ptr_dst are the HOST arrays again, checked on
+ *       every call; the records must be the plan of these very arrays.
+ * GPDE_EINVAL with a gpde_last_error() text, before any device call, for: dim outside 1..3; n_graphs < 0; a ptr array that is
+ * NULL, does not start at 0, decreases, or does not end at the point count (at most 2^31 - 1); r[b] not positive and finite;
+ * unknown flags; null positions, table, deg, rowptr, src / dst or ws; n_cells < n_graphs.  GPDE_EWORKSPACE for a short workspace.
+ * n_graphs = 0 and zero points are valid calls.  Additions to the ABI: GPDE_VERSION is unchanged. */
+enum { GPDE_RADIUS_BATCHED_REC_BYTES = 96 };
+GPDE_API int gpde_radius_csr_batched_plan(const double* bounds, const int64_t* ptr_src, const int64_t* ptr_dst, const double* r,
+                                 int64_t n_graphs, int dim, void* table, int64_t* n_cells, size_t* ws_bytes);
+GPDE_API int gpde_radius_csr_batched_count(const double* pos_src, int64_t n_src, const double* pos_dst, int64_t n_dst, int dim,
+                                  uint32_t flags, const int64_t* ptr_src, const int64_t* ptr_dst, int64_t n_graphs,
+                                  const void* table, int64_t n_cells, int32_t* deg, void* ws, size_t ws_bytes, void* stream);
+GPDE_API int gpde_radius_csr_batched_fill(const double* pos_src, int64_t n_src, const double* pos_dst, int64_t n_dst, int dim,
+                                 uint32_t flags, const int64_t* ptr_src, const int64_t* ptr_dst, int64_t n_graphs,
+                                 const void* table, int64_t n_cells, const int32_t* rowptr, int32_t* src, int32_t* dst,
+                                 int64_t n_edges, void* ws, size_t ws_bytes, void* stream);
+
 /* HIP-event timing of the kernels launched by gpde_nnconv_fwd on the calling thread (used by
  * bench.py for the roofline figure; events are recorded on the same stream as the kernels).
  * gpde_profile_begin() arms it; gpde_profile_end_kinds() disarms it, SYNCHRONISES on the recorded
