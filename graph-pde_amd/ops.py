@@ -2268,7 +2268,8 @@ def radius_in_degrees(pos: torch.Tensor, r: float, reference_ties: bool = False,
 
 
 def radius_csr(pos: torch.Tensor, r: float, reference_ties: bool = False, pos_dst: Optional[torch.Tensor] = None,
-               period=None, origin=None, return_geometry: bool = False):
+               period=None, origin=None, return_geometry: bool = False, max_num_neighbors: Optional[int] = None,
+               select: str = "nearest", seed: int = 0):
     """The radius graph of one point set as the `Csr` the operator consumes (no edge_index, no sort): rowptr / src / dst
     are what `csr_for(radius_graph(pos, r), n)` builds - bit for bit - and `perm` is the identity: per-edge tensors for
     this graph are laid out by CSR slot (`csr.edge_index` is the edge list in that order), or not needed at all
@@ -2278,7 +2279,17 @@ def radius_csr(pos: torch.Tensor, r: float, reference_ties: bool = False, pos_ds
     torus1d_connectivity (multipole utilities.py:1190-1266, 404-417) are meant to build.  `return_geometry=True` returns
     (Csr, geom): geom float32 [E, dim + 1] = the minimum-image displacement pos[src] - image(pos[dst]) and its norm, already in
     the slot order the operator reads (perm is the identity) - the first columns of the reference's torus edge attributes
-    [dx, dy, |d|, a_i, a_j] (utilities.py:1251-1257), which endpoint coordinates (`NodeAttr`) cannot give across the seam."""
+    [dx, dy, |d|, a_i, a_j] (utilities.py:1251-1257), which endpoint coordinates (`NodeAttr`) cannot give across the seam.
+
+    `max_num_neighbors=k`: cap the in-degree (PyG's argument of that name; the reference's thinned `gaussian_connectivity`) - a
+    destination with more than k sources within r keeps k of them, chosen by `select` (see select_in_edges for the contract):
+    "nearest" - the k nearest (exact float64 squared distance, minimum-image on a periodic box; ties by source order), or
+    "random" - a uniform k-subset drawn by a hash of (`seed`, destination id, source id): under aggr='mean' the unbiased
+    Monte-Carlo estimate of the full-ball mean, which the k nearest are not.  Rows stay in ascending source order, `perm` is the
+    identity and `geom` is gathered to the new slots.  The default (None) is the uncapped build, by the same calls as before.
+    The cap is defined on the exact arithmetic: with reference_ties=True it raises ValueError.  radius_graph*, radius_csr_raw,
+    radius_in_degrees, multilevel_radius_graphs and the rank partitioner (parallel.py) have no capped form."""
+    k = _cap_args(max_num_neighbors, select, seed, reference_ties)        # host checks first: no device is needed to be refused
     out = radius_csr_raw(pos, r, reference_ties, pos_dst, period=period, origin=origin, return_geometry=return_geometry)
     rowptr, src, dst = out[:3]
     e = int(src.numel())
@@ -2286,7 +2297,11 @@ def radius_csr(pos: torch.Tensor, r: float, reference_ties: bool = False, pos_ds
     # n_dst, n_src=n_src) builds, bit for bit; consumed by the module as conv((x_src, x_dst), csr, edge_attr)
     csr = Csr(int(rowptr.numel()) - 1, e, rowptr, src, dst, torch.arange(e, dtype=torch.int32, device=src.device),
               n_src_nodes=None if pos_dst is None else int(pos.size(0)))
-    return (csr, out[3]) if return_geometry else csr
+    if k is None:
+        return (csr, out[3]) if return_geometry else csr
+    key = edge_sqdist_keys(csr, pos, pos_dst, period=period, origin=origin) if select == "nearest" else edge_hash_keys(csr.src, csr.dst, seed)
+    csr, edge_ids = select_in_edges(csr, k, key)
+    return (csr, out[3][edge_ids]) if return_geometry else csr
 
 
 def multilevel_radius_graphs(pos_levels: Sequence[torch.Tensor], radii_inner: Sequence[float],
@@ -2305,6 +2320,177 @@ def multilevel_radius_graphs(pos_levels: Sequence[torch.Tensor], radii_inner: Se
                          origin=origin) for l in range(len(pos_levels) - 1)]
     up = [d.flip(0) for d in down]
     return {"inner": inner, "down": down, "up": up}
+
+
+# ----------------------------------------------------------------------------------------------
+# capped in-degree: keep the k nearest or k sampled in-edges of every destination (gpde_select.hip)
+# ----------------------------------------------------------------------------------------------
+SELECT_MODES = ("nearest", "random")
+
+
+def _cap_k(k) -> int:
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise ValueError(f"max_num_neighbors / k must be an int >= 1 (got {k!r})")
+    if k < 1:
+        raise ValueError(f"max_num_neighbors / k = {k} must be >= 1")
+    return int(k)
+
+
+def _cap_seed(seed) -> int:
+    if isinstance(seed, bool) or not isinstance(seed, int) or not -(1 << 63) <= seed < (1 << 63):
+        raise ValueError(f"seed must be an int in [-2^63, 2^63) (got {seed!r})")
+    return int(seed)
+
+
+def _cap_args(max_num_neighbors, select, seed, reference_ties: bool = False) -> Optional[int]:
+    """The host checks of the builders' cap arguments (ValueError): k, or None for the uncapped build."""
+    if select not in SELECT_MODES:
+        raise ValueError(f"select = {select!r} must be one of {SELECT_MODES}")
+    _cap_seed(seed)
+    if max_num_neighbors is None:
+        return None
+    k = _cap_k(max_num_neighbors)
+    if reference_ties:
+        raise ValueError("max_num_neighbors with reference_ties=True: the cap is defined on the exact distance arithmetic "
+                         "(reference_ties must be False)")
+    return k
+
+
+def float_keys_to_int64(key: torch.Tensor) -> torch.Tensor:
+    """A floating tensor as int64 keys of the same order (torch ops, any device): a < b gives m(a) < m(b), a == b gives
+    m(a) == m(b) (-0.0 and +0.0 are one key) - over negative values, subnormals and +-inf.  The value is widened to float64
+    (exact), -0.0 folded into +0.0, and the bits of a negative value are flipped below the sign.  NaN has no place in the order:
+    select_in_edges refuses it."""
+    if not key.is_floating_point():
+        raise ValueError(f"float_keys_to_int64 takes a floating tensor (got {key.dtype})")
+    bits = (key.detach().to(torch.float64) + 0.0).contiguous().view(torch.int64)
+    return bits ^ ((bits >> 63) & 0x7FFFFFFFFFFFFFFF)
+
+
+def select_in_edges(csr: Csr, k: int, key: torch.Tensor):
+    """Cap the in-degree of a destination `Csr` (gpde_csr_select_k): returns (Csr, edge_ids).
+      - a row with at most k in-edges is kept whole; a longer row keeps the k slots with the smallest (key, slot) in
+        lexicographic order - slots are distinct, so the choice is unique;
+      - kept edges stay in ascending slot order inside their row: ascending source order, and with it the operator's summation
+        order, is preserved; no atomics, two identical calls give identical bits;
+      - the selection for k is a subset of the selection for any k' > k.
+    `key`: int64 [E] in slot order (edge_sqdist_keys, edge_hash_keys, or the caller's), or a floating tensor, mapped to int64
+    order-preservingly (float_keys_to_int64); NaN is refused.  One synchronisation: the new edge count (the NaN test rides on it).
+    The new Csr has the gathered src / dst, the identity `perm`, `n_src_nodes` and the flow direction of the input and
+    max_in_degree = min(old, k).  edge_ids int64 [E'] = csr.perm[kept slots]: the rows of any tensor that addressed the INPUT
+    graph's edges - `edge_attr[edge_ids]`, `geom[edge_ids]` are the new graph's per-edge tensors, in its slot order.
+    k >= csr.max_in_degree returns the same rows and slots, with edge_ids = perm."""
+    k = _cap_k(k)
+    if not isinstance(csr, Csr):
+        raise ValueError(f"csr must be an ops.Csr (got {type(csr).__name__})")
+    if not isinstance(key, torch.Tensor) or key.dim() != 1 or int(key.numel()) != csr.n_edges:
+        got = tuple(key.shape) if isinstance(key, torch.Tensor) else type(key).__name__
+        raise ValueError(f"key must be a tensor [{csr.n_edges}]: one key per CSR slot (got {got})")
+    if key.dtype != torch.int64 and not key.is_floating_point():
+        raise ValueError(f"key must be int64 or floating (got {str(key.dtype).replace('torch.', '')})")
+    if key.device != csr.rowptr.device:
+        raise ValueError(f"key is on {key.device}, the graph on {csr.rowptr.device}")
+    _require_cuda(csr.rowptr, "csr")
+    lib = _lib.lib()
+    dev = csr.rowptr.device
+    n, e = csr.n_nodes, csr.n_edges
+    nan = torch.isnan(key).any() if key.is_floating_point() else torch.zeros((), dtype=torch.bool, device=dev)
+    key = (float_keys_to_int64(key) if key.is_floating_point() else key.detach()).contiguous()
+    rp = csr.rowptr.long()
+    rowptr64 = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum((rp[1:] - rp[:-1]).clamp(max=k), 0, out=rowptr64[1:])
+    e_new, has_nan = (int(v) for v in torch.stack([rowptr64[-1], nan.to(torch.int64)]).cpu())
+    if has_nan:
+        raise ValueError("key holds NaN: a NaN has no place in the order of the keys")
+    carry = dict(n_src_nodes=csr.n_src_nodes, _flow_flipped=csr._flow_flipped)
+    if e_new == e:                                   # no row is longer than k: the same rows and slots
+        out = Csr(n, e, csr.rowptr, csr.src, csr.dst, torch.arange(e, dtype=torch.int32, device=dev), _max_in_degree=csr._max_in_degree, **carry)
+        return out, csr.perm.long()
+    rowptr = rowptr64.to(torch.int32)
+    slots = torch.empty(e_new, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.gpde_csr_select_k(csr.rowptr.contiguous().data_ptr(), key.data_ptr(), n, e, k, rowptr.data_ptr(), slots.data_ptr(),
+                                         e_new, _stream_ptr(dev)), "gpde_csr_select_k")
+    sl = slots.long()
+    out = Csr(n, e_new, rowptr, csr.src[sl], csr.dst[sl], torch.arange(e_new, dtype=torch.int32, device=dev), _max_in_degree=k, **carry)
+    return out, csr.perm[sl].long()              # (some row was longer than k: the largest in-degree is now k)
+
+
+def _key_box(period, origin, dim: int):
+    """`period` / `origin` of edge_sqdist_keys as two lists of `dim` floats (a scalar: every axis; 0 / None: an open axis)."""
+    def per_axis(v, name):
+        if v is None or isinstance(v, (int, float)):
+            return [0.0 if v is None else float(v)] * dim
+        v = [0.0 if t is None else float(t) for t in (v.tolist() if isinstance(v, torch.Tensor) else v)]
+        if len(v) != dim:
+            raise ValueError(f"{name} has {len(v)} entries for positions of dimension {dim}")
+        return v
+    per, org = per_axis(period, "period"), per_axis(origin, "origin")
+    for a in range(dim):
+        if not (0.0 <= per[a] < float("inf")) or not abs(org[a]) < float("inf"):
+            raise ValueError(f"period[{a}] = {per[a]} must be >= 0 (0 = open axis) and origin[{a}] = {org[a]} finite")
+    return per, org
+
+
+def edge_sqdist_keys(csr: Csr, pos: torch.Tensor, pos_dst: Optional[torch.Tensor] = None, period=None, origin=None) -> torch.Tensor:
+    """int64 [E] by CSR slot: the IEEE-754 bits of the float64 squared distance of every edge (gpde_edge_keys_sqdist) - the
+    "nearest" key of select_in_edges (a non-negative double orders as its int64 bits).  `pos` [n_src, dim] are the positions
+    `csr.src` indexes, `pos_dst` [n_nodes, dim] those of the destinations (None: one point set).  Open axes: d = pos_dst[i] -
+    pos[j], d2 += d * d in axis order, unfused - the builders' exact arithmetic, bit for bit.  `period` / `origin` as in
+    radius_csr: on a periodic axis d = pos[j] - pos_dst[i], d -= L rint(d / L) on the raw coordinates - the minimum-image
+    difference in the form a float64 host computation follows operation by operation (it does not depend on `origin`)."""
+    if not isinstance(csr, Csr):
+        raise ValueError(f"csr must be an ops.Csr (got {type(csr).__name__})")
+    for t, name, rows in ((pos, "pos", csr.n_src), (pos_dst, "pos_dst", csr.n_nodes)):
+        if t is None and name == "pos_dst":
+            if csr.n_src_nodes is not None and csr.n_src != csr.n_nodes:
+                raise ValueError(f"a rectangular graph ({csr.n_src} sources, {csr.n_nodes} destinations) needs pos_dst")
+            continue
+        if not isinstance(t, torch.Tensor) or t.dim() not in (1, 2) or int(t.size(0)) != rows:
+            got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{name} must be a tensor [{rows}, dim] (or [{rows}]: one dimension): the points the graph was built on (got {got})")
+    dim = 1 if pos.dim() == 1 else int(pos.size(1))
+    if not 1 <= dim <= 3:
+        raise ValueError(f"positions of dimension {dim}: the radius graphs are built in 1..3 dimensions")
+    if pos_dst is not None and (1 if pos_dst.dim() == 1 else int(pos_dst.size(1))) != dim:
+        raise ValueError("pos and pos_dst must have the same dimension")
+    per, org = _key_box(period, origin, dim)
+    lib = _lib.lib()
+    pos, pd = _positions(pos, pos_dst)
+    dev = pos.device
+    if csr.rowptr.device != dev:
+        raise ValueError(f"pos is on {dev}, the graph on {csr.rowptr.device}")
+    keys = torch.empty(csr.n_edges, dtype=torch.int64, device=dev)
+    per_c = (ctypes.c_double * dim)(*per) if any(per) else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.gpde_edge_keys_sqdist(pos.data_ptr(), pd.data_ptr(), dim, per_c, (ctypes.c_double * dim)(*org), csr.src.contiguous().data_ptr(),
+                                             csr.dst.contiguous().data_ptr(), csr.n_edges, keys.data_ptr(), _stream_ptr(dev)),
+                   "gpde_edge_keys_sqdist")
+    return keys
+
+
+def edge_hash_keys(src_ids: torch.Tensor, dst_ids: torch.Tensor, seed: int = 0) -> torch.Tensor:
+    """int64 [E]: a counter-based hash of (seed, dst id, src id) per edge (gpde_edge_keys_hash; the constants are stated in
+    include/gpde.h) - the "random" key of select_in_edges.  It depends on the three numbers only - not on the slot order, the
+    builder or k - so the k smallest keys of a row are a uniform k-subset of it, reproducible from the seed: under aggr='mean'
+    the unbiased Monte-Carlo estimate of the full-ball mean.  The ids are explicit int32 vectors (`csr.src`, `csr.dst`; a batch
+    passes graph-local ids)."""
+    seed = _cap_seed(seed)
+    for t, name in ((src_ids, "src_ids"), (dst_ids, "dst_ids")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int32:
+            got = f"{str(t.dtype).replace('torch.', '')} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{name} must be an int32 vector [E] (got {got})")
+    if src_ids.numel() != dst_ids.numel() or src_ids.device != dst_ids.device:
+        raise ValueError(f"src_ids [{src_ids.numel()}] on {src_ids.device} and dst_ids [{dst_ids.numel()}] on {dst_ids.device} must match")
+    _require_cuda(src_ids, "src_ids")
+    lib = _lib.lib()
+    dev = src_ids.device
+    e = int(src_ids.numel())
+    keys = torch.empty(e, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.gpde_edge_keys_hash(src_ids.contiguous().data_ptr(), dst_ids.contiguous().data_ptr(), e, seed, keys.data_ptr(),
+                                           _stream_ptr(dev)), "gpde_edge_keys_hash")
+    return keys
 
 
 # ----------------------------------------------------------------------------------------------
@@ -2415,7 +2601,8 @@ def _graph_ids(ptr_dev: torch.Tensor, n: int) -> torch.Tensor:
 
 
 def radius_csr_batched(pos: torch.Tensor, ptr, r, *, pos_dst: Optional[torch.Tensor] = None, ptr_dst=None,
-                       reference_ties: bool = False, **single_graph_only):
+                       reference_ties: bool = False, max_num_neighbors: Optional[int] = None, select: str = "nearest", seed: int = 0,
+                       **single_graph_only):
     """The radius graphs of B independent point sets in ONE build (gpde_radius_csr_batched_*): PyG's
     `radius_graph(pos, r, batch=batch)` as the block-diagonal `Csr` the operator consumes.  Graph b owns the points
     pos[ptr[b]:ptr[b + 1]] (`ptr` int64 [B + 1], see ptr_from_batch; pass it as a host tensor - a device tensor costs one more
@@ -2426,7 +2613,12 @@ def radius_csr_batched(pos: torch.Tensor, ptr, r, *, pos_dst: Optional[torch.Ten
     `pos_dst` with `ptr_dst`: two point sets per graph - edges (j in pos -> i in pos_dst), a rectangular Csr (`n_src_nodes`).
     Two synchronisations per call whatever B is (the per-graph bounds [B, 2, dim] and the edge count), one radix sort, four
     launches - against two synchronisations, a sort and four launches PER GRAPH of a loop over radius_csr.
-    A periodic box, return_geometry, radius_in_degrees and the rank partitioner keep their single-graph forms."""
+    A periodic box, return_geometry, radius_in_degrees and the rank partitioner keep their single-graph forms.
+    `max_num_neighbors` / `select` / `seed`: the capped in-degree of radius_csr, per graph - "random" hashes GRAPH-LOCAL node ids
+    (global id minus the graph's ptr / ptr_dst entry), so for both modes the result is again the per-graph capped `radius_csr`
+    results concatenated with their offsets, bit for bit; edge_ptr is taken from the new rowptr.  radius_graph_batched has no
+    capped form."""
+    k = _cap_args(max_num_neighbors, select, seed, reference_ties)
     dim, ptr_h, ptr_dst_h, radii = batched_graph_args(pos, ptr, r, pos_dst, ptr_dst, single_graph_only)
     lib = _lib.lib()
     pos, pd = _positions(pos, pos_dst)
@@ -2469,7 +2661,15 @@ def radius_csr_batched(pos: torch.Tensor, ptr, r, *, pos_dst: Optional[torch.Ten
                                                     n_graphs, table.data_ptr(), n_cells, rowptr.data_ptr(), src.data_ptr(), dst.data_ptr(),
                                                     e, ws.data_ptr(), ws.numel(), _stream_ptr(dev)), "gpde_radius_csr_batched_fill")
     csr = Csr(nd, e, rowptr, src, dst, torch.arange(e, dtype=torch.int32, device=dev), n_src_nodes=None if pos_dst is None else n)
-    return csr, edge_ptr
+    if k is None:
+        return csr, edge_ptr
+    if select == "nearest":
+        key = edge_sqdist_keys(csr, pos, None if pos_dst is None else pd)        # global ids into the concatenated positions
+    else:
+        g = _graph_ids(ptr_dst_d, nd)[dst.long()] if e > 0 else torch.zeros(0, dtype=torch.int64, device=dev)   # the graph of every edge
+        key = edge_hash_keys((src.long() - ptr_d[g]).to(torch.int32), (dst.long() - ptr_dst_d[g]).to(torch.int32), seed)
+    csr, _ = select_in_edges(csr, k, key)
+    return csr, csr.rowptr.long()[ptr_dst_d]
 
 
 def radius_graph_batched(pos: torch.Tensor, ptr, r, *, pos_dst: Optional[torch.Tensor] = None, ptr_dst=None,

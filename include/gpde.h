@@ -682,6 +682,51 @@ GPDE_API int gpde_radius_csr_batched_fill(const double* pos_src, int64_t n_src, 
                                  const void* table, int64_t n_cells, const int32_t* rowptr, int32_t* src, int32_t* dst,
                                  int64_t n_edges, void* ws, size_t ws_bytes, void* stream);
 
+/* CAP A GRAPH'S IN-DEGREE: per destination row of a CSR keep the k in-edges of smallest key (gpde_select.hip).  The builders
+ * above emit the full ball of every destination and nothing bounds a row; the method itself estimates the kernel integral from
+ * m points of the ball (Nystrom), the reference's mesh generators offer a thinned connectivity next to ball_connectivity
+ * (gaussian_connectivity, graph-neural-operator utilities.py:257-263, 372-378) and PyG's radius_graph has max_num_neighbors.
+ * The selection works on a finished CSR - any builder's, or gpde_csr_from_coo's.
+ *   gpde_csr_select_k   rowptr int32 [n_rows + 1], keys int64 [n_edges] by CSR slot, k >= 1.  A row of at most k in-edges is kept
+ *       whole; a longer row keeps the k slots with the smallest (key, slot) in lexicographic order (slots are distinct: the choice
+ *       is unique).  rowptr_out int32 [n_rows + 1] is GIVEN by the caller - the exclusive scan of min(deg, k) - and n_out is its
+ *       total; slots_out int32 [n_out] receives the kept INPUT slots, ascending inside every row: source order, and with it the
+ *       operator's summation order, is preserved.  No atomics: two identical calls give identical bits.  The selection for k is a
+ *       subset of the selection for any k' > k.  One wave per row finds the k-th smallest key by bisection over the key bits and
+ *       emits in one pass in slot order; rows of up to 2048 keys are staged in LDS, longer ones are re-read.  Any row length.
+ *   gpde_edge_keys_sqdist   keys[s] = the IEEE-754 bits of the float64 squared distance of edge (src[s] in pos_src -> dst[s] in
+ *       pos_dst) - a non-negative double orders as its int64 bits.  Open axes: d = pos_dst[i][a] - pos_src[j][a], d2 += d * d in
+ *       axis order, contraction off: the arithmetic of gpde_radius_csr_* (flags = 0), so a float64 host computation reproduces
+ *       the bits.  period / origin: HOST arrays [dim] as in gpde_radius_csr_periodic_* (period[a] = 0: an open axis), or NULL (no
+ *       periodic axis / origin 0): on a periodic axis d = pos_src[j][a] - pos_dst[i][a], d -= L rint(d / L) on the RAW
+ *       coordinates (L = period[a]; rint rounds half to even) - the minimum-image difference in the form a float64 host
+ *       computation follows operation by operation; it does not depend on the origin, which is only checked.  (The periodic
+ *       BUILDER reduces both points into [origin, origin + L) and subtracts an image x_d +- L: the same distance up to rounding,
+ *       tens of ulp apart in d2 for an edge that crosses the seam.)  The node ids of src / dst are NOT checked
+ *       against the point counts (the call does not see them): they are a CSR's, built for these point sets.
+ *   gpde_edge_keys_hash     keys[s] = a counter-based hash of (seed, dst_ids[s], src_ids[s]) - independent of slot order, of the
+ *       builder and of k; the ids are explicit int32 arrays so that a batch can pass graph-local ids.  All arithmetic mod 2^64
+ *       (the constants below ARE the specification; seed is the int64 reinterpreted as uint64):
+ *           z = seed * GPDE_HASH_SEED_MUL + ((uint64)dst << 32 | (uint64)src)
+ *           z = (z ^ z >> 30) * GPDE_HASH_MUL1;   z = (z ^ z >> 27) * GPDE_HASH_MUL2;   z ^= z >> 31;   key = (int64)(z >> 1)
+ *       A uniform k-subset of the ball under aggr = mean is the UNBIASED Monte-Carlo estimate of the full-ball mean; the k
+ *       nearest are not (they sample the inner part of the ball only).
+ * Zero rows and zero edges are valid calls.  GPDE_EINVAL with a gpde_last_error() text, before any device call, for NULL
+ * arguments, k < 1, sizes outside an int32 CSR and an n_out that cannot be the total of rowptr_out (negative, or more than
+ * min(n_edges, n_rows * k); rowptr_out is device memory and no call here synchronises, so the exact total is the caller's word -
+ * the kernel writes no slot at or past n_out whatever rowptr_out holds); GPDE_EUNSUPPORTED for dim outside 1..3.
+ * Additions to the ABI: GPDE_VERSION is unchanged. */
+#define GPDE_HASH_SEED_MUL 0x9E3779B97F4A7C15ull
+#define GPDE_HASH_MUL1 0xBF58476D1CE4E5B9ull
+#define GPDE_HASH_MUL2 0x94D049BB133111EBull
+GPDE_API int gpde_csr_select_k(const int32_t* rowptr, const int64_t* keys, int64_t n_rows, int64_t n_edges, int64_t k,
+                      const int32_t* rowptr_out, int32_t* slots_out, int64_t n_out, void* stream);
+GPDE_API int gpde_edge_keys_sqdist(const double* pos_src, const double* pos_dst, int dim, const double* period,
+                          const double* origin, const int32_t* src, const int32_t* dst, int64_t n_edges, int64_t* keys,
+                          void* stream);
+GPDE_API int gpde_edge_keys_hash(const int32_t* src_ids, const int32_t* dst_ids, int64_t n_edges, int64_t seed,
+                        int64_t* keys, void* stream);
+
 /* HIP-event timing of the kernels launched by gpde_nnconv_fwd on the calling thread (used by
  * bench.py for the roofline figure; events are recorded on the same stream as the kernels).
  * gpde_profile_begin() arms it; gpde_profile_end_kinds() disarms it, SYNCHRONISES on the recorded
