@@ -488,3 +488,38 @@ class HiddenBipFunction(torch.autograd.Function):
             need_w_last=need[3], need_b_last=ctx.has_b_last and need[4], need_root=ctx.has_root and need[6],
             need_bias=ctx.has_bias and need[7])
         return gxs, gxd, (gh if need[2] else None), gwl, gbl, None, groot, gbias, None
+
+
+class GCNFunction(torch.autograd.Function):
+    """GCNConv: out = (A x) W + bias, A = the normalised adjacency of an `ops.GcnNorm` (gpde_gcn_fwd), differentiable in x, W and
+    bias.  With G = A^T grad_out (one launch of the aggregation kernel on the reversed graph): grad_x = G W^T, grad_W = x^T G
+    (torch.mm), grad_bias = grad_out.sum(0).  Under the forced route 'aggregate_first' the SAME launch also multiplies by W^T -
+    the fused kernel with `agg_out` = G leaves grad_x and G together; it is not the default because the fused kernel measured
+    slower than aggregation + torch.mm (ops.gcn_route).  Only x and W are saved (no activation besides the input); the kernel is
+    skipped when neither x nor W needs a gradient.  No atomics anywhere: two backward passes give the same bits."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, norm, route):
+        out = ops.gcn_forward_raw(x.detach(), norm, weight.detach(), None if bias is None else bias.detach(), route=route)
+        ctx.norm, ctx.has_bias, ctx.fused = norm, bias is not None, route == "aggregate_first"
+        ctx.save_for_backward(x, weight)
+        return out
+
+    @staticmethod
+    @once_differentiable        # the native backward is not itself differentiable: create_graph=True raises
+    def backward(ctx, grad_out):
+        x, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gx = gw = gb = None
+        if need[0] and ctx.fused:
+            # (weight.t() is a strided view: the operand gate hands the kernel a dense copy of W^T)
+            gx, g_agg = ops.gcn_forward_raw(grad_out, ctx.norm, weight.detach().t(), None, route="aggregate_first", agg_out=True, reverse=True)
+        elif need[0] or need[1]:
+            g_agg = ops.gcn_forward_raw(grad_out, ctx.norm, None, None, reverse=True)
+            if need[0]:
+                gx = torch.mm(g_agg, weight.detach().t())
+        if need[1]:
+            gw = torch.mm(x.detach().t(), g_agg)
+        if ctx.has_bias and need[2]:
+            gb = grad_out.sum(0)
+        return gx, gw, gb, None, None

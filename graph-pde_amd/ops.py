@@ -431,6 +431,8 @@ def cache_snapshot() -> list:
     and slot-ordered attribute copies, packed weights, staged constants): capture.py pins them for the lifetime of a recorded
     graph, whose kernels read those addresses whatever the LRU policies do afterwards."""
     pins = [v for v in _csr_cache.values()] + [v[1] for v in _pack_cache.values()] + [v for v in _stage_cache.values()]
+    for v in _gcn_norm_cache.values():       # coefficients of the GCN normalisation, with the reversed graph where a backward built it
+        pins.append((v[2].csr, v[2].coef, v[2].self_coef, v[2]._reversed))
     for v in _csr_cache.values():
         srt = v[2]._attr_sorted
         if srt:
@@ -453,6 +455,7 @@ def clear_caches():
     _pack_cache.clear()
     _pack_by_ptr.clear()
     _stage_cache.clear()
+    _gcn_norm_cache.clear()
 
 
 # ----------------------------------------------------------------------------------------------
@@ -2680,3 +2683,179 @@ def radius_graph_batched(pos: torch.Tensor, ptr, r, *, pos_dst: Optional[torch.T
     csr, edge_ptr = radius_csr_batched(pos, ptr, r, pos_dst=pos_dst, ptr_dst=ptr_dst, reference_ties=reference_ties, **single_graph_only)
     order = torch.sort(csr.src, stable=True).indices            # rows are destination-major: targets stay ascending per source
     return torch.stack([csr.src[order].long(), csr.dst[order].long()]), edge_ptr
+
+
+# ----------------------------------------------------------------------------------------------
+# GCNConv (include/gpde.h gpde_gcn_norm / gpde_gcn_fwd / gpde_gcn_plan; csrc/gpde_gcn.hip)
+# ----------------------------------------------------------------------------------------------
+GCN_ADD_SELF_LOOPS, GCN_IMPROVED, GCN_NORMALIZE = 1, 2, 4        # gpde_gcn_norm flags (tests/test_gcn_host.py checks them against the header)
+GCN_RELU = 1                                                     # gpde_gcn_fwd flag
+GCN_ROUTES = ("aggregate_first", "aggregate_mm", "transform_first")
+
+
+class GcnNorm:
+    """The symmetric normalisation of one graph: `coef` [E] by CSR slot and `self_coef` [N] (gpde_gcn_norm) on `csr`, and - built
+    on first use, in a backward - the same pair for the REVERSED graph (`reversed`): the backward of the aggregation is the
+    aggregation over the transposed matrix, and a graph with an edge j -> i need not hold i -> j."""
+
+    def __init__(self, csr: Csr, coef: torch.Tensor, self_coef: torch.Tensor, flags: int):
+        self.csr, self.coef, self.self_coef, self.flags = csr, coef, self_coef, flags
+        self._reversed = None
+
+    @property
+    def reversed(self):
+        """(csr_rev, coef_rev): the CSR of the edge list with its rows swapped and each reversed slot's coefficient.  It is built
+        from the forward CSR's own slot-order edge list (`Csr.edge_index`, flip=True), so its `perm` maps reversed slots to forward
+        slots directly - one gather - and a `Csr` handed in without an edge_index tensor, or a flipped flow, is no special case.
+        The diagonal (self_coef) is its own transpose."""
+        if self._reversed is None:
+            csr = self.csr
+            if csr.n_edges == 0:
+                self._reversed = (csr, self.coef)
+            else:
+                rev = build_csr(csr.edge_index, csr.n_nodes, flip=True)
+                self._reversed = (rev, gather_rows(self.coef.view(-1, 1), rev.perm).view(-1))
+        return self._reversed
+
+
+_gcn_norm_cache: "dict[tuple, tuple]" = {}       # key -> (Csr kept alive, edge_weight storage kept alive, GcnNorm, nbytes); LRU order
+_GCN_NORM_CACHE_MAX_ENTRIES = 64
+_GCN_NORM_CACHE_MAX_BYTES = 1 << 30                # what the entries pin: the CSR, the coefficients and - after a backward - the same again
+
+
+def gcn_flags(improved: bool = False, add_self_loops: bool = True, normalize: bool = True) -> int:
+    return (GCN_IMPROVED if improved else 0) | (GCN_ADD_SELF_LOOPS if add_self_loops else 0) | (GCN_NORMALIZE if normalize else 0)
+
+
+def gcn_norm(csr: Csr, edge_weight: Optional[torch.Tensor] = None, improved: bool = False, add_self_loops: bool = True,
+             normalize: bool = True) -> GcnNorm:
+    """gpde_gcn_norm, cached next to the CSR cache: PyG's `gcn_norm` with `add_remaining_self_loops` on the destination CSR.
+
+    coef_e = dinv[src] w_e dinv[dst] per CSR slot, self_coef_i = dinv[i]^2 * (self weight), dinv = deg^-1/2.  The degree is the
+    TARGET-side sum - deg[i] = the weights of the in-edges of i plus the self weight - as in PyG 1.6 and later; older PyG summed
+    over the source row, which is the same number on the symmetric graphs the reference's scripts use.  Every node gets exactly one
+    self loop of weight 1 (`improved`: 2); a node that already has self-loop edges takes the weight of the one with the largest
+    original edge id, and every self-loop slot gets coef = 0.  `add_self_loops=False`: no self term, existing self loops stay
+    ordinary edges.  `normalize=False`: coef = w, self_coef = 0.  `edge_weight` [E] is in the ORIGINAL edge order.
+
+    Key: the Csr object (csr_for keys it on edge_index identity and version), edge_weight storage / layout / version, the flags -
+    the 16 convs of one GCN_Net forward share one normalisation.  Square graphs only."""
+    if not isinstance(csr, Csr):
+        raise TypeError(f"gcn_norm takes an ops.Csr (ops.csr_for(edge_index, n_nodes)), got {type(csr).__name__}")
+    if csr.n_src_nodes is not None:
+        raise ValueError(f"GCN is defined on one node set: the CSR joins {csr.n_src_nodes} sources to {csr.n_nodes} destinations")
+    flags = gcn_flags(bool(improved), bool(add_self_loops), bool(normalize))
+    wkey = None
+    if edge_weight is not None:
+        if edge_weight.requires_grad:
+            raise NotImplementedError("the gradient with respect to edge_weight is not built: pass edge_weight.detach()")
+        watch(edge_weight)
+        st = edge_weight.untyped_storage()
+        wkey = (st.data_ptr(), edge_weight.storage_offset(), tuple(edge_weight.shape), tuple(edge_weight.stride()), _ver(edge_weight))
+    key = (id(csr), wkey, flags)
+    hit = _gcn_norm_cache.pop(key, None)
+    if hit is not None:
+        _gcn_norm_cache[key] = hit
+        return hit[2]
+    lib = _lib.lib()
+    _require_cuda(csr.rowptr, "csr")
+    dev = csr.rowptr.device
+    n, e = csr.n_nodes, csr.n_edges
+    ew = _operand(edge_weight, "edge_weight", (e,), dev)
+    coef = torch.empty(e, dtype=torch.float32, device=dev)
+    self_coef = torch.empty(n, dtype=torch.float32, device=dev)
+    ws = _alloc_ws(int(lib.gpde_gcn_norm_workspace_bytes(n, e)), dev)
+    p = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+    with torch.cuda.device(dev):
+        rc = lib.gpde_gcn_norm(csr.rowptr.data_ptr(), p(csr.src), p(csr.perm), p(ew), n, e, flags, p(coef), p(self_coef), ws.data_ptr(),
+                               ws.numel(), _stream_ptr(dev))
+    _lib.check(rc, "gpde_gcn_norm")
+    _lib.n_native_calls += 1
+    norm = GcnNorm(csr, coef, self_coef, flags)
+    # bytes an entry keeps alive once the CSR cache has let go of the graph: rowptr / src / dst / perm, coef, self_coef, edge_weight -
+    # counted twice, for the reversed graph a backward adds (GcnNorm.reversed)
+    nbytes = 2 * (16 * e + 8 * n + 4) + (0 if edge_weight is None else 4 * e)
+    _gcn_norm_cache[key] = (csr, None if edge_weight is None else edge_weight.untyped_storage(), norm, nbytes)
+    while len(_gcn_norm_cache) > _GCN_NORM_CACHE_MAX_ENTRIES or \
+            (len(_gcn_norm_cache) > 1 and sum(v[3] for v in _gcn_norm_cache.values()) > _GCN_NORM_CACHE_MAX_BYTES):
+        _gcn_norm_cache.pop(next(iter(_gcn_norm_cache)))
+    return norm
+
+
+def gcn_plan(in_channels: int, out_channels: int) -> dict:
+    """gpde_gcn_plan: the tiling gpde_gcn_fwd runs at these widths (host arithmetic, no device): destination rows per workgroup,
+    LDS row stride, channel passes per lane of the aggregation, 32-column blocks of the product, column blocks per wave, K tail,
+    column tail, LDS bytes."""
+    out = (ctypes.c_int32 * 8)()
+    _lib.check(_lib.lib().gpde_gcn_plan(int(in_channels), int(out_channels), out), "gpde_gcn_plan")
+    return dict(zip(("rows", "kstride", "passes", "col_blocks", "col_blocks_per_wave", "k_tail", "col_tail", "lds_bytes"),
+                    (int(v) for v in out)))
+
+
+def gcn_route(in_channels: int, out_channels: int) -> str:
+    """Which of GCN_ROUTES gcn_forward_raw takes by default:
+      'aggregate_first'   (A x) W in ONE launch of the fused kernel (aggregation, then the multiply on the LDS tile);
+      'aggregate_mm'      the aggregation kernel (W = NULL) at width `in`, then torch.mm;
+      'transform_first'   A (x W): torch.mm, then the aggregation kernel at width `out`.
+    The rule is what scripts/bench_gcn.py measured on the 421^2 grid (profiles/gcn_bench.txt): the fused kernel
+    was slower than 'aggregate_mm' at every width class (0.31 against 0.22 ms at 128 -> 128, 1.13 against 0.51 ms at 256 -> 256),
+    so it is never the default - it stays reachable, and tested, through `route=`; of the other two the narrower gather wins
+    by about 30 % (in < out: 'aggregate_mm', in > out: 'transform_first'); at in = out they measured within 4 % of each other - a
+    tie, which goes to 'transform_first'."""
+    return "aggregate_mm" if int(in_channels) < int(out_channels) else "transform_first"
+
+
+def _gcn_call(x, csr: Csr, coef, self_coef, w, bias, cin: int, cout: int, relu: bool, want_agg: bool):
+    lib = _lib.lib()
+    n, e, dev = csr.n_nodes, csr.n_edges, x.device
+    out = torch.empty(n, cout, dtype=torch.float32, device=dev)
+    agg = torch.empty(n, cin, dtype=torch.float32, device=dev) if want_agg else None
+    p = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+    with torch.cuda.device(dev):
+        rc = lib.gpde_gcn_fwd(p(x), n, e, csr.rowptr.data_ptr(), p(csr.src), p(coef), p(self_coef), p(w), p(bias), cin, cout,
+                              GCN_RELU if relu else 0, p(out), p(agg), _stream_ptr(dev))
+    _lib.check(rc, "gpde_gcn_fwd")
+    _lib.n_native_calls += 1
+    return out, agg
+
+
+def gcn_forward_raw(x: torch.Tensor, norm: GcnNorm, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor] = None,
+                    relu: bool = False, route: Optional[str] = None, agg_out: bool = False, reverse: bool = False):
+    """out = act((A x) W + bias), A = the normalised adjacency of `norm` (`reverse`: its transpose - the backward's operator).
+    x [N, in]; weight [in, out] or None (the aggregation alone, out = in); bias [out] or None.  `route`: None = gcn_route(in, out),
+    or one of GCN_ROUTES to force it; `agg_out` (the two aggregate routes): also return A x [N, in], the rows before the multiply.
+    Returns out, or (out, agg) with `agg_out`."""
+    _require_cuda(x, "x")
+    if not isinstance(norm, GcnNorm):
+        raise TypeError(f"norm must be the result of ops.gcn_norm, got {type(norm).__name__}")
+    dev = x.device
+    csr, coef = norm.reversed if reverse else (norm.csr, norm.coef)
+    n = csr.n_nodes
+    x_c = _operand(x, "x", (n, None), dev)
+    cin = int(x_c.size(1))
+    if weight is not None and weight.dim() != 2:
+        raise ValueError(f"weight must be float32 [{cin},*] on {dev}, got {tuple(weight.shape)}")
+    cout = cin if weight is None else int(weight.size(1))
+    if not (width_supported(cin, cin) and (weight is None or width_supported(cin, cout))):
+        raise NotImplementedError(f"in_channels {cin} -> out_channels {cout}: the native GCN operator is built for widths 1 .. {ANY_MAX_WIDTH}")
+    w_c = _operand(weight, "weight", (cin, cout), dev)
+    b_c = _operand(bias, "bias", (cout,), dev)
+    if csr.rowptr.device != dev:
+        raise ValueError(f"the graph lives on {csr.rowptr.device}, x on {dev}")
+    if route is None:
+        route = "aggregate_first" if weight is None else gcn_route(cin, cout)
+    if route not in GCN_ROUTES:
+        raise ValueError(f"route must be one of {GCN_ROUTES} or None, got {route!r}")
+    if route == "transform_first" and weight is not None:
+        if agg_out:
+            raise ValueError("agg_out is the aggregate routes' by-product: transform_first never forms A x")
+        out, _ = _gcn_call(torch.mm(x_c, w_c), csr, coef, norm.self_coef, None, b_c, cout, cout, relu, False)
+        return out
+    if route == "aggregate_mm" and weight is not None:
+        agg, _ = _gcn_call(x_c, csr, coef, norm.self_coef, None, None, cin, cin, False, False)
+        out = torch.mm(agg, w_c) if b_c is None else torch.addmm(b_c, agg, w_c)
+        if relu:
+            out.clamp_min_(0)
+        return (out, agg) if agg_out else out
+    out, agg = _gcn_call(x_c, csr, coef, norm.self_coef, w_c, b_c, cin, cout, relu, agg_out)
+    return (out, agg) if agg_out else out

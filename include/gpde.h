@@ -727,6 +727,42 @@ GPDE_API int gpde_edge_keys_sqdist(const double* pos_src, const double* pos_dst,
 GPDE_API int gpde_edge_keys_hash(const int32_t* src_ids, const int32_t* dst_ids, int64_t n_edges, int64_t seed,
                         int64_t* keys, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * GCNConv (gpde_gcn.hip): the graph convolution of Kipf & Welling, the baseline network of the multipole paper
+ * (multipole-graph-neural-operator/neurips4_GCN.py:28-31 `GCNConv(width, width)`, applied 16 times per forward), on the
+ * destination CSR of gpde_csr_from_coo.  Square graphs (one node set).
+ *   gpde_gcn_norm   PyG's `gcn_norm` with `add_remaining_self_loops`.  edge_weight [E] in ORIGINAL edge order (read through perm;
+ *       NULL: every weight 1; perm NULL: slot order).  With GPDE_GCN_NORMALIZE | GPDE_GCN_ADD_SELF_LOOPS every node gets exactly
+ *       one self loop of weight `fill` (2 with GPDE_GCN_IMPROVED, else 1); a node that already has self-loop edges takes the
+ *       weight of the one with the largest original edge id instead, and every self-loop SLOT gets coef = 0.  deg[i] = sum of w
+ *       over the other in-edges of i + the self weight - the TARGET-side degree of PyG >= 1.6 (older releases summed over the
+ *       source row: the same number on a symmetric graph) - summed per row in ascending slot order in float64, no atomics.
+ *       dinv = deg^-1/2 (0 where deg == 0; 1 / sqrt in float64), coef[slot] = dinv[src] w dinv[dst], self_coef[i] = dinv[i]^2 *
+ *       self weight.  NORMALIZE without ADD_SELF_LOOPS: no self term (self_coef = 0), existing self loops are ordinary edges.
+ *       Without NORMALIZE: coef = w, self_coef = 0 (GPDE_GCN_IMPROVED / ADD_SELF_LOOPS are then without effect).
+ *       coef [E] by CSR slot and self_coef [N] are overwritten.  Workspace: gpde_gcn_norm_workspace_bytes.
+ *   gpde_gcn_fwd    out[i] = (sum_{e -> i} coef[e] x[src[e]] + self_coef[i] x[i]) . W + bias        x [N][in], W [in][out] row-major,
+ *       out [N][out].  W == NULL: the aggregation alone (out_channels must equal in_channels); bias [out], self_coef [N] and
+ *       agg_out nullable; agg_out [N][in] receives the aggregated rows BEFORE the multiply (the backward's A^T g, from which
+ *       grad_W = x^T . agg_out follows).  flags: GPDE_GCN_RELU clamps the result at 0.  out / agg_out must not overlap x or each
+ *       other.  Aggregation first, then the multiply on the exact fp32 MFMA while the tile is in LDS; rows summed two-level (chains
+ *       of 64 in-edges); no atomics - two calls give the same bits.
+ *   gpde_gcn_plan   HOST ONLY: the launcher's tiling at these widths - out[0..7] = destination rows per workgroup, LDS row stride
+ *       (floats), channel passes per lane of the aggregation (ceil(in / 64)), 32-column blocks of the product, column blocks per
+ *       wave, K tail (in odd), column tail (out % 32 != 0), LDS bytes.
+ * 1 <= in_channels, out_channels <= GPDE_WECONV_ANY_MAX_WIDTH; other widths, NULL arrays, unknown flags: GPDE_EINVAL with a
+ * gpde_last_error() text before any device work.  n_nodes == 0 is a valid call that reads no pointer; with n_edges == 0 src,
+ * perm, edge_weight and coef may be NULL.  Additions to the ABI: GPDE_VERSION is unchanged. */
+enum { GPDE_GCN_ADD_SELF_LOOPS = 1, GPDE_GCN_IMPROVED = 2, GPDE_GCN_NORMALIZE = 4 /* gpde_gcn_norm flags */ };
+enum { GPDE_GCN_RELU = 1 /* gpde_gcn_fwd flags */ };
+GPDE_API size_t gpde_gcn_norm_workspace_bytes(int64_t n_nodes, int64_t n_edges);
+GPDE_API int gpde_gcn_norm(const int32_t* rowptr, const int32_t* src, const int32_t* perm, const float* edge_weight, int64_t n_nodes,
+                  int64_t n_edges, uint32_t flags, float* coef, float* self_coef, void* ws, size_t ws_bytes, void* stream);
+GPDE_API int gpde_gcn_fwd(const float* x, int64_t n_nodes, int64_t n_edges, const int32_t* rowptr, const int32_t* src,
+                 const float* coef, const float* self_coef, const float* W, const float* bias, int in_channels, int out_channels,
+                 uint32_t flags, float* out, float* agg_out, void* stream);
+GPDE_API int gpde_gcn_plan(int in_channels, int out_channels, int32_t* out);
+
 /* HIP-event timing of the kernels launched by gpde_nnconv_fwd on the calling thread (used by
  * bench.py for the roofline figure; events are recorded on the same stream as the kernels).
  * gpde_profile_begin() arms it; gpde_profile_end_kinds() disarms it, SYNCHRONISES on the recorded

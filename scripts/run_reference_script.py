@@ -175,7 +175,7 @@ def run(script: str, overrides: dict, workdir: str | None = None, n_samples: int
         composite: bool = False) -> dict:
     """`seed`: torch / numpy / random are seeded before the script starts (the scripts seed nothing themselves), so two runs see
     the same initial weights, sample order and random sub-graphs.  `composite`: the modules' forward is replaced by the
-    stock-torch-ops composite of tests/helpers/composite_nnconv.py - the OTHER arm of the script-level parity test."""
+    stock-torch-ops composites of tests/helpers/composite_nnconv.py and composite_gcn.py - the OTHER arm of the script-level parity test."""
     script = find_script(script)
     install_torch_drift_compat()
     import torch
@@ -189,8 +189,9 @@ def run(script: str, overrides: dict, workdir: str | None = None, n_samples: int
         if REPO not in sys.path:
             sys.path.insert(0, REPO)
         import graph_pde_amd  # noqa: F401
-        from tests.helpers import composite_nnconv
+        from tests.helpers import composite_gcn, composite_nnconv
         run.composite_counter = composite_nnconv.install()
+        composite_gcn.install(run.composite_counter)            # GCNConv (neurips4_GCN.py): the same counter
     if n_samples is None:
         n_samples = max([int(v) for k, v in overrides.items() if k in ("ntrain", "ntest")] + [2])
     own_tmp = None
