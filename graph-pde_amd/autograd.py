@@ -41,6 +41,33 @@ def _saved_attr(ctx, t):
 ACCUMULATE_GRAD_HIDDEN = os.environ.get("GPDE_ACCUMULATE_DLDH", "1") != "0"
 
 
+CAN_TELL_BACKWARD_PASS = hasattr(torch._C, "_current_graph_task_id")
+
+
+def in_backward_pass() -> bool:
+    """Whether the caller runs inside an autograd backward pass - a forward does when torch.utils.checkpoint recomputes a segment.
+    The running sums and (x, grad_out) pairs that the applications of a module leave on their shared token then belong to the pass
+    in flight: forward-time housekeeping must not clear them.
+    On a torch without `torch._C._current_graph_task_id` the question cannot be answered (`CAN_TELL_BACKWARD_PASS` is False, this
+    returns False): the in-place sums on the H / W_e tokens are off there anyway (their `share` conditions need the same symbol,
+    nothing is ever in flight on them), and hidden_cache.lookup_deferred hands out no virtual-H node - the one place where a
+    forward inside a backward pass would lose work - so such calls take the direct operator."""
+    return CAN_TELL_BACKWARD_PASS and torch._C._current_graph_task_id() >= 0
+
+
+def saved_tensor_hooks_active() -> bool:
+    """Whether what a forward saves for its backward goes through saved-tensor hooks right now: a segment under
+    torch.utils.checkpoint(use_reentrant=False) - in its forward AND in its recomputation -, torch.autograd.graph.save_on_cpu.
+    A node built there saves placeholders that belong to that segment; unknown (an older torch) counts as no."""
+    top = getattr(torch._C._autograd, "_top_saved_tensors_default_hooks", None)
+    if top is None:
+        return False
+    try:
+        return top(False) is not None
+    except TypeError:
+        return top() is not None
+
+
 class NNConvFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, edge_index, edge_attr, root, bias, aggr, n_layers, *params):
@@ -268,7 +295,7 @@ class NNConvDeferredFunction(torch.autograd.Function):
         else:
             out = ops.nnconv_forward_raw(x.detach(), csr, edge_attr.detach(), pm, root, bias, aggr, z_keep=ctx.z)
         ctx.csr, ctx.aggr, ctx.n_layers, ctx.token = csr, aggr, n_layers, token
-        if token.valid:
+        if token.valid and not in_backward_pass():
             token.drop_stale()
         token.serial += 1
         ctx.serial = token.serial

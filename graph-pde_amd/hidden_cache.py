@@ -31,8 +31,9 @@ from typing import List, Optional
 
 import torch
 
+from . import autograd as _ag
 from . import ops
-from .autograd import DeferredHiddenFunction, DeferredToken, EdgeWeightsFunction, HiddenFunction, HiddenToken
+from .autograd import DeferredHiddenFunction, DeferredToken, EdgeWeightsFunction, HiddenFunction, HiddenToken, in_backward_pass
 
 MODE = os.environ.get("GPDE_HIDDEN_CACHE", "auto")
 _env_gb = os.environ.get("GPDE_HIDDEN_CACHE_GB", "")
@@ -80,7 +81,8 @@ stats = {"hits": 0, "builds": 0, "direct": 0, "we_hits": 0, "we_builds": 0}     
 
 class _Entry:
     __slots__ = ("key", "hidden", "token", "attr_ref", "csr", "last_key", "repeats", "hits_on_hidden", "hn", "we", "we_key",
-                 "we_refs", "big_key", "dkey", "dtoken", "dvirtual", "dcount", "drefs", "twe", "twe_key", "twe_token", "twe_h", "last_partial")
+                 "we_refs", "big_key", "dkey", "dtoken", "dvirtual", "dcount", "drefs", "twe", "twe_key", "twe_token", "twe_h", "last_partial",
+                 "key_refs", "dkey_refs", "we_key_refs", "twe_key_refs")
 
     def __init__(self):
         self.key = None
@@ -106,6 +108,12 @@ class _Entry:
         self.twe_token = None
         self.last_partial = None    # (n_edges, hn) of the last PARTIAL H built: the next build keeps that size while it still fits (see lookup)
         self.twe_h = None
+        # weak references to the parameter OBJECTS behind key / dkey / we_key / twe_key (_param_refs): the keys name parameters by
+        # address + version, and both repeat when a replaced parameter lands on the freed address of the old one
+        self.key_refs = None
+        self.dkey_refs = None
+        self.we_key_refs = None
+        self.twe_key_refs = None
 
 
 _entries: "weakref.WeakKeyDictionary[torch.nn.Module, _Entry]" = weakref.WeakKeyDictionary()
@@ -147,6 +155,19 @@ def snapshot() -> list:
     return pins
 
 
+def _param_refs(params) -> tuple:
+    """Weak references to the parameter objects a key was built from, kept next to the key (as ops.pack_mlp does).  A key names a
+    parameter by (data_ptr, version); a NEW tensor object - `conv.nn = new_mlp.to(dev)`, the device copy ops.stage_const makes
+    again after its cache evicted the last one - starts at version 0 and often at the address the old one just freed.  A live
+    object keeps its address, a dead one fails `_same_params`: equal keys then really mean the same parameters."""
+    return tuple(None if p is None else weakref.ref(p) for p in params)
+
+
+def _same_params(refs, params) -> bool:
+    return refs is not None and len(refs) == len(params) and \
+        all((p is None) if r is None else (r() is p) for r, p in zip(refs, params))
+
+
 def _key(edge_attr, csr, hidden_params: List[Optional[torch.Tensor]], precision: str):
     ops.watch(edge_attr.table if isinstance(edge_attr, ops.NodeAttr) else edge_attr, *hidden_params)
     if isinstance(edge_attr, ops.NodeAttr):      # attributes described by node data: keyed on the table's memory + version + slots
@@ -172,17 +193,26 @@ def lookup(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, weights, b
     if mode == "off":
         stats["direct"] += 1
         return None
+    if torch.is_grad_enabled() and _ag.saved_tensor_hooks_active():
+        # a checkpointed segment (forward or recomputation): a shared node built here would save that segment's placeholders and
+        # poison every later step that hangs on it, and a segment must take the same route both times whatever the cache holds
+        # by then - it takes the direct operator and leaves the entry alone
+        stats["direct"] += 1
+        stats["hooked_direct"] = stats.get("hooked_direct", 0) + 1
+        return None
     precision = ops.DEFAULT_PRECISION if precision is None else precision
     hw, hb = list(weights[:-1]), list(biases[:-1])
     key = _key(edge_attr, csr, hw + hb, precision)
     ent = _entries.get(module)
     if ent is None:
         ent = _entries[module] = _Entry()
-    if ent.hidden is not None and ent.key == key and ent.token.valid:
+    if ent.hidden is not None and ent.key == key and ent.token.valid and _same_params(ent.key_refs, hw + hb):
         ent.hits_on_hidden += 1
         # a backward pass that never reached the H node (input gradients only, an exception) left its running dL/dH sum on the
-        # token: [E, K2P], 24 GB at s=121.  No pass is in flight at forward time - drop it
-        ent.token.gh_acc, ent.token.gh_adds = None, 0
+        # token: [E, K2P], 24 GB at s=121.  Dropped at forward time - unless this forward runs INSIDE a backward pass
+        # (a checkpointed segment recomputing): the sum then belongs to the pass in flight
+        if not in_backward_pass():
+            ent.token.gh_acc, ent.token.gh_adds = None, 0
         if ent.hn == csr.n_nodes or allow_partial:
             stats["hits"] += 1
             if ent.hn < csr.n_nodes:
@@ -237,6 +267,7 @@ def lookup(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, weights, b
         stats["direct"] += 1
         return None
     ent.key, ent.hidden, ent.token, ent.attr_ref, ent.csr, ent.hn = key, hidden, token, edge_attr, csr, hn
+    ent.key_refs = _param_refs(hw + hb)
     ent.hits_on_hidden = 0
     if hn < csr.n_nodes:
         ent.big_key = key            # the whole H does not fit: a training call shares a virtual-H node (lookup_deferred)
@@ -272,8 +303,9 @@ def lookup_deferred(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, w
     repeating this (edge_attr, weights) key, its H was wanted but does not fit the budget, the hidden layers require a
     gradient and the kernel MLP is in the deferred form (ops.deferred_supported).  All applications of one forward share the
     returned node until its backward has run."""
-    if DEFER_MODE == "off" or aggr not in ("add", "mean") or not torch.is_grad_enabled():
-        return None
+    if DEFER_MODE == "off" or aggr not in ("add", "mean") or not torch.is_grad_enabled() or not _ag.CAN_TELL_BACKWARD_PASS or \
+            _ag.saved_tensor_hooks_active():
+        return None         # (a torch that cannot tell a forward inside a backward pass: autograd.in_backward_pass; a checkpointed segment: lookup)
     ent = _entries.get(module)
     if ent is None:
         return None
@@ -282,10 +314,16 @@ def lookup_deferred(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, w
     if not any(p is not None and p.requires_grad for p in hw + hb) or edge_attr.requires_grad:
         return None
     key = _key(edge_attr, csr, hw + hb, precision)
-    if ent.dtoken is not None and ent.dkey == key and ent.dtoken.valid:
+    # the virtual node also saved the LAST Linear (its deferred pass forms dL/dH through it): a node built before a write to that
+    # layer - by a forward whose backward never ran - must not serve the next step
+    w_last, b_last = weights[-1], biases[-1]
+    dkey = (key, (w_last.data_ptr(), ops._ver(w_last)), (0, 0) if b_last is None else (b_last.data_ptr(), ops._ver(b_last)))
+    named = hw + hb + [w_last, b_last]
+    if ent.dtoken is not None and ent.dkey == dkey and ent.dtoken.valid and _same_params(ent.dkey_refs, named):
         ent.dcount += 1
         ent.dtoken.hpart = hpart
-        if ent.dtoken.drop_stale():      # a backward over this (still valid) node ended without its deferred pass
+        # (not from a forward that runs inside a backward pass - a checkpointed segment: the pairs are that pass's own)
+        if not in_backward_pass() and ent.dtoken.drop_stale():      # a backward over this (still valid) node ended without its deferred pass
             stats["deferred_stale_dropped"] = stats.get("deferred_stale_dropped", 0) + 1
         stats["deferred_hits"] = stats.get("deferred_hits", 0) + 1
         return ent.dvirtual, ent.dtoken
@@ -299,10 +337,10 @@ def lookup_deferred(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, w
     token = DeferredToken()
     token.hpart = hpart
     n = len(weights)
-    w_last, b_last = weights[-1], biases[-1]
     virtual = DeferredHiddenFunction.apply(edge_attr, csr, aggr, token, n, *hw, w_last.detach(),
                                            *hb, None if b_last is None else b_last.detach())
-    ent.dkey, ent.dtoken, ent.dvirtual, ent.drefs, ent.dcount = key, token, virtual, (edge_attr, csr), 1
+    ent.dkey, ent.dtoken, ent.dvirtual, ent.drefs, ent.dcount = dkey, token, virtual, (edge_attr, csr), 1
+    ent.dkey_refs = _param_refs(named)
     stats["deferred_builds"] = stats.get("deferred_builds", 0) + 1
     return virtual, token
 
@@ -341,10 +379,13 @@ def lookup_edge_weights_train(module: torch.nn.Module, hidden: torch.Tensor, csr
         return None
     w_last, b_last = weights[-1], biases[-1]
     key = ((w_last.data_ptr(), ops._ver(w_last)), (0, 0) if b_last is None else (b_last.data_ptr(), ops._ver(b_last)))
-    if ent.twe is not None and ent.twe_h is hidden and ent.twe_key == key and ent.twe_token.valid:
+    if ent.twe is not None and ent.twe_h is hidden and ent.twe_key == key and ent.twe_token.valid and \
+            _same_params(ent.twe_key_refs, [w_last, b_last]):
         stats["we_hits"] += 1
-        # (a backward pass that never reached the W_e node left its running sums on the token: no pass is in flight at forward time)
-        ent.twe_token.gh_acc, ent.twe_token.gh_adds, ent.twe_token.side_acc = None, 0, None
+        # (a backward pass that never reached the W_e node left its running sums on the token; a forward inside a backward pass -
+        # a checkpointed segment - leaves them alone, as `lookup` does)
+        if not in_backward_pass():
+            ent.twe_token.gh_acc, ent.twe_token.gh_adds, ent.twe_token.side_acc = None, 0, None
         return ent.twe
     ent.twe, ent.twe_key, ent.twe_token, ent.twe_h = None, None, None, None
     # memory of the training form: W_e, one dL/dW_e per application in flight and autograd's running sum of them - 16 KiB per
@@ -361,6 +402,7 @@ def lookup_edge_weights_train(module: torch.nn.Module, hidden: torch.Tensor, csr
         stats["oom_fallbacks"] = stats.get("oom_fallbacks", 0) + 1
         return None
     ent.twe, ent.twe_key, ent.twe_token, ent.twe_h = we, key, token, hidden
+    ent.twe_key_refs = _param_refs([w_last, b_last])
     stats["we_builds"] += 1
     return we
 
@@ -378,7 +420,8 @@ def lookup_edge_weights(module: torch.nn.Module, edge_attr: torch.Tensor, csr, p
     w_last, b_last = weights[-1], biases[-1]
     key = (_key(edge_attr, csr, list(weights[:-1]) + list(biases[:-1]), precision)[:-1],
            (w_last.data_ptr(), ops._ver(w_last)), (0, 0) if b_last is None else (b_last.data_ptr(), ops._ver(b_last)))
-    if ent is not None and ent.we is not None and ent.we_key == key:
+    params = list(weights) + list(biases)
+    if ent is not None and ent.we is not None and ent.we_key == key and _same_params(ent.we_key_refs, params):
         stats["we_hits"] += 1
         return ent.we
     now = force or explicit
@@ -386,7 +429,8 @@ def lookup_edge_weights(module: torch.nn.Module, edge_attr: torch.Tensor, csr, p
         # peek only: the H policy (who repeats, who gets built) is driven by ONE lookup() per call, made by the caller's
         # ordinary path.  W_e is derived from an H that is already there - i.e. from the call after H was built.
         hkey = _key(edge_attr, csr, list(weights[:-1]) + list(biases[:-1]), precision)
-        if ent is None or ent.hidden is None or ent.key != hkey or not ent.token.valid or ent.hn != csr.n_nodes:
+        if ent is None or ent.hidden is None or ent.key != hkey or not ent.token.valid or ent.hn != csr.n_nodes or \
+                not _same_params(ent.key_refs, list(weights[:-1]) + list(biases[:-1])):
             return None
     hit = lookup(module, edge_attr, csr, pm, weights, biases, precision, mode="on" if now else None, allow_partial=False)
     ent = _entries.get(module)
@@ -402,6 +446,6 @@ def lookup_edge_weights(module: torch.nn.Module, edge_attr: torch.Tensor, csr, p
         torch.cuda.empty_cache()
         stats["oom_fallbacks"] = stats.get("oom_fallbacks", 0) + 1
         return None
-    ent.we_key, ent.we_refs = key, (edge_attr, csr)
+    ent.we_key, ent.we_refs, ent.we_key_refs = key, (edge_attr, csr), _param_refs(params)
     stats["we_builds"] += 1
     return ent.we

@@ -636,9 +636,12 @@ class NNConv_old(MessagePassing):
                         if tok is not None and _ag.ACCUMULATE_GRAD_HIDDEN:
                             # root / bias behind private identity nodes, one per step and module: the applications sum their
                             # gradients in place there (autograd.SharedParamFunction)
-                            if tok.side_in is None or tok.side_in[2] is not root or tok.side_in[3] is not bias:
+                            # (... of THESE parameter objects at THEIR current versions: the W_e node outlives a forward whose
+                            # backward never ran, and a root / bias written in place since then invalidates the old views)
+                            vers = (None if root is None else ops._ver(root), None if bias is None else ops._ver(bias))
+                            if tok.side_in is None or tok.side_in[2] is not root or tok.side_in[3] is not bias or tok.side_in[4] != vers:
                                 tok.side_in = (None if root is None else SharedParamFunction.apply(root, tok, 0),
-                                               None if bias is None else SharedParamFunction.apply(bias, tok, 1), root, bias)
+                                               None if bias is None else SharedParamFunction.apply(bias, tok, 1), root, bias, vers)
                             return WeConvFunction.apply(x, we, csr, tok.side_in[0], tok.side_in[1], self.aggr, tok)
                         return WeConvFunction.apply(x, we, csr, root, bias, self.aggr, None)
                 return NNConvHiddenFunction.apply(x, hidden, csr, pm, weights[-1], biases[-1],

@@ -223,6 +223,13 @@ ATTR_SLOT_ORDER = os.environ.get("GPDE_ATTR_SLOT_ORDER", "1") != "0"
 _ATTR_SLOT_ORDER_MIN_EDGES = 32768
 
 
+def identity_probe(e: int, device=None, k: int = 4096) -> torch.Tensor:
+    """min(e, k) slot indices spread evenly over [0, e - 1], int64, first 0 and last e - 1, built in integers.  (A float32
+    linspace rounds its end point above 2^24: for e = 95,530,006 the last index came out as 95,530,008, past the end.)"""
+    k = min(int(e), int(k))
+    return (torch.arange(k, dtype=torch.int64, device=device) * (int(e) - 1)) // max(k - 1, 1)
+
+
 def attr_in_slot_order(csr: "Csr", edge_attr: torch.Tensor):
     """(edge_attr rows gathered into CSR slot order, identity perm) - cached on the CSR per edge_attr memory + version.
 
@@ -242,8 +249,8 @@ def attr_in_slot_order(csr: "Csr", edge_attr: torch.Tensor):
         # of the same length on the headline graph - 21 of the 23 ms a NEW sample's first call spent here (profiles/
         # r06_attr_reorder_probe.txt; the gather itself is 2.2 ms).  A graph in the reference's source-major order fails the
         # comparison at almost every slot: 4096 sampled slots decide it; only a sample that passes is followed by the full check.
-        probe = torch.linspace(0, e - 1, min(e, 4096), device=csr.perm.device).to(torch.int32)
-        csr._perm_is_identity = bool(torch.equal(csr.perm[probe.long()], probe)) and bool(torch.equal(csr.perm, csr._identity))
+        probe = identity_probe(e, csr.perm.device)
+        csr._perm_is_identity = bool(torch.equal(csr.perm[probe], probe.to(torch.int32))) and bool(torch.equal(csr.perm, csr._identity))
     if csr._perm_is_identity:
         return edge_attr, csr.perm
     st = edge_attr.untyped_storage()
