@@ -416,66 +416,30 @@ class WeConvFunction(torch.autograd.Function):
         return gx, gwe, None, groot, gbias if ctx.has_bias else None, None, None
 
 
+def _root_term(x_dst, root):
+    """PyG: `if x_r is not None and root_weight: out += lin(x_r)` - a call without destination features has no root term."""
+    return None if x_dst is None else root
+
+
 class WeConvAnyFunction(torch.autograd.Function):
-    """The operator given the per-edge weights at ANY width 1 .. 256 (gpde_nnconv_fwd_edgeweights_any: gather, message, add /
-    mean, update in one streaming kernel), differentiable in x, W_e [E, in * out], root and bias
-    (gpde_nnconv_bwd_edgeweights_any).  The sibling of WeConvFunction for modules whose widths are not (64, 64): W_e is the
-    caller's own tensor (`nn(pseudo)`), nothing is shared between applications."""
-
-    @staticmethod
-    def forward(ctx, x, we, csr, root, bias, aggr):
-        out = ops.nnconv_forward_edgeweights_any_raw(x.detach(), csr, we.detach(), root, bias, aggr)
-        ctx.csr, ctx.aggr, ctx.has_bias = csr, aggr, bias is not None
-        ctx.save_for_backward(x, we, root)
-        return out
-
-    @staticmethod
-    @once_differentiable        # the native backward is not itself differentiable: create_graph=True raises
-    def backward(ctx, grad_out):
-        x, we, root = ctx.saved_tensors
-        gx, gwe, groot, gbias = ops.nnconv_backward_edgeweights_any_raw(x, ctx.csr, we, root, ctx.aggr, grad_out,
-                                                                        need_root=root is not None, need_bias=ctx.has_bias)
-        return gx, gwe, None, groot, gbias if ctx.has_bias else None, None
-
-
-class HiddenAnyFunction(torch.autograd.Function):
-    """The RE-ASSOCIATED operator at any width 1 .. 256 (gpde_nnconv_fwd_hidden_any: aggregation of x_j (x) h_e per node, the last
-    Linear per node, update()), differentiable in x, the last hidden activations H [E, K], the last Linear (w_last [in * out, K],
-    b_last [in * out]), root and bias (gpde_nnconv_bwd_hidden_any).  H is the caller's own tensor - relu(L_{n-1}(...)) evaluated by
-    torch, rows in CSR slot order -, so dL/dH flows on through the caller's earlier layers by ordinary autograd; [E, in * out] is
-    never formed."""
-
-    @staticmethod
-    def forward(ctx, x, hidden, w_last, b_last, csr, root, bias, aggr):
-        out = ops.nnconv_forward_hidden_any_raw(x.detach(), csr, hidden.detach(), w_last, b_last, root, bias, aggr)
-        ctx.csr, ctx.aggr, ctx.has_bias = csr, aggr, bias is not None
-        ctx.has_b_last, ctx.has_root = b_last is not None, root is not None
-        ctx.save_for_backward(x, hidden, w_last, b_last, root)
-        return out
-
-    @staticmethod
-    @once_differentiable        # the native backward is not itself differentiable: create_graph=True raises
-    def backward(ctx, grad_out):
-        x, hidden, w_last, b_last, root = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        gx, gh, gwl, gbl, groot, gbias = ops.nnconv_backward_hidden_any_raw(
-            x, ctx.csr, hidden, w_last, b_last, root, ctx.aggr, grad_out, need_x=need[0], need_w_last=need[2],
-            need_b_last=ctx.has_b_last and need[3], need_root=ctx.has_root and need[5], need_bias=ctx.has_bias and need[6])
-        return gx, (gh if need[1] else None), gwl, gbl, None, groot, gbias, None
-
-
-class WeConvBipFunction(torch.autograd.Function):
-    """WeConvAnyFunction BETWEEN TWO NODE SETS (gpde_nnconv_fwd_edgeweights_bip / gpde_nnconv_bwd_edgeweights_bip): x_src
-    [n_src, in_src] is gathered along the edges of the rectangular `csr`, x_dst [n_dst, in_dst] (or None: no root term) enters
-    `x_dst . root`, out is [n_dst, out].  Differentiable in x_src, x_dst, W_e [E, in_src * out], root [in_dst, out] and bias."""
+    """The operator given the per-edge weights at ANY width 1 .. 256 (gpde_nnconv_fwd_edgeweights_any / _bip: gather, message, add /
+    mean, update in one streaming kernel), differentiable in x_src, x_dst, W_e [E, in_src * out], root [in_dst, out] and bias
+    (gpde_nnconv_bwd_edgeweights_any / _bip).  x_src [n_src, in_src] is gathered along the edges of `csr`, x_dst [n_dst, in_dst]
+    enters `x_dst . root`, out is [n_dst, out].  `x_dst` None: no root term.  `x_dst` ops._ONE_SET: ONE node set - x_src is the table
+    of the root term too, through the `_any` entry points (whose grad_x holds both terms in one ordered sum; the same tensor in both
+    slots would have autograd add two partial gradients, with other bits).  The sibling of WeConvFunction for modules whose widths
+    are not (64, 64): W_e is the caller's own tensor (`nn(pseudo)`), nothing is shared between applications."""
 
     @staticmethod
     def forward(ctx, x_src, x_dst, we, csr, root, bias, aggr):
-        if x_dst is None:
-            root = None                 # PyG: `if x_r is not None and root_weight: out += lin(x_r)`
-        out = ops.nnconv_forward_edgeweights_bip_raw(x_src.detach(), None if x_dst is None else x_dst.detach(), csr, we.detach(), root, bias, aggr)
-        ctx.csr, ctx.aggr, ctx.has_bias, ctx.has_dst, ctx.has_root = csr, aggr, bias is not None, x_dst is not None, root is not None
-        ctx.save_for_backward(x_src, x_dst, we, root)
+        root = _root_term(x_dst, root)
+        ctx.one, ctx.has_dst = x_dst is ops._ONE_SET, torch.is_tensor(x_dst)
+        if ctx.one:
+            out = ops.nnconv_forward_edgeweights_any_raw(x_src.detach(), csr, we.detach(), root, bias, aggr)
+        else:
+            out = ops.nnconv_forward_edgeweights_bip_raw(x_src.detach(), x_dst.detach() if ctx.has_dst else None, csr, we.detach(), root, bias, aggr)
+        ctx.csr, ctx.aggr, ctx.has_bias, ctx.has_root = csr, aggr, bias is not None, root is not None
+        ctx.save_for_backward(x_src, x_dst if ctx.has_dst else None, we, root)
         return out
 
     @staticmethod
@@ -483,26 +447,35 @@ class WeConvBipFunction(torch.autograd.Function):
     def backward(ctx, grad_out):
         x_src, x_dst, we, root = ctx.saved_tensors
         need = ctx.needs_input_grad
-        gxs, gxd, gwe, groot, gbias = ops.nnconv_backward_edgeweights_bip_raw(
-            x_src, x_dst, ctx.csr, we, root, ctx.aggr, grad_out, need_x_src=need[0], need_x_dst=ctx.has_dst and need[1],
-            need_root=ctx.has_root and need[4], need_bias=ctx.has_bias and need[5])
+        kw = dict(need_root=ctx.has_root and need[4], need_bias=ctx.has_bias and need[5])
+        if ctx.one:         # (this entry point always writes grad_x; no x_dst input, no gradient in its slot)
+            gxd = None
+            gxs, gwe, groot, gbias = ops.nnconv_backward_edgeweights_any_raw(x_src, ctx.csr, we, root, ctx.aggr, grad_out, **kw)
+        else:
+            gxs, gxd, gwe, groot, gbias = ops.nnconv_backward_edgeweights_bip_raw(
+                x_src, x_dst, ctx.csr, we, root, ctx.aggr, grad_out, need_x_src=need[0], need_x_dst=ctx.has_dst and need[1], **kw)
         return gxs, gxd, (gwe if need[2] else None), None, groot, gbias, None
 
 
-class HiddenBipFunction(torch.autograd.Function):
-    """HiddenAnyFunction BETWEEN TWO NODE SETS (gpde_nnconv_fwd_hidden_bip / gpde_nnconv_bwd_hidden_bip): Z' is aggregated per
-    destination from x_src, the last Linear runs per destination, x_dst [n_dst, in_dst] (or None) enters the root term.
-    Differentiable in x_src, x_dst, H [E, K], the last Linear (w_last [in_src * out, K], b_last), root [in_dst, out] and bias."""
+class HiddenAnyFunction(torch.autograd.Function):
+    """The RE-ASSOCIATED operator at any width 1 .. 256 (gpde_nnconv_fwd_hidden_any / _bip: aggregation of x_j (x) h_e per
+    destination, the last Linear per destination, update()), differentiable in x_src, x_dst, the last hidden activations H [E, K],
+    the last Linear (w_last [in_src * out, K], b_last [in_src * out]), root [in_dst, out] and bias (gpde_nnconv_bwd_hidden_any /
+    _bip).  `x_dst`: as WeConvAnyFunction takes it.  H is the caller's own tensor - relu(L_{n-1}(...)) evaluated by torch, rows in
+    CSR slot order -, so dL/dH flows on through the caller's earlier layers by ordinary autograd; [E, in * out] is never formed."""
 
     @staticmethod
     def forward(ctx, x_src, x_dst, hidden, w_last, b_last, csr, root, bias, aggr):
-        if x_dst is None:
-            root = None
-        out = ops.nnconv_forward_hidden_bip_raw(x_src.detach(), None if x_dst is None else x_dst.detach(), csr, hidden.detach(), w_last, b_last,
-                                                root, bias, aggr)
-        ctx.csr, ctx.aggr, ctx.has_bias, ctx.has_dst = csr, aggr, bias is not None, x_dst is not None
+        root = _root_term(x_dst, root)
+        ctx.one, ctx.has_dst = x_dst is ops._ONE_SET, torch.is_tensor(x_dst)
+        if ctx.one:
+            out = ops.nnconv_forward_hidden_any_raw(x_src.detach(), csr, hidden.detach(), w_last, b_last, root, bias, aggr)
+        else:
+            out = ops.nnconv_forward_hidden_bip_raw(x_src.detach(), x_dst.detach() if ctx.has_dst else None, csr, hidden.detach(), w_last, b_last,
+                                                    root, bias, aggr)
+        ctx.csr, ctx.aggr, ctx.has_bias = csr, aggr, bias is not None
         ctx.has_b_last, ctx.has_root = b_last is not None, root is not None
-        ctx.save_for_backward(x_src, x_dst, hidden, w_last, b_last, root)
+        ctx.save_for_backward(x_src, x_dst if ctx.has_dst else None, hidden, w_last, b_last, root)
         return out
 
     @staticmethod
@@ -510,10 +483,16 @@ class HiddenBipFunction(torch.autograd.Function):
     def backward(ctx, grad_out):
         x_src, x_dst, hidden, w_last, b_last, root = ctx.saved_tensors
         need = ctx.needs_input_grad
-        gxs, gxd, gh, gwl, gbl, groot, gbias = ops.nnconv_backward_hidden_bip_raw(
-            x_src, x_dst, ctx.csr, hidden, w_last, b_last, root, ctx.aggr, grad_out, need_x_src=need[0], need_x_dst=ctx.has_dst and need[1],
-            need_w_last=need[3], need_b_last=ctx.has_b_last and need[4], need_root=ctx.has_root and need[6],
-            need_bias=ctx.has_bias and need[7])
+        kw = dict(need_w_last=need[3], need_b_last=ctx.has_b_last and need[4], need_root=ctx.has_root and need[6],
+                  need_bias=ctx.has_bias and need[7])
+        if ctx.one:         # (no x_dst input, no gradient in its slot)
+            gxd = None
+            gxs, gh, gwl, gbl, groot, gbias = ops.nnconv_backward_hidden_any_raw(x_src, ctx.csr, hidden, w_last, b_last, root, ctx.aggr, grad_out,
+                                                                                 need_x=need[0], **kw)
+        else:
+            gxs, gxd, gh, gwl, gbl, groot, gbias = ops.nnconv_backward_hidden_bip_raw(
+                x_src, x_dst, ctx.csr, hidden, w_last, b_last, root, ctx.aggr, grad_out, need_x_src=need[0],
+                need_x_dst=ctx.has_dst and need[1], **kw)
         return gxs, gxd, (gh if need[2] else None), gwl, gbl, None, groot, gbias, None
 
 

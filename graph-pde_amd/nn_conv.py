@@ -23,8 +23,8 @@ from torch.nn import Parameter
 
 from . import hidden_cache, ops
 from . import autograd as _ag
-from .autograd import (HiddenAnyFunction, HiddenBipFunction, NNConvDeferredFunction, NNConvFunction, NNConvHiddenFunction, SharedParamFunction,
-                       WeConvAnyFunction, WeConvBipFunction, WeConvFunction)
+from .autograd import (HiddenAnyFunction, NNConvDeferredFunction, NNConvFunction, NNConvHiddenFunction, SharedParamFunction, WeConvAnyFunction,
+                       WeConvFunction)
 from .message_passing import MessagePassing
 
 
@@ -51,6 +51,19 @@ def _uniform(size, tensor):
         bound = 1.0 / math.sqrt(size)
         with torch.no_grad():
             tensor.uniform_(-bound, bound)
+
+
+def _on_dev(t, dev, needs_grad):
+    """`t` (or None) on `dev`: itself when it is there, a differentiable `.to(dev)` when a gradient is needed, else the device copy
+    that ops.stage_const caches on the tensor's storage + version."""
+    if t is None or t.device == dev:
+        return t
+    return t.to(dev) if needs_grad and t.requires_grad else ops.stage_const(t, dev)
+
+
+def _slot_rows(csr, rows):
+    """`rows` [E, .], one per edge of the caller's list, in CSR slot order: the order the kernels address a per-edge operand in."""
+    return rows if bool(getattr(csr, "_perm_is_identity", False)) else rows.index_select(0, csr.perm.long().to(rows.device))
 
 
 class _GatherRows(torch.autograd.Function):
@@ -206,7 +219,7 @@ class NNConv_old(MessagePassing):
             edge_index = csr.edge_index
             if csr._flow_flipped:
                 edge_index = edge_index.flip(0)
-                pseudo = pseudo.index_select(0, csr.perm.long().to(pseudo.device))
+                pseudo = _slot_rows(csr, pseudo)
         return self._max_chain(edge_index.to(x.device), x, pseudo)
 
     def _max_chain(self, edge_index, x, pseudo):
@@ -345,10 +358,7 @@ class NNConv_old(MessagePassing):
             raise RuntimeError(f"kernel network {type(self.nn).__name__} is not a Linear / ReLU chain: its per-edge weights are materialised as in the "
                                f"reference (nn_conv.py:274) - {csr.n_edges} edges x 16 KiB = {need / 2**30:.1f} GiB (twice that with gradients), "
                                f"{free / 2**30:.1f} GiB free")
-        perm = csr.perm.long()
-        # rows in CSR slot order (the order the kernels address W_e in); `nn` acts row by row, batch statistics are order-free
-        pseudo_s = pseudo if bool(getattr(csr, "_perm_is_identity", False)) else pseudo.index_select(0, perm)
-        weight = self.nn(pseudo_s)
+        weight = self.nn(_slot_rows(csr, pseudo))       # (`nn` acts row by row, batch statistics are order-free)
         if weight.dim() != 2 or weight.size(0) != csr.n_edges or weight.size(1) != ops.WIDTH * ops.WIDTH:
             raise ValueError(f"nn(pseudo) must be [E, {ops.WIDTH * ops.WIDTH}] (in_channels * out_channels, nn_conv.py:274), got {tuple(weight.shape)}")
         weight = weight.float().contiguous()
@@ -406,15 +416,12 @@ class NNConv_old(MessagePassing):
 
     def _propagate_any_width(self, x, edge_index, pseudo, residual=None, relu=False):
         """propagate() of a module whose widths are not (64, 64), for EVERY kernel network (the Linear / ReLU chain included):
-        the route of `_propagate_general_nn` at run-time widths.  `weight = self.nn(pseudo)` by the caller's module where it
-        lives, rows in CSR slot order, [E, in * out] - the tensor the reference materialises (nn_conv.py:274) - then gather,
-        message, aggregate and update() (nn_conv.py:275-282) as ONE native kernel (gpde_nnconv_fwd_edgeweights_any; backward
-        gpde_nnconv_bwd_edgeweights_any, whose dL/dW_e autograd carries back into `nn`).  CPU tensors are staged to the HIP
-        device around the operator (`.to()` is differentiable) and the result returns to the caller's device.  `residual` /
-        `relu`: fused into the kernel's epilogue; callers pass them only when no gradient is needed.  aggr='max': the native
-        kernel when no gradient is needed, else PyG's chain over the native `message()` / `update()`, as at 64.
-        A Linear / ReLU chain under add / mean whose per-edge weights do not fit (GPDE_ANY_REASSOC=auto), or every such call (=on),
-        takes `_propagate_any_reassociated` instead (ops.any_width_route states the rule)."""
+        the route of `_propagate_general_nn` at run-time widths, on ONE node set.  This front validates, builds the square CSR and
+        decides the route (ops.any_width_route states the rule: the per-edge weights materialised as in the reference, or - a
+        Linear / ReLU chain under add / mean that does not fit, GPDE_ANY_REASSOC=auto, or every such call, =on - the last Linear
+        re-associated); `_any_width_operator` runs it.  `residual` / `relu`: fused into the kernel's epilogue; callers pass them
+        only when no gradient is needed.  aggr='max': the native kernel when no gradient is needed, else PyG's chain over the
+        native `message()` / `update()`, as at 64."""
         self._check_width()
         cin, cout = int(self.in_channels), int(self.out_channels)
         if x.dim() != 2 or x.size(1) != cin:
@@ -431,84 +438,90 @@ class NNConv_old(MessagePassing):
             csr = edge_index
         else:
             csr = ops.csr_for(edge_index if edge_index.device == dev else ops.stage_const(edge_index, dev), x.size(0))
-        need = csr.n_edges * cin * cout * 4
-        free, _ = ops.device_free_bytes(dev)
         # the route (ops.any_width_route; GPDE_ANY_REASSOC = auto | on | off): a call whose per-edge weights fit runs on them exactly
         # as before; a Linear / ReLU chain under add / mean that does not fit (auto), or every such call (on), re-associates the
         # last Linear and never forms [E, in * out]
-        lin = ops.mlp_linears(self.nn) if self._nn_is_linear_relu_chain() else None
-        chain = lin is not None and lin[-1].out_features == cin * cout
-        route = ops.any_width_route(csr.n_nodes, csr.n_edges, cin, cout, lin[-1].in_features if chain else None, self.aggr, chain, free)
-        if route["route"] == "reassociated":
-            return self._propagate_any_reassociated(x, csr, pseudo, lin, dev, needs_grad, residual, relu)
+        route, lin, free = self._any_width_route(csr, dev)
         if route["route"] == "refused":
             other = ""
             if route["eligible"] and ops.ANY_REASSOC != "off":
                 other = (f"; re-associated (GPDE_ANY_REASSOC={ops.ANY_REASSOC}): hidden activations and one node block of Z' = "
                          f"{route['bytes_reassociated'] / 2**30:.2f} GiB (twice that with gradients)")
             raise RuntimeError(f"{self!r}: at widths other than {ops.WIDTH} -> {ops.WIDTH} the per-edge weights are materialised as in the reference "
-                               f"(nn_conv.py:274) - {csr.n_edges} edges x {cin} x {cout} x 4 B = {need / 2**30:.2f} GiB (twice that with "
-                               f"gradients), {free / 2**30:.2f} GiB free{other}")
-        # rows in CSR slot order (the order the kernels address W_e in); `nn` acts row by row, batch statistics are order-free
-        pseudo_s = pseudo if bool(getattr(csr, "_perm_is_identity", False)) else pseudo.index_select(0, csr.perm.long().to(pseudo.device))
-        weight = self.nn(pseudo_s)
-        if weight.dim() != 2 or weight.size(0) != csr.n_edges or weight.size(1) != cin * cout:
-            raise ValueError(f"nn(pseudo) must be [E, {cin * cout}] = [{csr.n_edges}, in_channels * out_channels] (nn_conv.py:274), got {tuple(weight.shape)}")
-        weight = weight.float().to(dev).contiguous()
+                               f"(nn_conv.py:274) - {csr.n_edges} edges x {cin} x {cout} x 4 B = {route['bytes_materialised'] / 2**30:.2f} GiB "
+                               f"(twice that with gradients), {free / 2**30:.2f} GiB free{other}")
+        return self._any_width_operator(x, ops._ONE_SET, csr, pseudo, route["route"] == "reassociated", lin, dev, needs_grad, residual, relu)
 
-        def on_dev(t):
-            if t is None or t.device == dev:
-                return t
-            return t.to(dev) if needs_grad and t.requires_grad else ops.stage_const(t, dev)
-        root, bias = on_dev(self.root), on_dev(self.bias)
-        if needs_grad:
-            out = WeConvAnyFunction.apply(x.to(dev), weight, csr, root, bias, self.aggr)
+    def _any_width_route(self, csr, dev):
+        """(ops.any_width_route of a call on `csr`, the Linear layers of `nn` when it is a Linear / ReLU chain - else None -, the free
+        bytes of `dev`)."""
+        cin, cout = int(self._in_src()), int(self.out_channels)
+        free, _ = ops.device_free_bytes(dev)
+        lin = ops.mlp_linears(self.nn) if self._nn_is_linear_relu_chain() else None
+        chain = lin is not None and lin[-1].out_features == cin * cout
+        return ops.any_width_route(csr.n_nodes, csr.n_edges, cin, cout, lin[-1].in_features if chain else None, self.aggr, chain, free), lin, free
+
+    def _any_width_operator(self, x_src, x_dst, csr, pseudo, reassociated, lin, dev, needs_grad, residual, relu):
+        """The operator of `_propagate_any_width` (`x_dst` ops._ONE_SET) and of `_propagate_rect` (`x_dst` a tensor or None) once the
+        route is decided - a call on one node set is the two-set call that hands one table twice.  Rows of `pseudo` in CSR slot
+        order, where the module lives; parameters and CPU tensors staged to `dev` (`.to()` is differentiable), the result back on
+        the caller's device.
+        Materialised: `weight = self.nn(pseudo)` [E, in_src * out] by the caller's module - the tensor the reference materialises
+        (nn_conv.py:274) -, then gather, message, aggregate and update() (nn_conv.py:275-282) as ONE native kernel
+        (gpde_nnconv_fwd_edgeweights_any / _bip; the backward's dL/dW_e autograd carries back into `nn`).
+        Re-associated (`lin`: a Linear / ReLU chain, add / mean): H = relu(L_{n-1}(... pseudo)) [E, K] by torch, then aggregation, the
+        LAST Linear per destination and update() as ONE native call (gpde_nnconv_fwd_hidden_any / _bip; dL/dH flows on through the
+        earlier layers by autograd).
+        `residual` [n_dst, out] / `relu`: the kernel's epilogue on the materialised call without a gradient, torch ops otherwise."""
+        one = x_dst is ops._ONE_SET
+        cin, cout = int(self._in_src()), int(self.out_channels)
+        pseudo_s = _slot_rows(csr, pseudo)              # (`nn` acts row by row, batch statistics are order-free)
+        on_dev = lambda t: _on_dev(t, dev, needs_grad)
+        root, bias = (None if x_dst is None else on_dev(self.root)), on_dev(self.bias)      # PyG: no x_dst, no root term
+        xs_d = x_src.to(dev) if needs_grad else x_src.detach().to(dev)
+        xd_d = x_dst if not torch.is_tensor(x_dst) else x_dst.to(dev) if needs_grad else x_dst.detach().to(dev)
+        fused = False
+        if reassociated:
+            h = pseudo_s
+            for l in lin[:-1]:
+                h = torch.relu(torch.nn.functional.linear(h, l.weight, l.bias))
+            hidden = h.float().to(dev).contiguous()
+            # (.float(): a float64 kernel network runs with float32 x on the other route too, through `weight.float()`)
+            w_last, b_last = on_dev(lin[-1].weight).float(), None if lin[-1].bias is None else on_dev(lin[-1].bias).float()
+            if needs_grad:
+                out = HiddenAnyFunction.apply(xs_d, xd_d, hidden, w_last, b_last, csr, root, bias, self.aggr)
+            elif one:
+                out = ops.nnconv_forward_hidden_any_raw(xs_d, csr, hidden.detach(), w_last, b_last, root, bias, self.aggr)
+            else:
+                out = ops.nnconv_forward_hidden_bip_raw(xs_d, xd_d, csr, hidden.detach(), w_last, b_last, root, bias, self.aggr)
+        else:
+            weight = self.nn(pseudo_s)
+            if weight.dim() != 2 or weight.size(0) != csr.n_edges or weight.size(1) != cin * cout:
+                raise ValueError(f"nn(pseudo) must be [E, {cin * cout}] = [{csr.n_edges}, {'in_channels' if one else 'in_src'} * out_channels] "
+                                 f"(nn_conv.py:274), got {tuple(weight.shape)}")
+            weight = weight.float().to(dev).contiguous()
+            if needs_grad:
+                out = WeConvAnyFunction.apply(xs_d, xd_d, weight, csr, root, bias, self.aggr)
+            else:
+                res, fused = (None if residual is None else residual.detach().to(dev)), True
+                if one:
+                    out = ops.nnconv_forward_edgeweights_any_raw(xs_d, csr, weight.detach(), root, bias, self.aggr, residual=res, relu=relu)
+                else:
+                    out = ops.nnconv_forward_edgeweights_bip_raw(xs_d, xd_d, csr, weight.detach(), root, bias, self.aggr, residual=res, relu=relu)
+        if not fused:
             if residual is not None:
                 out = residual.to(dev) + out
             if relu:
                 out = torch.relu(out)
-        else:
-            out = ops.nnconv_forward_edgeweights_any_raw(x.detach().to(dev), csr, weight.detach(), root, bias, self.aggr,
-                                                         residual=None if residual is None else residual.to(dev), relu=relu)
-        return out.to(x.device)
-
-    def _propagate_any_reassociated(self, x, csr, pseudo, lin, dev, needs_grad, residual, relu):
-        """The re-associated route of `_propagate_any_width` (a Linear / ReLU chain, add / mean): H = relu(L_{n-1}(... pseudo)) by
-        torch where the module lives, rows in CSR slot order, [E, K] - staged like the per-edge weights of the other route - then
-        aggregation, the LAST Linear per node and update() as ONE native call (gpde_nnconv_fwd_hidden_any; backward
-        gpde_nnconv_bwd_hidden_any, whose dL/dH autograd carries back into the earlier layers).  `residual` / `relu` are torch
-        ops after the call: the fused epilogue is a property of the materialised route."""
-        pseudo_s = pseudo if bool(getattr(csr, "_perm_is_identity", False)) else pseudo.index_select(0, csr.perm.long().to(pseudo.device))
-        h = pseudo_s
-        for l in lin[:-1]:
-            h = torch.relu(torch.nn.functional.linear(h, l.weight, l.bias))
-        hidden = h.float().to(dev).contiguous()
-
-        def on_dev(t):
-            if t is None or t.device == dev:
-                return t
-            return t.to(dev) if needs_grad and t.requires_grad else ops.stage_const(t, dev)
-        # (.float(): a float64 kernel network runs with float32 x on the other route too, through `weight.float()`)
-        w_last, b_last = on_dev(lin[-1].weight).float(), None if lin[-1].bias is None else on_dev(lin[-1].bias).float()
-        root, bias = on_dev(self.root), on_dev(self.bias)
-        if needs_grad:
-            out = HiddenAnyFunction.apply(x.to(dev), hidden, w_last, b_last, csr, root, bias, self.aggr)
-        else:
-            out = ops.nnconv_forward_hidden_any_raw(x.detach().to(dev), csr, hidden.detach(), w_last, b_last, root, bias, self.aggr)
-        if residual is not None:
-            out = residual.to(dev) + out
-        if relu:
-            out = torch.relu(out)
-        return out.to(x.device)
+        return out.to(x_src.device)
 
     def _propagate_rect(self, x_src, x_dst, n_src, n_dst, edge_index, pseudo, residual, relu):
         """propagate() BETWEEN TWO NODE SETS: sources x_src [n_src, in_src], destinations x_dst [n_dst, in_dst] or None, edges
         (edge_index[0] in [0, n_src)) -> (edge_index[1] in [0, n_dst)) (rows swapped under flow='target_to_source'), out
         [n_dst, out].  The two routes of `_propagate_any_width` at EVERY width, 64 -> 64 included, on the rectangular entry points
-        (gpde_nnconv_*_edgeweights_bip / gpde_nnconv_*_hidden_bip; ops.any_width_route decides with n_dst as its node count):
-        `nn(pseudo)` or the hidden layers by the caller's module on rows in CSR slot order, CPU tensors staged around the
-        operator, `residual` [n_dst, out] / `relu` fused into the materialised inference call and composed from torch ops
-        otherwise.  x_dst None: no root term although the module may have a root (PyG's rule)."""
+        (gpde_nnconv_*_edgeweights_bip / gpde_nnconv_*_hidden_bip; ops.any_width_route decides with n_dst as its node count).
+        This front validates, builds the rectangular CSR and decides the route; `_any_width_operator` runs it.  x_dst None: no root
+        term although the module may have a root (PyG's rule).  aggr='max' with a gradient is not built."""
         cin, cind, cout = self._in_src(), self._in_dst(), self.out_channels
         if not (ops.width_supported(cin, cout) and ops.width_supported(cind, cout)):
             raise NotImplementedError(f"the MI355X operator is built for 1 <= in_channels, out_channels <= {ops.ANY_MAX_WIDTH}, got "
@@ -533,53 +546,12 @@ class NNConv_old(MessagePassing):
                               flip=self._flipped())
         if pseudo.size(0) != csr.n_edges:
             raise ValueError(f"edge_attr has {pseudo.size(0)} rows, edge_index {csr.n_edges} edges")
-        need = csr.n_edges * cin * cout * 4
-        free, _ = ops.device_free_bytes(dev)
-        lin = ops.mlp_linears(self.nn) if self._nn_is_linear_relu_chain() else None
-        chain = lin is not None and lin[-1].out_features == cin * cout
-        route = ops.any_width_route(n_dst, csr.n_edges, cin, cout, lin[-1].in_features if chain else None, self.aggr, chain, free)
+        route, lin, free = self._any_width_route(csr, dev)
         if route["route"] == "refused":
             raise RuntimeError(f"{self!r}: a call between two node sets materialises the per-edge weights as the reference does (nn_conv.py:274) - "
-                               f"{csr.n_edges} edges x {cin} x {cout} x 4 B = {need / 2**30:.2f} GiB (twice that with gradients), "
-                               f"{free / 2**30:.2f} GiB free (GPDE_ANY_REASSOC={ops.ANY_REASSOC})")
-
-        def on_dev(t):
-            if t is None or t.device == dev:
-                return t
-            return t.to(dev) if needs_grad and t.requires_grad else ops.stage_const(t, dev)
-        # rows in CSR slot order (the order the kernels address W_e / H in); `nn` acts row by row
-        pseudo_s = pseudo if bool(getattr(csr, "_perm_is_identity", False)) else pseudo.index_select(0, csr.perm.long().to(pseudo.device))
-        root, bias = (None if x_dst is None else on_dev(self.root)), on_dev(self.bias)
-        xs_d = x_src.to(dev) if needs_grad else x_src.detach().to(dev)
-        xd_d = None if x_dst is None else (x_dst.to(dev) if needs_grad else x_dst.detach().to(dev))
-        fused = False
-        if route["route"] == "reassociated":
-            h = pseudo_s
-            for l in lin[:-1]:
-                h = torch.relu(torch.nn.functional.linear(h, l.weight, l.bias))
-            hidden = h.float().to(dev).contiguous()
-            w_last, b_last = on_dev(lin[-1].weight).float(), None if lin[-1].bias is None else on_dev(lin[-1].bias).float()
-            if needs_grad:
-                out = HiddenBipFunction.apply(xs_d, xd_d, hidden, w_last, b_last, csr, root, bias, self.aggr)
-            else:
-                out = ops.nnconv_forward_hidden_bip_raw(xs_d, xd_d, csr, hidden.detach(), w_last, b_last, root, bias, self.aggr)
-        else:
-            weight = self.nn(pseudo_s)
-            if weight.dim() != 2 or weight.size(0) != csr.n_edges or weight.size(1) != cin * cout:
-                raise ValueError(f"nn(pseudo) must be [E, {cin * cout}] = [{csr.n_edges}, in_src * out_channels] (nn_conv.py:274), got {tuple(weight.shape)}")
-            weight = weight.float().to(dev).contiguous()
-            if needs_grad:
-                out = WeConvBipFunction.apply(xs_d, xd_d, weight, csr, root, bias, self.aggr)
-            else:
-                out = ops.nnconv_forward_edgeweights_bip_raw(xs_d, xd_d, csr, weight.detach(), root, bias, self.aggr,
-                                                             residual=None if residual is None else residual.detach().to(dev), relu=relu)
-                fused = True
-        if not fused:
-            if residual is not None:
-                out = residual.to(dev) + out
-            if relu:
-                out = torch.relu(out)
-        return out.to(x_src.device)
+                               f"{csr.n_edges} edges x {cin} x {cout} x 4 B = {route['bytes_materialised'] / 2**30:.2f} GiB (twice that with "
+                               f"gradients), {free / 2**30:.2f} GiB free (GPDE_ANY_REASSOC={ops.ANY_REASSOC})")
+        return self._any_width_operator(x_src, x_dst, csr, pseudo, route["route"] == "reassociated", lin, dev, needs_grad, residual, relu)
 
     def _propagate(self, x, edge_index, pseudo, weights, biases, root, bias, use_hidden_cache):
         """propagate() of the reference (gather, message, aggregate, update) as ONE native operator on device
@@ -675,12 +647,7 @@ class NNConv_old(MessagePassing):
         (a model moved back with `model.cpu()`): a differentiable `.to(dev)` when a gradient is needed, otherwise the
         device copy cached by ops.stage_const on the CPU tensor's storage + version - repeated evaluation calls then
         share one copy and one pack instead of re-packing 24 MB per call."""
-        def one(t):
-            if t is None or t.device == dev:
-                return t
-            if need_grad and t.requires_grad:
-                return t.to(dev)
-            return ops.stage_const(t, dev)
+        one = lambda t: _on_dev(t, dev, need_grad)
         lin = ops.mlp_linears(self.nn)
         return [one(l.weight) for l in lin], [one(l.bias) for l in lin], one(self.root), one(self.bias)
 
@@ -717,7 +684,7 @@ class NNConv_old(MessagePassing):
             weight = weight.float().to(dev).contiguous()
             csr = ops.build_csr(ident, e)
             if torch.is_grad_enabled() and (x_j.requires_grad or weight.requires_grad):
-                out = WeConvAnyFunction.apply(x_j.float().to(dev), weight, csr, None, None, "add")
+                out = WeConvAnyFunction.apply(x_j.float().to(dev), ops._ONE_SET, weight, csr, None, None, "add")
             else:
                 out = ops.nnconv_forward_edgeweights_any_raw(x_j.detach().float().to(dev), csr, weight.detach(), None, None, "add")
             return out.to(x_j.device)
@@ -740,17 +707,13 @@ class NNConv_old(MessagePassing):
             cin, cout = int(self.in_channels), int(self.out_channels)
             x = x.unsqueeze(-1) if x.dim() == 1 else x
             wants = need_grad and (x.requires_grad or any(t is not None and t.requires_grad for t in (self.root, self.bias)))
-
-            def on_dev(t):
-                if t is None or t.device == dev:
-                    return t
-                return t.to(dev) if wants and t.requires_grad else ops.stage_const(t, dev)
+            root, bias = _on_dev(self.root, dev, wants), _on_dev(self.bias, dev, wants)
             csr = ops.build_csr(empty, x.size(0))
             no_we = torch.empty(0, cin * cout, dtype=torch.float32, device=dev)
             if wants:
-                term = WeConvAnyFunction.apply(x.float().to(dev), no_we, csr, on_dev(self.root), on_dev(self.bias), "add")
+                term = WeConvAnyFunction.apply(x.float().to(dev), ops._ONE_SET, no_we, csr, root, bias, "add")
             else:
-                term = ops.nnconv_forward_edgeweights_any_raw(x.detach().float().to(dev), csr, no_we, on_dev(self.root), on_dev(self.bias), "add")
+                term = ops.nnconv_forward_edgeweights_any_raw(x.detach().float().to(dev), csr, no_we, root, bias, "add")
             return aggr_out + term.to(aggr_out.device)
         weights, biases, root, bias = self._params_on(dev, need_grad)
         k0 = weights[0].size(1)

@@ -272,6 +272,11 @@ def _require_cuda(t, name: str):
             "(no CPU / composite fallback exists by design)")
 
 
+def _ptr(t):
+    """`t.data_ptr()`, NULL for an operand that is not there."""
+    return None if t is None else t.data_ptr()
+
+
 def _dense16(t: torch.Tensor) -> torch.Tensor:
     """`t` itself when it is dense (contiguous) and starts on a 16-byte boundary, else a fresh dense copy (the allocators of
     torch hand out blocks aligned far beyond 16 bytes).  The 64-wide kernels read their operands with 16-byte vector accesses."""
@@ -1057,7 +1062,6 @@ def nnconv_backward_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor,
         ws = alloc_bwd_ws(lib, n, e, nl, dims_c, dev, 0 if hidden_saved is None else e * hidden_width(dims) * 4)
     rph = csr.rowptr_host
     srp, ssl = csr.src_order
-    p = lambda t: None if t is None else t.data_ptr()
     nas = edge_attr.c_struct() if is_na else None
     ga = torch.zeros(e, dims[0], dtype=torch.float32, device=dev) if need_attr else None
     if hidden_saved is not None and (need_attr or hidden_saved.dtype != torch.float32 or
@@ -1066,9 +1070,9 @@ def nnconv_backward_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor,
     hidden_saved = _operand(hidden_saved, "hidden_saved", (e, hidden_width(dims)), dev)
     with torch.cuda.device(dev):
         rc = lib.gpde_nnconv_bwd(x.data_ptr(), n, None if is_na else edge_attr.data_ptr(), None if nas is None else ctypes.byref(nas),
-                                 p(hidden_saved), e, csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(), None if is_na else perm.data_ptr(),
-                                 rph.data_ptr(), p(srp), p(ssl), nl, dims_c, arr(ws_), arr(bs_), p(root_c), _AGGR[aggr],
-                                 grad_out.data_ptr(), p(z_saved), gx.data_ptr(), None, p(ga), arr(gW), arr(gb), p(groot), p(gbias), 0,
+                                 _ptr(hidden_saved), e, csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(), None if is_na else perm.data_ptr(),
+                                 rph.data_ptr(), _ptr(srp), _ptr(ssl), nl, dims_c, arr(ws_), arr(bs_), _ptr(root_c), _AGGR[aggr],
+                                 grad_out.data_ptr(), _ptr(z_saved), gx.data_ptr(), None, _ptr(ga), arr(gW), arr(gb), _ptr(groot), _ptr(gbias), 0,
                                  ws.data_ptr(), ws.numel(), _stream_ptr(dev))
     _lib.check(rc, "gpde_nnconv_bwd")
     _lib.n_native_calls += 1
@@ -1134,15 +1138,14 @@ def nnconv_backward_light_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor
         _lib.check(-2, "gpde_nnconv_bwd_workspace_bytes")
     ws = _alloc_ws(nbytes, dev)
     srp, ssl = csr.src_order
-    p = lambda t: None if t is None else t.data_ptr()
     nas = edge_attr.c_struct() if is_na else None
     with torch.cuda.device(dev):
         rc = lib.gpde_nnconv_bwd_light(x.data_ptr(), n, None if is_na else edge_attr.data_ptr(), None if nas is None else ctypes.byref(nas),
                                        e, csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(), None if is_na else perm.data_ptr(),
-                                       csr.rowptr_host.data_ptr(), p(srp), p(ssl), nl, dims_c,
-                                       _ptr_array(ws_), _ptr_array(bs_), p(root_c), _AGGR[aggr], grad_out.data_ptr(), p(z_saved),
-                                       p(hidden_part) if hidden_nodes > 0 else None, int(hidden_nodes) if hidden_part is not None else 0,
-                                       gx.data_ptr(), gw.data_ptr(), p(gb), p(groot), p(gbias), ws.data_ptr(), ws.numel(),
+                                       csr.rowptr_host.data_ptr(), _ptr(srp), _ptr(ssl), nl, dims_c,
+                                       _ptr_array(ws_), _ptr_array(bs_), _ptr(root_c), _AGGR[aggr], grad_out.data_ptr(), _ptr(z_saved),
+                                       _ptr(hidden_part) if hidden_nodes > 0 else None, int(hidden_nodes) if hidden_part is not None else 0,
+                                       gx.data_ptr(), gw.data_ptr(), _ptr(gb), _ptr(groot), _ptr(gbias), ws.data_ptr(), ws.numel(),
                                        _stream_ptr(dev))
     _lib.check(rc, "gpde_nnconv_bwd_light")
     _lib.n_native_calls += 1
@@ -1435,10 +1438,9 @@ def nnconv_backward_edgeweights_raw(x: torch.Tensor, csr: Csr, edge_weights: tor
         gbias = torch.empty(WIDTH, dtype=torch.float32, device=dev) if need_bias else None
     ws = _alloc_ws(int(lib.gpde_nnconv_bwd_edgeweights_workspace_bytes(n, e)), dev)
     srp, ssl = csr.src_order
-    p = lambda t: None if t is None else t.data_ptr()
     with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_bwd_edgeweights_acc(x.data_ptr(), n, we.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(), p(srp), p(ssl),
-                                                 p(root_c), _AGGR[aggr], grad_out.data_ptr(), gx.data_ptr(), gwe.data_ptr(), p(groot), p(gbias),
+        rc = lib.gpde_nnconv_bwd_edgeweights_acc(x.data_ptr(), n, we.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(), _ptr(srp), _ptr(ssl),
+                                                 _ptr(root_c), _AGGR[aggr], grad_out.data_ptr(), gx.data_ptr(), gwe.data_ptr(), _ptr(groot), _ptr(gbias),
                                                  bits, ws.data_ptr(), ws.numel(), _stream_ptr(dev))
     _lib.check(rc, "gpde_nnconv_bwd_edgeweights_acc")
     _lib.n_native_calls += 1
@@ -1469,94 +1471,6 @@ def any_width_plan(in_channels: int, out_channels: int, aligned: bool = True, ag
     _lib.check(_lib.lib().gpde_nnconv_edgeweights_any_plan(int(in_channels), int(out_channels), 1 if aligned else 0, _AGGR_WE[aggr], out),
                "gpde_nnconv_edgeweights_any_plan")
     return dict(zip(("V", "LC", "R", "ES", "B", "lanes"), (int(v) for v in out)))
-
-
-def _any_widths(x: torch.Tensor, csr: Csr, edge_weights: torch.Tensor, out_channels: Optional[int]):
-    """(in_channels, out_channels) of a call of the any-width operator from its tensors, shapes checked."""
-    n, e = csr.n_nodes, csr.n_edges
-    if x.dtype != torch.float32 or x.dim() != 2 or x.size(0) != n or x.size(1) < 1:
-        raise ValueError(f"x must be float32 [{n}, in_channels], got {x.dtype} {tuple(x.shape)}")
-    cin = int(x.size(1))
-    we = edge_weights
-    if we.dtype != torch.float32 or we.dim() != 2 or we.size(0) != e or we.size(1) % cin != 0 or we.size(1) == 0 or we.device != x.device:
-        raise ValueError(f"edge_weights must be float32 [{e}, {cin} * out_channels] on {x.device}, got {we.dtype} {tuple(we.shape)}")
-    cout = int(we.size(1)) // cin
-    if out_channels is not None and int(out_channels) != cout:
-        raise ValueError(f"edge_weights has {we.size(1)} columns = {cin} x {cout}, not {cin} x {out_channels}")
-    if not width_supported(cin, cout):
-        raise NotImplementedError(f"in_channels {cin} -> out_channels {cout}: the native operator is built for widths 1 .. {ANY_MAX_WIDTH}")
-    return cin, cout
-
-
-def nnconv_forward_edgeweights_any_raw(x, csr: Csr, edge_weights, root, bias, aggr: str, residual=None, relu: bool = False,
-                                       out_channels: Optional[int] = None) -> torch.Tensor:
-    """gpde_nnconv_fwd_edgeweights_any: the operator given the per-edge weights [E, in * out] (CSR slot order) at any width
-    1 .. 256 - gather, message, add / mean / max, update() (+ residual [N, out], ReLU) in one launch."""
-    lib = _lib.lib()
-    _require_cuda(x, "x")
-    if aggr not in _AGGR_WE:
-        raise NotImplementedError(f"aggr={aggr!r}")
-    cin, cout = _any_widths(x, csr, edge_weights, out_channels)
-    n, e, dev = csr.n_nodes, csr.n_edges, x.device
-    x_c = x.detach().contiguous()
-    we = edge_weights.detach().contiguous()     # (a dense tensor is passed as it is, aligned or not: the dword route stays)
-    root_c = None if root is None else root.detach().contiguous()
-    bias_c = None if bias is None else bias.detach().contiguous()
-    if root_c is not None and (root_c.dtype != torch.float32 or tuple(root_c.shape) != (cin, cout) or root_c.device != dev):
-        raise ValueError(f"root must be float32 [{cin},{cout}] on {dev}, got {root_c.dtype} {tuple(root_c.shape)}")
-    if bias_c is not None and (bias_c.dtype != torch.float32 or tuple(bias_c.shape) != (cout,) or bias_c.device != dev):
-        raise ValueError(f"bias must be float32 [{cout}] on {dev}, got {bias_c.dtype} {tuple(bias_c.shape)}")
-    res = None
-    if residual is not None:
-        _require_cuda(residual, "residual")
-        if residual.dtype != torch.float32 or tuple(residual.shape) != (n, cout) or residual.device != dev:
-            raise ValueError(f"residual must be float32 [{n},{cout}] on {dev}, got {residual.dtype} {tuple(residual.shape)}")
-        res = residual.detach().contiguous()
-    out = torch.empty(n, cout, dtype=torch.float32, device=dev)
-    p = lambda t: None if t is None else t.data_ptr()
-    with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_fwd_edgeweights_any(x_c.data_ptr(), n, we.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(), p(root_c),
-                                                 p(bias_c), p(res), 1 if relu else 0, _AGGR_WE[aggr], cin, cout, out.data_ptr(),
-                                                 _stream_ptr(dev))
-    _lib.check(rc, "gpde_nnconv_fwd_edgeweights_any")
-    _lib.n_native_calls += 1
-    return out
-
-
-def nnconv_backward_edgeweights_any_raw(x: torch.Tensor, csr: Csr, edge_weights: torch.Tensor, root: Optional[torch.Tensor], aggr: str,
-                                        grad_out: torch.Tensor, need_root: bool = True, need_bias: bool = True):
-    """gpde_nnconv_bwd_edgeweights_any: backward of the any-width operator given the per-edge weights ('add' / 'mean').  Returns
-    (grad_x [N, in], grad_edge_weights [E, in * out], grad_root [in, out] or None, grad_bias [out] or None)."""
-    lib = _lib.lib()
-    for t, nm in ((x, "x"), (edge_weights, "edge_weights"), (grad_out, "grad_out")):
-        _require_cuda(t, nm)
-    if aggr not in _AGGR:
-        raise NotImplementedError(f"aggr={aggr!r}: the gradient of the per-edge weight operator is built for 'add' and 'mean'")
-    cin, cout = _any_widths(x, csr, edge_weights, None)
-    n, e, dev = csr.n_nodes, csr.n_edges, x.device
-    x = x.detach().contiguous()
-    grad_out = grad_out.detach().contiguous().float()
-    if tuple(grad_out.shape) != (n, cout):
-        raise ValueError(f"grad_out must be [{n},{cout}], got {tuple(grad_out.shape)}")
-    we = edge_weights.detach().contiguous()     # (a dense tensor is passed as it is, aligned or not: the dword route stays)
-    root_c = None if root is None else root.detach().contiguous()
-    if root_c is not None and (root_c.dtype != torch.float32 or tuple(root_c.shape) != (cin, cout)):
-        raise ValueError(f"root must be float32 [{cin},{cout}], got {root_c.dtype} {tuple(root_c.shape)}")
-    want_root = need_root and root is not None
-    gx = torch.empty(n, cin, dtype=torch.float32, device=dev)
-    gwe = torch.empty(e, cin * cout, dtype=torch.float32, device=dev)
-    groot = torch.empty(cin, cout, dtype=torch.float32, device=dev) if want_root else None
-    gbias = torch.empty(cout, dtype=torch.float32, device=dev) if need_bias else None
-    ws = _alloc_ws(int(lib.gpde_nnconv_bwd_edgeweights_any_workspace_bytes(n, e, cin, cout)), dev)
-    srp, ssl = csr.src_order
-    p = lambda t: None if t is None else t.data_ptr()
-    with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_bwd_edgeweights_any(x.data_ptr(), n, we.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(), p(srp), p(ssl),
-                                                 p(root_c), _AGGR[aggr], cin, cout, grad_out.data_ptr(), gx.data_ptr(), gwe.data_ptr(),
-                                                 p(groot), p(gbias), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "gpde_nnconv_bwd_edgeweights_any")
-    _lib.n_native_calls += 1
-    return gx, gwe, groot, gbias
 
 
 # ... re-associated at any width (include/gpde.h gpde_nnconv_fwd_hidden_any / gpde_nnconv_bwd_hidden_any; csrc/gpde_reassoc_any.hip):
@@ -1622,56 +1536,227 @@ def any_width_route(n_nodes: int, n_edges: int, in_channels: int, out_channels: 
     return out
 
 
-def _hidden_any_args(x, csr: Csr, hidden, w_last, b_last, root):
-    """Shapes of a call of the re-associated any-width operator checked; (in_channels, out_channels, k_hidden)."""
-    n, e = csr.n_nodes, csr.n_edges
-    if x.dtype != torch.float32 or x.dim() != 2 or x.size(0) != n or x.size(1) < 1:
-        raise ValueError(f"x must be float32 [{n}, in_channels], got {x.dtype} {tuple(x.shape)}")
-    cin, dev = int(x.size(1)), x.device
-    if hidden.dtype != torch.float32 or hidden.dim() != 2 or hidden.size(0) != e or hidden.size(1) < 1 or hidden.device != dev:
-        raise ValueError(f"hidden must be float32 [{e}, k_hidden] on {dev}, got {hidden.dtype} {tuple(hidden.shape)}")
-    k = int(hidden.size(1))
+# ... on one node set or between two (include/gpde.h gpde_nnconv_*_edgeweights_{any,bip} / gpde_nnconv_*_hidden_{any,bip}).  The library
+# runs each pair in ONE body - a call on one node set is the two-set call that hands one table twice - and so does this file: four
+# bodies take (x_src, x_dst, csr, ...), x_src [n_src, in_src] gathered by the edges, x_dst [n_dst, in_dst] in the root term, out
+# [n_dst, out].  `x_dst` None: no destination features, so no root term.  `x_dst` _ONE_SET: one node set - the `_any` entry point and
+# its argument list, x_src also the table of the root term (NOT the same tensor passed twice: the library adds the root term inside
+# the ordered sum of grad_x, two partial gradients added by the caller would have other bits).
+_ONE_SET = object()
+
+
+def _dense(t):
+    """Operand of the any-width entry points: dense, nothing more (not `_dense16` / `_operand`) - a dense tensor that starts off a
+    16-byte boundary reaches the library as it is and takes the dword route there."""
+    return t if t is None or t is _ONE_SET else t.detach().contiguous()
+
+
+def _last_linear_args(w_last, b_last, cin: int, k: int, dev) -> int:
+    """The last Linear of a re-associated call checked (w_last [in_src * out, K], b_last [in_src * out] or None); out_channels."""
     if w_last.dtype != torch.float32 or w_last.dim() != 2 or w_last.size(1) != k or w_last.size(0) % cin != 0 or w_last.size(0) == 0 or \
             w_last.device != dev:
         raise ValueError(f"w_last must be float32 [{cin} * out_channels, {k}] on {dev}, got {w_last.dtype} {tuple(w_last.shape)}")
     cout = int(w_last.size(0)) // cin
     if b_last is not None and (b_last.dtype != torch.float32 or tuple(b_last.shape) != (cin * cout,) or b_last.device != dev):
         raise ValueError(f"b_last must be float32 [{cin * cout}] on {dev}, got {b_last.dtype} {tuple(b_last.shape)}")
-    if root is not None and (root.dtype != torch.float32 or tuple(root.shape) != (cin, cout) or root.device != dev):
-        raise ValueError(f"root must be float32 [{cin},{cout}] on {dev}, got {root.dtype} {tuple(root.shape)}")
-    if not width_supported(cin, cout):
-        raise NotImplementedError(f"in_channels {cin} -> out_channels {cout}: the native operator is built for widths 1 .. {ANY_MAX_WIDTH}")
-    if k > ANY_MAX_HIDDEN:
+    return cout
+
+
+def _any_args(x_src, x_dst, csr: Csr, root, per_edge, last=None, out_channels: Optional[int] = None):
+    """The node tables, the per-edge operand - W_e [E, in_src * out], or H [E, K] with `last` = (w_last, b_last) - and root of a call
+    checked; (in_src, in_dst, out_channels, K or None).  The messages are those of the entry point that will run: it names its table
+    `x` on one node set, `x_src` / `x_dst` between two, and states every fault of the per-edge operand or of root in one message
+    on one node set, their column count in a message of its own between two.  `out_channels`: what the caller expects W_e to hold."""
+    one = x_dst is _ONE_SET
+    n_dst, e, pe_name = csr.n_nodes, csr.n_edges, "edge_weights" if last is None else "hidden"
+    n_src = n_dst if one else csr.n_src
+    if x_src.dtype != torch.float32 or x_src.dim() != 2 or x_src.size(0) != n_src or x_src.size(1) < 1:
+        raise ValueError(f"{'x' if one else 'x_src'} must be float32 [{n_src}, {'in_channels' if one else 'in_src'}], got {x_src.dtype} "
+                         f"{tuple(x_src.shape)}")
+    dev, cin = x_src.device, int(x_src.size(1))
+    if not one and x_dst is not None and (x_dst.dtype != torch.float32 or x_dst.dim() != 2 or x_dst.size(0) != n_dst or x_dst.size(1) < 1 or
+                                          x_dst.device != dev):
+        raise ValueError(f"x_dst must be float32 [{n_dst}, in_dst] on {dev}, got {x_dst.dtype} {tuple(x_dst.shape)}")
+    cind = cin if one or x_dst is None else int(x_dst.size(1))
+    bad = per_edge.dtype != torch.float32 or per_edge.dim() != 2 or per_edge.size(0) != e or per_edge.size(1) < 1 or per_edge.device != dev
+    ragged = last is None and not bad and per_edge.size(1) % cin != 0
+    if bad or (one and ragged):
+        cols = "." if not one else f"{cin} * out_channels" if last is None else "k_hidden"
+        raise ValueError(f"{pe_name} must be float32 [{e}, {cols}] on {dev}, got {per_edge.dtype} {tuple(per_edge.shape)}")
+    if ragged:
+        raise ValueError(f"edge_weights must be [{e}, {cin} * out_channels], got {tuple(per_edge.shape)}")
+    if last is None:
+        cout, k = int(per_edge.size(1)) // cin, None
+        if out_channels is not None and int(out_channels) != cout:
+            raise ValueError(f"edge_weights has {per_edge.size(1)} columns = {cin} x {cout}, not {cin} x {out_channels}")
+    else:
+        k = int(per_edge.size(1))
+        cout = _last_linear_args(last[0], last[1], cin, k, dev)
+    if root is not None and x_dst is None:
+        raise ValueError("root without x_dst: the root term is x_dst . root (pass root=None for a call without destination features)")
+    if root is not None:
+        bad = root.dtype != torch.float32 or root.dim() != 2 or root.size(0) != cind or root.device != dev
+        if bad or (one and root.size(1) != cout):
+            raise ValueError(f"root must be float32 {f'[{cin},{cout}]' if one else f'[{cind}, out_channels]'} on {dev}, got {root.dtype} "
+                             f"{tuple(root.shape)}")
+        if root.size(1) != cout:
+            raise ValueError(f"root must be [{cind},{cout}], got {tuple(root.shape)}")
+    if not (width_supported(cin, cout) and width_supported(cind, cout)):
+        raise NotImplementedError(f"{f'in_channels {cin}' if one else f'(in_src {cin}, in_dst {cind})'} -> out_channels {cout}: the native "
+                                  f"operator is built for widths 1 .. {ANY_MAX_WIDTH}")
+    if k is not None and k > ANY_MAX_HIDDEN:
         raise NotImplementedError(f"last hidden width {k}: the re-associated any-width operator is built for 1 .. {ANY_MAX_HIDDEN}")
-    return cin, cout, k
+    return cin, cind, cout, k
+
+
+def _any_f32(t, name: str, shape, dev):
+    """`t` (bias [out], residual [n_dst, out]; or None) checked and dense."""
+    if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or t.device != dev):
+        raise ValueError(f"{name} must be float32 [{','.join(str(s) for s in shape)}] on {dev}, got {t.dtype} {tuple(t.shape)}")
+    return _dense(t)
+
+
+def _any_grad_out(grad_out, n_dst: int, cout: int):
+    grad_out = grad_out.detach().contiguous().float()
+    if tuple(grad_out.shape) != (n_dst, cout):
+        raise ValueError(f"grad_out must be [{n_dst},{cout}], got {tuple(grad_out.shape)}")
+    return grad_out
+
+
+def _any_native(stem: str, xs, xd, csr: Csr, widths, before, after):
+    """One native call: gpde_nnconv_<stem>_any(x, n, *before, in, out, *after, stream) when `xd` is _ONE_SET, else
+    gpde_nnconv_<stem>_bip(x_src, n_src, x_dst, n_dst, *before, in_src, in_dst, out, *after, stream)."""
+    one, dev = xd is _ONE_SET, xs.device
+    name = f"gpde_nnconv_{stem}_{'any' if one else 'bip'}"
+    tables = (xs.data_ptr(), csr.n_nodes) if one else (xs.data_ptr(), csr.n_src, _ptr(xd), csr.n_nodes)
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.lib(), name)(*tables, *before, *((widths[0], widths[2]) if one else widths), *after, _stream_ptr(dev))
+    _lib.check(rc, name)
+    _lib.n_native_calls += 1
+
+
+def _x_name(x_dst) -> str:
+    return "x" if x_dst is _ONE_SET else "x_src"
+
+
+def _any_fwd_edgeweights(x_src, x_dst, csr: Csr, edge_weights, root, bias, aggr: str, residual, relu: bool, out_channels=None):
+    _require_cuda(x_src, _x_name(x_dst))
+    if aggr not in _AGGR_WE:
+        raise NotImplementedError(f"aggr={aggr!r}")
+    xs, xd, we, root_c = _dense(x_src), _dense(x_dst), _dense(edge_weights), _dense(root)
+    widths = _any_args(xs, xd, csr, root_c, we, out_channels=out_channels)[:3]
+    n_dst, cout, dev = csr.n_nodes, widths[2], xs.device
+    bias_c = _any_f32(bias, "bias", (cout,), dev)
+    if residual is not None:
+        _require_cuda(residual, "residual")
+    res = _any_f32(residual, "residual", (n_dst, cout), dev)
+    out = torch.empty(n_dst, cout, dtype=torch.float32, device=dev)
+    _any_native("fwd_edgeweights", xs, xd, csr, widths,
+                (we.data_ptr(), csr.n_edges, csr.rowptr.data_ptr(), csr.src.data_ptr(), _ptr(root_c), _ptr(bias_c), _ptr(res), 1 if relu else 0,
+                 _AGGR_WE[aggr]), (out.data_ptr(),))
+    return out
+
+
+def _any_bwd_edgeweights(x_src, x_dst, csr: Csr, edge_weights, root, aggr: str, grad_out, need_x_src, need_x_dst, need_root, need_bias):
+    """Returns (grad_x_src, grad_x_dst, grad_edge_weights, grad_root, grad_bias).  One node set: grad_x_dst is None and the entry
+    point takes no NULL grad_x - `need_x_src` must be True."""
+    lib = _lib.lib()
+    for t, nm in ((x_src, _x_name(x_dst)), (edge_weights, "edge_weights"), (grad_out, "grad_out")):
+        _require_cuda(t, nm)
+    if aggr not in _AGGR:
+        raise NotImplementedError(f"aggr={aggr!r}: the gradient of the per-edge weight operator is built for 'add' and 'mean'")
+    one = x_dst is _ONE_SET
+    xs, xd, we, root_c = _dense(x_src), _dense(x_dst), _dense(edge_weights), _dense(root)
+    cin, cind, cout, _ = _any_args(xs, xd, csr, root_c, we)
+    n_src, n_dst, e, dev = int(xs.size(0)), csr.n_nodes, csr.n_edges, xs.device
+    grad_out = _any_grad_out(grad_out, n_dst, cout)
+    new = lambda want, *shape: torch.empty(*shape, dtype=torch.float32, device=dev) if want else None
+    gxs, gxd = new(need_x_src, n_src, cin), new(need_x_dst and not one and xd is not None, n_dst, cind)
+    gwe = new(True, e, cin * cout)
+    groot, gbias = new(need_root and root is not None, cind, cout), new(need_bias, cout)
+    if one:
+        ws = _alloc_ws(int(lib.gpde_nnconv_bwd_edgeweights_any_workspace_bytes(n_dst, e, cin, cout)), dev)
+    else:
+        ws = _alloc_ws(int(lib.gpde_nnconv_bwd_edgeweights_bip_workspace_bytes(n_src, n_dst, e, cin, cind, cout)), dev)
+    # one node set: grad_x is always written, so the source order is always taken (on a graph without edges too)
+    srp, ssl = csr.src_order if (one or (need_x_src and e > 0)) else (None, None)
+    _any_native("bwd_edgeweights", xs, xd, csr, (cin, cind, cout),
+                (we.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(), _ptr(srp), _ptr(ssl), _ptr(root_c), _AGGR[aggr]),
+                (grad_out.data_ptr(), *((gxs.data_ptr(),) if one else (_ptr(gxs), _ptr(gxd))), gwe.data_ptr(), _ptr(groot), _ptr(gbias),
+                 ws.data_ptr(), ws.numel()))
+    return gxs, gxd, gwe, groot, gbias
+
+
+def _any_hidden_operands(x_src, x_dst, csr: Csr, hidden, w_last, b_last, root, aggr: str, grad_out=None):
+    """What the forward and the backward given H share: device and aggr checks, dense operands, the shape gate."""
+    for t, nm in ((x_src, _x_name(x_dst)), (hidden, "hidden"), (w_last, "w_last")) + (() if grad_out is None else ((grad_out, "grad_out"),)):
+        _require_cuda(t, nm)
+    if aggr not in _AGGR:
+        raise NotImplementedError(f"aggr={aggr!r}: the re-associated operator is built for 'add' and 'mean'")
+    xs, xd, hid, wl, bl, root_c = (_dense(t) for t in (x_src, x_dst, hidden, w_last, b_last, root))
+    return xs, xd, hid, wl, bl, root_c, _any_args(xs, xd, csr, root_c, hid, last=(wl, bl))
+
+
+def _any_fwd_hidden(x_src, x_dst, csr: Csr, hidden, w_last, b_last, root, bias, aggr: str, ws_bytes):
+    lib = _lib.lib()
+    xs, xd, hid, wl, bl, root_c, (cin, cind, cout, k) = _any_hidden_operands(x_src, x_dst, csr, hidden, w_last, b_last, root, aggr)
+    n_dst, e, dev = csr.n_nodes, csr.n_edges, xs.device
+    bias_c = _any_f32(bias, "bias", (cout,), dev)
+    query = lib.gpde_nnconv_fwd_hidden_any_workspace_bytes if xd is _ONE_SET else lib.gpde_nnconv_fwd_hidden_bip_workspace_bytes
+    ws = _alloc_ws(_hidden_any_ws_bytes(query, n_dst, e, cin, cout, k, dev) if ws_bytes is None else int(ws_bytes), dev)
+    out = torch.empty(n_dst, cout, dtype=torch.float32, device=dev)
+    _any_native("fwd_hidden", xs, xd, csr, (cin, cind, cout),
+                (hid.data_ptr(), e, k, csr.rowptr.data_ptr(), csr.src.data_ptr(), wl.data_ptr(), _ptr(bl), _ptr(root_c), _ptr(bias_c), _AGGR[aggr]),
+                (out.data_ptr(), ws.data_ptr(), ws.numel()))
+    return out
+
+
+def _any_bwd_hidden(x_src, x_dst, csr: Csr, hidden, w_last, b_last, root, aggr: str, grad_out, need_x_src, need_x_dst, need_w_last,
+                    need_b_last, need_root, need_bias, ws_bytes):
+    """Returns (grad_x_src, grad_x_dst, grad_hidden, grad_w_last, grad_b_last, grad_root, grad_bias); grad_x_dst is None on one node set."""
+    lib = _lib.lib()
+    xs, xd, hid, wl, bl, root_c, (cin, cind, cout, k) = _any_hidden_operands(x_src, x_dst, csr, hidden, w_last, b_last, root, aggr, grad_out)
+    one = xd is _ONE_SET
+    n_src, n_dst, e, dev = int(xs.size(0)), csr.n_nodes, csr.n_edges, xs.device
+    grad_out = _any_grad_out(grad_out, n_dst, cout)
+    new = lambda want, *shape: torch.empty(*shape, dtype=torch.float32, device=dev) if want else None
+    gxs, gxd, gh = new(need_x_src, n_src, cin), new(need_x_dst and not one and xd is not None, n_dst, cind), new(True, e, k)
+    gwl, gbl = new(need_w_last, cin * cout, k), new(need_b_last and b_last is not None, cin * cout)
+    groot, gbias = new(need_root and root is not None, cind, cout), new(need_bias, cout)
+    if one:
+        query = lib.gpde_nnconv_bwd_hidden_any_workspace_bytes
+    else:       # (the two-set backward's query takes in_dst as well)
+        query = lambda n, ee, ci, co, kk: lib.gpde_nnconv_bwd_hidden_bip_workspace_bytes(n, ee, ci, cind, co, kk)
+    ws = _alloc_ws(_hidden_any_ws_bytes(query, n_dst, e, cin, cout, k, dev) if ws_bytes is None else int(ws_bytes), dev)
+    srp, ssl = csr.src_order if (need_x_src and e > 0) else (None, None)
+    _any_native("bwd_hidden", xs, xd, csr, (cin, cind, cout),
+                (hid.data_ptr(), e, k, csr.rowptr.data_ptr(), csr.src.data_ptr(), wl.data_ptr(), _ptr(bl), _ptr(root_c), _AGGR[aggr]),
+                (grad_out.data_ptr(), *((_ptr(gxs),) if one else (_ptr(gxs), _ptr(gxd))), gh.data_ptr(), _ptr(gwl), _ptr(gbl), _ptr(groot),
+                 _ptr(gbias), _ptr(srp), _ptr(ssl), ws.data_ptr(), ws.numel()))
+    return gxs, gxd, gh, gwl, gbl, groot, gbias
+
+
+# the eight entry points by name (tests and callers spy on, trace and patch these): each a delegation to its body
+def nnconv_forward_edgeweights_any_raw(x, csr: Csr, edge_weights, root, bias, aggr: str, residual=None, relu: bool = False,
+                                       out_channels: Optional[int] = None) -> torch.Tensor:
+    """gpde_nnconv_fwd_edgeweights_any: the operator given the per-edge weights [E, in * out] (CSR slot order) at any width
+    1 .. 256 - gather, message, add / mean / max, update() (+ residual [N, out], ReLU) in one launch."""
+    return _any_fwd_edgeweights(x, _ONE_SET, csr, edge_weights, root, bias, aggr, residual, relu, out_channels)
+
+
+def nnconv_backward_edgeweights_any_raw(x: torch.Tensor, csr: Csr, edge_weights: torch.Tensor, root: Optional[torch.Tensor], aggr: str,
+                                        grad_out: torch.Tensor, need_root: bool = True, need_bias: bool = True):
+    """gpde_nnconv_bwd_edgeweights_any: backward of the any-width operator given the per-edge weights ('add' / 'mean').  Returns
+    (grad_x [N, in], grad_edge_weights [E, in * out], grad_root [in, out] or None, grad_bias [out] or None)."""
+    gx, _, gwe, groot, gbias = _any_bwd_edgeweights(x, _ONE_SET, csr, edge_weights, root, aggr, grad_out, True, False, need_root, need_bias)
+    return gx, gwe, groot, gbias
 
 
 def nnconv_forward_hidden_any_raw(x, csr: Csr, hidden, w_last, b_last, root, bias, aggr: str, ws_bytes: Optional[int] = None) -> torch.Tensor:
     """gpde_nnconv_fwd_hidden_any: the any-width operator given the last hidden activations [E, K] (CSR slot order) and the last
     Linear (w_last [in * out, K], b_last [in * out] or None) - aggregation, last Linear per node, update().  'add' / 'mean'.
     `ws_bytes`: the workspace to run in (default: the library's preferred size); less gives more node blocks."""
-    lib = _lib.lib()
-    for t, nm in ((x, "x"), (hidden, "hidden"), (w_last, "w_last")):
-        _require_cuda(t, nm)
-    if aggr not in _AGGR:
-        raise NotImplementedError(f"aggr={aggr!r}: the re-associated operator is built for 'add' and 'mean'")
-    x_c, hid = x.detach().contiguous(), hidden.detach().contiguous()
-    wl = w_last.detach().contiguous()
-    bl, root_c, bias_c = (None if t is None else t.detach().contiguous() for t in (b_last, root, bias))
-    cin, cout, k = _hidden_any_args(x_c, csr, hid, wl, bl, root_c)
-    n, e, dev = csr.n_nodes, csr.n_edges, x.device
-    if bias_c is not None and (bias_c.dtype != torch.float32 or tuple(bias_c.shape) != (cout,) or bias_c.device != dev):
-        raise ValueError(f"bias must be float32 [{cout}] on {dev}, got {bias_c.dtype} {tuple(bias_c.shape)}")
-    ws = _alloc_ws(_hidden_any_ws_bytes(lib.gpde_nnconv_fwd_hidden_any_workspace_bytes, n, e, cin, cout, k, dev) if ws_bytes is None else int(ws_bytes), dev)
-    out = torch.empty(n, cout, dtype=torch.float32, device=dev)
-    p = lambda t: None if t is None else t.data_ptr()
-    with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_fwd_hidden_any(x_c.data_ptr(), n, hid.data_ptr(), e, k, csr.rowptr.data_ptr(), csr.src.data_ptr(), wl.data_ptr(),
-                                            p(bl), p(root_c), p(bias_c), _AGGR[aggr], cin, cout, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                            _stream_ptr(dev))
-    _lib.check(rc, "gpde_nnconv_fwd_hidden_any")
-    _lib.n_native_calls += 1
-    return out
+    return _any_fwd_hidden(x, _ONE_SET, csr, hidden, w_last, b_last, root, bias, aggr, ws_bytes)
 
 
 def nnconv_backward_hidden_any_raw(x, csr: Csr, hidden, w_last, b_last, root, aggr: str, grad_out, need_x: bool = True,
@@ -1680,98 +1765,16 @@ def nnconv_backward_hidden_any_raw(x, csr: Csr, hidden, w_last, b_last, root, ag
     """gpde_nnconv_bwd_hidden_any: backward of the re-associated any-width operator.  Returns (grad_x [N, in], grad_hidden [E, K] -
     dL/d hidden, the caller's ReLU not applied -, grad_w_last [in * out, K], grad_b_last [in * out], grad_root [in, out], grad_bias
     [out]); an output that is not needed (or has no input: b_last / root None) is None."""
-    lib = _lib.lib()
-    for t, nm in ((x, "x"), (hidden, "hidden"), (w_last, "w_last"), (grad_out, "grad_out")):
-        _require_cuda(t, nm)
-    if aggr not in _AGGR:
-        raise NotImplementedError(f"aggr={aggr!r}: the re-associated operator is built for 'add' and 'mean'")
-    x_c, hid = x.detach().contiguous(), hidden.detach().contiguous()
-    wl = w_last.detach().contiguous()
-    bl, root_c = (None if t is None else t.detach().contiguous() for t in (b_last, root))
-    cin, cout, k = _hidden_any_args(x_c, csr, hid, wl, bl, root_c)
-    n, e, dev = csr.n_nodes, csr.n_edges, x.device
-    grad_out = grad_out.detach().contiguous().float()
-    if tuple(grad_out.shape) != (n, cout):
-        raise ValueError(f"grad_out must be [{n},{cout}], got {tuple(grad_out.shape)}")
-    new = lambda want, *shape: torch.empty(*shape, dtype=torch.float32, device=dev) if want else None
-    gx, gh = new(need_x, n, cin), new(True, e, k)
-    gwl, gbl = new(need_w_last, cin * cout, k), new(need_b_last and b_last is not None, cin * cout)
-    groot, gbias = new(need_root and root is not None, cin, cout), new(need_bias, cout)
-    ws = _alloc_ws(_hidden_any_ws_bytes(lib.gpde_nnconv_bwd_hidden_any_workspace_bytes, n, e, cin, cout, k, dev) if ws_bytes is None else int(ws_bytes), dev)
-    srp, ssl = csr.src_order if (need_x and e > 0) else (None, None)
-    p = lambda t: None if t is None else t.data_ptr()
-    with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_bwd_hidden_any(x_c.data_ptr(), n, hid.data_ptr(), e, k, csr.rowptr.data_ptr(), csr.src.data_ptr(), wl.data_ptr(),
-                                            p(bl), p(root_c), _AGGR[aggr], cin, cout, grad_out.data_ptr(), p(gx), gh.data_ptr(), p(gwl), p(gbl),
-                                            p(groot), p(gbias), p(srp), p(ssl), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "gpde_nnconv_bwd_hidden_any")
-    _lib.n_native_calls += 1
-    return gx, gh, gwl, gbl, groot, gbias
-
-
-# ... between two node sets (include/gpde.h gpde_nnconv_*_edgeweights_bip / gpde_nnconv_*_hidden_bip): the any-width operators on a
-# RECTANGULAR graph - x_src [n_src, in_src] gathered by the edges, x_dst [n_dst, in_dst] (or None) in the root term, out [n_dst, out]
-def _bip_args(x_src, x_dst, csr: Csr, root, per_edge, per_edge_name: str):
-    """Shapes of a rectangular call checked; (in_src, in_dst, out_channels or None).  `per_edge`: W_e [E, in_src * out] or H [E, K]."""
-    n_src, n_dst, e = csr.n_src, csr.n_nodes, csr.n_edges
-    if x_src.dtype != torch.float32 or x_src.dim() != 2 or x_src.size(0) != n_src or x_src.size(1) < 1:
-        raise ValueError(f"x_src must be float32 [{n_src}, in_src], got {x_src.dtype} {tuple(x_src.shape)}")
-    dev, cin = x_src.device, int(x_src.size(1))
-    if x_dst is not None and (x_dst.dtype != torch.float32 or x_dst.dim() != 2 or x_dst.size(0) != n_dst or x_dst.size(1) < 1 or x_dst.device != dev):
-        raise ValueError(f"x_dst must be float32 [{n_dst}, in_dst] on {dev}, got {x_dst.dtype} {tuple(x_dst.shape)}")
-    cind = cin if x_dst is None else int(x_dst.size(1))
-    if per_edge.dtype != torch.float32 or per_edge.dim() != 2 or per_edge.size(0) != e or per_edge.size(1) < 1 or per_edge.device != dev:
-        raise ValueError(f"{per_edge_name} must be float32 [{e}, .] on {dev}, got {per_edge.dtype} {tuple(per_edge.shape)}")
-    if root is not None and x_dst is None:
-        raise ValueError("root without x_dst: the root term is x_dst . root (pass root=None for a call without destination features)")
-    if root is not None and (root.dtype != torch.float32 or root.dim() != 2 or root.size(0) != cind or root.device != dev):
-        raise ValueError(f"root must be float32 [{cind}, out_channels] on {dev}, got {root.dtype} {tuple(root.shape)}")
-    return cin, cind
-
-
-def _bip_check_widths(cin: int, cind: int, cout: int):
-    if not (width_supported(cin, cout) and width_supported(cind, cout)):
-        raise NotImplementedError(f"(in_src {cin}, in_dst {cind}) -> out_channels {cout}: the native operator is built for widths 1 .. {ANY_MAX_WIDTH}")
+    g = _any_bwd_hidden(x, _ONE_SET, csr, hidden, w_last, b_last, root, aggr, grad_out, need_x, False, need_w_last, need_b_last, need_root,
+                        need_bias, ws_bytes)
+    return (g[0], *g[2:])
 
 
 def nnconv_forward_edgeweights_bip_raw(x_src, x_dst, csr: Csr, edge_weights, root, bias, aggr: str, residual=None, relu: bool = False) -> torch.Tensor:
     """gpde_nnconv_fwd_edgeweights_bip: the operator between two node sets given the per-edge weights [E, in_src * out] (CSR slot
     order) - gather from x_src, message, add / mean / max over the n_dst destinations, + x_dst . root + bias (+ residual
     [n_dst, out], ReLU) in one launch.  `x_dst` None: no root term (root must be None)."""
-    lib = _lib.lib()
-    _require_cuda(x_src, "x_src")
-    if aggr not in _AGGR_WE:
-        raise NotImplementedError(f"aggr={aggr!r}")
-    xs = x_src.detach().contiguous()
-    xd = None if x_dst is None else x_dst.detach().contiguous()
-    we = edge_weights.detach().contiguous()     # (a dense tensor is passed as it is, aligned or not: the dword route stays)
-    root_c = None if root is None else root.detach().contiguous()
-    bias_c = None if bias is None else bias.detach().contiguous()
-    cin, cind = _bip_args(xs, xd, csr, root_c, we, "edge_weights")
-    if we.size(1) % cin != 0:
-        raise ValueError(f"edge_weights must be [{csr.n_edges}, {cin} * out_channels], got {tuple(we.shape)}")
-    cout = int(we.size(1)) // cin
-    _bip_check_widths(cin, cind, cout)
-    n_src, n_dst, e, dev = csr.n_src, csr.n_nodes, csr.n_edges, xs.device
-    if root_c is not None and root_c.size(1) != cout:
-        raise ValueError(f"root must be [{cind},{cout}], got {tuple(root_c.shape)}")
-    if bias_c is not None and (bias_c.dtype != torch.float32 or tuple(bias_c.shape) != (cout,) or bias_c.device != dev):
-        raise ValueError(f"bias must be float32 [{cout}] on {dev}, got {bias_c.dtype} {tuple(bias_c.shape)}")
-    res = None
-    if residual is not None:
-        _require_cuda(residual, "residual")
-        if residual.dtype != torch.float32 or tuple(residual.shape) != (n_dst, cout) or residual.device != dev:
-            raise ValueError(f"residual must be float32 [{n_dst},{cout}] on {dev}, got {residual.dtype} {tuple(residual.shape)}")
-        res = residual.detach().contiguous()
-    out = torch.empty(n_dst, cout, dtype=torch.float32, device=dev)
-    p = lambda t: None if t is None else t.data_ptr()
-    with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_fwd_edgeweights_bip(xs.data_ptr(), n_src, p(xd), n_dst, we.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(),
-                                                 p(root_c), p(bias_c), p(res), 1 if relu else 0, _AGGR_WE[aggr], cin, cind, cout,
-                                                 out.data_ptr(), _stream_ptr(dev))
-    _lib.check(rc, "gpde_nnconv_fwd_edgeweights_bip")
-    _lib.n_native_calls += 1
-    return out
+    return _any_fwd_edgeweights(x_src, x_dst, csr, edge_weights, root, bias, aggr, residual, relu)
 
 
 def nnconv_backward_edgeweights_bip_raw(x_src, x_dst, csr: Csr, edge_weights, root, aggr: str, grad_out, need_x_src: bool = True,
@@ -1779,82 +1782,14 @@ def nnconv_backward_edgeweights_bip_raw(x_src, x_dst, csr: Csr, edge_weights, ro
     """gpde_nnconv_bwd_edgeweights_bip ('add' / 'mean').  Returns (grad_x_src [n_src, in_src], grad_x_dst [n_dst, in_dst],
     grad_edge_weights [E, in_src * out], grad_root [in_dst, out], grad_bias [out]); an output that is not needed or has no input
     (x_dst / root None) is None."""
-    lib = _lib.lib()
-    for t, nm in ((x_src, "x_src"), (edge_weights, "edge_weights"), (grad_out, "grad_out")):
-        _require_cuda(t, nm)
-    if aggr not in _AGGR:
-        raise NotImplementedError(f"aggr={aggr!r}: the gradient of the per-edge weight operator is built for 'add' and 'mean'")
-    xs = x_src.detach().contiguous()
-    xd = None if x_dst is None else x_dst.detach().contiguous()
-    we = edge_weights.detach().contiguous()     # (a dense tensor is passed as it is, aligned or not: the dword route stays)
-    root_c = None if root is None else root.detach().contiguous()
-    cin, cind = _bip_args(xs, xd, csr, root_c, we, "edge_weights")
-    if we.size(1) % cin != 0:
-        raise ValueError(f"edge_weights must be [{csr.n_edges}, {cin} * out_channels], got {tuple(we.shape)}")
-    cout = int(we.size(1)) // cin
-    _bip_check_widths(cin, cind, cout)
-    n_src, n_dst, e, dev = csr.n_src, csr.n_nodes, csr.n_edges, xs.device
-    grad_out = grad_out.detach().contiguous().float()
-    if tuple(grad_out.shape) != (n_dst, cout):
-        raise ValueError(f"grad_out must be [{n_dst},{cout}], got {tuple(grad_out.shape)}")
-    new = lambda want, *shape: torch.empty(*shape, dtype=torch.float32, device=dev) if want else None
-    gxs, gxd = new(need_x_src, n_src, cin), new(need_x_dst and xd is not None, n_dst, cind)
-    gwe = new(True, e, cin * cout)
-    groot, gbias = new(need_root and root is not None, cind, cout), new(need_bias, cout)
-    ws = _alloc_ws(int(lib.gpde_nnconv_bwd_edgeweights_bip_workspace_bytes(n_src, n_dst, e, cin, cind, cout)), dev)
-    srp, ssl = csr.src_order if (need_x_src and e > 0) else (None, None)
-    p = lambda t: None if t is None else t.data_ptr()
-    with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_bwd_edgeweights_bip(xs.data_ptr(), n_src, p(xd), n_dst, we.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(),
-                                                 p(srp), p(ssl), p(root_c), _AGGR[aggr], cin, cind, cout, grad_out.data_ptr(), p(gxs), p(gxd),
-                                                 gwe.data_ptr(), p(groot), p(gbias), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "gpde_nnconv_bwd_edgeweights_bip")
-    _lib.n_native_calls += 1
-    return gxs, gxd, gwe, groot, gbias
-
-
-def _hidden_bip_args(xs, xd, csr: Csr, hid, wl, bl, root_c):
-    cin, cind = _bip_args(xs, xd, csr, root_c, hid, "hidden")
-    k, dev = int(hid.size(1)), xs.device
-    if wl.dtype != torch.float32 or wl.dim() != 2 or wl.size(1) != k or wl.size(0) % cin != 0 or wl.size(0) == 0 or wl.device != dev:
-        raise ValueError(f"w_last must be float32 [{cin} * out_channels, {k}] on {dev}, got {wl.dtype} {tuple(wl.shape)}")
-    cout = int(wl.size(0)) // cin
-    if bl is not None and (bl.dtype != torch.float32 or tuple(bl.shape) != (cin * cout,) or bl.device != dev):
-        raise ValueError(f"b_last must be float32 [{cin * cout}] on {dev}, got {bl.dtype} {tuple(bl.shape)}")
-    if root_c is not None and root_c.size(1) != cout:
-        raise ValueError(f"root must be [{cind},{cout}], got {tuple(root_c.shape)}")
-    _bip_check_widths(cin, cind, cout)
-    if k > ANY_MAX_HIDDEN:
-        raise NotImplementedError(f"last hidden width {k}: the re-associated any-width operator is built for 1 .. {ANY_MAX_HIDDEN}")
-    return cin, cind, cout, k
+    return _any_bwd_edgeweights(x_src, x_dst, csr, edge_weights, root, aggr, grad_out, need_x_src, need_x_dst, need_root, need_bias)
 
 
 def nnconv_forward_hidden_bip_raw(x_src, x_dst, csr: Csr, hidden, w_last, b_last, root, bias, aggr: str, ws_bytes: Optional[int] = None) -> torch.Tensor:
     """gpde_nnconv_fwd_hidden_bip: the re-associated operator between two node sets given the last hidden activations [E, K] (CSR
     slot order) and the last Linear (w_last [in_src * out, K], b_last) - Z' per destination, last Linear per destination,
     + x_dst . root + bias.  'add' / 'mean'."""
-    lib = _lib.lib()
-    for t, nm in ((x_src, "x_src"), (hidden, "hidden"), (w_last, "w_last")):
-        _require_cuda(t, nm)
-    if aggr not in _AGGR:
-        raise NotImplementedError(f"aggr={aggr!r}: the re-associated operator is built for 'add' and 'mean'")
-    xs, hid, wl = x_src.detach().contiguous(), hidden.detach().contiguous(), w_last.detach().contiguous()
-    xd, bl, root_c, bias_c = (None if t is None else t.detach().contiguous() for t in (x_dst, b_last, root, bias))
-    cin, cind, cout, k = _hidden_bip_args(xs, xd, csr, hid, wl, bl, root_c)
-    n_src, n_dst, e, dev = csr.n_src, csr.n_nodes, csr.n_edges, xs.device
-    if bias_c is not None and (bias_c.dtype != torch.float32 or tuple(bias_c.shape) != (cout,) or bias_c.device != dev):
-        raise ValueError(f"bias must be float32 [{cout}] on {dev}, got {bias_c.dtype} {tuple(bias_c.shape)}")
-    query = lambda n, ee, ci, co, kk: lib.gpde_nnconv_fwd_hidden_bip_workspace_bytes(n, ee, ci, co, kk)
-    ws = _alloc_ws(_hidden_any_ws_bytes(query, n_dst, e, cin, cout, k, dev) if ws_bytes is None else int(ws_bytes), dev)
-    out = torch.empty(n_dst, cout, dtype=torch.float32, device=dev)
-    p = lambda t: None if t is None else t.data_ptr()
-    with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_fwd_hidden_bip(xs.data_ptr(), n_src, p(xd), n_dst, hid.data_ptr(), e, k, csr.rowptr.data_ptr(), csr.src.data_ptr(),
-                                            wl.data_ptr(), p(bl), p(root_c), p(bias_c), _AGGR[aggr], cin, cind, cout, out.data_ptr(),
-                                            ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "gpde_nnconv_fwd_hidden_bip")
-    _lib.n_native_calls += 1
-    return out
+    return _any_fwd_hidden(x_src, x_dst, csr, hidden, w_last, b_last, root, bias, aggr, ws_bytes)
 
 
 def nnconv_backward_hidden_bip_raw(x_src, x_dst, csr: Csr, hidden, w_last, b_last, root, aggr: str, grad_out, need_x_src: bool = True,
@@ -1862,34 +1797,8 @@ def nnconv_backward_hidden_bip_raw(x_src, x_dst, csr: Csr, hidden, w_last, b_las
                                    need_bias: bool = True, ws_bytes: Optional[int] = None):
     """gpde_nnconv_bwd_hidden_bip.  Returns (grad_x_src, grad_x_dst, grad_hidden [E, K], grad_w_last, grad_b_last, grad_root
     [in_dst, out], grad_bias); an output that is not needed or has no input is None."""
-    lib = _lib.lib()
-    for t, nm in ((x_src, "x_src"), (hidden, "hidden"), (w_last, "w_last"), (grad_out, "grad_out")):
-        _require_cuda(t, nm)
-    if aggr not in _AGGR:
-        raise NotImplementedError(f"aggr={aggr!r}: the re-associated operator is built for 'add' and 'mean'")
-    xs, hid, wl = x_src.detach().contiguous(), hidden.detach().contiguous(), w_last.detach().contiguous()
-    xd, bl, root_c = (None if t is None else t.detach().contiguous() for t in (x_dst, b_last, root))
-    cin, cind, cout, k = _hidden_bip_args(xs, xd, csr, hid, wl, bl, root_c)
-    n_src, n_dst, e, dev = csr.n_src, csr.n_nodes, csr.n_edges, xs.device
-    grad_out = grad_out.detach().contiguous().float()
-    if tuple(grad_out.shape) != (n_dst, cout):
-        raise ValueError(f"grad_out must be [{n_dst},{cout}], got {tuple(grad_out.shape)}")
-    new = lambda want, *shape: torch.empty(*shape, dtype=torch.float32, device=dev) if want else None
-    gxs, gxd, gh = new(need_x_src, n_src, cin), new(need_x_dst and xd is not None, n_dst, cind), new(True, e, k)
-    gwl, gbl = new(need_w_last, cin * cout, k), new(need_b_last and b_last is not None, cin * cout)
-    groot, gbias = new(need_root and root is not None, cind, cout), new(need_bias, cout)
-    query = lambda n, ee, ci, co, kk: lib.gpde_nnconv_bwd_hidden_bip_workspace_bytes(n, ee, ci, cind, co, kk)
-    ws = _alloc_ws(_hidden_any_ws_bytes(query, n_dst, e, cin, cout, k, dev) if ws_bytes is None else int(ws_bytes), dev)
-    srp, ssl = csr.src_order if (need_x_src and e > 0) else (None, None)
-    p = lambda t: None if t is None else t.data_ptr()
-    with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_bwd_hidden_bip(xs.data_ptr(), n_src, p(xd), n_dst, hid.data_ptr(), e, k, csr.rowptr.data_ptr(), csr.src.data_ptr(),
-                                            wl.data_ptr(), p(bl), p(root_c), _AGGR[aggr], cin, cind, cout, grad_out.data_ptr(), p(gxs), p(gxd),
-                                            gh.data_ptr(), p(gwl), p(gbl), p(groot), p(gbias), p(srp), p(ssl), ws.data_ptr(), ws.numel(),
-                                            _stream_ptr(dev))
-    _lib.check(rc, "gpde_nnconv_bwd_hidden_bip")
-    _lib.n_native_calls += 1
-    return gxs, gxd, gh, gwl, gbl, groot, gbias
+    return _any_bwd_hidden(x_src, x_dst, csr, hidden, w_last, b_last, root, aggr, grad_out, need_x_src, need_x_dst, need_w_last, need_b_last,
+                           need_root, need_bias, ws_bytes)
 
 
 def edge_weights_backward_raw(grad_we: torch.Tensor, hidden: torch.Tensor, dims: Sequence[int], w_last: torch.Tensor,
@@ -1951,13 +1860,12 @@ def nnconv_forward_mixed_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor,
         nas = edge_attr.c_struct()
     else:
         edge_attr, perm = attr_in_slot_order(csr, _dense16(edge_attr.detach()))
-    p = lambda t: None if t is None else t.data_ptr()
     with torch.cuda.device(x.device):
         rc = lib.gpde_nnconv_fwd_mixed_keepz(x.data_ptr(), n, None if is_na else edge_attr.data_ptr(), None if nas is None else ctypes.byref(nas),
-                                             p(hidden) if hidden_nodes > 0 else None, p(hmax), max(int(hidden_nodes), 0), e,
+                                             _ptr(hidden) if hidden_nodes > 0 else None, _ptr(hmax), max(int(hidden_nodes), 0), e,
                                              csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(),
-                                             p(perm), len(pm.dims) - 1, pm.dims_c, pm.packed.data_ptr(),
-                                             p(root_c), p(bias_c), _AGGR[aggr], _PRECISION[precision], p(z_keep),
+                                             _ptr(perm), len(pm.dims) - 1, pm.dims_c, pm.packed.data_ptr(),
+                                             _ptr(root_c), _ptr(bias_c), _AGGR[aggr], _PRECISION[precision], _ptr(z_keep),
                                              out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(x.device))
     _lib.check(rc, "gpde_nnconv_fwd_mixed_keepz")
     _lib.n_native_calls += 1
@@ -1997,18 +1905,17 @@ def nnconv_backward_hidden_raw(x: torch.Tensor, csr: Csr, hidden: torch.Tensor, 
     if nbytes == 0:
         _lib.check(-2, "gpde_nnconv_bwd_workspace_bytes")
     ws = _alloc_ws(nbytes, dev)
-    p = lambda t: None if t is None else t.data_ptr()
     srp, ssl = csr.src_order
     P_ = ctypes.c_void_p                                   # the hidden form: the arrays carry their LAST entries only
     Wa = (P_ * nl)(*([None] * (nl - 1) + [w_last.data_ptr()]))
-    Ba = (P_ * nl)(*([None] * (nl - 1) + [p(b_c)]))
+    Ba = (P_ * nl)(*([None] * (nl - 1) + [_ptr(b_c)]))
     gWa = (P_ * nl)(*([None] * (nl - 1) + [gw.data_ptr()]))
-    gBa = (P_ * nl)(*([None] * (nl - 1) + [p(gb)]))
+    gBa = (P_ * nl)(*([None] * (nl - 1) + [_ptr(gb)]))
     with torch.cuda.device(dev):
         rc = lib.gpde_nnconv_bwd(x.data_ptr(), n, None, None, hidden.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(),
-                                 csr.dst.data_ptr(), None, csr.rowptr_host.data_ptr(), p(srp), p(ssl), nl, dims_c, Wa, Ba,
-                                 p(root_c), _AGGR[aggr], grad_out.data_ptr(), p(z_saved), gx.data_ptr(), gh.data_ptr(), None,
-                                 gWa, gBa, p(groot), p(gbias), _lib.GPDE_BWD_ACCUMULATE_GRAD_HIDDEN if accumulate else 0,
+                                 csr.dst.data_ptr(), None, csr.rowptr_host.data_ptr(), _ptr(srp), _ptr(ssl), nl, dims_c, Wa, Ba,
+                                 _ptr(root_c), _AGGR[aggr], grad_out.data_ptr(), _ptr(z_saved), gx.data_ptr(), gh.data_ptr(), None,
+                                 gWa, gBa, _ptr(groot), _ptr(gbias), _lib.GPDE_BWD_ACCUMULATE_GRAD_HIDDEN if accumulate else 0,
                                  ws.data_ptr(), ws.numel(), _stream_ptr(dev))
     _lib.check(rc, "gpde_nnconv_bwd (hidden given)")
     _lib.n_native_calls += 1
