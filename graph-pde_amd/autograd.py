@@ -529,3 +529,31 @@ class GCNFunction(torch.autograd.Function):
         if ctx.has_bias and need[2]:
             gb = grad_out.sum(0)
         return gx, gw, gb, None, None
+
+
+class DiagConvFunction(torch.autograd.Function):
+    """The DIAGONAL-kernel operator (gpde_diagconv_fwd: gather, x_j (.) k_e, add / mean, update() in one streaming kernel),
+    differentiable in x_src, x_dst, the per-edge kernel k [E, w] (CSR slot order), root [in_dst, w] and bias (gpde_diagconv_bwd).
+    `x_dst`: as WeConvAnyFunction takes it - a tensor, None (no root term) or ops._ONE_SET (one node set: grad_x_src then holds the
+    source sum and g . root^T, added in the library).  k is the caller's own tensor (`nn(pseudo)`, a Gaussian, ...): dL/dk flows
+    on into whatever produced it by ordinary autograd."""
+
+    @staticmethod
+    def forward(ctx, x_src, x_dst, k, csr, root, bias, aggr):
+        root = _root_term(x_dst, root)
+        ctx.one, ctx.has_dst = x_dst is ops._ONE_SET, torch.is_tensor(x_dst)
+        xd = x_dst.detach() if ctx.has_dst else x_dst
+        out = ops.diagconv_forward_raw(x_src.detach(), xd, csr, k.detach(), root, bias, aggr)
+        ctx.csr, ctx.aggr, ctx.has_bias, ctx.has_root = csr, aggr, bias is not None, root is not None
+        ctx.save_for_backward(x_src, x_dst if ctx.has_dst else None, k, root)
+        return out
+
+    @staticmethod
+    @once_differentiable        # the native backward is not itself differentiable: create_graph=True raises
+    def backward(ctx, grad_out):
+        x_src, x_dst, k, root = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gxs, gxd, gk, groot, gbias = ops.diagconv_backward_raw(
+            x_src, ops._ONE_SET if ctx.one else x_dst, ctx.csr, k, root, ctx.aggr, grad_out, need_x_src=need[0],
+            need_x_dst=ctx.has_dst and need[1], need_root=ctx.has_root and need[4], need_bias=ctx.has_bias and need[5])
+        return gxs, gxd, (gk if need[2] else None), None, groot, gbias, None

@@ -733,9 +733,8 @@ class NNConv_old(MessagePassing):
 
 class NNConv(NNConv_old):
     """`torch_geometric.nn.NNConv` as the MGKN scripts use it (full edge kernel, same math as
-    NNConv_old).  Note: the dead-code diagonal variant that
-    graph-neural-operator/nn_conv.py:8-96 also calls `NNConv` is never instantiated by any script
-    and is not built."""
+    NNConv_old).  Note: the diagonal variant that
+    graph-neural-operator/nn_conv.py:8-96 also calls `NNConv` is `graph_pde_amd.NNConvDiag` (diag_conv.py)."""
     pass
 
 

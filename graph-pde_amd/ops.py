@@ -2773,3 +2773,141 @@ def gcn_forward_raw(x: torch.Tensor, norm: GcnNorm, weight: Optional[torch.Tenso
         return (out, agg) if agg_out else out
     out, agg = _gcn_call(x_c, csr, coef, norm.self_coef, w_c, b_c, cin, cout, relu, agg_out)
     return (out, agg) if agg_out else out
+
+
+# ----------------------------------------------------------------------------------------------
+# the diagonal-kernel operator (include/gpde.h gpde_diagconv_*; csrc/gpde_diagconv.hip): k [E, w] per edge, message x_j (.) k_e
+# ----------------------------------------------------------------------------------------------
+_DIAG_PLAN_KEYS = ("V", "LC", "ES", "pass_edges", "chain_edges", "lanes", "per_lane", "consecutive", "active_lanes", "lds_bytes")
+
+
+def diag_plan(w: int, aligned: bool = True, aggr: str = "add") -> dict:
+    """gpde_diagconv_plan: the lane tiling gpde_diagconv.hip runs at width `w` - V (floats per access), LC (column lanes), ES (edge
+    slots per wave), the in-edges of a pass (in flight before the first FMA) and of a chain (the first level of the two-level row
+    sum), the lanes that hold a slot, channels per column lane, whether a lane's channels are consecutive (w % 4 == 0), the lanes
+    that own a channel, LDS bytes.  `aligned`: every buffer of the call is 16-byte aligned (else V = 1 at every width; the tiling
+    and the summation order do not change).  Host arithmetic, no device."""
+    if aggr not in _AGGR_WE:
+        raise NotImplementedError(f"aggr={aggr!r}")
+    out = (ctypes.c_int32 * len(_DIAG_PLAN_KEYS))()
+    _lib.check(_lib.lib().gpde_diagconv_plan(int(w), 1 if aligned else 0, _AGGR_WE[aggr], out), "gpde_diagconv_plan")
+    return dict(zip(_DIAG_PLAN_KEYS, (int(v) for v in out)))
+
+
+def _diag_args(x_src, x_dst, csr: Csr, edge_kernel, root):
+    """The node tables, k [E, w] and root of a diagonal call checked; (w, in_dst).  `x_dst`: _ONE_SET, a tensor or None, as
+    `_any_args` takes it."""
+    one = x_dst is _ONE_SET
+    n_dst, e = csr.n_nodes, csr.n_edges
+    n_src = n_dst if one else csr.n_src
+    if one and csr.n_src != n_dst:
+        raise ValueError(f"a call on one node set needs a square graph, got {csr.n_src} sources and {n_dst} destinations")
+    if x_src.dtype != torch.float32 or x_src.dim() != 2 or x_src.size(0) != n_src or x_src.size(1) < 1:
+        raise ValueError(f"{_x_name(x_dst)} must be float32 [{n_src}, width], got {x_src.dtype} {tuple(x_src.shape)}")
+    dev, w = x_src.device, int(x_src.size(1))
+    if not one and x_dst is not None and (x_dst.dtype != torch.float32 or x_dst.dim() != 2 or x_dst.size(0) != n_dst or x_dst.size(1) < 1 or
+                                          x_dst.device != dev):
+        raise ValueError(f"x_dst must be float32 [{n_dst}, in_dst] on {dev}, got {x_dst.dtype} {tuple(x_dst.shape)}")
+    cind = w if one or x_dst is None else int(x_dst.size(1))
+    if edge_kernel.dtype != torch.float32 or tuple(edge_kernel.shape) != (e, w) or edge_kernel.device != dev:
+        raise ValueError(f"edge_kernel must be float32 [{e},{w}] (one value per edge and channel of {_x_name(x_dst)}) on {dev}, got "
+                         f"{edge_kernel.dtype} {tuple(edge_kernel.shape)}")
+    if root is not None and x_dst is None:
+        raise ValueError("root without x_dst: the root term is x_dst . root (pass root=None for a call without destination features)")
+    if root is not None and (root.dtype != torch.float32 or tuple(root.shape) != (cind, w) or root.device != dev):
+        raise ValueError(f"root must be float32 [{cind},{w}] on {dev}, got {root.dtype} {tuple(root.shape)}")
+    if csr.rowptr.device != dev:
+        raise ValueError(f"the graph lives on {csr.rowptr.device}, {_x_name(x_dst)} on {dev}")
+    if not (width_supported(w, w) and width_supported(cind, w)):
+        raise NotImplementedError(f"width {w} (in_dst {cind}): the native diagonal operator is built for widths 1 .. {ANY_MAX_WIDTH}")
+    return w, cind
+
+
+def _diag_tables(xs, xd, csr: Csr):
+    """(x_src ptr, n_src, x_dst ptr, n_dst) of a native call: one node set hands one table twice."""
+    if xd is _ONE_SET:
+        return xs.data_ptr(), csr.n_nodes, xs.data_ptr(), csr.n_nodes
+    return xs.data_ptr(), csr.n_src, _ptr(xd), csr.n_nodes
+
+
+def diagconv_forward_raw(x_src, x_dst, csr: Csr, edge_kernel, root, bias, aggr: str, residual=None, relu: bool = False):
+    """gpde_diagconv_fwd: out_i = aggr_{e: j -> i} x_src[j] * edge_kernel[e] + x_dst[i] . root + bias (+ residual, ReLU) in one
+    launch.  x_src [n_src, w]; `x_dst` ops._ONE_SET (one node set: x_src is the table of the root term too), a tensor [n_dst, in_dst]
+    or None (no root term: root must be None); edge_kernel [E, w] in CSR slot order; root [in_dst, w], bias [w], residual
+    [n_dst, w] or None; aggr add / mean / max.  Operands are made dense, nothing more: one that starts off a 16-byte boundary takes
+    the dword route (the same bits).  The result is a fresh tensor: this wrapper takes no caller-given output (DESIGN.md "Operand
+    layouts" holds every public `out=` to 16-byte alignment, and this kernel's dword route exists for buffers that are not)."""
+    return _diagconv_forward(x_src, x_dst, csr, edge_kernel, root, bias, aggr, residual, relu, None)
+
+
+def _diagconv_forward(x_src, x_dst, csr: Csr, edge_kernel, root, bias, aggr: str, residual, relu: bool, out):
+    """The body of diagconv_forward_raw.  `out`: None, or the float32 [n_dst, w] tensor to write - dense, any 4-byte alignment (off a
+    16-byte boundary the kernel takes its dword route), not x_src's or residual's memory; validated here (the tests reach the dword
+    stores through it)."""
+    _require_cuda(x_src, _x_name(x_dst))
+    if aggr not in _AGGR_WE:
+        raise NotImplementedError(f"aggr={aggr!r}")
+    xs, xd, k, root_c = _dense(x_src), _dense(x_dst), _dense(edge_kernel), _dense(root)
+    w, cind = _diag_args(xs, xd, csr, k, root_c)
+    n_dst, dev = csr.n_nodes, xs.device
+    bias_c = _any_f32(bias, "bias", (w,), dev)
+    res = _any_f32(residual, "residual", (n_dst, w), dev)
+    if out is None:
+        out = torch.empty(n_dst, w, dtype=torch.float32, device=dev)
+    else:
+        if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (n_dst, w) or out.device != dev:
+            raise ValueError(f"out must be float32 [{n_dst},{w}] on {dev}, got "
+                             f"{(out.dtype, tuple(out.shape), out.device) if torch.is_tensor(out) else type(out).__name__}")
+        if not out.is_contiguous():
+            raise ValueError(f"out is written by the kernel in place: it must be contiguous, got strides {tuple(out.stride())} (views are "
+                             "not copied)")
+        lo, hi = out.data_ptr(), out.data_ptr() + out.numel() * 4
+        for t, nm in ((xs, _x_name(x_dst)), (res, "residual")):
+            if t is not None and t.numel() and lo < t.data_ptr() + t.numel() * 4 and t.data_ptr() < hi:
+                raise ValueError(f"out shares memory with {nm}: other waves still read those rows")
+    with torch.cuda.device(dev):
+        rc = _lib.lib().gpde_diagconv_fwd(*_diag_tables(xs, xd, csr), k.data_ptr(), csr.n_edges, csr.rowptr.data_ptr(), csr.src.data_ptr(),
+                                          _ptr(root_c), _ptr(bias_c), _ptr(res), 1 if relu else 0, _AGGR_WE[aggr], w, cind, out.data_ptr(),
+                                          _stream_ptr(dev))
+    _lib.check(rc, "gpde_diagconv_fwd")
+    _lib.n_native_calls += 1
+    return out
+
+
+def diagconv_backward_raw(x_src, x_dst, csr: Csr, edge_kernel, root, aggr: str, grad_out, need_x_src: bool = True, need_x_dst: bool = True,
+                          need_root: bool = True, need_bias: bool = True):
+    """gpde_diagconv_bwd ('add' / 'mean').  Returns (grad_x_src [n_src, w], grad_x_dst [n_dst, in_dst], grad_edge_kernel [E, w],
+    grad_root [in_dst, w], grad_bias [w]); an output that is not needed or has no input (x_dst / root None) is None.  One node set
+    (`x_dst` ops._ONE_SET): grad_x_dst is None and grad_x_src holds both terms, the source sum and g . root^T.  grad_x_src is summed
+    by one owner per source in ascending slot order (csr.src_order), never by atomics."""
+    lib = _lib.lib()
+    for t, nm in ((x_src, _x_name(x_dst)), (edge_kernel, "edge_kernel"), (grad_out, "grad_out")):
+        _require_cuda(t, nm)
+    if aggr not in _AGGR:
+        raise NotImplementedError(f"aggr={aggr!r}: the gradient of the diagonal operator is built for 'add' and 'mean'")
+    one = x_dst is _ONE_SET
+    xs, xd, k, root_c = _dense(x_src), _dense(x_dst), _dense(edge_kernel), _dense(root)
+    w, cind = _diag_args(xs, xd, csr, k, root_c)
+    n_src, n_dst, e, dev = int(xs.size(0)), csr.n_nodes, csr.n_edges, xs.device
+    grad_out = _any_grad_out(grad_out, n_dst, w)
+    new = lambda want, *shape: torch.empty(*shape, dtype=torch.float32, device=dev) if want else None
+    # (two node sets given the SAME memory twice: the library reads "one table twice and no grad_x_dst" as one node set and would
+    # add g . root^T to grad_x_src - such a call always takes its grad_x_dst, needed or not)
+    same_table = not one and xd is not None and xd.data_ptr() == xs.data_ptr() and n_src == n_dst and cind == w
+    gxs, gxd = new(need_x_src, n_src, w), new((need_x_dst or same_table) and not one and xd is not None, n_dst, cind)
+    gk = new(True, e, w)
+    groot, gbias = new(need_root and root is not None, cind, w), new(need_bias, w)
+    ws = _alloc_ws(int(lib.gpde_diagconv_bwd_workspace_bytes(n_dst, w, cind)), dev)
+    if need_x_src and e > 0:
+        if DX_MODE == "atomic":
+            raise NotImplementedError("GPDE_BWD_DX=atomic: the diagonal operator sums grad_x per source in slot order only")
+        srp, ssl = csr.src_order
+    else:
+        srp, ssl = None, None
+    with torch.cuda.device(dev):
+        rc = lib.gpde_diagconv_bwd(*_diag_tables(xs, xd, csr), k.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(),
+                                   _ptr(srp), _ptr(ssl), _ptr(root_c), _AGGR[aggr], w, cind, grad_out.data_ptr(), _ptr(gxs), _ptr(gxd),
+                                   gk.data_ptr(), _ptr(groot), _ptr(gbias), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+    _lib.check(rc, "gpde_diagconv_bwd")
+    _lib.n_native_calls += 1
+    return gxs, (gxd if need_x_dst else None), gk, groot, gbias

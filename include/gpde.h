@@ -763,6 +763,45 @@ GPDE_API int gpde_gcn_fwd(const float* x, int64_t n_nodes, int64_t n_edges, cons
                  uint32_t flags, float* out, float* agg_out, void* stream);
 GPDE_API int gpde_gcn_plan(int in_channels, int out_channels, int32_t* out);
 
+/* The DIAGONAL-kernel operator (gpde_diagconv.hip): the reference's `NNConv` / `NNConv_Gaussian` (nn_conv.py:8-96, 99-194), whose
+ * kernel emits `width` values per edge that diag_embed makes a diagonal width x width matrix - the message is x_j (.) k_e:
+ *     out_i = aggr_{e: j -> i} x_src[j] (.) k_e  +  x_dst[i] . root + bias  (+ residual, ReLU)
+ *   x_src [n_src][width] is what the edges gather, k [E][width] fp32 in CSR slot order, x_dst [n_dst][in_dst] (nullable: no root
+ *   term) and root [in_dst][width] (nullable) enter the root term only, bias [width] and residual [n_dst][width] nullable (residual
+ *   must not be out), out [n_dst][width].  A call on ONE node set hands one table twice (x_dst = x_src, n_dst = n_src, in_dst =
+ *   width).  aggr add / mean / max in the forward (mean divides by clamp(count, 1); a destination without in-edges aggregates to 0,
+ *   also for max), add / mean in the backward (GPDE_AGGR_MAX: GPDE_EUNSUPPORTED - its gradient is composed by the caller).
+ *   gpde_diagconv_bwd   (outputs overwritten, NULL skips the term)
+ *       grad_k [E][width]            = x_j (.) gT_i, gT_i = g_i (/ clamp(deg_i, 1) for mean); needs src and x_src
+ *       grad_x_src [n_src][width]    = sum_{e: j ->} k_e (.) gT_dst(e), ONE owner per source in ascending slot order over src_rowptr /
+ *                                      src_slots (gpde_csr_source_order over n_src) - required with it when n_edges > 0, as are k
+ *                                      and dst [E] (the destination of each CSR slot); never atomics
+ *       grad_x_dst [n_dst][in_dst]   = g . root^T (0 without root).  One node set - x_dst == x_src (the same address), n_dst == n_src,
+ *                                      in_dst == width and grad_x_dst == NULL: that term is ADDED to grad_x_src instead
+ *       grad_root [in_dst][width]    = x_dst^T g,  grad_bias [width] = colsum g (ordered strips)
+ *       ws: gpde_diagconv_bwd_workspace_bytes(n_dst, width, in_dst) bytes (gT for mean, the strip partials).
+ *   gpde_diagconv_plan  HOST ONLY, from the function the launchers call: out[0..9] = V (floats per access: 4 when vec4 != 0 and
+ *       width % 4 == 0, else 1), LC (column lanes, a power of two), ES (edge slots per wave = 64 / LC), in-edges per pass (their
+ *       loads are in flight before the first FMA), in-edges per chain (first level of the two-level row sum), LC * ES, channels per
+ *       column lane, 1 when a lane's channels are consecutive (width % 4 == 0: 4 lc .. 4 lc + 3, read by one 16-byte or four dword
+ *       accesses) and 0 when strided by LC, lanes that own a channel, LDS bytes.  The tiling and the summation order depend on
+ *       width alone: an unaligned buffer changes the instructions (V), not the bits.
+ * Plain fp32 fmaf, no atomics, every sum in an order fixed by the graph: two calls give the same bits.  1 <= width, in_dst <=
+ * GPDE_WECONV_ANY_MAX_WIDTH, else GPDE_EUNSUPPORTED.  GPDE_EINVAL with a gpde_last_error() text, before any device call, for NULL
+ * required pointers, an unknown aggr, edges without sources or destinations, root without x_dst, residual == out and an out that
+ * overlaps x_src (other waves still gather those rows).  Zero nodes
+ * and zero edges are valid calls.  Additions to the ABI: GPDE_VERSION is unchanged. */
+GPDE_API int gpde_diagconv_plan(int width, int vec4, int aggr, int32_t* out);
+GPDE_API int gpde_diagconv_fwd(const float* x_src, int64_t n_src, const float* x_dst, int64_t n_dst, const float* k, int64_t n_edges,
+                      const int32_t* rowptr, const int32_t* src, const float* root, const float* bias, const float* residual,
+                      int relu, int aggr, int width, int in_dst, float* out, void* stream);
+GPDE_API size_t gpde_diagconv_bwd_workspace_bytes(int64_t n_dst, int width, int in_dst);
+GPDE_API int gpde_diagconv_bwd(const float* x_src, int64_t n_src, const float* x_dst, int64_t n_dst, const float* k, int64_t n_edges,
+                      const int32_t* rowptr, const int32_t* src, const int32_t* dst, const int32_t* src_rowptr,
+                      const int32_t* src_slots, const float* root, int aggr, int width, int in_dst, const float* grad_out,
+                      float* grad_x_src, float* grad_x_dst, float* grad_k, float* grad_root, float* grad_bias, void* ws,
+                      size_t ws_bytes, void* stream);
+
 /* HIP-event timing of the kernels launched by gpde_nnconv_fwd on the calling thread (used by
  * bench.py for the roofline figure; events are recorded on the same stream as the kernels).
  * gpde_profile_begin() arms it; gpde_profile_end_kinds() disarms it, SYNCHRONISES on the recorded
