@@ -326,52 +326,83 @@ namespace {
 // aggregation, the last Linear and update() run (gpde_nnconv_fwd_hidden)
 // `kt` != 0: edge_attr is a NODE table [n_nodes][kt] and slot d of an edge's attribute is
 // table[(sel[d] >> 8 ? dst : src)][sel[d] & 255] (gpde_nnconv_fwd_nodeattr)
-int fwd_impl(const float* x, int64_t n_nodes, const float* edge_attr, int64_t n_edges,
-             const int32_t* rowptr, const int32_t* src, const int32_t* dst, const int32_t* perm,
-             int n_layers, const int32_t* dims, const void* packed, const float* root,
-             const float* bias, int aggr, uint32_t flags, const float* hidden, float* out, void* ws,
-             size_t ws_bytes, hipStream_t stream, int kt = 0, const int* sel = nullptr,
-             const float* hidden_absmax = nullptr, int64_t hidden_nodes = -1, const float* residual = nullptr,
-             int relu_out = 0, float* z_keep = nullptr) {
+// The arguments of fwd_impl by name.  A default means "not given"; `fwd_common` fills what every entry point has.
+struct FwdArgs {
+    const float* x = nullptr;
+    int64_t n_nodes = 0, n_edges = 0;
+    const int32_t *rowptr = nullptr, *src = nullptr, *dst = nullptr;
+    int n_layers = 0;
+    const int32_t* dims = nullptr;
+    const void* packed = nullptr;
+    const float *root = nullptr, *bias = nullptr;
+    int aggr = 0;
+    float* out = nullptr;
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+    hipStream_t stream = nullptr;
+    // what an entry point may have
+    const float* edge_attr = nullptr;       // [n_edges][k0] read through `perm`, or the node table when kt != 0
+    const int32_t* perm = nullptr;
+    uint32_t flags = 0;
+    const float *hidden = nullptr, *hidden_absmax = nullptr;
+    int64_t hidden_nodes = -1;              // -1: `hidden` covers every edge
+    int kt = 0;                             // row stride of the node table
+    const int* sel = nullptr;
+    const float* residual = nullptr;
+    int relu_out = 0;
+    float* z_keep = nullptr;
+};
+
+FwdArgs fwd_common(const float* x, int64_t n_nodes, int64_t n_edges, const int32_t* rowptr, const int32_t* src, const int32_t* dst,
+                   int n_layers, const int32_t* dims, const void* packed, const float* root, const float* bias, int aggr,
+                   float* out, void* ws, size_t ws_bytes, void* stream) {
+    FwdArgs a;
+    a.x = x; a.n_nodes = n_nodes; a.n_edges = n_edges; a.rowptr = rowptr; a.src = src; a.dst = dst;
+    a.n_layers = n_layers; a.dims = dims; a.packed = packed; a.root = root; a.bias = bias; a.aggr = aggr;
+    a.out = out; a.ws = ws; a.ws_bytes = ws_bytes; a.stream = (hipStream_t)stream;
+    return a;
+}
+
+int fwd_impl(const FwdArgs& a) {
     // hidden_nodes in [0, n_nodes): MIXED call (gpde_nnconv_fwd_mixed_keepz) -- `hidden` covers the in-edges of
     // nodes [0, hidden_nodes) only (a graph whose H does not fit memory, e.g. 391 GB at the 241^2 graph);
     // those nodes aggregate from it, the others run the fused kernel on edge_attr
-    const bool mixed = hidden && hidden_nodes >= 0 && hidden_nodes < n_nodes;
-    if (aggr != GPDE_AGGR_ADD && aggr != GPDE_AGGR_MEAN) {
-        gpde_set_error("gpde_nnconv_fwd: aggr %d not implemented (add=0, mean=1)", aggr);
+    const bool mixed = a.hidden && a.hidden_nodes >= 0 && a.hidden_nodes < a.n_nodes;
+    if (a.aggr != GPDE_AGGR_ADD && a.aggr != GPDE_AGGR_MEAN) {
+        gpde_set_error("gpde_nnconv_fwd: aggr %d not implemented (add=0, mean=1)", a.aggr);
         return GPDE_EUNSUPPORTED;
     }
-    if (n_nodes == 0) return GPDE_OK;
-    if (!ws) { gpde_set_error("gpde_nnconv_fwd: workspace is null"); return GPDE_EWORKSPACE; }
+    if (a.n_nodes == 0) return GPDE_OK;
+    if (!a.ws) { gpde_set_error("gpde_nnconv_fwd: workspace is null"); return GPDE_EWORKSPACE; }
     Plan P;
-    int rc = make_plan(n_nodes, n_edges, n_layers, dims, ws_bytes, false, &P, nullptr, hidden != nullptr && !mixed);
+    int rc = make_plan(a.n_nodes, a.n_edges, a.n_layers, a.dims, a.ws_bytes, false, &P, nullptr, a.hidden != nullptr && !mixed);
     if (rc != GPDE_OK) return rc;
     const GpdePackLayout& L = P.L;
-    const int mode = (hidden && !mixed) ? 2 : L.mode;
+    const int mode = (a.hidden && !mixed) ? 2 : L.mode;
     if (mixed && L.mode != 1) { gpde_set_error("gpde_nnconv_fwd_mixed_keepz: built for 3-Linear kernel MLPs"); return GPDE_EUNSUPPORTED; }
-    const float* pk = (const float*)packed;
-    char* w = (char*)ws;
+    const float* pk = (const float*)a.packed;
+    char* w = (char*)a.ws;
     w = (char*)(((uintptr_t)w + kAlign - 1) / kAlign * kAlign);
     float* part = (float*)(w + P.off_part);
     float* zbuf = (float*)(w + P.off_z);
     float* ha = (float*)(w + P.off_ha);
     float* hb = (float*)(w + P.off_hb);
 
-    const float* hfinal = hidden;
-    if (!hidden && L.mode == 2 && n_edges > 0) {   // (a mixed call has L.mode == 1)
+    const float* hfinal = a.hidden;
+    if (!a.hidden && L.mode == 2 && a.n_edges > 0) {   // (a mixed call has L.mode == 1)
         // front layers over all edges (CSR order), ping-pong between ha / hb
-        const float* in = edge_attr;
+        const float* in = a.edge_attr;
         int ldx = L.k0, kin = L.k0;
-        const int32_t* gather = perm;
+        const int32_t* gather = a.perm;
         float* bufs[2] = {ha, hb};
-        for (int l = 0; l < n_layers - 1; ++l) {
+        for (int l = 0; l < a.n_layers - 1; ++l) {
             GpdeDenseArgs d;
             d.X = in; d.ldx = ldx; d.kin = kin; d.gather = gather; d.row0 = 0;
             d.W = pk + L.off_front_w[l]; d.ldw = L.frontKP[l];
             d.b = pk + L.off_front_b[l];
             d.Y = bufs[l & 1]; d.KoutP = L.frontKP[l + 1];
-            d.rows = (int)n_edges; d.relu = 1;
-            rc = gpde_launch_dense(d, stream);
+            d.rows = (int)a.n_edges; d.relu = 1;
+            rc = gpde_launch_dense(d, a.stream);
             if (rc != GPDE_OK) return rc;
             in = d.Y; ldx = kin = d.KoutP; gather = nullptr;
         }
@@ -383,116 +414,116 @@ int fwd_impl(const float* x, int64_t n_nodes, const float* edge_attr, int64_t n_
     // trip per node - a loss when a node has two or three in-edges (MGKN-orthogonal Burgers: 8192 nodes, 16 k edges,
     // 2 x 2.1 GB of Z per call).  There W_e = W3 . h_e is formed tile by tile on the split-f16 GEMM and contracted
     // with x_j in its epilogue ([E][4096] never exists), messages are summed per destination in CSR order.
-    const bool edge_path = !z_keep && takes_edge_path(P, flags, n_nodes, n_edges, hidden != nullptr, hidden_absmax != nullptr,
-                                                      mixed, kt);
+    const bool edge_path = !a.z_keep && takes_edge_path(P, a.flags, a.n_nodes, a.n_edges, a.hidden != nullptr,
+                                                        a.hidden_absmax != nullptr, mixed, a.kt);
     if (edge_path) {
         float* Hbuf = zbuf;                                  // the Z region is free on this path
-        float* ews = zbuf + (hidden ? 0 : (size_t)n_edges * L.K2P);
-        const float* Hrows = hidden;
-        if (!hidden) {
-            ProfScope ps(GPDE_PROF_FUSED, stream);
+        float* ews = zbuf + (a.hidden ? 0 : (size_t)a.n_edges * L.K2P);
+        const float* Hrows = a.hidden;
+        if (!a.hidden) {
+            ProfScope ps(GPDE_PROF_FUSED, a.stream);
             GpdeFusedArgs f{};
-            f.attr = edge_attr; f.rowptr = rowptr; f.perm = perm;
+            f.attr = a.edge_attr; f.rowptr = a.rowptr; f.perm = a.perm;
             f.w1 = pk + L.off_w1; f.w2t = pk + L.off_w2t; f.b2 = pk + L.off_b2;
             f.w2h = pk + L.off_w2h; f.ucol = pk + L.off_ucol; f.w1h = pk + L.off_w1h; f.fcol = pk + L.off_fcol;
             f.hout = Hbuf; f.hmax_out = nullptr; f.k0 = L.k0; f.K1P = L.K1P; f.K2P = L.K2P;
-            f.nc0 = 0; f.nc1 = (int)n_nodes; f.e_chunk0 = 0;
+            f.nc0 = 0; f.nc1 = (int)a.n_nodes; f.e_chunk0 = 0;
             const int ns = L.K2P / GP_TN;
             int groups = gpde_num_cus() / ns; if (groups < 1) groups = 1;
-            const int64_t gcap = ((n_edges + GP_TE - 1) / GP_TE + GP_WAVES - 1) / GP_WAVES;
+            const int64_t gcap = ((a.n_edges + GP_TE - 1) / GP_TE + GP_WAVES - 1) / GP_WAVES;
             if (groups > gcap) groups = (int)gcap;
             f.n_groups = groups;
-            if ((rc = gpde_launch_fused_store(f, stream)) != GPDE_OK) return rc;
+            if ((rc = gpde_launch_fused_store(f, a.stream)) != GPDE_OK) return rc;
             Hrows = Hbuf;
         }
         {
-            ProfScope ps(GPDE_PROF_GEMM3, stream);
-            rc = gpde_launch_edge_messages(Hrows, L.K2P, n_edges, pk + L.off_w3s, pk + L.off_ucol3, x, src, rowptr, n_nodes,
-                                           ews, part, stream);
+            ProfScope ps(GPDE_PROF_GEMM3, a.stream);
+            rc = gpde_launch_edge_messages(Hrows, L.K2P, a.n_edges, pk + L.off_w3s, pk + L.off_ucol3, a.x, a.src, a.rowptr, a.n_nodes,
+                                           ews, part, a.stream);
             if (rc != GPDE_OK) return rc;
         }
         GpdeEpilogueArgs e;
-        e.part = part; e.x = x; e.rowptr = rowptr; e.src = src;
-        e.b3 = pk + L.off_b3; e.root = root; e.bias = bias; e.out = out;
-        e.nc0 = 0; e.nn = (int)n_nodes; e.splits = 1; e.aggr = aggr;
-        e.residual = residual; e.relu_out = relu_out;
-        ProfScope ps2(GPDE_PROF_EPILOGUE, stream);
-        return gpde_launch_epilogue(e, stream);
+        e.part = part; e.x = a.x; e.rowptr = a.rowptr; e.src = a.src;
+        e.b3 = pk + L.off_b3; e.root = a.root; e.bias = a.bias; e.out = a.out;
+        e.nc0 = 0; e.nn = (int)a.n_nodes; e.splits = 1; e.aggr = a.aggr;
+        e.residual = a.residual; e.relu_out = a.relu_out;
+        ProfScope ps2(GPDE_PROF_EPILOGUE, a.stream);
+        return gpde_launch_epilogue(e, a.stream);
     }
 
     const unsigned* xs = nullptr;
     const unsigned* scal = nullptr;
-    const FusedChoice fc = choose_fused(L, mode, flags, n_edges, kt);
-    if (kt && fc.kind == FK_GENERIC) {
+    const FusedChoice fc = choose_fused(L, mode, a.flags, a.n_edges, a.kt);
+    if (a.kt && fc.kind == FK_GENERIC) {
         gpde_set_error("gpde_nnconv_fwd_mixed_keepz (node_attr): built for 3-Linear kernel MLPs on the f16-split kernel only");
         return GPDE_EUNSUPPORTED;
     }
-    if ((!hidden || mixed) && fc.g2f16) {
-        ProfScope psp(GPDE_PROF_PREP, stream);
-        rc = gpde_launch_g2_prep(x, n_nodes, edge_attr, n_edges, L.k0, pk + L.off_w1 + (size_t)L.K1P * 8,
-                                 (unsigned*)(w + P.off_scal), (unsigned*)(w + P.off_xs), stream, kt, sel, src, dst);
+    if ((!a.hidden || mixed) && fc.g2f16) {
+        ProfScope psp(GPDE_PROF_PREP, a.stream);
+        rc = gpde_launch_g2_prep(a.x, a.n_nodes, a.edge_attr, a.n_edges, L.k0, pk + L.off_w1 + (size_t)L.K1P * 8,
+                                 (unsigned*)(w + P.off_scal), (unsigned*)(w + P.off_xs), a.stream, a.kt, a.sel, a.src, a.dst);
         if (rc != GPDE_OK) return rc;
         xs = (const unsigned*)(w + P.off_xs);
         scal = (const unsigned*)(w + P.off_scal);
     }
 
     // hidden activations given together with their maximum: the streaming aggregation on split f16
-    if (hidden && !mixed && hidden_absmax && n_edges >= 32768 && !(flags & GPDE_FWD_AGG_F32)) {
-        rc = gpde_launch_g2_prep(x, n_nodes, nullptr, 0, 0, nullptr, (unsigned*)(w + P.off_scal),
-                                 (unsigned*)(w + P.off_xs), stream);
+    if (a.hidden && !mixed && a.hidden_absmax && a.n_edges >= 32768 && !(a.flags & GPDE_FWD_AGG_F32)) {
+        rc = gpde_launch_g2_prep(a.x, a.n_nodes, nullptr, 0, 0, nullptr, (unsigned*)(w + P.off_scal),
+                                 (unsigned*)(w + P.off_xs), a.stream);
         if (rc != GPDE_OK) return rc;
         xs = (const unsigned*)(w + P.off_xs);
         scal = (const unsigned*)(w + P.off_scal);
     }
 
-    const int64_t hn = mixed ? hidden_nodes : (hidden ? n_nodes : 0);     // nodes served from `hidden`
-    for (int64_t nc0 = 0, nc1 = 0; nc0 < n_nodes; nc0 = nc1) {
-        const int64_t lim = nc0 < hn ? hn : n_nodes;                       // a chunk never straddles hn
+    const int64_t hn = mixed ? a.hidden_nodes : (a.hidden ? a.n_nodes : 0);   // nodes served from `hidden`
+    for (int64_t nc0 = 0, nc1 = 0; nc0 < a.n_nodes; nc0 = nc1) {
+        const int64_t lim = nc0 < hn ? hn : a.n_nodes;                         // a chunk never straddles hn
         nc1 = (nc0 + P.nodes_per_chunk < lim) ? nc0 + P.nodes_per_chunk : lim;
         const bool from_h = nc0 < hn;
         const int nn = (int)(nc1 - nc0);
         const int splits = pick_splits(nn);
-        if (n_edges > 0) {
+        if (a.n_edges > 0) {
             GpdeFusedArgs f{};
-            f.x = x; f.attr = edge_attr; f.rowptr = rowptr; f.src = src; f.dst = dst; f.perm = perm;
+            f.x = a.x; f.attr = a.edge_attr; f.rowptr = a.rowptr; f.src = a.src; f.dst = a.dst; f.perm = a.perm;
             f.w1 = pk + L.off_w1; f.w2t = pk + L.off_w2t; f.b2 = pk + L.off_b2;
             f.w2h = pk + L.off_w2h; f.ucol = pk + L.off_ucol;
             f.w1h = pk + L.off_w1h; f.fcol = pk + L.off_fcol;
-            float* zc = z_keep ? z_keep + (size_t)nc0 * GP_W * L.K2P : zbuf;
+            float* zc = a.z_keep ? a.z_keep + (size_t)nc0 * GP_W * L.K2P : zbuf;
             f.hbuf = hfinal; f.zbuf = zc; f.xs = xs; f.scal = scal;
-            f.kt = kt; f.hmax = (from_h && xs) ? (const unsigned*)hidden_absmax : nullptr;
-            for (int d = 0; d < 8; ++d) f.sel[d] = (kt && sel) ? sel[d < L.k0 ? d : L.k0 - 1] : 0;
+            f.kt = a.kt; f.hmax = (from_h && xs) ? (const unsigned*)a.hidden_absmax : nullptr;
+            for (int d = 0; d < 8; ++d) f.sel[d] = (a.kt && a.sel) ? a.sel[d < L.k0 ? d : L.k0 - 1] : 0;
             f.k0 = L.k0; f.K1P = L.K1P; f.K2P = L.K2P;
             f.nc0 = (int)nc0; f.nc1 = (int)nc1; f.e_chunk0 = 0; f.n_groups = P.n_groups;
             {
-                ProfScope ps(GPDE_PROF_FUSED, stream);
-                if (!from_h && fc.kind == FK_V6 && P.nblk_max && L.K2P / GP_TN <= 64 && !(flags & GPDE_FWD_STATIC_RANGES)) {
+                ProfScope ps(GPDE_PROF_FUSED, a.stream);
+                if (!from_h && fc.kind == FK_V6 && P.nblk_max && L.K2P / GP_TN <= 64 && !(a.flags & GPDE_FWD_STATIC_RANGES)) {
                     int32_t* blk = (int32_t*)(w + P.off_blk);
                     f.blk = blk; f.qn = blk + P.nblk_max + 1; f.qctr = (unsigned*)(blk + P.nblk_max + 2);
-                    rc = gpde_launch_block_bounds(rowptr, (int)nc0, (int)nc1, P.nblk_max, blk, blk + P.nblk_max + 1,
-                                                  (unsigned*)(blk + P.nblk_max + 2), L.K2P / GP_TN, stream);
+                    rc = gpde_launch_block_bounds(a.rowptr, (int)nc0, (int)nc1, P.nblk_max, blk, blk + P.nblk_max + 1,
+                                                  (unsigned*)(blk + P.nblk_max + 2), L.K2P / GP_TN, a.stream);
                     if (rc != GPDE_OK) return rc;
                 }
-                if (from_h) rc = gpde_launch_zagg(f, stream);
-                else if (fc.kind == FK_V6) rc = gpde_launch_fused_f16v6(f, stream);
-                else if (fc.kind == FK_V3) rc = gpde_launch_fused_f16v3(f, stream);
-                else rc = gpde_launch_fused(mode, (flags & GPDE_FWD_F16SPLIT) != 0 && mode == 1, f, stream);
+                if (from_h) rc = gpde_launch_zagg(f, a.stream);
+                else if (fc.kind == FK_V6) rc = gpde_launch_fused_f16v6(f, a.stream);
+                else if (fc.kind == FK_V3) rc = gpde_launch_fused_f16v3(f, a.stream);
+                else rc = gpde_launch_fused(mode, (a.flags & GPDE_FWD_F16SPLIT) != 0 && mode == 1, f, a.stream);
             }
             if (rc != GPDE_OK) return rc;
-            ProfScope ps1(GPDE_PROF_GEMM3, stream);
+            ProfScope ps1(GPDE_PROF_GEMM3, a.stream);
             GpdeGemm3Args g;
             g.zbuf = zc; g.w3q = pk + L.off_w3q; g.part = part; g.nn = nn; g.K2P = L.K2P;
-            g.splits = splits; g.rowptr = rowptr; g.nc0 = (int)nc0;
-            rc = gpde_launch_gemm3(g, stream);
+            g.splits = splits; g.rowptr = a.rowptr; g.nc0 = (int)nc0;
+            rc = gpde_launch_gemm3(g, a.stream);
             if (rc != GPDE_OK) return rc;
         }
         GpdeEpilogueArgs e;
-        e.part = part; e.x = x; e.rowptr = rowptr; e.src = src;
-        e.b3 = pk + L.off_b3; e.root = root; e.bias = bias; e.out = out;
-        e.nc0 = (int)nc0; e.nn = nn; e.splits = splits; e.aggr = aggr;
-        e.residual = residual; e.relu_out = relu_out;
-        ProfScope ps2(GPDE_PROF_EPILOGUE, stream);
-        rc = gpde_launch_epilogue(e, stream);
+        e.part = part; e.x = a.x; e.rowptr = a.rowptr; e.src = a.src;
+        e.b3 = pk + L.off_b3; e.root = a.root; e.bias = a.bias; e.out = a.out;
+        e.nc0 = (int)nc0; e.nn = nn; e.splits = splits; e.aggr = a.aggr;
+        e.residual = a.residual; e.relu_out = a.relu_out;
+        ProfScope ps2(GPDE_PROF_EPILOGUE, a.stream);
+        rc = gpde_launch_epilogue(e, a.stream);
         if (rc != GPDE_OK) return rc;
     }
     return GPDE_OK;
@@ -511,8 +542,9 @@ extern "C" int gpde_nnconv_fwd(const float* x, int64_t n_nodes, const float* edg
         gpde_set_error("gpde_nnconv_fwd: null/negative argument");
         return GPDE_EINVAL;
     }
-    return fwd_impl(x, n_nodes, edge_attr, n_edges, rowptr, src, dst, perm, n_layers, dims, packed, root, bias,
-                    aggr, flags, nullptr, out, ws, ws_bytes, (hipStream_t)stream_);
+    FwdArgs a = fwd_common(x, n_nodes, n_edges, rowptr, src, dst, n_layers, dims, packed, root, bias, aggr, out, ws, ws_bytes, stream_);
+    a.edge_attr = edge_attr; a.perm = perm; a.flags = flags;
+    return fwd_impl(a);
 }
 
 // The general forward (round 5: the mixed, node-table and node-table + partial-H forwards folded into one): attributes from `edge_attr` +
@@ -551,12 +583,10 @@ extern "C" int gpde_nnconv_fwd_mixed_keepz(const float* x, int64_t n_nodes, cons
         attr = na->table;
         perm = nullptr;
     }
-    if (hidden_nodes == 0)
-        return fwd_impl(x, n_nodes, attr, n_edges, rowptr, src, dst, perm, n_layers, dims, packed, root, bias,
-                        aggr, flags, nullptr, out, ws, ws_bytes, (hipStream_t)stream_, kt, kt ? sel : nullptr, nullptr, -1, nullptr, 0, z_keep);
-    return fwd_impl(x, n_nodes, attr, n_edges, rowptr, src, dst, perm, n_layers, dims, packed, root, bias,
-                    aggr, flags, hidden, out, ws, ws_bytes, (hipStream_t)stream_, kt, kt ? sel : nullptr, hidden_absmax,
-                    hidden_nodes, nullptr, 0, z_keep);
+    FwdArgs a = fwd_common(x, n_nodes, n_edges, rowptr, src, dst, n_layers, dims, packed, root, bias, aggr, out, ws, ws_bytes, stream_);
+    a.edge_attr = attr; a.perm = perm; a.flags = flags; a.kt = kt; a.sel = kt ? sel : nullptr; a.z_keep = z_keep;
+    if (hidden_nodes != 0) { a.hidden = hidden; a.hidden_absmax = hidden_absmax; a.hidden_nodes = hidden_nodes; }
+    return fwd_impl(a);
 }
 
 extern "C" int gpde_nnconv_fwd_hidden(const float* x, int64_t n_nodes, const float* hidden,
@@ -569,8 +599,9 @@ extern "C" int gpde_nnconv_fwd_hidden(const float* x, int64_t n_nodes, const flo
         gpde_set_error("gpde_nnconv_fwd_hidden: null/negative argument");
         return GPDE_EINVAL;
     }
-    return fwd_impl(x, n_nodes, nullptr, n_edges, rowptr, src, dst, nullptr, n_layers, dims, packed, root, bias,
-                    aggr, 0, hidden, out, ws, ws_bytes, (hipStream_t)stream_, 0, nullptr, hidden_absmax);
+    FwdArgs a = fwd_common(x, n_nodes, n_edges, rowptr, src, dst, n_layers, dims, packed, root, bias, aggr, out, ws, ws_bytes, stream_);
+    a.hidden = hidden; a.hidden_absmax = hidden_absmax;
+    return fwd_impl(a);
 }
 
 extern "C" int gpde_nnconv_fwd_act(const float* x, int64_t n_nodes, const float* edge_attr, int64_t n_edges,
@@ -583,9 +614,9 @@ extern "C" int gpde_nnconv_fwd_act(const float* x, int64_t n_nodes, const float*
         gpde_set_error("gpde_nnconv_fwd_act: null/negative argument (or residual aliases out)");
         return GPDE_EINVAL;
     }
-    return fwd_impl(x, n_nodes, edge_attr, n_edges, rowptr, src, dst, perm, n_layers, dims, packed, root, bias,
-                    aggr, flags, nullptr, out, ws, ws_bytes, (hipStream_t)stream_, 0, nullptr, nullptr, -1, residual,
-                    relu_out);
+    FwdArgs a = fwd_common(x, n_nodes, n_edges, rowptr, src, dst, n_layers, dims, packed, root, bias, aggr, out, ws, ws_bytes, stream_);
+    a.edge_attr = edge_attr; a.perm = perm; a.flags = flags; a.residual = residual; a.relu_out = relu_out;
+    return fwd_impl(a);
 }
 
 extern "C" int gpde_nnconv_fwd_hidden_act(const float* x, int64_t n_nodes, const float* hidden, const float* hidden_absmax,
@@ -598,9 +629,9 @@ extern "C" int gpde_nnconv_fwd_hidden_act(const float* x, int64_t n_nodes, const
         gpde_set_error("gpde_nnconv_fwd_hidden_act: null/negative argument (or residual aliases out)");
         return GPDE_EINVAL;
     }
-    return fwd_impl(x, n_nodes, nullptr, n_edges, rowptr, src, dst, nullptr, n_layers, dims, packed, root, bias,
-                    aggr, 0, hidden, out, ws, ws_bytes, (hipStream_t)stream_, 0, nullptr, hidden_absmax, -1, residual,
-                    relu_out);
+    FwdArgs a = fwd_common(x, n_nodes, n_edges, rowptr, src, dst, n_layers, dims, packed, root, bias, aggr, out, ws, ws_bytes, stream_);
+    a.hidden = hidden; a.hidden_absmax = hidden_absmax; a.residual = residual; a.relu_out = relu_out;
+    return fwd_impl(a);
 }
 
 extern "C" int gpde_nnconv_fwd_keepz(const float* x, int64_t n_nodes, const float* edge_attr, const float* hidden,
@@ -613,11 +644,11 @@ extern "C" int gpde_nnconv_fwd_keepz(const float* x, int64_t n_nodes, const floa
         gpde_set_error("gpde_nnconv_fwd_keepz: null/negative argument");
         return GPDE_EINVAL;
     }
-    if (hidden)
-        return fwd_impl(x, n_nodes, nullptr, n_edges, rowptr, src, dst, nullptr, n_layers, dims, packed, root, bias, aggr, 0,
-                        hidden, out, ws, ws_bytes, (hipStream_t)stream_, 0, nullptr, hidden_absmax, -1, nullptr, 0, z_keep);
-    return fwd_impl(x, n_nodes, edge_attr, n_edges, rowptr, src, dst, perm, n_layers, dims, packed, root, bias, aggr, flags,
-                    nullptr, out, ws, ws_bytes, (hipStream_t)stream_, 0, nullptr, nullptr, -1, nullptr, 0, z_keep);
+    FwdArgs a = fwd_common(x, n_nodes, n_edges, rowptr, src, dst, n_layers, dims, packed, root, bias, aggr, out, ws, ws_bytes, stream_);
+    a.z_keep = z_keep;
+    if (hidden) { a.hidden = hidden; a.hidden_absmax = hidden_absmax; }      // (attributes, perm and flags are not read)
+    else { a.edge_attr = edge_attr; a.perm = perm; a.flags = flags; }
+    return fwd_impl(a);
 }
 
 extern "C" int gpde_profile_begin(void) {

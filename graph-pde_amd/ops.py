@@ -277,6 +277,11 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def _ptr_array(ts):
+    """The `void*` array of a native call over a list of tensors (NULL for a None entry)."""
+    return (ctypes.c_void_p * len(ts))(*[_ptr(t) for t in ts])
+
+
 def _dense16(t: torch.Tensor) -> torch.Tensor:
     """`t` itself when it is dense (contiguous) and starts on a 16-byte boundary, else a fresh dense copy (the allocators of
     torch hand out blocks aligned far beyond 16 bytes).  The 64-wide kernels read their operands with 16-byte vector accesses."""
@@ -318,6 +323,30 @@ def _operands(ts, name: str, shapes, dev):
 def _mlp_shapes(dims: Sequence[int]):
     """([weight shapes], [bias shapes]) of the Linear layers of widths `dims`."""
     return [(dims[l + 1], dims[l]) for l in range(len(dims) - 1)], [(dims[l + 1],) for l in range(len(dims) - 1)]
+
+
+def _mlp_operands(weights, biases, dev, dims: Optional[Sequence[int]] = None):
+    """The kernel MLP of a native call: (dims, dims_c, weights, biases) with every given layer checked as an operand (None
+    entries pass through).  `dims`: all layer widths where `weights` holds only the first layers; else read off the weights."""
+    if dims is None:
+        dims = [int(weights[0].size(1))] + [int(w.size(0)) for w in weights]
+    w_shapes, b_shapes = _mlp_shapes(dims)
+    return (dims, _lib.dims_array(dims), _operands([None if w is None else w.detach() for w in weights], "weights", w_shapes, dev),
+            _operands([None if b is None else b.detach() for b in biases], "biases", b_shapes, dev))
+
+
+def _update_grads(root, need_root: bool, need_bias: bool, dev):
+    """(grad_root [64, 64] or None, grad_bias [64] or None): the update() gradients a 64-wide backward call writes."""
+    return (torch.empty(WIDTH, WIDTH, dtype=torch.float32, device=dev) if (need_root and root is not None) else None,
+            torch.empty(WIDTH, dtype=torch.float32, device=dev) if need_bias else None)
+
+
+def _queried_ws(query: str, dev, *args) -> torch.Tensor:
+    """A workspace of the size the library's `query` names for `args` (0 = the query refused the shape: its message is raised)."""
+    nbytes = int(getattr(_lib.lib(), query)(*args))
+    if nbytes == 0:
+        _lib.check(-2, query)
+    return _alloc_ws(nbytes, dev)
 
 
 def build_csr(edge_index: torch.Tensor, n_nodes: int, n_src: Optional[int] = None, flip: bool = False) -> Csr:
@@ -756,6 +785,95 @@ def _out_ws(out, ws, n, dev):
             _operand(ws, "ws", (None,), dev, writable=True, dtype=torch.uint8))
 
 
+def _attr_source(csr: "Csr", edge_attr, keep_rows: bool = False):
+    """The attribute source of a native call: (`edge_attr` pointer, `node_attr` reference, `perm` pointer, what must stay alive
+    during the call).  A NodeAttr goes by reference (GpdeNodeAttr) and leaves both pointers NULL; a tensor (already detached
+    where the caller does not differentiate it) goes in CSR slot order with its permutation (`attr_in_slot_order`), or -
+    `keep_rows` - in the caller's row order with the CSR's own `perm`; None: a call that reads no attributes."""
+    if edge_attr is None:
+        return None, None, None, None
+    if isinstance(edge_attr, NodeAttr):
+        nas = edge_attr.c_struct()
+        return None, ctypes.byref(nas), None, (edge_attr, nas)
+    if keep_rows:
+        attr, perm = _dense16(edge_attr), csr.perm
+    else:
+        attr, perm = attr_in_slot_order(csr, _dense16(edge_attr))
+    return attr.data_ptr(), None, perm.data_ptr(), (attr, perm)
+
+
+def _forward64(label: str, x: torch.Tensor, csr: Csr, pm: PackedMlp, root, bias, aggr: str, flags: int, attr=None,
+               hidden: Optional[torch.Tensor] = None, hmax: Optional[torch.Tensor] = None, hidden_nodes: Optional[int] = None,
+               residual: Optional[torch.Tensor] = None, relu: bool = False, z_keep: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The one body of the 64-wide forward wrappers: one native call on the current stream.  `x` has passed its wrapper's own
+    gate, `flags` is the wrapper's GPDE_FWD_* word, `label` its name in a library error.  `attr`: the attribute source - an
+    [E, k0] tensor, a NodeAttr, or None (every node aggregates from H).  `hidden` / `hmax`: the last hidden activations and
+    their max |H| scalar - with `hidden_nodes` None H of EVERY edge, with `hidden_nodes` = k the rows of the in-edges of
+    nodes [0, k) only (the general entry point; k = 0: no H).  `residual` / `relu`: out = act(residual + NNConv(x)) in the
+    last kernel; `z_keep` (zeros [N, 64 * K2P]): Z of every node is left there for the backward (`z_buffer`)."""
+    lib = _lib.lib()
+    _require_cuda(x, "x")
+    if aggr not in _AGGR:
+        raise NotImplementedError(f"aggr={aggr!r}: 'add' and 'mean' only")
+    n, e, dev, k2p = csr.n_nodes, csr.n_edges, x.device, hidden_width(pm.dims)
+    x = _operand(x, "x", (n, WIDTH), dev)
+    if isinstance(attr, NodeAttr):
+        _require_cuda(attr.table, "node table")
+        if attr.table.size(0) != n or attr.k0 != pm.dims[0]:
+            raise ValueError(f"node table must have {n} rows and {pm.dims[0]} slots")
+    elif attr is not None:
+        _require_cuda(attr, "edge_attr")
+        if attr.dim() != 2 or attr.size(0) != e or attr.size(1) != pm.dims[0]:
+            raise ValueError(f"edge_attr must be [{e},{pm.dims[0]}], got {tuple(attr.shape)}")
+        if attr.device != dev:
+            raise ValueError(f"edge_attr is on {attr.device}, x on {dev}")
+        if attr.dtype != torch.float32:
+            raise NotImplementedError(f"float32 only (got x {x.dtype}, edge_attr {attr.dtype})")
+    general = hidden_nodes is not None or isinstance(attr, NodeAttr)         # gpde_nnconv_fwd_mixed_keepz
+    if hidden_nodes is not None:             # a partial H: its rows end where the in-edges of node `hidden_nodes` begin
+        hidden_nodes = max(int(hidden_nodes), 0)
+        hidden = hidden if hidden_nodes > 0 else None
+    if hidden is not None:
+        _require_cuda(hidden, "hidden")
+        hidden = _operand(hidden, "hidden", (e if hidden_nodes is None else int(csr.rowptr_host[hidden_nodes]), k2p), dev)
+    attr_p, na_ref, perm_p, _alive = _attr_source(csr, attr)
+    root_c, bias_c = _root_bias(root, bias, dev)
+    out, ws = _out_ws(out, ws, n, dev)
+    z_keep = _operand(z_keep, "z_keep", (n, WIDTH * k2p), dev, writable=True)
+    residual = _check_residual(residual, x, n)
+    glue = residual is not None or relu
+    if z_keep is not None and glue:
+        raise ValueError("z_keep cannot be combined with the fused glue")
+    if general and glue:
+        raise NotImplementedError("the fused glue with node-table attributes or a partial H is not built")
+    if out is None:
+        out = torch.empty(n, WIDTH, dtype=torch.float32, device=dev)
+    if ws is None:
+        ws = _alloc_ws(workspace_bytes(n, e, pm), dev)
+    # the runs of arguments every entry point shares, in the header's order
+    head = (x.data_ptr(), n)
+    graph = (csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr())
+    mlp = (len(pm.dims) - 1, pm.dims_c, pm.packed.data_ptr(), _ptr(root_c), _ptr(bias_c), _AGGR[aggr])
+    tail = (out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+    act = (_ptr(residual), 1 if relu else 0)
+    with torch.cuda.device(dev):
+        if general:
+            rc = lib.gpde_nnconv_fwd_mixed_keepz(*head, attr_p, na_ref, _ptr(hidden), _ptr(hmax), hidden_nodes or 0, e, *graph, perm_p,
+                                                 *mlp, flags, _ptr(z_keep), *tail)
+        elif z_keep is not None:
+            rc = lib.gpde_nnconv_fwd_keepz(*head, attr_p, _ptr(hidden), _ptr(hmax), e, *graph, perm_p, *mlp, flags, z_keep.data_ptr(), *tail)
+        elif hidden is not None:
+            rc = lib.gpde_nnconv_fwd_hidden_act(*head, hidden.data_ptr(), _ptr(hmax), e, *graph, *mlp, *act, *tail)
+        elif glue:
+            rc = lib.gpde_nnconv_fwd_act(*head, attr_p, e, *graph, perm_p, *mlp, flags, *act, *tail)
+        else:
+            rc = lib.gpde_nnconv_fwd(*head, attr_p, e, *graph, perm_p, *mlp, flags, *tail)
+    _lib.check(rc, label)
+    _lib.n_native_calls += 1
+    return out
+
+
 def nnconv_forward_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor, pm: PackedMlp,
                        root: Optional[torch.Tensor], bias: Optional[torch.Tensor], aggr: str,
                        out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
@@ -765,9 +883,6 @@ def nnconv_forward_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor, pm: P
     `residual` / `relu` (opt-in): out = act(residual + NNConv(x)) in the last kernel
     (gpde_nnconv_fwd_act).  `z_keep` (zeros [N, 64 * K2P]): gpde_nnconv_fwd_keepz - Z of every node is left there for
     the backward (`z_buffer`)."""
-    lib = _lib.lib()
-    _require_cuda(x, "x")
-    _require_cuda(edge_attr, "edge_attr")
     if isinstance(edge_attr, NodeAttr):         # attributes from node data (row f3): the training-side forward entry point
         if residual is not None or relu:
             raise NotImplementedError("the fused glue with node-table attributes is not built")
@@ -778,56 +893,15 @@ def nnconv_forward_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor, pm: P
             f"aggr={aggr!r}: the fused MI355X operator implements 'add' and 'mean' (every reference "
             "script uses 'mean'); 'max' cannot use the re-associated contraction")
     flags = _fwd_flags(csr, precision)
-    precision = DEFAULT_PRECISION if precision is None else precision
     if x.dtype != torch.float32 or edge_attr.dtype != torch.float32:
         raise NotImplementedError(f"float32 only (got x {x.dtype}, edge_attr {edge_attr.dtype})")
     if x.dim() != 2 or x.size(1) != WIDTH:
         raise NotImplementedError(f"node features must be [N,{WIDTH}] (in_channels = out_channels = "
                                   f"{WIDTH}), got {tuple(x.shape)}")
-    n, e = csr.n_nodes, csr.n_edges
-    if x.size(0) != n:
-        raise ValueError(f"x has {x.size(0)} rows, CSR was built for {n} nodes")
-    if edge_attr.dim() != 2 or edge_attr.size(0) != e or edge_attr.size(1) != pm.dims[0]:
-        raise ValueError(f"edge_attr must be [{e},{pm.dims[0]}], got {tuple(edge_attr.shape)}")
-    x = _operand(x, "x", (n, WIDTH), x.device)
-    if edge_attr.device != x.device:
-        raise ValueError(f"edge_attr is on {edge_attr.device}, x on {x.device}")
-    edge_attr, perm = attr_in_slot_order(csr, _dense16(edge_attr))
-    root_c, bias_c = _root_bias(root, bias, x.device)
-    out, ws = _out_ws(out, ws, n, x.device)
-    z_keep = _operand(z_keep, "z_keep", (n, WIDTH * hidden_width(pm.dims)), x.device, writable=True)
-    residual = _check_residual(residual, x, n)
-    if z_keep is not None and (residual is not None or relu):
-        raise ValueError("z_keep cannot be combined with the fused glue")
-    if out is None:
-        out = torch.empty(n, WIDTH, dtype=torch.float32, device=x.device)
-    if ws is None:
-        ws = _alloc_ws(workspace_bytes(n, e, pm), x.device)
-    with torch.cuda.device(x.device):
-        if z_keep is not None:
-            rc = lib.gpde_nnconv_fwd_keepz(x.data_ptr(), n, edge_attr.data_ptr(), None, None, e, csr.rowptr.data_ptr(),
-                                           csr.src.data_ptr(), csr.dst.data_ptr(), perm.data_ptr(), len(pm.dims) - 1, pm.dims_c,
-                                           pm.packed.data_ptr(), None if root_c is None else root_c.data_ptr(),
-                                           None if bias_c is None else bias_c.data_ptr(), _AGGR[aggr], flags,
-                                           z_keep.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(x.device))
-        elif residual is None and not relu:
-            rc = lib.gpde_nnconv_fwd(x.data_ptr(), n, edge_attr.data_ptr(), e, csr.rowptr.data_ptr(),
-                                     csr.src.data_ptr(), csr.dst.data_ptr(), perm.data_ptr(),
-                                     len(pm.dims) - 1, pm.dims_c, pm.packed.data_ptr(),
-                                     None if root_c is None else root_c.data_ptr(),
-                                     None if bias_c is None else bias_c.data_ptr(), _AGGR[aggr],
-                                     flags, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(x.device))
-        else:
-            rc = lib.gpde_nnconv_fwd_act(x.data_ptr(), n, edge_attr.data_ptr(), e, csr.rowptr.data_ptr(),
-                                         csr.src.data_ptr(), csr.dst.data_ptr(), perm.data_ptr(),
-                                         len(pm.dims) - 1, pm.dims_c, pm.packed.data_ptr(),
-                                         None if root_c is None else root_c.data_ptr(),
-                                         None if bias_c is None else bias_c.data_ptr(), _AGGR[aggr],
-                                         flags, None if residual is None else residual.data_ptr(),
-                                         1 if relu else 0, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(x.device))
-    _lib.check(rc, "gpde_nnconv_fwd")
-    _lib.n_native_calls += 1
-    return out
+    if x.size(0) != csr.n_nodes:
+        raise ValueError(f"x has {x.size(0)} rows, CSR was built for {csr.n_nodes} nodes")
+    return _forward64("gpde_nnconv_fwd", x, csr, pm, root, bias, aggr, flags, attr=edge_attr, residual=residual, relu=relu,
+                      z_keep=z_keep, out=out, ws=ws)
 
 
 class NodeAttr:
@@ -904,37 +978,11 @@ def nnconv_forward_nodeattr_raw(x: torch.Tensor, csr: Csr, na: NodeAttr, pm: Pac
                                 root: Optional[torch.Tensor], bias: Optional[torch.Tensor], aggr: str,
                                 out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
                                 precision: Optional[str] = None) -> torch.Tensor:
-    """The forward with edge attributes read from a node table (`node_attr` of gpde_nnconv_fwd_mixed_keepz, no kept H, no kept Z)."""
-    lib = _lib.lib()
-    _require_cuda(x, "x")
-    _require_cuda(na.table, "node table")
-    if aggr not in _AGGR:
-        raise NotImplementedError(f"aggr={aggr!r}: 'add' and 'mean' only")
-    precision = DEFAULT_PRECISION if precision is None else precision
-    n, e = csr.n_nodes, csr.n_edges
-    if x.dtype != torch.float32 or x.dim() != 2 or x.size(1) != WIDTH or x.size(0) != n:
-        raise ValueError(f"x must be float32 [{n},{WIDTH}]")
-    if na.table.size(0) != n or na.k0 != pm.dims[0]:
-        raise ValueError(f"node table must have {n} rows and {pm.dims[0]} slots, got {na.table.size(0)} / {na.k0}")
-    x = _operand(x, "x", (n, WIDTH), x.device)
-    nas = na.c_struct()
-    root_c, bias_c = _root_bias(root, bias, x.device)
-    out, ws = _out_ws(out, ws, n, x.device)
-    if out is None:
-        out = torch.empty(n, WIDTH, dtype=torch.float32, device=x.device)
-    if ws is None:
-        ws = _alloc_ws(workspace_bytes(n, e, pm), x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.gpde_nnconv_fwd_mixed_keepz(x.data_ptr(), n, None, ctypes.byref(nas), None, None, 0, e,
-                                             csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(), None,
-                                             len(pm.dims) - 1, pm.dims_c, pm.packed.data_ptr(),
-                                             None if root_c is None else root_c.data_ptr(),
-                                             None if bias_c is None else bias_c.data_ptr(), _AGGR[aggr],
-                                             _PRECISION[precision], None, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                             _stream_ptr(x.device))
-    _lib.check(rc, "gpde_nnconv_fwd_mixed_keepz (node table)")
-    _lib.n_native_calls += 1
-    return out
+    """The forward with edge attributes read from a node table (`node_attr` of gpde_nnconv_fwd_mixed_keepz, no kept H, no kept Z):
+    nnconv_forward_mixed_raw without a partial H."""
+    if na.table.size(0) != csr.n_nodes or na.k0 != pm.dims[0]:
+        raise ValueError(f"node table must have {csr.n_nodes} rows and {pm.dims[0]} slots, got {na.table.size(0)} / {na.k0}")
+    return nnconv_forward_mixed_raw(x, csr, na, None, None, 0, pm, root, bias, aggr, precision=precision, out=out, ws=ws)
 
 
 # Precision policy of the forward: which ASSOCIATION a call's sum is computed in.  The fused operator re-associates
@@ -1026,53 +1074,39 @@ def nnconv_backward_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor,
     if aggr not in _AGGR:
         raise NotImplementedError(f"aggr={aggr!r}")
     n, e, dev = csr.n_nodes, csr.n_edges, x.device
-    nl = len(weights)
-    dims = [int(weights[0].size(1))] + [int(w.size(0)) for w in weights]
-    dims_c = _lib.dims_array(dims)
     x = _operand(x.detach(), "x", (n, WIDTH), dev)
-    is_na = isinstance(edge_attr, NodeAttr)
-    if need_attr:
-        if is_na or dims[0] > 8:
-            raise NotImplementedError("the edge-attribute gradient is built for attribute tensors of <= 8 slots")
-        edge_attr, perm = _dense16(edge_attr.detach()), csr.perm      # the caller's rows: the gradient goes back by perm
-    elif not is_na:
-        edge_attr, perm = attr_in_slot_order(csr, _dense16(edge_attr.detach()))
+    dims, dims_c, ws_, bs_ = _mlp_operands(weights, biases, dev)
+    nl, k2p = len(ws_), hidden_width(dims)
+    if need_attr and (isinstance(edge_attr, NodeAttr) or dims[0] > 8):
+        raise NotImplementedError("the edge-attribute gradient is built for attribute tensors of <= 8 slots")
+    # (`need_attr`: the caller's rows - the gradient goes back by perm)
+    attr_p, na_ref, perm_p, _alive = _attr_source(csr, edge_attr.detach(), keep_rows=need_attr)
     grad_out = _operand(grad_out.detach().float(), "grad_out", (n, WIDTH), dev)
-    w_shapes, b_shapes = _mlp_shapes(dims)
-    ws_ = _operands([w.detach() for w in weights], "weights", w_shapes, dev)
-    bs_ = _operands([None if b is None else b.detach() for b in biases], "biases", b_shapes, dev)
     root_c, _ = _root_bias(root, None, dev)
     ws = _operand(ws, "ws", (None,), dev, writable=True, dtype=torch.uint8)
-    z_saved = _operand(z_saved, "z_saved", (n, WIDTH * hidden_width(dims)), dev)
+    z_saved = _operand(z_saved, "z_saved", (n, WIDTH * k2p), dev)
     gx = torch.empty(n, WIDTH, dtype=torch.float32, device=dev)
     gW = [torch.empty_like(w) for w in ws_]
     gb = [None if b is None else torch.empty_like(b) for b in bs_]
-    groot = torch.empty(WIDTH, WIDTH, dtype=torch.float32, device=dev) if (need_root and root is not None) else None
-    gbias = torch.empty(WIDTH, dtype=torch.float32, device=dev) if need_bias else None
-    P = ctypes.c_void_p
-    arr = lambda ts: (P * nl)(*[None if t is None else t.data_ptr() for t in ts])
+    groot, gbias = _update_grads(root, need_root, need_bias, dev)
+    ga = torch.zeros(e, dims[0], dtype=torch.float32, device=dev) if need_attr else None
     if n == 0:
         # a graph without nodes (message() of an edgeless graph runs the operator on E = 0 one-edge graphs): every sum is empty
         for t in gW + gb + [groot, gbias]:
             if t is not None:
                 t.zero_()
-        ga = torch.zeros(e, dims[0], dtype=torch.float32, device=dev) if need_attr else None
         return (gx, gW, gb, groot, gbias, ga) if need_attr else (gx, gW, gb, groot, gbias)
     if ws is None:
-        ws = alloc_bwd_ws(lib, n, e, nl, dims_c, dev, 0 if hidden_saved is None else e * hidden_width(dims) * 4)
-    rph = csr.rowptr_host
+        ws = alloc_bwd_ws(lib, n, e, nl, dims_c, dev, 0 if hidden_saved is None else e * k2p * 4)
     srp, ssl = csr.src_order
-    nas = edge_attr.c_struct() if is_na else None
-    ga = torch.zeros(e, dims[0], dtype=torch.float32, device=dev) if need_attr else None
-    if hidden_saved is not None and (need_attr or hidden_saved.dtype != torch.float32 or
-                                     tuple(hidden_saved.shape) != (e, hidden_width(dims))):
-        raise ValueError(f"hidden_saved must be float32 [{e},{hidden_width(dims)}] (and excludes need_attr)")
-    hidden_saved = _operand(hidden_saved, "hidden_saved", (e, hidden_width(dims)), dev)
+    if hidden_saved is not None and (need_attr or hidden_saved.dtype != torch.float32 or tuple(hidden_saved.shape) != (e, k2p)):
+        raise ValueError(f"hidden_saved must be float32 [{e},{k2p}] (and excludes need_attr)")
+    hidden_saved = _operand(hidden_saved, "hidden_saved", (e, k2p), dev)
     with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_bwd(x.data_ptr(), n, None if is_na else edge_attr.data_ptr(), None if nas is None else ctypes.byref(nas),
-                                 _ptr(hidden_saved), e, csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(), None if is_na else perm.data_ptr(),
-                                 rph.data_ptr(), _ptr(srp), _ptr(ssl), nl, dims_c, arr(ws_), arr(bs_), _ptr(root_c), _AGGR[aggr],
-                                 grad_out.data_ptr(), _ptr(z_saved), gx.data_ptr(), None, _ptr(ga), arr(gW), arr(gb), _ptr(groot), _ptr(gbias), 0,
+        rc = lib.gpde_nnconv_bwd(x.data_ptr(), n, attr_p, na_ref, _ptr(hidden_saved), e, csr.rowptr.data_ptr(), csr.src.data_ptr(),
+                                 csr.dst.data_ptr(), perm_p, csr.rowptr_host.data_ptr(), _ptr(srp), _ptr(ssl), nl, dims_c,
+                                 _ptr_array(ws_), _ptr_array(bs_), _ptr(root_c), _AGGR[aggr], grad_out.data_ptr(), _ptr(z_saved),
+                                 gx.data_ptr(), None, _ptr(ga), _ptr_array(gW), _ptr_array(gb), _ptr(groot), _ptr(gbias), 0,
                                  ws.data_ptr(), ws.numel(), _stream_ptr(dev))
     _lib.check(rc, "gpde_nnconv_bwd")
     _lib.n_native_calls += 1
@@ -1114,35 +1148,23 @@ def nnconv_backward_light_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor
     if aggr not in _AGGR:
         raise NotImplementedError(f"aggr={aggr!r}")
     n, e, dev = csr.n_nodes, csr.n_edges, x.device
-    nl = len(weights)
-    dims = [int(weights[0].size(1))] + [int(w.size(0)) for w in weights]
-    dims_c = _lib.dims_array(dims)
     x = _operand(x.detach(), "x", (n, WIDTH), dev)
-    is_na = isinstance(edge_attr, NodeAttr)
-    if not is_na:
-        edge_attr, perm = attr_in_slot_order(csr, _dense16(edge_attr.detach()))
+    attr_p, na_ref, perm_p, _alive = _attr_source(csr, edge_attr.detach())
     grad_out = _operand(grad_out.detach().float(), "grad_out", (n, WIDTH), dev)
-    w_shapes, b_shapes = _mlp_shapes(dims)
-    ws_ = _operands([w.detach() for w in weights], "weights", w_shapes, dev)
-    bs_ = _operands([None if b is None else b.detach() for b in biases], "biases", b_shapes, dev)
+    dims, dims_c, ws_, bs_ = _mlp_operands(weights, biases, dev)
+    nl, k2p = len(ws_), hidden_width(dims)
     root_c, _ = _root_bias(root, None, dev)
-    z_saved = _operand(z_saved, "z_saved", (n, WIDTH * hidden_width(dims)), dev)
-    hidden_part = _operand(hidden_part, "hidden_part", (None, hidden_width(dims)), dev)
+    z_saved = _operand(z_saved, "z_saved", (n, WIDTH * k2p), dev)
+    hidden_part = _operand(hidden_part, "hidden_part", (None, k2p), dev)
     gx = torch.empty(n, WIDTH, dtype=torch.float32, device=dev)
     gw = torch.empty_like(ws_[-1])
     gb = None if bs_[-1] is None else torch.empty_like(bs_[-1])
-    groot = torch.empty(WIDTH, WIDTH, dtype=torch.float32, device=dev) if (need_root and root is not None) else None
-    gbias = torch.empty(WIDTH, dtype=torch.float32, device=dev) if need_bias else None
-    nbytes = int(lib.gpde_nnconv_bwd_workspace_bytes(n, e, nl, dims_c))
-    if nbytes == 0:
-        _lib.check(-2, "gpde_nnconv_bwd_workspace_bytes")
-    ws = _alloc_ws(nbytes, dev)
+    groot, gbias = _update_grads(root, need_root, need_bias, dev)
+    ws = _queried_ws("gpde_nnconv_bwd_workspace_bytes", dev, n, e, nl, dims_c)
     srp, ssl = csr.src_order
-    nas = edge_attr.c_struct() if is_na else None
     with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_bwd_light(x.data_ptr(), n, None if is_na else edge_attr.data_ptr(), None if nas is None else ctypes.byref(nas),
-                                       e, csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(), None if is_na else perm.data_ptr(),
-                                       csr.rowptr_host.data_ptr(), _ptr(srp), _ptr(ssl), nl, dims_c,
+        rc = lib.gpde_nnconv_bwd_light(x.data_ptr(), n, attr_p, na_ref, e, csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(),
+                                       perm_p, csr.rowptr_host.data_ptr(), _ptr(srp), _ptr(ssl), nl, dims_c,
                                        _ptr_array(ws_), _ptr_array(bs_), _ptr(root_c), _AGGR[aggr], grad_out.data_ptr(), _ptr(z_saved),
                                        _ptr(hidden_part) if hidden_nodes > 0 else None, int(hidden_nodes) if hidden_part is not None else 0,
                                        gx.data_ptr(), gw.data_ptr(), _ptr(gb), _ptr(groot), _ptr(gbias), ws.data_ptr(), ws.numel(),
@@ -1163,39 +1185,26 @@ def nnconv_backward_deferred_raw(xs: Sequence[torch.Tensor], gs: Sequence[torch.
     if L < 1 or len(gs) != L:
         raise ValueError("one (input, output gradient) pair per deferred application")
     n, e, dev = csr.n_nodes, csr.n_edges, edge_attr.device
-    nl = len(weights)
-    dims = [int(weights[0].size(1))] + [int(w.size(0)) for w in weights]
-    dims_c = _lib.dims_array(dims)
     Lp = deferred_layers_padded(L)
     x_stack = torch.zeros(Lp, n, WIDTH, dtype=torch.float32, device=dev)
     g_stack = torch.empty(L, n, WIDTH, dtype=torch.float32, device=dev)
     for l in range(L):
         x_stack[l].copy_(_operand(xs[l].detach(), f"xs[{l}]", (n, WIDTH), dev))
         g_stack[l].copy_(_operand(gs[l].detach().float(), f"gs[{l}]", (n, WIDTH), dev))
-    is_na = isinstance(edge_attr, NodeAttr)
-    if not is_na:
-        edge_attr, perm = attr_in_slot_order(csr, _dense16(edge_attr.detach()))
-    w_shapes, b_shapes = _mlp_shapes(dims)
-    ws_ = _operands([w.detach() for w in weights], "weights", w_shapes, dev)
-    bs_ = _operands([None if b is None else b.detach() for b in biases], "biases", b_shapes, dev)
+    attr_p, na_ref, perm_p, _alive = _attr_source(csr, edge_attr.detach())
+    dims, dims_c, ws_, bs_ = _mlp_operands(weights, biases, dev)
+    nl = len(ws_)
     hidden_part = _operand(hidden_part, "hidden_part", (None, hidden_width(dims)), dev)
     gW = [torch.empty_like(w) for w in ws_[:-1]] + [None]
     gb = [None if b is None else torch.empty_like(b) for b in bs_[:-1]] + [None]
-    nbytes = int(lib.gpde_nnconv_bwd_deferred_workspace_bytes(n, e, nl, dims_c, L))
-    if nbytes == 0:
-        _lib.check(-2, "gpde_nnconv_bwd_deferred_workspace_bytes")
-    ws = _alloc_ws(nbytes, dev)
-    nas = edge_attr.c_struct() if is_na else None
+    ws = _queried_ws("gpde_nnconv_bwd_deferred_workspace_bytes", dev, n, e, nl, dims_c, L)
     with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_bwd_deferred(x_stack.data_ptr(), g_stack.data_ptr(), L, n, None if is_na else edge_attr.data_ptr(),
-                                          None if nas is None else ctypes.byref(nas), e, csr.rowptr.data_ptr(),
-                                          csr.src.data_ptr(), csr.dst.data_ptr(), None if is_na else perm.data_ptr(),
-                                          csr.rowptr_host.data_ptr(), nl, dims_c,
+        rc = lib.gpde_nnconv_bwd_deferred(x_stack.data_ptr(), g_stack.data_ptr(), L, n, attr_p, na_ref, e, csr.rowptr.data_ptr(),
+                                          csr.src.data_ptr(), csr.dst.data_ptr(), perm_p, csr.rowptr_host.data_ptr(), nl, dims_c,
                                           _ptr_array(ws_), _ptr_array(bs_), _AGGR[aggr],
-                                          hidden_part.data_ptr() if (hidden_part is not None and hidden_nodes > 0) else None,
+                                          _ptr(hidden_part) if hidden_nodes > 0 else None,
                                           int(hidden_nodes) if hidden_part is not None else 0,
-                                          _ptr_array(gW), _ptr_array(gb), ws.data_ptr(),
-                                          ws.numel(), _stream_ptr(dev))
+                                          _ptr_array(gW), _ptr_array(gb), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
     _lib.check(rc, "gpde_nnconv_bwd_deferred")
     _lib.n_native_calls += 1
     return gW[:-1], gb[:-1]
@@ -1209,11 +1218,6 @@ def hidden_width(dims: Sequence[int]) -> int:
     return (int(dims[-2]) + 127) // 128 * 128
 
 
-def _ptr_array(ts):
-    P = ctypes.c_void_p
-    return (P * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
-
-
 def hidden_forward_raw(csr: Csr, edge_attr: torch.Tensor, pm: PackedMlp,
                        weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Tensor]],
                        precision: Optional[str] = None, n_nodes_limit: Optional[int] = None) -> torch.Tensor:
@@ -1224,51 +1228,38 @@ def hidden_forward_raw(csr: Csr, edge_attr: torch.Tensor, pm: PackedMlp,
     precision = DEFAULT_PRECISION if precision is None else precision
     if precision not in _PRECISION:
         raise ValueError(f"precision must be one of {sorted(_PRECISION)}, got {precision!r}")
-    e, dev = csr.n_edges, edge_attr.device
-    if isinstance(edge_attr, NodeAttr):
-        n_lim = csr.n_nodes if n_nodes_limit is None else int(n_nodes_limit)
-        e = e if n_nodes_limit is None else int(csr.rowptr_host[n_lim])
-        hidden = torch.empty(e, hidden_width(pm.dims), dtype=torch.float32, device=dev)
-        hmax = torch.zeros(1, dtype=torch.float32, device=dev)
-        na = edge_attr.c_struct()
-        with torch.cuda.device(dev):
-            rc = lib.gpde_hidden_fwd(None, ctypes.byref(na), e, csr.rowptr.data_ptr(), n_lim, None, csr.src.data_ptr(), csr.dst.data_ptr(),
-                                     len(pm.dims) - 1, pm.dims_c, pm.packed.data_ptr(), None, None, _PRECISION[precision],
-                                     hidden.data_ptr(), hmax.data_ptr(), None, 0, _stream_ptr(dev))
-        _lib.check(rc, "gpde_hidden_fwd (node table)")
-        _lib.n_native_calls += 1
-        return hidden, hmax
-    if edge_attr.dtype != torch.float32 or edge_attr.dim() != 2 or edge_attr.size(0) != e or \
-            edge_attr.size(1) != pm.dims[0]:
+    e, dev, nl, flags = csr.n_edges, edge_attr.device, len(pm.dims) - 1, _PRECISION[precision]
+    is_na = isinstance(edge_attr, NodeAttr)
+    if not is_na and (edge_attr.dtype != torch.float32 or edge_attr.dim() != 2 or edge_attr.size(0) != e or
+                      edge_attr.size(1) != pm.dims[0]):
         raise ValueError(f"edge_attr must be float32 [{e},{pm.dims[0]}], got {edge_attr.dtype} {tuple(edge_attr.shape)}")
-    edge_attr, perm = attr_in_slot_order(csr, _dense16(edge_attr.detach()))
+    attr_p, na_ref, perm_p, _alive = _attr_source(csr, edge_attr.detach())
     n_lim = csr.n_nodes
     if n_nodes_limit is not None:           # H of the in-edges of nodes [0, n_nodes_limit) only (mixed forward)
         n_lim = int(n_nodes_limit)
         e = int(csr.rowptr_host[n_lim])
-    nl = len(pm.dims) - 1
-    w_shapes, b_shapes = _mlp_shapes(pm.dims)
-    ws_ = _operands([None if w is None else w.detach() for w in weights], "weights", w_shapes, dev)    # last entry unused
-    bs_ = _operands([None if b is None else b.detach() for b in biases], "biases", b_shapes, dev)
     hidden = torch.empty(e, hidden_width(pm.dims), dtype=torch.float32, device=dev)
-    nbytes = int(lib.gpde_hidden_workspace_bytes(e, nl, pm.dims_c))
-    fast = (_PRECISION[precision] & _lib.GPDE_FWD_F16SPLIT) and nl == 3
-    ws = torch.empty(1 if fast else max(nbytes, 1), dtype=torch.uint8, device=dev)
+    if is_na:
+        # a node table runs the fused store kernel only: it reads the endpoints of every slot and the packed weights, no workspace
+        fast, ends, wa, ba, ws = True, (csr.src.data_ptr(), csr.dst.data_ptr()), None, None, None
+    else:
+        _, _, ws_, bs_ = _mlp_operands(weights, biases, dev, pm.dims)       # last entry unused
+        ends, wa, ba = (None, None), _ptr_array(ws_), _ptr_array(bs_)
+        nbytes = int(lib.gpde_hidden_workspace_bytes(e, nl, pm.dims_c))
+        fast = (flags & _lib.GPDE_FWD_F16SPLIT) and nl == 3
+        ws = torch.empty(1 if fast else max(nbytes, 1), dtype=torch.uint8, device=dev)
     hmax = torch.zeros(1, dtype=torch.float32, device=dev) if fast else None
+
+    def call(hmax, ws):
+        return lib.gpde_hidden_fwd(attr_p, na_ref, e, csr.rowptr.data_ptr(), n_lim, perm_p, *ends, nl, pm.dims_c, pm.packed.data_ptr(),
+                                   wa, ba, flags, hidden.data_ptr(), _ptr(hmax), _ptr(ws), 0 if ws is None else ws.numel(),
+                                   _stream_ptr(dev))
     with torch.cuda.device(dev):
-        rc = lib.gpde_hidden_fwd(edge_attr.data_ptr(), None, e, csr.rowptr.data_ptr(), n_lim,
-                                 perm.data_ptr(), None, None, nl, pm.dims_c, pm.packed.data_ptr(),
-                                 _ptr_array(ws_), _ptr_array(bs_), _PRECISION[precision],
-                                 hidden.data_ptr(), None if hmax is None else hmax.data_ptr(),
-                                 ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-        if rc in (-1, -3) and fast:    # shape not covered by the fused kernel: the general path needs ws
-            ws = _alloc_ws(nbytes, dev)
-            hmax = None                # ... and does not record max |H|
-            rc = lib.gpde_hidden_fwd(edge_attr.data_ptr(), None, e, csr.rowptr.data_ptr(), n_lim,
-                                     perm.data_ptr(), None, None, nl, pm.dims_c, pm.packed.data_ptr(),
-                                     _ptr_array(ws_), _ptr_array(bs_), _PRECISION[precision],
-                                     hidden.data_ptr(), None, ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "gpde_hidden_fwd")
+        rc = call(hmax, ws)
+        if rc in (-1, -3) and fast and not is_na:    # shape not covered by the fused kernel: the general path needs ws
+            hmax = None                              # ... and does not record max |H|
+            rc = call(hmax, _alloc_ws(nbytes, dev))
+    _lib.check(rc, "gpde_hidden_fwd (node table)" if is_na else "gpde_hidden_fwd")
     _lib.n_native_calls += 1
     return hidden, hmax
 
@@ -1280,48 +1271,11 @@ def nnconv_forward_hidden_raw(x: torch.Tensor, csr: Csr, hidden: torch.Tensor, p
                               relu: bool = False, z_keep: Optional[torch.Tensor] = None) -> torch.Tensor:
     """gpde_nnconv_fwd_hidden: aggregation + last Linear + update() from given hidden activations
     (`hmax`: the max |H| scalar hidden_forward_raw returned; enables the split-f16 aggregation)."""
-    lib = _lib.lib()
-    _require_cuda(x, "x")
-    _require_cuda(hidden, "hidden")
-    if aggr not in _AGGR:
-        raise NotImplementedError(f"aggr={aggr!r}: 'add' and 'mean' only")
-    n, e = csr.n_nodes, csr.n_edges
+    n = csr.n_nodes
     if x.dtype != torch.float32 or x.dim() != 2 or x.size(1) != WIDTH or x.size(0) != n:
         raise ValueError(f"x must be float32 [{n},{WIDTH}], got {x.dtype} {tuple(x.shape)}")
-    x = _operand(x, "x", (n, WIDTH), x.device)
-    hidden = _operand(hidden, "hidden", (e, hidden_width(pm.dims)), x.device)
-    root_c, bias_c = _root_bias(root, bias, x.device)
-    out, ws = _out_ws(out, ws, n, x.device)
-    z_keep = _operand(z_keep, "z_keep", (n, WIDTH * hidden_width(pm.dims)), x.device, writable=True)
-    residual = _check_residual(residual, x, n)
-    if out is None:
-        out = torch.empty(n, WIDTH, dtype=torch.float32, device=x.device)
-    if ws is None:
-        ws = _alloc_ws(workspace_bytes(n, e, pm), x.device)
-    if z_keep is not None:
-        if residual is not None or relu:
-            raise ValueError("z_keep cannot be combined with the fused glue")
-        with torch.cuda.device(x.device):
-            rc = lib.gpde_nnconv_fwd_keepz(x.data_ptr(), n, None, hidden.data_ptr(), None if hmax is None else hmax.data_ptr(), e,
-                                           csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(), None, len(pm.dims) - 1,
-                                           pm.dims_c, pm.packed.data_ptr(), None if root_c is None else root_c.data_ptr(),
-                                           None if bias_c is None else bias_c.data_ptr(), _AGGR[aggr], 0, z_keep.data_ptr(),
-                                           out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(x.device))
-        _lib.check(rc, "gpde_nnconv_fwd_keepz")
-        _lib.n_native_calls += 1
-        return out
-    with torch.cuda.device(x.device):
-        rc = lib.gpde_nnconv_fwd_hidden_act(x.data_ptr(), n, hidden.data_ptr(),
-                                            None if hmax is None else hmax.data_ptr(), e, csr.rowptr.data_ptr(),
-                                            csr.src.data_ptr(), csr.dst.data_ptr(), len(pm.dims) - 1,
-                                            pm.dims_c, pm.packed.data_ptr(),
-                                            None if root_c is None else root_c.data_ptr(),
-                                            None if bias_c is None else bias_c.data_ptr(), _AGGR[aggr],
-                                            None if residual is None else residual.data_ptr(), 1 if relu else 0,
-                                            out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(x.device))
-    _lib.check(rc, "gpde_nnconv_fwd_hidden")
-    _lib.n_native_calls += 1
-    return out
+    return _forward64("gpde_nnconv_fwd_hidden" if z_keep is None else "gpde_nnconv_fwd_keepz", x, csr, pm, root, bias, aggr, 0,
+                      hidden=hidden, hmax=hmax, residual=residual, relu=relu, z_keep=z_keep, out=out, ws=ws)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1833,43 +1787,12 @@ def nnconv_forward_mixed_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor,
     """gpde_nnconv_fwd_mixed_keepz: nodes [0, hidden_nodes) aggregate from `hidden` (their in-edges' rows), the
     rest run the fused kernel -- for graphs whose full H does not fit memory.  `z_keep`: as nnconv_forward_raw.
     `edge_attr` may be a NodeAttr (the call's `node_attr`; `hidden` None / hidden_nodes 0: no partial H)."""
-    lib = _lib.lib()
-    _require_cuda(x, "x")
-    precision = DEFAULT_PRECISION if precision is None else precision
-    if aggr not in _AGGR:
-        raise NotImplementedError(f"aggr={aggr!r}: 'add' and 'mean' only")
-    n, e = csr.n_nodes, csr.n_edges
+    n = csr.n_nodes
     if x.dtype != torch.float32 or x.dim() != 2 or x.size(1) != WIDTH or x.size(0) != n:
         raise ValueError(f"x must be float32 [{n},{WIDTH}]")
-    eh = int(csr.rowptr_host[hidden_nodes]) if hidden_nodes > 0 else 0
-    if hidden_nodes > 0:
-        hidden = _operand(hidden, "hidden", (eh, hidden_width(pm.dims)), x.device)
-    x = _operand(x, "x", (n, WIDTH), x.device)
-    root_c, bias_c = _root_bias(root, bias, x.device)
-    out, ws = _out_ws(out, ws, n, x.device)
-    z_keep = _operand(z_keep, "z_keep", (n, WIDTH * hidden_width(pm.dims)), x.device, writable=True)
-    if out is None:
-        out = torch.empty(n, WIDTH, dtype=torch.float32, device=x.device)
-    if ws is None:
-        ws = _alloc_ws(workspace_bytes(n, e, pm), x.device)
-    is_na = isinstance(edge_attr, NodeAttr)
-    nas, perm = None, None
-    if is_na:
-        if edge_attr.table.size(0) != n or edge_attr.k0 != pm.dims[0]:
-            raise ValueError(f"node table must have {n} rows and {pm.dims[0]} slots")
-        nas = edge_attr.c_struct()
-    else:
-        edge_attr, perm = attr_in_slot_order(csr, _dense16(edge_attr.detach()))
-    with torch.cuda.device(x.device):
-        rc = lib.gpde_nnconv_fwd_mixed_keepz(x.data_ptr(), n, None if is_na else edge_attr.data_ptr(), None if nas is None else ctypes.byref(nas),
-                                             _ptr(hidden) if hidden_nodes > 0 else None, _ptr(hmax), max(int(hidden_nodes), 0), e,
-                                             csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(),
-                                             _ptr(perm), len(pm.dims) - 1, pm.dims_c, pm.packed.data_ptr(),
-                                             _ptr(root_c), _ptr(bias_c), _AGGR[aggr], _PRECISION[precision], _ptr(z_keep),
-                                             out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(x.device))
-    _lib.check(rc, "gpde_nnconv_fwd_mixed_keepz")
-    _lib.n_native_calls += 1
-    return out
+    flags = _PRECISION[DEFAULT_PRECISION if precision is None else precision]
+    return _forward64("gpde_nnconv_fwd_mixed_keepz", x, csr, pm, root, bias, aggr, flags, attr=edge_attr.detach(), hidden=hidden,
+                      hmax=hmax, hidden_nodes=hidden_nodes, z_keep=z_keep, out=out, ws=ws)
 
 
 def nnconv_backward_hidden_raw(x: torch.Tensor, csr: Csr, hidden: torch.Tensor, dims: Sequence[int],
@@ -1899,18 +1822,11 @@ def nnconv_backward_hidden_raw(x: torch.Tensor, csr: Csr, hidden: torch.Tensor, 
     gh = grad_hidden_acc if accumulate else torch.empty_like(hidden)
     gw = torch.empty_like(w_last)
     gb = None if b_c is None else torch.empty_like(b_c)
-    groot = torch.empty(WIDTH, WIDTH, dtype=torch.float32, device=dev) if (need_root and root is not None) else None
-    gbias = torch.empty(WIDTH, dtype=torch.float32, device=dev) if need_bias else None
-    nbytes = int(lib.gpde_nnconv_bwd_workspace_bytes(n, e, nl, dims_c))
-    if nbytes == 0:
-        _lib.check(-2, "gpde_nnconv_bwd_workspace_bytes")
-    ws = _alloc_ws(nbytes, dev)
+    groot, gbias = _update_grads(root, need_root, need_bias, dev)
+    ws = _queried_ws("gpde_nnconv_bwd_workspace_bytes", dev, n, e, nl, dims_c)
     srp, ssl = csr.src_order
-    P_ = ctypes.c_void_p                                   # the hidden form: the arrays carry their LAST entries only
-    Wa = (P_ * nl)(*([None] * (nl - 1) + [w_last.data_ptr()]))
-    Ba = (P_ * nl)(*([None] * (nl - 1) + [_ptr(b_c)]))
-    gWa = (P_ * nl)(*([None] * (nl - 1) + [gw.data_ptr()]))
-    gBa = (P_ * nl)(*([None] * (nl - 1) + [_ptr(gb)]))
+    front = [None] * (nl - 1)                              # the hidden form: the arrays carry their LAST entries only
+    Wa, Ba, gWa, gBa = (_ptr_array(front + [t]) for t in (w_last, b_c, gw, gb))
     with torch.cuda.device(dev):
         rc = lib.gpde_nnconv_bwd(x.data_ptr(), n, None, None, hidden.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(),
                                  csr.dst.data_ptr(), None, csr.rowptr_host.data_ptr(), _ptr(srp), _ptr(ssl), nl, dims_c, Wa, Ba,
@@ -1933,21 +1849,15 @@ def hidden_backward_raw(csr: Csr, edge_attr: torch.Tensor, dims: Sequence[int],
     nl = len(dims) - 1
     if len(weights) != nl - 1:
         raise ValueError("hidden_backward_raw takes the hidden layers only")
-    dims_c = _lib.dims_array(dims)
-    is_na = isinstance(edge_attr, NodeAttr)
-    if not is_na:
-        edge_attr, perm = attr_in_slot_order(csr, _dense16(edge_attr.detach()))
+    attr_p, na_ref, perm_p, _alive = _attr_source(csr, edge_attr.detach())
     grad_hidden = _operand(grad_hidden.detach(), "grad_hidden", (e, hidden_width(dims)), dev)
-    w_shapes, b_shapes = _mlp_shapes(dims)
-    ws_ = _operands([w.detach() for w in weights], "weights", w_shapes, dev) + [None]
-    bs_ = _operands([None if b is None else b.detach() for b in biases], "biases", b_shapes, dev) + [None]
+    _, dims_c, ws_, bs_ = _mlp_operands(weights, biases, dev, dims)
+    ws_, bs_ = ws_ + [None], bs_ + [None]
     gW = [torch.empty_like(w) for w in ws_[:-1]] + [None]
     gb = [None if b is None else torch.empty_like(b) for b in bs_[:-1]] + [None]
     ws = alloc_bwd_ws(lib, 0, e, nl, dims_c, dev)
-    nas = edge_attr.c_struct() if is_na else None
     with torch.cuda.device(dev):
-        rc = lib.gpde_hidden_bwd(None if is_na else edge_attr.data_ptr(), None if nas is None else ctypes.byref(nas), e,
-                                 None if is_na else perm.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(), nl, dims_c,
+        rc = lib.gpde_hidden_bwd(attr_p, na_ref, e, perm_p, csr.src.data_ptr(), csr.dst.data_ptr(), nl, dims_c,
                                  _ptr_array(ws_), _ptr_array(bs_), grad_hidden.data_ptr(),
                                  _ptr_array(gW), _ptr_array(gb), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
     _lib.check(rc, "gpde_hidden_bwd")
