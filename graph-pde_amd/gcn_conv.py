@@ -104,6 +104,7 @@ class GCNConv(MessagePassing):
         with ops.ver_scope():
             if self.cached and self._cached_device is not None and self._cached_device.csr.rowptr.device == x.device:
                 norm = self._cached_device
+                norm.order()             # (pinned here, never looked up again: a call on another stream is a cache hit like any other)
                 if norm.csr.n_nodes != x.size(0):
                     raise ValueError(f"cached=True pinned a graph of {norm.csr.n_nodes} nodes, x has {x.size(0)} rows")
             else:

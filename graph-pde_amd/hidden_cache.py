@@ -82,7 +82,7 @@ stats = {"hits": 0, "builds": 0, "direct": 0, "we_hits": 0, "we_builds": 0}     
 class _Entry:
     __slots__ = ("key", "hidden", "token", "attr_ref", "csr", "last_key", "repeats", "hits_on_hidden", "hn", "we", "we_key",
                  "we_refs", "big_key", "dkey", "dtoken", "dvirtual", "dcount", "drefs", "twe", "twe_key", "twe_token", "twe_h", "last_partial",
-                 "key_refs", "dkey_refs", "we_key_refs", "twe_key_refs")
+                 "key_refs", "dkey_refs", "we_key_refs", "twe_key_refs", "tag", "dtag", "we_tag", "twe_tag")
 
     def __init__(self):
         self.key = None
@@ -114,6 +114,8 @@ class _Entry:
         self.dkey_refs = None
         self.we_key_refs = None
         self.twe_key_refs = None
+        # where hidden / dvirtual / we / twe were built (ops.StreamTag): a hit from another stream goes through ops.order_hit
+        self.tag = self.dtag = self.we_tag = self.twe_tag = None
 
 
 _entries: "weakref.WeakKeyDictionary[torch.nn.Module, _Entry]" = weakref.WeakKeyDictionary()
@@ -217,6 +219,7 @@ def lookup(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, weights, b
             stats["hits"] += 1
             if ent.hn < csr.n_nodes:
                 ent.big_key = key
+            ops.order_hit(ent.tag, "hidden", (ent.hidden, ent.token.hmax))
             return ent.hidden, ent.token.hmax, ent.hn
     repeated = ent.last_key == key
     if repeated:
@@ -268,6 +271,7 @@ def lookup(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, weights, b
         return None
     ent.key, ent.hidden, ent.token, ent.attr_ref, ent.csr, ent.hn = key, hidden, token, edge_attr, csr, hn
     ent.key_refs = _param_refs(hw + hb)
+    ent.tag = ops.stream_tag(hidden.device)
     ent.hits_on_hidden = 0
     if hn < csr.n_nodes:
         ent.big_key = key            # the whole H does not fit: a training call shares a virtual-H node (lookup_deferred)
@@ -326,6 +330,7 @@ def lookup_deferred(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, w
         if not in_backward_pass() and ent.dtoken.drop_stale():      # a backward over this (still valid) node ended without its deferred pass
             stats["deferred_stale_dropped"] = stats.get("deferred_stale_dropped", 0) + 1
         stats["deferred_hits"] = stats.get("deferred_hits", 0) + 1
+        ops.order_hit(ent.dtag, "deferred", (ent.dvirtual,))
         return ent.dvirtual, ent.dtoken
     if ent.dtoken is not None and ent.dcount <= 1:
         ent.repeats = False             # the last virtual H served a single application: stop speculating
@@ -341,6 +346,7 @@ def lookup_deferred(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, w
                                            *hb, None if b_last is None else b_last.detach())
     ent.dkey, ent.dtoken, ent.dvirtual, ent.drefs, ent.dcount = dkey, token, virtual, (edge_attr, csr), 1
     ent.dkey_refs = _param_refs(named)
+    ent.dtag = ops.stream_tag(virtual.device)
     stats["deferred_builds"] = stats.get("deferred_builds", 0) + 1
     return virtual, token
 
@@ -386,6 +392,7 @@ def lookup_edge_weights_train(module: torch.nn.Module, hidden: torch.Tensor, csr
         # a checkpointed segment - leaves them alone, as `lookup` does)
         if not in_backward_pass():
             ent.twe_token.gh_acc, ent.twe_token.gh_adds, ent.twe_token.side_acc = None, 0, None
+        ops.order_hit(ent.twe_tag, "edge_weights", (ent.twe,))
         return ent.twe
     ent.twe, ent.twe_key, ent.twe_token, ent.twe_h = None, None, None, None
     # memory of the training form: W_e, one dL/dW_e per application in flight and autograd's running sum of them - 16 KiB per
@@ -403,6 +410,7 @@ def lookup_edge_weights_train(module: torch.nn.Module, hidden: torch.Tensor, csr
         return None
     ent.twe, ent.twe_key, ent.twe_token, ent.twe_h = we, key, token, hidden
     ent.twe_key_refs = _param_refs([w_last, b_last])
+    ent.twe_tag = ops.stream_tag(we.device)
     stats["we_builds"] += 1
     return we
 
@@ -423,6 +431,7 @@ def lookup_edge_weights(module: torch.nn.Module, edge_attr: torch.Tensor, csr, p
     params = list(weights) + list(biases)
     if ent is not None and ent.we is not None and ent.we_key == key and _same_params(ent.we_key_refs, params):
         stats["we_hits"] += 1
+        ops.order_hit(ent.we_tag, "edge_weights", (ent.we,))
         return ent.we
     now = force or explicit
     if not now:
@@ -447,5 +456,6 @@ def lookup_edge_weights(module: torch.nn.Module, edge_attr: torch.Tensor, csr, p
         stats["oom_fallbacks"] = stats.get("oom_fallbacks", 0) + 1
         return None
     ent.we_key, ent.we_refs, ent.we_key_refs = key, (edge_attr, csr), _param_refs(params)
+    ent.we_tag = ops.stream_tag(ent.we.device)
     stats["we_builds"] += 1
     return ent.we

@@ -20,6 +20,78 @@ WIDTH = _lib.GPDE_WIDTH
 
 
 # ----------------------------------------------------------------------------------------------
+# cached device buffers and streams (DESIGN.md "Streams"): what the library cached itself, the library orders
+# ----------------------------------------------------------------------------------------------
+cross_stream_hits: "dict[str, int]" = {}    # cache name -> hits from another stream than the entry's builder that were ordered (tests)
+
+
+def _current_stream(dev):
+    return torch.cuda.current_stream(dev)
+
+
+def _capturing() -> bool:
+    return torch.cuda.is_current_stream_capturing()
+
+
+class StreamTag:
+    """Where a cached entry was built: made right after its LAST build kernel was launched.  `stream`: the stream current then;
+    `event`: recorded on it at that point (None for an entry built while the stream was being captured - nothing ran - or
+    `synced`: the builder waited on the host for the device after the build, as build_csr does when it reads the bad-edge count
+    back - such an entry cannot be read unfinished and needs no event); `ordered`: the other streams that have already been
+    queued behind the build."""
+    __slots__ = ("dev", "stream", "event", "synced", "ordered")
+
+    def __init__(self, dev, synced: bool = False):
+        self.dev, self.synced, self.ordered = dev, synced, None
+        self.stream = _current_stream(dev)
+        self.event = None
+        if not synced and not _capturing():
+            self.event = torch.cuda.Event()
+            self.event.record(self.stream)
+
+
+def stream_tag(dev, synced: bool = False) -> Optional[StreamTag]:
+    """The StreamTag of an entry just built on `dev` (None off the GPU: the host tier builds entries from CPU stand-ins)."""
+    return StreamTag(dev, synced) if torch.device(dev).type == "cuda" else None
+
+
+def order_hit(tag: Optional[StreamTag], cache: str, buffers=()):
+    """A cache hit: called before the entry's device buffers go to a native call.  On the stream the entry was built on - every
+    training loop - this compares two stream handles and returns: no event call, no allocation.  From another stream, once per
+    entry and stream: the stream waits for the build's event and every buffer is `record_stream`ed on it, so that the caching
+    allocator does not hand the block out again (after `clear_caches()`, an LRU eviction, a replaced pack) while that stream may
+    still read it.  While the stream is being captured nothing is issued: capture.py warms up, synchronises the device and records
+    on one stream, and pins what the graph reads."""
+    if tag is None or _current_stream(tag.dev) == tag.stream:
+        return
+    _order_cross_stream(tag, _current_stream(tag.dev), cache, buffers)
+
+
+def _wait_for_build(tag: StreamTag, stream):
+    if tag.event is not None:
+        stream.wait_event(tag.event)
+    elif not tag.synced:                     # built during a capture: no event exists - behind everything queued on the builder
+        stream.wait_stream(tag.stream)
+
+
+def _keep_for(t: torch.Tensor, stream):
+    t.detach().record_stream(stream)
+
+
+def _order_cross_stream(tag: StreamTag, stream, cache: str, buffers):
+    if _capturing() or (tag.ordered is not None and stream in tag.ordered):
+        return
+    _wait_for_build(tag, stream)
+    for t in buffers:
+        if t is not None:
+            _keep_for(t, stream)
+    if tag.ordered is None:
+        tag.ordered = set()
+    tag.ordered.add(stream)
+    cross_stream_hits[cache] = cross_stream_hits.get(cache, 0) + 1
+
+
+# ----------------------------------------------------------------------------------------------
 # destination-sorted CSR, cached per edge_index tensor
 # ----------------------------------------------------------------------------------------------
 @dataclass
@@ -39,6 +111,8 @@ class Csr:
     n_src_nodes: Optional[int] = None        # a RECTANGULAR graph: `src` indexes this many source nodes, `n_nodes` counts the destination
     #                                          rows (rowptr has n_nodes + 1 entries); None: square, one node set
     _flow_flipped: bool = False              # built from edge_index with its rows swapped (flow='target_to_source' of the module)
+    _src_order_tag: Optional[StreamTag] = None   # where src_order was built (order_hit)
+    _identity_tag: Optional[StreamTag] = None    # where _identity was built (attr_in_slot_order)
 
     @property
     def n_src(self) -> int:
@@ -72,7 +146,9 @@ class Csr:
                 rc = lib.gpde_csr_source_order(self.src.data_ptr(), self.n_edges, n_src, srp.data_ptr(),
                                                ssl.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
             _lib.check(rc, "gpde_csr_source_order")
-            self._src_order = (srp, ssl)
+            self._src_order, self._src_order_tag = (srp, ssl), stream_tag(dev)
+            return self._src_order
+        order_hit(self._src_order_tag, "src_order", self._src_order)
         return self._src_order
 
     @property
@@ -244,6 +320,7 @@ def attr_in_slot_order(csr: "Csr", edge_attr: torch.Tensor):
         return edge_attr, csr.perm
     if csr._identity is None:
         csr._identity = torch.arange(e, dtype=torch.int32, device=csr.perm.device)
+        csr._identity_tag = stream_tag(csr.perm.device, synced=True)      # (complete: the probe below waits for the device)
         csr._attr_sorted = {}
         # is `perm` the identity (a graph already in slot order)?  A full comparison is a pass over 95.5 M indices plus a byte mask
         # of the same length on the headline graph - 21 of the 23 ms a NEW sample's first call spent here (profiles/
@@ -261,7 +338,11 @@ def attr_in_slot_order(csr: "Csr", edge_attr: torch.Tensor):
         out = gather_rows(src, csr.perm)
         while len(csr._attr_sorted) >= 2:
             csr._attr_sorted.pop(next(iter(csr._attr_sorted)))
-        hit = csr._attr_sorted[key] = (edge_attr, out)  # the source tensor is kept alive: its address is part of the key
+        hit = csr._attr_sorted[key] = (edge_attr, out, stream_tag(out.device))  # the source tensor is kept alive: its address is part of the key
+    else:
+        order_hit(hit[2], "attr_slot_order", (hit[1],))
+    # the identity permutation serves every entry of this CSR, built or hit: kept for a stream other than the one it was made on
+    order_hit(csr._identity_tag, "attr_identity", (csr._identity,))
     return hit[1], csr._identity
 
 
@@ -419,7 +500,7 @@ def _build_csr_general(edge_index: torch.Tensor, n_dst: int, n_src: Optional[int
     return Csr(n_dst, e, rowptr, src, dst, perm, _max_in_degree=max_deg, n_src_nodes=n_src, _flow_flipped=flip)
 
 
-_csr_cache: "dict[tuple, tuple]" = {}      # key -> (storage kept alive, nbytes, Csr); LRU order
+_csr_cache: "dict[tuple, tuple]" = {}      # key -> (storage kept alive, nbytes, Csr, StreamTag or None); LRU order
 _CSR_CACHE_MAX_ENTRIES = 64
 _CSR_CACHE_MAX_BYTES = 8 << 30
 
@@ -446,9 +527,13 @@ def csr_for(edge_index: torch.Tensor, n_nodes: int, n_src: Optional[int] = None,
     hit = _csr_cache.pop(key, None)
     if hit is not None:
         _csr_cache[key] = hit            # move to the MRU end
-        return hit[2]
+        csr = hit[2]
+        if hit[3] is not None:               # (an entry without a tag - off the GPU - may be a stand-in without these arrays)
+            order_hit(hit[3], "csr", (csr.rowptr, csr.src, csr.dst, csr.perm))
+        return csr
     csr = build_csr(edge_index, n_nodes, n_src, flip)
-    _csr_cache[key] = (storage, storage.nbytes(), csr)
+    # (build_csr read the bad-edge count back: the arrays are complete - a hit from another stream only keeps them from being recycled)
+    _csr_cache[key] = (storage, storage.nbytes(), csr, stream_tag(edge_index.device, synced=int(edge_index.size(1)) > 0))
     while len(_csr_cache) > _CSR_CACHE_MAX_ENTRIES or \
             (len(_csr_cache) > 1 and sum(v[1] for v in _csr_cache.values()) > _CSR_CACHE_MAX_BYTES):
         _csr_cache.pop(next(iter(_csr_cache)))
@@ -497,6 +582,7 @@ def clear_caches():
     _pack_by_ptr.clear()
     _stage_cache.clear()
     _gcn_norm_cache.clear()
+    cross_stream_hits.clear()
 
 
 # ----------------------------------------------------------------------------------------------
@@ -540,6 +626,7 @@ class PackedMlp:
     dims: Tuple[int, ...]
     packed: torch.Tensor            # float32 flat buffer in libgpde layout
     dims_c: object                  # ctypes int32 array (kept alive)
+    tag: Optional[StreamTag] = None  # where pack_mlp built it (order_hit)
 
 
 _pack_cache: "dict[tuple, tuple]" = {}       # key -> (weakrefs of the parameters, PackedMlp); LRU order
@@ -568,6 +655,7 @@ def pack_mlp(weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Te
         # same parameter objects still alive => the addresses were not recycled
         if all(r() is t for r, t in zip(refs, list(weights) + [b for b in biases if b is not None])):
             _pack_cache[key] = hit           # MRU
+            order_hit(pm.tag, "pack_mlp", (pm.packed,))
             return pm
     dims_c = _lib.dims_array(dims)
     nbytes = int(lib.gpde_mlp_pack_bytes(n, dims_c))
@@ -583,7 +671,7 @@ def pack_mlp(weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Te
     with torch.cuda.device(dev):
         rc = lib.gpde_mlp_pack(n, dims_c, wp, bp, packed.data_ptr(), nbytes, _stream_ptr(dev))
     _lib.check(rc, "gpde_mlp_pack")
-    pm = PackedMlp(dims, packed, dims_c)
+    pm = PackedMlp(dims, packed, dims_c, stream_tag(dev))
     old_key = _pack_by_ptr.get(ptrs)
     if old_key is not None:
         _pack_cache.pop(old_key, None)       # the same parameters at an older version
@@ -2525,6 +2613,13 @@ class GcnNorm:
     def __init__(self, csr: Csr, coef: torch.Tensor, self_coef: torch.Tensor, flags: int):
         self.csr, self.coef, self.self_coef, self.flags = csr, coef, self_coef, flags
         self._reversed = None
+        self._tag = self._reversed_tag = None       # where the coefficients / the reversed pair were built (order_hit)
+
+    def order(self):
+        """A hit on this normalisation - from the cache of gcn_norm or from a module that pinned it (GCNConv(cached=True)): the
+        coefficients and the arrays of the graph they index, ordered for the current stream (order_hit)."""
+        csr = self.csr
+        order_hit(self._tag, "gcn_norm", (self.coef, self.self_coef, csr.rowptr, csr.src, csr.dst, csr.perm))
 
     @property
     def reversed(self):
@@ -2539,6 +2634,11 @@ class GcnNorm:
             else:
                 rev = build_csr(csr.edge_index, csr.n_nodes, flip=True)
                 self._reversed = (rev, gather_rows(self.coef.view(-1, 1), rev.perm).view(-1))
+                self._reversed_tag = stream_tag(self.coef.device)
+                return self._reversed
+        if self._reversed_tag is not None:
+            rev, coef = self._reversed
+            order_hit(self._reversed_tag, "gcn_norm", (rev.rowptr, rev.src, rev.dst, rev.perm, coef))
         return self._reversed
 
 
@@ -2580,6 +2680,7 @@ def gcn_norm(csr: Csr, edge_weight: Optional[torch.Tensor] = None, improved: boo
     hit = _gcn_norm_cache.pop(key, None)
     if hit is not None:
         _gcn_norm_cache[key] = hit
+        hit[2].order()
         return hit[2]
     lib = _lib.lib()
     _require_cuda(csr.rowptr, "csr")
@@ -2596,6 +2697,7 @@ def gcn_norm(csr: Csr, edge_weight: Optional[torch.Tensor] = None, improved: boo
     _lib.check(rc, "gpde_gcn_norm")
     _lib.n_native_calls += 1
     norm = GcnNorm(csr, coef, self_coef, flags)
+    norm._tag = stream_tag(dev)
     # bytes an entry keeps alive once the CSR cache has let go of the graph: rowptr / src / dst / perm, coef, self_coef, edge_weight -
     # counted twice, for the reversed graph a backward adds (GcnNorm.reversed)
     nbytes = 2 * (16 * e + 8 * n + 4) + (0 if edge_weight is None else 4 * e)

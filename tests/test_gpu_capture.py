@@ -100,11 +100,13 @@ def test_captured_call_takes_new_inputs_and_checks_shapes():
         gp.capture(model, x0.cpu())
 
 
-@pytest.mark.parametrize("name", sorted(mgkn_workloads.WORKLOADS))
-def test_captured_training_step_follows_the_direct_steps(name):
+@pytest.mark.parametrize("name,twin_between", [pytest.param(n, False, id=n) for n in sorted(mgkn_workloads.WORKLOADS)] +
+                         [pytest.param("mgkn_orthogonal_burgers1d", True, id="mgkn_orthogonal_burgers1d-twin_between")])
+def test_captured_training_step_follows_the_direct_steps(name, twin_between):
     """A whole optimisation step (forward with autograd, loss, native backward of every call, Adam with its step count on the
     device) recorded once: four replays leave the weights where four direct steps of a twin model leave them (to the summation-order
-    level) with the same losses, and a DIRECT forward afterwards sees the updated weights (the replay drops the host-side caches)."""
+    level) with the same losses, and a DIRECT forward afterwards sees the updated weights (the replay drops the host-side caches).
+    `twin_between`: the twin's direct steps run between the recording and the first replay instead of in front of both."""
     d = torch.device("cuda:0")
     hidden_cache.clear()
     wl_a = mgkn_workloads.WORKLOADS[name](d, capturable=True)
@@ -112,16 +114,21 @@ def test_captured_training_step_follows_the_direct_steps(name):
     for ma, mb in zip(wl_a.modules, wl_b.modules):
         mb.load_state_dict(ma.state_dict())
     warm = 3
-    # the twin's direct steps FIRST, then the recording and its replays with nothing else training on the device in between.  (Round 6:
-    # with the twin's eager training steps BETWEEN the recording and the first replay, that replay's forward returned another loss -
-    # 59.3 for 72.9 - while a recording replayed on its own follows the direct steps exactly (scripts/dbg_capture_train3.py /
-    # dbg_capture_train4.py; the round-5 library shows the same when replays and twin steps alternate).  Not understood; a second
-    # model TRAINING eagerly on the same device between a recording and its replays is outside what gp.capture promises for now -
-    # stated in capture.py.)
-    lb_warm = [float(wl_b.train_step().detach()) for _ in range(warm)]
-    lb = [float(wl_b.train_step().detach()) for _ in range(4)]
-    torch.cuda.synchronize()
+    # the twin's direct steps in front of the recording, or between the recording and its first replay.  (Round 6 saw the first replay
+    # return another loss in the second order - 59.3 for 72.9 - and left it unexplained; run again in that order later (DESIGN.md
+    # §6h), the replays gave the direct steps' losses to the last digit, and the order became a case of this test.)
+    def twin_steps():
+        lb_warm = [float(wl_b.train_step().detach()) for _ in range(warm)]
+        assert len(lb_warm) == warm
+        return [float(wl_b.train_step().detach()) for _ in range(4)]
+    if not twin_between:
+        lb = twin_steps()
+        torch.cuda.synchronize()
     cap = gp.capture(wl_a.train_step, warmup=warm, updates_parameters=True)          # (recording executes nothing: 3 steps so far)
+    if twin_between:
+        torch.cuda.synchronize()
+        lb = twin_steps()
+        torch.cuda.synchronize()
     calls = _lib.n_native_calls
     la = []
     for _ in range(4):
