@@ -241,8 +241,8 @@ struct FusedChoice { FusedKind kind; bool g2f16; };
 FusedChoice choose_fused(const GpdePackLayout& L, int mode, uint32_t flags, int64_t n_edges, int kt) {
     FusedChoice c{FK_GENERIC, false};
     if (mode != 1 || !(flags & GPDE_FWD_F16SPLIT)) return c;
-    GpdeFusedArgs probe{};
-    probe.k0 = L.k0; probe.K1P = L.K1P; probe.K2P = L.K2P; probe.kt = kt;
+    GpdeFusedArgs probe = gpde_fused_probe(L);
+    probe.kt = kt;
     if (!gpde_fused_f16v3_supported(probe)) return c;
     c.kind = FK_V3;
     // f16-split aggregation inside the fused kernel: worth its three tiny pre-pass launches from a few ten
@@ -260,11 +260,7 @@ bool takes_edge_path(const Plan& P, uint32_t flags, int64_t n_nodes, int64_t n_e
                      bool mixed, int kt) {
     const GpdePackLayout& L = P.L;
     bool store_ok = false;
-    if (L.mode == 1 && L.k0 + 1 <= 8) {
-        GpdeFusedArgs probe{};
-        probe.k0 = L.k0; probe.K1P = L.K1P; probe.K2P = L.K2P;
-        store_ok = gpde_fused_store_supported(probe);
-    }
+    if (L.mode == 1 && L.k0 + 1 <= 8) store_ok = gpde_fused_store_supported(gpde_fused_probe(L));
     return ((flags & GPDE_FWD_F16SPLIT) || (hidden && hidden_absmax)) && !mixed && !kt && L.has_w3s && P.n_chunks == 1 &&
            n_edges >= 4096 && n_edges <= 4 * n_nodes && n_edges < ((int64_t)1 << 24) &&
            !(flags & GPDE_FWD_NO_EDGE_PATH) &&
@@ -424,15 +420,10 @@ int fwd_impl(const FwdArgs& a) {
             ProfScope ps(GPDE_PROF_FUSED, a.stream);
             GpdeFusedArgs f{};
             f.attr = a.edge_attr; f.rowptr = a.rowptr; f.perm = a.perm;
-            f.w1 = pk + L.off_w1; f.w2t = pk + L.off_w2t; f.b2 = pk + L.off_b2;
-            f.w2h = pk + L.off_w2h; f.ucol = pk + L.off_ucol; f.w1h = pk + L.off_w1h; f.fcol = pk + L.off_fcol;
-            f.hout = Hbuf; f.hmax_out = nullptr; f.k0 = L.k0; f.K1P = L.K1P; f.K2P = L.K2P;
+            gpde_fused_set_pack(f, pk, L);
+            f.hout = Hbuf; f.hmax_out = nullptr;
             f.nc0 = 0; f.nc1 = (int)a.n_nodes; f.e_chunk0 = 0;
-            const int ns = L.K2P / GP_TN;
-            int groups = gpde_num_cus() / ns; if (groups < 1) groups = 1;
-            const int64_t gcap = ((a.n_edges + GP_TE - 1) / GP_TE + GP_WAVES - 1) / GP_WAVES;
-            if (groups > gcap) groups = (int)gcap;
-            f.n_groups = groups;
+            f.n_groups = gpde_fused_groups(L.K2P, gpde_group_cap_fwd(a.n_edges));
             if ((rc = gpde_launch_fused_store(f, a.stream)) != GPDE_OK) return rc;
             Hrows = Hbuf;
         }
@@ -486,14 +477,11 @@ int fwd_impl(const FwdArgs& a) {
         if (a.n_edges > 0) {
             GpdeFusedArgs f{};
             f.x = a.x; f.attr = a.edge_attr; f.rowptr = a.rowptr; f.src = a.src; f.dst = a.dst; f.perm = a.perm;
-            f.w1 = pk + L.off_w1; f.w2t = pk + L.off_w2t; f.b2 = pk + L.off_b2;
-            f.w2h = pk + L.off_w2h; f.ucol = pk + L.off_ucol;
-            f.w1h = pk + L.off_w1h; f.fcol = pk + L.off_fcol;
+            gpde_fused_set_pack(f, pk, L);
             float* zc = a.z_keep ? a.z_keep + (size_t)nc0 * GP_W * L.K2P : zbuf;
             f.hbuf = hfinal; f.zbuf = zc; f.xs = xs; f.scal = scal;
             f.kt = a.kt; f.hmax = (from_h && xs) ? (const unsigned*)a.hidden_absmax : nullptr;
             for (int d = 0; d < 8; ++d) f.sel[d] = (a.kt && a.sel) ? a.sel[d < L.k0 ? d : L.k0 - 1] : 0;
-            f.k0 = L.k0; f.K1P = L.K1P; f.K2P = L.K2P;
             f.nc0 = (int)nc0; f.nc1 = (int)nc1; f.e_chunk0 = 0; f.n_groups = P.n_groups;
             {
                 ProfScope ps(GPDE_PROF_FUSED, a.stream);

@@ -867,7 +867,7 @@ GpdeGemmArgs gemm0() {
 
 // C (+)= A^T . B over `rows` rows, split-K with ordered partial reduction
 int gemm_tn_acc(const float* A, int lda, int M, const float* B, int ldb, int Ncols, int rows, float* C,
-                int ldc_dense, float* part, size_t part_floats, int accumulate, hipStream_t st) {
+                float* part, size_t part_floats, int accumulate, hipStream_t st) {
     const int tiles = ((M + 127) / 128) * ((Ncols + 127) / 128);
     int splits = 1;
     // skinny outputs (dW_1: 1024 x 8) are pure streaming of the tall operand: enough splits to put ~1024 workgroups
@@ -878,7 +878,6 @@ int gemm_tn_acc(const float* A, int lda, int M, const float* B, int ldb, int Nco
     GpdeGemmArgs g = gemm0();
     g.A = A; g.lda = lda; g.a_kcontig = 0; g.B = B; g.ldb = ldb; g.b_kcontig = 0;
     g.M = M; g.N = Ncols; g.K = rows; g.ldc = Ncols;
-    (void)ldc_dense;
     if (splits == 1) {            // one partial: straight into C (C + P is what either accumulate form computes)
         g.C = C; g.accumulate = accumulate ? 1 : 0;
         return gpde_launch_gemm(g, st);
@@ -1008,7 +1007,7 @@ int bwd_node_terms(const float* x, int N, const float* root, const float* grad_o
         if ((rc = gpde_launch_gemm(g, st)) != GPDE_OK) return rc;
     }
     if (grad_root)
-        if ((rc = gemm_tn_acc(x, GP_W, GP_W, grad_out, GP_W, GP_W, N, grad_root, GP_W, part, part_floats, acc_root, st)) != GPDE_OK) return rc;
+        if ((rc = gemm_tn_acc(x, GP_W, GP_W, grad_out, GP_W, GP_W, N, grad_root, part, part_floats, acc_root, st)) != GPDE_OK) return rc;
     if (grad_bias) {
         int splits = 1; while (splits < 64 && N / (splits * 2) >= 64) splits *= 2;
         hipLaunchKernelGGL(k_colsum, dim3(1, splits), dim3(256), 0, st, grad_out, N, GP_W, GP_W, splits, part, (unsigned*)nullptr);
@@ -1224,7 +1223,7 @@ extern "C" int gpde_edge_weights_bwd(const float* grad_edge_weights, const float
         g.C = grad_hidden; g.ldc = K2P; g.M = E; g.N = K2P; g.K = NW3; g.mask = hidden; g.ldmask = K2P;
         if ((rc = gpde_launch_gemm(g, st)) != GPDE_OK) return rc;
         if (grad_w_last)
-            if ((rc = gemm_tn_acc(grad_edge_weights, NW3, NW3, hidden, K2P, K2P, E, F(P.off_dw3p), K2P, F(P.off_part), (size_t)16 * wn, 0, st)) != GPDE_OK) return rc;
+            if ((rc = gemm_tn_acc(grad_edge_weights, NW3, NW3, hidden, K2P, K2P, E, F(P.off_dw3p), F(P.off_part), (size_t)16 * wn, 0, st)) != GPDE_OK) return rc;
     }
     if (grad_w_last)
         hipLaunchKernelGGL(k_unpad_mat, dim3(nblk((size_t)NW3 * k2)), dim3(T), 0, st, F(P.off_dw3p), NW3, k2, K2P, grad_w_last);
@@ -1254,130 +1253,204 @@ namespace {
 //                                       dU_2 = (sum_l x_j^(l) . dZ_i^(l)) (.) [H_2 > 0]  (a K = 64 L contraction), then ONE MLP backward
 enum BwdPhase { BWD_FULL = 0, BWD_CONV = 1, BWD_MLP = 2, BWD_LIGHT = 3, BWD_DEFER = 4 };
 
+// The arguments of bwd_impl by name.  A default means "not given"; `bwd_common` fills what every entry point has.
+struct BwdArgs {
+    // graph
+    const float* x = nullptr;
+    int64_t n_nodes = 0, n_edges = 0;
+    const int32_t *rowptr = nullptr, *src = nullptr, *dst = nullptr, *rowptr_host = nullptr;
+    const int32_t *src_rowptr = nullptr, *src_slots = nullptr;   // CSR slots regrouped by source: grad_x summed in slot order
+    int aggr = GPDE_AGGR_ADD;
+    // attribute source: a tensor [n_edges][k0] read through `perm`, or with kt > 0 a NODE table [n_nodes][kt] - slot d of an
+    // edge's attribute is table[(sel[d] >> 8 ? dst : src)][sel[d] & 255] (row f3: GpdeNodeAttr) and perm is unused
+    const float* edge_attr = nullptr;
+    const int32_t *perm = nullptr, *sel = nullptr;
+    int kt = 0;
+    // kernel MLP
+    int n_layers = 0;
+    const int32_t* dims = nullptr;
+    const float *const *W = nullptr, *const *b = nullptr;
+    const float* root = nullptr;
+    // incoming gradients
+    const float* grad_out = nullptr;
+    const float* grad_hidden_in = nullptr;      // BWD_MLP: dL/dU of the last hidden layer [CSR slot][K2P]
+    // outputs
+    float *grad_x = nullptr, *grad_root = nullptr, *grad_bias = nullptr;
+    float *const *grad_W = nullptr, *const *grad_b = nullptr;
+    float* grad_attr = nullptr;                 // BWD_FULL, tensor attributes of <= 8 slots: dL/d edge_attr [E][k0] in the CALLER's edge order
+    float* grad_hidden_out = nullptr;           // BWD_CONV: dL/dU of the last hidden layer [CSR slot][K2P]
+    // kept state
+    const float* z_saved = nullptr;             // Z of the keep-Z forward: dW_3 is taken from it instead of re-aggregating
+    const float* hidden = nullptr;              // BWD_CONV: the last hidden activations of every edge [CSR slot][K2P]
+    // hpart (BWD_FULL / LIGHT / DEFER): the last hidden activations of the in-edges of nodes [0, hpart_nodes) are GIVEN (a partial
+    // H kept by the caller, CSR slots [0, rowptr[hpart_nodes])): node chunks below that bound read them instead of recomputing
+    const float* hpart = nullptr;
+    int64_t hpart_nodes = 0;
+    // gh_accumulate (BWD_CONV): dL/dU is ADDED to grad_hidden_out (the applications of a module sharing its hidden activations
+    // sum it there, in call order - the same additions autograd would make with six [E][K2P] tensors)
+    bool gh_accumulate = false;
+    // deferred stacks (BWD_DEFER): layer inputs and output gradients of the n_defer applications, [n_defer][n_nodes][64] each
+    int n_defer = 0;
+    const float *x_stack = nullptr, *g_stack = nullptr;
+    // workspace and stream
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+    hipStream_t st = nullptr;
+};
+
+BwdArgs bwd_common(int64_t n_edges, int n_layers, const int32_t* dims, const float* const* W, const float* const* b,
+                   float* const* grad_W, float* const* grad_b, void* ws, size_t ws_bytes, void* stream) {
+    BwdArgs a;
+    a.n_edges = n_edges; a.n_layers = n_layers; a.dims = dims; a.W = W; a.b = b; a.grad_W = grad_W; a.grad_b = grad_b;
+    a.ws = ws; a.ws_bytes = ws_bytes; a.st = (hipStream_t)stream;
+    return a;
+}
+void bwd_graph(BwdArgs& a, int64_t n_nodes, const int32_t* rowptr, const int32_t* src, const int32_t* dst,
+               const int32_t* rowptr_host, int aggr) {
+    a.n_nodes = n_nodes; a.rowptr = rowptr; a.src = src; a.dst = dst; a.rowptr_host = rowptr_host; a.aggr = aggr;
+}
+void bwd_attr_source(BwdArgs& a, const float* edge_attr, const int32_t* perm, const GpdeNodeAttr* node_attr) {
+    if (node_attr) { a.edge_attr = node_attr->table; a.kt = node_attr->stride; a.sel = node_attr->sel; }
+    else { a.edge_attr = edge_attr; a.perm = perm; }
+}
+
+// What a stage works on: in-edges of the nodes [na, nb) = CSR slots [e0, e0 + rows) (BWD_MLP: plain edge chunks, na = nb = -1)
+struct Chunk {
+    int na, nb, e0, rows;
+    const float* h;      // the chunk's last hidden activations when they are GIVEN (hpart), row 0 = slot e0; else null
+    bool du_pre;         // set by the per-edge stage: its kernel wrote dU_2^T, its row scales and tile column partials
+};
+
 // gpde_bwd_trace_begin / _end (include/gpde.h): one GPDE_BWD_TRACE_FIELDS record per chunk bwd_impl processes, on this thread
 // (a record type of this namespace: the vector's instantiations stay internal, -fvisibility=hidden does not cover std::)
 struct BwdTraceRec { int32_t f[GPDE_BWD_TRACE_FIELDS]; };
 thread_local bool g_bwd_trace_on = false;
 thread_local std::vector<BwdTraceRec> g_bwd_trace;
 
-int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_attr, int64_t n_edges,
-             const int32_t* rowptr, const int32_t* src, const int32_t* dst, const int32_t* perm,
-             const int32_t* rowptr_host, int n_layers, const int32_t* dims, const float* const* W,
-             const float* const* b, const float* root, int aggr, const float* grad_out, float* grad_x,
-             float* const* grad_W, float* const* grad_b, float* grad_root, float* grad_bias,
-             const float* hidden, float* grad_hidden_out, const float* grad_hidden_in, void* ws,
-             size_t ws_bytes, hipStream_t st, const int32_t* src_rowptr = nullptr, const int32_t* src_slots = nullptr,
-             const float* z_saved = nullptr, int n_defer = 0, const float* x_stack = nullptr, const float* g_stack = nullptr,
-             const float* hpart = nullptr, int64_t hpart_nodes = 0, int kt = 0, const int32_t* sel = nullptr,
-             float* grad_attr = nullptr, bool gh_accumulate = false) {
-    // gh_accumulate (BWD_CONV): dL/dU of the last hidden layer is ADDED to grad_hidden_out (the applications of a module sharing its
-    // hidden activations sum it there, in call order - the same additions autograd would make with six [E][K2P] tensors)
-    // grad_attr (BWD_FULL, tensor attributes of <= 8 slots): [E][k0] in the CALLER's edge order, dL/d edge_attr
-    // kt > 0: `edge_attr` is a NODE table [n_nodes][kt] and slot d of an edge's attribute is table[(sel[d] >> 8 ? dst : src)][sel[d] & 255]
-    // (row f3: GpdeNodeAttr); perm is unused
-    // hpart (BWD_LIGHT / BWD_DEFER): the last hidden activations of the in-edges of nodes [0, hpart_nodes) are GIVEN (a partial
-    // H kept by the caller, CSR slots [0, rowptr[hpart_nodes])): node chunks below that bound read them instead of recomputing
-    const bool do_conv = phase != BWD_MLP && phase != BWD_DEFER, do_mlp = phase != BWD_CONV && phase != BWD_LIGHT;
+// the record of the chunk in progress: each field is set where its branch is taken.  Unarmed, the trace costs the one
+// thread-local read of `on`: every write tests it first
+struct BwdTrace {
+    const bool on = g_bwd_trace_on;
+    int phase = 0, call_amax = 0;
+    BwdTraceRec rec{};
+    void set(int field, int value) { if (on) rec.f[field] = value; }
+    void begin(const Chunk& c) {
+        if (!on) return;
+        rec = BwdTraceRec{};
+        rec.f[GPDE_BWD_TRACE_PHASE] = phase; rec.f[GPDE_BWD_TRACE_CALL_AMAX] = call_amax;
+        rec.f[GPDE_BWD_TRACE_NA] = c.na; rec.f[GPDE_BWD_TRACE_NB] = c.nb; rec.f[GPDE_BWD_TRACE_E0] = c.e0; rec.f[GPDE_BWD_TRACE_ROWS] = c.rows;
+    }
+    void emit() { if (on) g_bwd_trace.push_back(rec); }
+};
+
+// One backward call: the plan, the workspace, the decisions taken once (setup) and one function per stage.
+struct BwdCall {
+    const BwdPhase phase;
+    const BwdArgs& a;
     const GpdeSwitches& SW = gpde_switches();       // developer / A-B switches, read once per process (gpde_common.h)
+    const hipStream_t st;
+    const bool do_conv, do_mlp, light;
+    static constexpr int T = 256;
     BwdPlan P;
-    const bool h_all = phase == BWD_FULL && hpart && hpart_nodes >= n_nodes;     // H of every edge kept by the forward
-    int rc = make_bwd_plan(n_nodes, n_edges, n_layers, dims, ws_bytes, false, &P, phase == BWD_DEFER ? n_defer : 0, h_all);
+    GpdePackLayout PL;
+    char* w = nullptr;
+    int n = 0, K2P = 0, N = 0;
+    // decided by setup(), constant afterwards
+    bool f16s_du1 = false, f16s_dw2 = false;        // dU_1 / dW_2 on the split-f16 GEMMs
+    bool fast_last = false;                         // the last hidden layer of the recompute on the fused store kernel (pack at off_pack)
+    bool h1_on_the_fly = false;                     // H_1 is never written from 8192 rows on
+    bool call_amax = false;                         // one bound per attribute slot for the whole call (off_amax8)
+    bool zagg16 = false;                            // Z re-aggregated on the split-f16 kernel (x pairs at off_xs)
+    NodeAttrSel nas{};
+    BwdTrace tr;
+
+    BwdCall(BwdPhase ph, const BwdArgs& args)
+        : phase(ph), a(args), st(args.st), do_conv(ph != BWD_MLP && ph != BWD_DEFER), do_mlp(ph != BWD_CONV && ph != BWD_LIGHT),
+          light(ph == BWD_LIGHT) {}
+    float* F(size_t off) const { return (float*)(w + off); }
+    bool skip_h1(int rows) const { return h1_on_the_fly && rows >= 8192; }
+    int run();
+    int setup();
+    int recompute(const Chunk& c, int last);
+    int mlp_backward(const Chunk& c, const float* dUlast);
+    int next_chunk(int na, Chunk* c);
+    int defer_chunk(const Chunk& c);
+    int conv_chunk(Chunk& c);
+    int chunk_z(const Chunk& c, const float* Hlast, const float** Z);
+    int last_layer_grads(const Chunk& c, const float* Z);
+    int edge_kernel(const Chunk& c, bool gh_acc) const;
+    int edge_backward(Chunk& c, const float* Hlast, float* dUc);
+    int finish();
+};
+
+// padded weights, zeroed accumulators, the operand images, the call-wide bounds - and the refusals of the phases
+int BwdCall::setup() {
+    const int32_t* dims = a.dims;
+    const bool h_all = phase == BWD_FULL && a.hpart && a.hpart_nodes >= a.n_nodes;     // H of every edge kept by the forward
+    int rc = make_bwd_plan(a.n_nodes, a.n_edges, a.n_layers, dims, a.ws_bytes, false, &P, phase == BWD_DEFER ? a.n_defer : 0, h_all);
     if (rc != GPDE_OK) return rc;
-    const int n = n_layers, K2P = P.K2P;
-    const int N = (int)n_nodes;
-    // the record of the chunk in progress: each field is set (trs) where its branch is taken.  Unarmed, the trace costs the one
-    // thread-local read here: every write below tests the local `trace` first
-    const bool trace = g_bwd_trace_on;
-    BwdTraceRec trr{};
-    int32_t* tr = trr.f;
-    int tr_amax = 0;
-    auto trs = [&](int field, int value) { if (trace) tr[field] = value; };
-    auto tr_begin = [&](int na_, int nb_, int e0_, int rows_) {
-        if (!trace) return;
-        for (int f_ = 0; f_ < GPDE_BWD_TRACE_FIELDS; ++f_) tr[f_] = 0;
-        tr[GPDE_BWD_TRACE_PHASE] = phase; tr[GPDE_BWD_TRACE_CALL_AMAX] = tr_amax;
-        tr[GPDE_BWD_TRACE_NA] = na_; tr[GPDE_BWD_TRACE_NB] = nb_; tr[GPDE_BWD_TRACE_E0] = e0_; tr[GPDE_BWD_TRACE_ROWS] = rows_;
-    };
-    auto tr_emit = [&]() { if (trace) g_bwd_trace.push_back(trr); };
-    char* w = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    auto F = [&](size_t off) { return (float*)(w + off); };
-    const int T = 256;
+    n = a.n_layers; K2P = P.K2P; N = (int)a.n_nodes;
+    tr.phase = phase;
+    w = (char*)(((uintptr_t)a.ws + 255) / 256 * 256);
 
     // ---- padded weights, zeroed gradient accumulators --------------------------------------------------
     for (int l = 1; l < n && do_mlp; ++l) {
         const size_t wn = (size_t)P.KP[l] * P.KP[l - 1];
-        hipLaunchKernelGGL(k_pad_mat, dim3(nblk(wn)), dim3(T), 0, st, W[l - 1], dims[l], dims[l - 1], dims[l - 1],
+        hipLaunchKernelGGL(k_pad_mat, dim3(nblk(wn)), dim3(T), 0, st, a.W[l - 1], dims[l], dims[l - 1], dims[l - 1],
                            P.KP[l], P.KP[l - 1], F(P.off_wp[l]));
-        if (b[l - 1]) hipLaunchKernelGGL(k_pad_mat, dim3(nblk(P.KP[l])), dim3(T), 0, st, b[l - 1], 1, dims[l], dims[l], 1, P.KP[l], F(P.off_bp[l]));
+        if (a.b[l - 1]) hipLaunchKernelGGL(k_pad_mat, dim3(nblk(P.KP[l])), dim3(T), 0, st, a.b[l - 1], 1, dims[l], dims[l], 1, P.KP[l], F(P.off_bp[l]));
         else GP_HIP_CHECK(gpde_zero_async(F(P.off_bp[l]), (size_t)P.KP[l] * 4, st));
         GP_HIP_CHECK(gpde_zero_async(F(P.off_dwp[l]), wn * 4, st));
         GP_HIP_CHECK(gpde_zero_async(F(P.off_dbp[l]), (size_t)P.KP[l] * 4, st));
     }
-    const bool f16s_du1 = do_mlp && P.f16s_du1 && !SW.bwd_gemm_f32;
-    const bool f16s_dw2 = f16s_du1 && P.f16s_dw2 && !SW.bwd_dw2_f32;
+    f16s_du1 = do_mlp && P.f16s_du1 && !SW.bwd_gemm_f32;
+    f16s_dw2 = f16s_du1 && P.f16s_dw2 && !SW.bwd_dw2_f32;
     if (f16s_du1) {
         // B operand of dU_1 = dU_2 . W_2: rows = k1 (output), contraction = k2  ->  W_2^T, split + swizzled like the forward's W2
         const size_t wn = (size_t)P.KP[2] * P.KP[1];
         hipLaunchKernelGGL(k_transpose, dim3(nblk(wn)), dim3(T), 0, st, F(P.off_wp[2]), P.KP[2], P.KP[1], F(P.off_w2t));
         if ((rc = gpde_pack_split_nk(F(P.off_w2t), P.KP[1], P.KP[2], P.KP[1], P.KP[2], F(P.off_w2ts), F(P.off_ucol2), st)) != GPDE_OK) return rc;
     }
-    const size_t w3n = (size_t)GP_W * GP_W * K2P;
-    if (phase == BWD_DEFER)
-        hipLaunchKernelGGL(k_pad_mat, dim3(nblk(w3n)), dim3(T), 0, st, W[n - 1], GP_W * GP_W, dims[n - 1], dims[n - 1],
+    if (do_conv || phase == BWD_DEFER)
+        hipLaunchKernelGGL(k_pad_mat, dim3(nblk((size_t)GP_W * GP_W * K2P)), dim3(T), 0, st, a.W[n - 1], GP_W * GP_W, dims[n - 1], dims[n - 1],
                            GP_W * GP_W, K2P, F(P.off_w3p));
     if (do_conv) {
-        hipLaunchKernelGGL(k_pad_mat, dim3(nblk(w3n)), dim3(T), 0, st, W[n - 1], GP_W * GP_W, dims[n - 1], dims[n - 1],
-                           GP_W * GP_W, K2P, F(P.off_w3p));
-        if (b[n - 1]) GP_HIP_CHECK(gpde_copy_async(F(P.off_b3), b[n - 1], GP_W * GP_W * 4, st));
+        if (a.b[n - 1]) GP_HIP_CHECK(gpde_copy_async(F(P.off_b3), a.b[n - 1], GP_W * GP_W * 4, st));
         else GP_HIP_CHECK(gpde_zero_async(F(P.off_b3), GP_W * GP_W * 4, st));
         GP_HIP_CHECK(gpde_zero_async(F(P.off_dw3p), (P.off_db3 - P.off_dw3p) + (size_t)GP_W * GP_W * 4, st));      // dw3p and db3
-        if (grad_x) GP_HIP_CHECK(gpde_zero_async(grad_x, (size_t)N * GP_W * 4, st));
+        if (a.grad_x) GP_HIP_CHECK(gpde_zero_async(a.grad_x, (size_t)N * GP_W * 4, st));
     }
-    float* dx = grad_x;
 
     // FULL phase, 3-Linear kernels: the expensive last hidden layer of the recompute runs on the forward's
     // fused f16-split kernel with the store epilogue (3x the fp32 GEMM's rate); the first hidden layer is
     // still needed in memory (dW_2 = dU_2^T H_1) and comes from the GEMM below
-    GpdePackLayout PL;
-    bool fast_last = false;
     const bool recomputes = phase == BWD_FULL || phase == BWD_LIGHT || phase == BWD_DEFER;
-    if (recomputes && P.pack_bytes && rowptr && gpde_pack_layout(n, dims, &PL) == GPDE_OK && PL.mode == 1) {
-        GpdeFusedArgs probe{};
-        probe.k0 = PL.k0; probe.K1P = PL.K1P; probe.K2P = PL.K2P;
-        if (gpde_fused_store_supported(probe)) {
-            if ((rc = gpde_mlp_pack(n, dims, W, b, F(P.off_pack), P.pack_bytes, st)) != GPDE_OK) return rc;
-            fast_last = true;
-        }
+    if (recomputes && P.pack_bytes && a.rowptr && gpde_pack_layout(n, dims, &PL) == GPDE_OK && PL.mode == 1 &&
+        gpde_fused_store_supported(gpde_fused_probe(PL))) {
+        if ((rc = gpde_mlp_pack(n, dims, a.W, a.b, F(P.off_pack), P.pack_bytes, st)) != GPDE_OK) return rc;
+        fast_last = true;
     }
     // 3-Linear kernels on the split-f16 GEMMs: the first hidden layer H_1 is never written.  Its only consumers in the
     // backward are dW_2 = dU_2^T . H_1 (operand image generated straight from the 8 attribute slots, k_first_layer_pack)
     // and the ReLU mask of dU_1 (128 bytes of bits per edge instead of 4 KiB).  GPDE_BWD_H1_MATERIALIZE=1: the tensor (A/B).
-    const bool h1_on_the_fly = n == 3 && f16s_du1 && f16s_dw2 && dims[0] <= 8 && P.KP[0] >= 8 && !SW.bwd_h1_materialize;
-    auto skip_h1 = [&](int rows) { return h1_on_the_fly && rows >= 8192; };
-    const bool call_amax = do_mlp && h1_on_the_fly && n_edges > 0 && dims[0] <= 7 && (!kt || (src && dst));
+    h1_on_the_fly = n == 3 && f16s_du1 && f16s_dw2 && dims[0] <= 8 && P.KP[0] >= 8 && !SW.bwd_h1_materialize;
+    nas.kt = a.kt;
+    for (int d = 0; d < 8; ++d) nas.sel[d] = (a.kt && a.sel) ? a.sel[d < dims[0] ? d : dims[0] - 1] : 0;
+    call_amax = do_mlp && h1_on_the_fly && a.n_edges > 0 && dims[0] <= 7 && (!a.kt || (a.src && a.dst));
     if (call_amax) {
-        tr_amax = 1;
+        tr.call_amax = 1;
         // one bound per attribute slot for the whole call (k_attr_absmax_all): 24 bytes per edge read once - 0.1 ms at s=121
         GP_HIP_CHECK(gpde_zero_async(F(P.off_amax8), 16 * 4, st));
-        NodeAttrSel ns_{};
-        ns_.kt = kt;
-        for (int d_ = 0; d_ < 8; ++d_) ns_.sel[d_] = (kt && sel) ? sel[d_ < dims[0] ? d_ : dims[0] - 1] : 0;
-        int nb_ = (int)((n_edges + 255) / 256); if (nb_ > 1024) nb_ = 1024;
-        hipLaunchKernelGGL(k_attr_absmax_all, dim3(nb_), dim3(256), 0, st, edge_attr, n_edges, kt ? kt : dims[0], dims[0], ns_, src, dst,
+        int nb = (int)((a.n_edges + 255) / 256); if (nb > 1024) nb = 1024;
+        hipLaunchKernelGGL(k_attr_absmax_all, dim3(nb), dim3(256), 0, st, a.edge_attr, a.n_edges, a.kt ? a.kt : dims[0], dims[0], nas, a.src, a.dst,
                            (unsigned*)F(P.off_amax8));
     }
-    if ((phase == BWD_LIGHT && !fast_last) || (phase == BWD_DEFER && !(fast_last && f16s_du1 && f16s_dw2 && n == 3))) {
+    if ((light && !fast_last) || (phase == BWD_DEFER && !(fast_last && f16s_du1 && f16s_dw2 && n == 3))) {
         gpde_set_error("gpde_nnconv_bwd_%s: kernel MLP outside the depth-deferred form (3 Linear layers of widths that are multiples of 128, "
-                       "k0 <= 7): use gpde_nnconv_bwd", phase == BWD_LIGHT ? "light" : "deferred");
+                       "k0 <= 7): use gpde_nnconv_bwd", light ? "light" : "deferred");
         return GPDE_EUNSUPPORTED;
     }
-    const bool light = phase == BWD_LIGHT;
-    // recompute of the hidden chain for rows [e0, e0 + rows) = in-edges of nodes [na_, nb_): layers 1 .. last
-    int rc_na = 0, rc_nb = 0;
-    NodeAttrSel nas{};
-    nas.kt = kt;
-    for (int d_ = 0; d_ < 8; ++d_) nas.sel[d_] = (kt && sel) ? sel[d_ < dims[0] ? d_ : dims[0] - 1] : 0;
-    if (kt && ((recomputes && !fast_last) || !src || !dst)) {
+    if (a.kt && ((recomputes && !fast_last) || !a.src || !a.dst)) {
         gpde_set_error("gpde_nnconv_bwd: node-table attributes need the 3-Linear split-f16 form (and src / dst)");
         return GPDE_EUNSUPPORTED;
     }
@@ -1385,376 +1458,414 @@ int bwd_impl(BwdPhase phase, const float* x, int64_t n_nodes, const float* edge_
     // given-H path uses (gpde_zagg_kernel<true>, ~3x the fp32-MFMA form's rate): x as split pairs once per call, and ONE bound for
     // every H value - the forward's a-priori bound max|b2| + max_k ||W2_k||_1 . max_e B_e, which holds for recomputed and for
     // given (partial-H) rows alike since both come from this kernel MLP.
-    bool zagg16 = false;
-    if ((phase == BWD_FULL || light) && fast_last && !z_saved && n_edges >= 32768 && N > 0 && x) {
-        if ((rc = gpde_launch_g2_prep(x, N, edge_attr, n_edges, PL.k0, F(P.off_pack) + PL.off_w1 + (size_t)PL.K1P * 8, (unsigned*)F(P.off_scal),
-                                      (unsigned*)F(P.off_xs), st, kt, kt ? nas.sel : nullptr, src, dst)) != GPDE_OK) return rc;
+    if ((phase == BWD_FULL || light) && fast_last && !a.z_saved && a.n_edges >= 32768 && N > 0 && a.x) {
+        if ((rc = gpde_launch_g2_prep(a.x, N, a.edge_attr, a.n_edges, PL.k0, F(P.off_pack) + PL.off_w1 + (size_t)PL.K1P * 8, (unsigned*)F(P.off_scal),
+                                      (unsigned*)F(P.off_xs), st, a.kt, a.kt ? nas.sel : nullptr, a.src, a.dst)) != GPDE_OK) return rc;
         hipLaunchKernelGGL(k_h_bound_word, dim3(1), dim3(1), 0, st, F(P.off_pack) + PL.off_fcol, (const unsigned*)F(P.off_scal), (unsigned*)F(P.off_scal) + 2);
         zagg16 = true;
     }
-    const float* chunk_h = nullptr;          // the current chunk's last hidden activations when they are given (hpart)
-    auto recompute = [&](int e0, int rows, int last) -> int {
-        if (!light) {    // (the light pass needs the last hidden layer only, which the fused kernel forms from the attributes itself)
-            if (kt) hipLaunchKernelGGL(k_gather_attr_nodes, dim3(nblk((size_t)rows * P.KP[0])), dim3(T), 0, st, edge_attr, nas, src, dst, e0,
-                                       rows, dims[0], P.KP[0], F(P.off_H[0]));
-            else hipLaunchKernelGGL(k_gather_attr, dim3(nblk((size_t)rows * P.KP[0])), dim3(T), 0, st, edge_attr, perm, e0,
-                                    rows, dims[0], P.KP[0], F(P.off_H[0]));
-        }
-        if (last == n - 1 && chunk_h) {                     // given (partial H of the caller / H kept by the forward): read, not recomputed
-            last = n - 2;
-            trs(GPDE_BWD_TRACE_HLAST, 1); trs(GPDE_BWD_TRACE_FROM_H, 1);
-        } else if (fast_last && last == n - 1) {
-            trs(GPDE_BWD_TRACE_HLAST, 2);
-            const float* pk = F(P.off_pack);
-            GpdeFusedArgs f{};
-            f.attr = edge_attr; f.rowptr = rowptr; f.perm = perm;
-            f.src = src; f.dst = dst; f.kt = kt;
-            for (int d_ = 0; d_ < 8; ++d_) f.sel[d_] = nas.sel[d_];
-            f.w1 = pk + PL.off_w1; f.w2t = pk + PL.off_w2t; f.b2 = pk + PL.off_b2;
-            f.w2h = pk + PL.off_w2h; f.ucol = pk + PL.off_ucol; f.w1h = pk + PL.off_w1h; f.fcol = pk + PL.off_fcol;
-            f.hout = F(P.off_H[n - 1]); f.k0 = PL.k0; f.K1P = PL.K1P; f.K2P = PL.K2P;
-            f.nc0 = rc_na; f.nc1 = rc_nb; f.e_chunk0 = e0;
-            if (kt && !gpde_fused_f16v6_supported(f)) { gpde_set_error("node-table attributes: kernel MLP outside the one-wave-per-SIMD store kernel"); return GPDE_EUNSUPPORTED; }
-            const int ns = PL.K2P / GP_TN;
-            int groups = gpde_num_cus() / ns; if (groups < 1) groups = 1;
-            const int gcap = (rows / GP_TE + GP_WAVES) / GP_WAVES; if (groups > gcap) groups = gcap;
-            f.n_groups = groups;
-            int rc2 = gpde_launch_fused_store(f, st);
-            if (rc2 != GPDE_OK) return rc2;
-            last = n - 2;
-        }
-        if (light) return GPDE_OK;
-        for (int l = 1; l <= last; ++l) {
-            if (l == 1 && last == 1 && skip_h1(rows)) { trs(GPDE_BWD_TRACE_H1, 3); continue; }
-            if (l == n - 1) trs(GPDE_BWD_TRACE_HLAST, 3);
-            if (l == 1 && dims[0] <= 8 && P.KP[0] >= 8 && P.KP[1] % 4 == 0 && rows >= 1024) {
-                trs(GPDE_BWD_TRACE_H1, 2);
-                const int cb = (P.KP[1] + 255) / 256;
-                int rb = rows / 64; if (rb > 4096 / cb) rb = 4096 / cb; if (rb < 1) rb = 1;
-                hipLaunchKernelGGL(k_first_layer, dim3(cb, rb), dim3(T), 0, st, F(P.off_H[0]), P.KP[0], F(P.off_wp[1]), P.KP[0],
-                                   F(P.off_bp[1]), rows, P.KP[1], F(P.off_H[1]));
-                continue;
-            }
-            if (l == 1) trs(GPDE_BWD_TRACE_H1, 1);
-            GpdeGemmArgs g = gemm0();
-            g.A = F(P.off_H[l - 1]); g.lda = P.KP[l - 1]; g.B = F(P.off_wp[l]); g.ldb = P.KP[l - 1];
-            g.C = F(P.off_H[l]); g.ldc = P.KP[l]; g.M = rows; g.N = P.KP[l]; g.K = P.KP[l - 1];
-            g.bias = F(P.off_bp[l]); g.relu = 1;
-            int rc2 = gpde_launch_gemm(g, st);
-            if (rc2 != GPDE_OK) return rc2;
-        }
-        return GPDE_OK;
-    };
-    // MLP backward over rows [e0, e0 + rows): dU_last given (read only), activations H[0 .. n-2] in the
-    // workspace, H[n-1] = Hlast
-    if (grad_attr && (phase != BWD_FULL || kt || dims[0] > 8 || P.KP[0] < 8 || !perm)) {
+    if (a.grad_attr && (phase != BWD_FULL || a.kt || dims[0] > 8 || P.KP[0] < 8 || !a.perm)) {
         gpde_set_error("gpde_nnconv_bwd: the edge-attribute gradient is built for the full backward on an attribute tensor of <= 8 slots");
         return GPDE_EUNSUPPORTED;
     }
-    int mlp_e0 = 0;                          // first CSR slot of the chunk mlp_backward is working on
-    bool du_pre = false;                     // the per-edge kernel of this chunk wrote dU_2^T, its row scales and tile column partials
-    auto mlp_backward = [&](const float* dUlast, int rows) -> int {
-        const float* dUc = dUlast;
-        float* bufs[2] = {F(P.off_dU[0]), F(P.off_dU[1])};
-        // The layer GEMMs below read every row of dU_l from all their column-slice workgroups and write dU_{l-1}
-        // rows of the same indices: the output must never be the buffer the input lives in.  In the FULL phase
-        // dU_last IS bufs[0] (the per-edge kernel wrote it there), so the first output goes to bufs[1].  (Rounds 1-2
-        // started at bufs[0]: a workgroup that finished its tile early overwrote rows a sibling slice was still
-        // reading - the intermittent 1e-3 error in grad_W1)
-        int nb_ = dUlast == bufs[0] ? 1 : 0;
-        bool fl_in_kernel = false;           // the dW_2 GEMM of this chunk generated H_1 itself (round 6 plan)
-        bool dw1_done = false;               // the dU_1 GEMM's epilogue formed dW_1 / db_1 (k_dw_first has nothing left to do)
-        for (int l = n - 1; l >= 1; --l) {
-            const int Kl = P.KP[l], Kin = P.KP[l - 1];
-            int rc2;
-            if (l == 1 && grad_attr) {       // dU_1 is complete here: the gradient of the attributes through W_1
-                trs(GPDE_BWD_TRACE_GRAD_ATTR, 1);
-                hipLaunchKernelGGL(k_grad_attr, dim3((rows + 3) / 4), dim3(T), 0, st, dUc, Kl, F(P.off_wp[1]), Kin, perm, mlp_e0, rows,
-                                   dims[0], grad_attr);
-            }
-            if (l == 1 && dw1_done) continue;
-            if (l == 1 && dims[0] <= 8 && Kin >= 8 && Kin % 4 == 0 && Kl % 4 == 0 && rows >= 1024) {
-                // dW_1 and db_1 from one pass over dU_1 (k_dw_first; attribute slots beyond k0 are zero columns of H_0)
-                const int cb = (Kl + 255) / 256;
-                int splits = 1; while (splits < 256 && cb * splits < 1024 && rows / (splits * 2) >= 64) splits *= 2;
-                while (splits > 1 && (size_t)splits * Kl * 9 > P.part_floats) splits /= 2;
-                if ((size_t)splits * Kl * 9 <= P.part_floats) {
-                    trs(GPDE_BWD_TRACE_DW1, 2);
-                    hipLaunchKernelGGL(k_dw_first, dim3(cb, splits), dim3(T), 0, st, dUc, F(P.off_H[0]), Kin, rows, Kl, splits, F(P.off_part));
-                    hipLaunchKernelGGL(k_dw_first_reduce, dim3(nblk((size_t)Kl * 9)), dim3(T), 0, st, F(P.off_part), splits, Kl, Kin,
-                                       F(P.off_dwp[l]), F(P.off_dbp[l]));
-                    continue;      // l == 1 is the last layer of the loop: nothing below it to back-propagate into
-                }
-            }
-            const bool tn_split = l == 2 && f16s_dw2 && rows >= 8192;
-            // one pass over dU_2 for its transposed copy, db_2, and the row scales of the dU_1 GEMM
-            const bool du_one_pass = tn_split && f16s_du1;
-            unsigned* du_bits = tn_split ? (unsigned*)F(P.off_dubits) : nullptr;
-            if (!du_one_pass) {   // db_l = column sums of dU_l; the same pass collects the column maxima the split dW_2 GEMM scales with
-                const int cb = (Kl + 255) / 256;
-                int splits = 1; while (splits < 512 && cb * splits < 2048 && rows / (splits * 2) >= 64) splits *= 2;
-                while (splits > 1 && (size_t)splits * Kl > P.part_floats) splits /= 2;
-                if (du_bits) GP_HIP_CHECK(gpde_zero_async(du_bits, (size_t)Kl * 4, st));
-                hipLaunchKernelGGL(k_colsum, dim3(cb, splits), dim3(T), 0, st, dUc, rows, Kl, Kl, splits, F(P.off_part), du_bits);
-                if ((rc2 = gpde_launch_reduce_splits(F(P.off_part), Kl, splits, Kl, F(P.off_dbp[l]), 1, st)) != GPDE_OK) return rc2;
-            }
-            if (tn_split) {
-                // dW_2 += dU_2^T . H_1 on the split-f16 GEMM (contraction over the edges: both operands transposed)
-                trs(GPDE_BWD_TRACE_DW2, 1);
-                GpdeFirstLayerSpec fl{F(P.off_H[0]), P.KP[0], F(P.off_wp[1]), P.KP[0], F(P.off_bp[1]), (uint32_t*)F(P.off_maskbits), dims[0],
-                                      call_amax ? (const unsigned*)F(P.off_amax8) : nullptr};
-                fl_in_kernel = skip_h1(rows) && gpde_first_layer_in_kernel(fl, rows, tn_ksplits(rows, P.KP[2], P.KP[1]));
-                if (fl_in_kernel) trs(GPDE_BWD_TRACE_H1, 3);
-                GpdeDuStats dst_{F(P.off_dbp[l]), F(P.off_rowsc), F(P.off_rowsc) + rows,
-                                 du_pre ? F(P.off_tcs) : nullptr, du_pre ? (const unsigned*)F(P.off_tcm) : nullptr};
-                if ((rc2 = gpde_launch_gemm_f16s_tn(dUc, Kl, Kl, F(P.off_H[l - 1]), Kin, Kin, rows, tn_ksplits(rows, P.KP[2], P.KP[1]),
-                                                    F(P.off_tnws), F(P.off_part), st, du_one_pass ? nullptr : du_bits,
-                                                    skip_h1(rows) ? &fl : nullptr, du_one_pass ? &dst_ : nullptr)) != GPDE_OK) return rc2;
-                if ((rc2 = gpde_launch_reduce_splits(F(P.off_part), (size_t)Kl * Kin, tn_ksplits(rows, P.KP[2], P.KP[1]), (size_t)Kl * Kin,
-                                                     F(P.off_dwp[l]), 1, st)) != GPDE_OK) return rc2;
-            } else {
-                if (l == 2) trs(GPDE_BWD_TRACE_DW2, 2);
-                if (l == 1) trs(GPDE_BWD_TRACE_DW1, 3);
-                if ((rc2 = gemm_tn_acc(dUc, Kl, Kl, F(P.off_H[l - 1]), Kin, Kin, rows, F(P.off_dwp[l]), Kin,
-                                       F(P.off_part), P.part_floats, 1, st)) != GPDE_OK) return rc2;
-            }
-            if (l > 1 && l == 2 && f16s_du1 && rows >= 64) {
-                trs(GPDE_BWD_TRACE_DU1, 1);
-                float* dUo = bufs[nb_]; nb_ ^= 1;
-                GpdeGemmF16sArgs g{};
-                g.A = dUc; g.lda = Kl; g.M = rows; g.bsplit = F(P.off_w2ts); g.ucol = F(P.off_ucol2);
-                g.mask = F(P.off_H[l - 1]); g.ldmask = Kin; g.C = dUo; g.ldc = Kin; g.K = Kl; g.N = Kin;
-                if (tn_split && skip_h1(rows)) { g.mask = nullptr; g.ldmask = 0; g.maskbits = (const uint32_t*)F(P.off_maskbits); g.ldmb = Kin / 32; }
-                if (tn_split && fl_in_kernel && dims[0] <= 7 && !grad_attr &&
-                    gpde_gemm_f16s_dw_part_floats(rows, Kin) <= (size_t)rows * Kin) {
-                    // round 6: this GEMM's epilogue forms dW_1 / db_1 from the tile in its registers: dU_1 (4 KiB per edge) is neither
-                    // written nor read back by k_dw_first - unless the attribute gradient wants the tensor.  Scratch of the tile partials: the dU_1 buffer itself (512 bytes per row of its 4 KiB)
-                    g.fl_mode = 2; g.fl_attr = F(P.off_H[0]); g.fl_ld0 = P.KP[0]; g.fl_rows = rows;
-                    g.fl_dw_part = dUo; g.fl_dw_out = F(P.off_dwp[1]); g.fl_dw_ld = P.KP[0]; g.fl_db_out = F(P.off_dbp[1]);
-                    g.fl_skip_store = 1;
-                    dw1_done = true;
-                    trs(GPDE_BWD_TRACE_DW1, 1);
-                }
-                // (row scales: a pass over dU_2, 3.9 ms at s=121.  Collecting the row maxima inside gpde_edge_bwd2_kernel was
-                // tried in round 3: 16 more registers spill 15 VGPRs of a kernel that sits at its 256-register limit, +5 ms.)
-                if (du_one_pass) {                    // row scales left in off_rowsc by the transposing pass above
-                    g.sc = F(P.off_rowsc); g.isc = F(P.off_rowsc) + rows;
-                    if ((rc2 = gpde_launch_gemm_f16s_nt(g, nullptr, st)) != GPDE_OK) return rc2;
-                } else if ((rc2 = gpde_launch_gemm_f16s_nt(g, F(P.off_rowsc), st)) != GPDE_OK) return rc2;
-                dUc = dUo;
-            } else if (l > 1) {
-                if (l == 2) trs(GPDE_BWD_TRACE_DU1, 2);
-                float* dUo = bufs[nb_]; nb_ ^= 1;
-                GpdeGemmArgs g = gemm0();
-                g.A = dUc; g.lda = Kl; g.B = F(P.off_wp[l]); g.ldb = Kin; g.b_kcontig = 0;
-                g.C = dUo; g.ldc = Kin; g.M = rows; g.N = Kin; g.K = Kl;
-                g.mask = F(P.off_H[l - 1]); g.ldmask = Kin;
-                if ((rc2 = gpde_launch_gemm(g, st)) != GPDE_OK) return rc2;
-                dUc = dUo;
-            }
-        }
-        return GPDE_OK;
-    };
+    return GPDE_OK;
+}
 
-    if (phase == BWD_MLP) {
-        // plain edge chunks: nothing here depends on the destination structure
-        for (int64_t e0 = 0; e0 < n_edges; e0 += P.Ec) {
-            const int rows = (int)((n_edges - e0) < P.Ec ? (n_edges - e0) : P.Ec);
-            tr_begin(-1, -1, (int)e0, rows);
-            if ((rc = recompute((int)e0, rows, n - 2)) != GPDE_OK) return rc;
-            // activations below the last hidden layer are recomputed; the last one is needed only as
-            // the ReLU mask, which the incoming dL/dU already carries
-            if ((rc = mlp_backward(grad_hidden_in + (size_t)e0 * K2P, rows)) != GPDE_OK) return rc;
-            tr_emit();
-        }
-        GP_LAUNCH_CHECK("gpde_hidden_bwd kernels");
+// recompute of the hidden chain for the chunk's rows: layers 1 .. last (the last hidden layer n - 1 is read where it is given)
+int BwdCall::recompute(const Chunk& c, int last) {
+    const int32_t* dims = a.dims;
+    const int e0 = c.e0, rows = c.rows;
+    if (!light) {    // (the light pass needs the last hidden layer only, which the fused kernel forms from the attributes itself)
+        if (a.kt) hipLaunchKernelGGL(k_gather_attr_nodes, dim3(nblk((size_t)rows * P.KP[0])), dim3(T), 0, st, a.edge_attr, nas, a.src, a.dst, e0,
+                                     rows, dims[0], P.KP[0], F(P.off_H[0]));
+        else hipLaunchKernelGGL(k_gather_attr, dim3(nblk((size_t)rows * P.KP[0])), dim3(T), 0, st, a.edge_attr, a.perm, e0,
+                                rows, dims[0], P.KP[0], F(P.off_H[0]));
     }
-
-    // ---- node-aligned chunks ----------------------------------------------------------------------------------
-    if (phase == BWD_DEFER && n_edges > 0)
-        if ((rc = gpde_launch_xstack_scales(x_stack, (size_t)N * GP_W, P.L, N, F(P.off_xsc), F(P.off_xsc) + N, st)) != GPDE_OK) return rc;
-    int na = 0;
-    while ((do_conv || phase == BWD_DEFER) && na < N && n_edges > 0) {
-        // largest nb with (nb - na) <= Nc and edges <= Ec (at least one node)
-        int lo = na + 1, hi = (int)((int64_t)na + P.Nc < N ? na + P.Nc : N);
-        const bool from_h = hpart && na < hpart_nodes;
-        if (from_h && hi > hpart_nodes) hi = (int)hpart_nodes;        // a chunk never straddles the end of the given H
-        const int64_t ebase = rowptr_host[na];
-        if (phase == BWD_CONV) P.Ec = n_edges;       // H and dU live outside the workspace: no edge limit
-        if (rowptr_host[lo] - ebase > P.Ec) {
-            gpde_set_error("gpde_nnconv_bwd: node %d has in-degree %d > %lld edges per chunk; give more workspace",
-                           na, (int)(rowptr_host[lo] - ebase), (long long)P.Ec);
-            return GPDE_EWORKSPACE;
-        }
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (rowptr_host[mid] - ebase <= P.Ec) lo = mid; else hi = mid - 1;
-        }
-        const int nb = lo, nn = nb - na;
-        const int e0 = (int)ebase, e1 = rowptr_host[nb], rows = e1 - e0;
-        float* gT = F(P.off_gT); float* S = F(P.off_S); float* dS = F(P.off_dS);
-        float* Z = F(P.off_Z); float* dZ = F(P.off_dZ);
-        chunk_h = from_h ? hpart + (size_t)e0 * K2P : nullptr;
-        tr_begin(na, nb, e0, rows);
-        if (phase == BWD_DEFER) {
-            if (rows > 0) {
-                rc_na = na; rc_nb = nb;
-                if ((rc = recompute(e0, rows, n - 1)) != GPDE_OK) return rc;
-                const float* H2 = chunk_h ? chunk_h : F(P.off_H[n - 1]);
-                // dZ^(l)[i][c][k] = sum_o gT^(l)[i][o] W3[c*64+o][k] of every deferred layer, then the nodes' split images
-                const size_t dzl = (size_t)P.Nc * GP_W * K2P;
-                for (int l = 0; l < P.L; ++l) {
-                    hipLaunchKernelGGL(k_scale_g, dim3((nn + 3) / 4), dim3(T), 0, st, g_stack + (size_t)l * N * GP_W, rowptr, aggr, na, nn, gT);
-                    GpdeGemmArgs g = gemm0();
-                    g.A = gT; g.lda = GP_W; g.B = F(P.off_w3p); g.ldb = K2P; g.b_kcontig = 0;
-                    g.C = F(P.off_dzstack) + (size_t)l * dzl; g.ldc = GP_W * K2P; g.M = nn; g.N = K2P; g.K = GP_W;
-                    g.batches = GP_W; g.strideA = 0; g.strideB = (size_t)GP_W * K2P; g.strideC = K2P;
-                    if ((rc = gpde_launch_gemm(g, st)) != GPDE_OK) return rc;
-                }
-                if ((rc = gpde_launch_dz_image(F(P.off_dzstack), dzl, P.L, P.Lp, nn, K2P, (unsigned*)F(P.off_nbits), F(P.off_nscale),
-                                               F(P.off_nscale) + P.Nc, F(P.off_dzimg), st)) != GPDE_OK) return rc;
-                const int ntiles = gpde_tile_count(rowptr_host, na, nb);
-                int32_t* tiles = (int32_t*)F(P.off_tiles);
-                if ((rc = gpde_launch_tile_list(rowptr, na, nn, e0, tiles, st)) != GPDE_OK) return rc;
-                // dU_2 of the chunk's edges: (sum over the layers of x_j . dZ_i) masked by the recomputed H_2 > 0
-                float* dU2 = F(P.off_dU[0]);
-                if ((rc = gpde_launch_gemm_f16s_gather(x_stack, (size_t)N * GP_W, P.Lp, F(P.off_xsc), F(P.off_xsc) + N, src + e0, rows, tiles, ntiles,
-                                                       F(P.off_dzimg), F(P.off_nscale) + P.Nc, H2, K2P, dU2, K2P, K2P, st)) != GPDE_OK) return rc;
-                if ((rc = mlp_backward(dU2, rows)) != GPDE_OK) return rc;
-            }
-            tr_emit();
-            na = nb;
+    if (last == n - 1 && c.h) {                     // given (partial H of the caller / H kept by the forward): read, not recomputed
+        last = n - 2;
+        tr.set(GPDE_BWD_TRACE_HLAST, 1); tr.set(GPDE_BWD_TRACE_FROM_H, 1);
+    } else if (fast_last && last == n - 1) {
+        tr.set(GPDE_BWD_TRACE_HLAST, 2);
+        GpdeFusedArgs f{};
+        f.attr = a.edge_attr; f.rowptr = a.rowptr; f.perm = a.perm;
+        f.src = a.src; f.dst = a.dst; f.kt = a.kt;
+        for (int d = 0; d < 8; ++d) f.sel[d] = nas.sel[d];
+        gpde_fused_set_pack(f, F(P.off_pack), PL);
+        f.hout = F(P.off_H[n - 1]);
+        f.nc0 = c.na; f.nc1 = c.nb; f.e_chunk0 = e0;
+        if (a.kt && !gpde_fused_f16v6_supported(f)) { gpde_set_error("node-table attributes: kernel MLP outside the one-wave-per-SIMD store kernel"); return GPDE_EUNSUPPORTED; }
+        f.n_groups = gpde_fused_groups(PL.K2P, gpde_group_cap_bwd_chunk(rows));
+        int rc = gpde_launch_fused_store(f, st);
+        if (rc != GPDE_OK) return rc;
+        last = n - 2;
+    }
+    if (light) return GPDE_OK;
+    for (int l = 1; l <= last; ++l) {
+        if (l == 1 && last == 1 && skip_h1(rows)) { tr.set(GPDE_BWD_TRACE_H1, 3); continue; }
+        if (l == n - 1) tr.set(GPDE_BWD_TRACE_HLAST, 3);
+        if (l == 1 && dims[0] <= 8 && P.KP[0] >= 8 && P.KP[1] % 4 == 0 && rows >= 1024) {
+            tr.set(GPDE_BWD_TRACE_H1, 2);
+            const int cb = (P.KP[1] + 255) / 256;
+            int rb = rows / 64; if (rb > 4096 / cb) rb = 4096 / cb; if (rb < 1) rb = 1;
+            hipLaunchKernelGGL(k_first_layer, dim3(cb, rb), dim3(T), 0, st, F(P.off_H[0]), P.KP[0], F(P.off_wp[1]), P.KP[0],
+                               F(P.off_bp[1]), rows, P.KP[1], F(P.off_H[1]));
             continue;
         }
-        hipLaunchKernelGGL(k_scale_g, dim3((nn + 3) / 4), dim3(T), 0, st, grad_out, rowptr, aggr, na, nn, gT);
-        if (rows > 0) {
-            // hidden activations of the chunk's edges: recomputed, or rows of the given cache
-            if (phase == BWD_FULL || light) { rc_na = na; rc_nb = nb; if ((rc = recompute(e0, rows, n - 1)) != GPDE_OK) return rc; }
-            const float* Hlast = chunk_h ? chunk_h : (phase == BWD_FULL || light) ? F(P.off_H[n - 1]) : nullptr;
-            if (!Hlast) { Hlast = hidden + (size_t)e0 * K2P; trs(GPDE_BWD_TRACE_HLAST, 1); trs(GPDE_BWD_TRACE_FROM_H, 1); }
-            // Z of the chunk's nodes: kept by the forward (gpde_nnconv_fwd_keepz), else re-aggregated from the recomputed /
-            // given activations
-            if (z_saved) { Z = const_cast<float*>(z_saved) + (size_t)na * GP_W * K2P; trs(GPDE_BWD_TRACE_Z, 1); }     // read only below
-            else GP_HIP_CHECK(gpde_zero_async(Z, (size_t)nn * GP_W * K2P * 4, st));
-            if (!z_saved) {
-                GpdeFusedArgs f{};
-                f.x = x; f.attr = edge_attr; f.rowptr = rowptr; f.src = src; f.dst = dst; f.perm = perm;
-                f.hbuf = Hlast; f.zbuf = Z; f.k0 = dims[0]; f.K1P = 32; f.K2P = K2P;
-                f.nc0 = na; f.nc1 = nb; f.e_chunk0 = e0;
-                trs(GPDE_BWD_TRACE_Z, 2);
-                if (zagg16) { f.xs = (const unsigned*)F(P.off_xs); f.scal = (const unsigned*)F(P.off_scal); f.hmax = (const unsigned*)F(P.off_scal) + 2; trs(GPDE_BWD_TRACE_Z, 3); }
-                const int ns = K2P / GP_TN;
-                int groups = gpde_num_cus() / ns; if (groups < 1) groups = 1;
-                const int gcap = (rows / GP_TE + GP_WAVES) / GP_WAVES; if (groups > gcap) groups = gcap;
-                f.n_groups = groups;
-                if ((rc = gpde_launch_zagg(f, st)) != GPDE_OK) return rc;
-            }
-            hipLaunchKernelGGL(k_nbr_sum, dim3(nn), dim3(T), 0, st, x, rowptr, src, na, nn, S);
-            // db3[c][o] += S^T gT ;  dW3[c][o][k] += gT^T Z[:, c, :]
-            if ((rc = gemm_tn_acc(S, GP_W, GP_W, gT, GP_W, GP_W, nn, F(P.off_db3), GP_W, F(P.off_part), P.part_floats, 1, st)) != GPDE_OK) return rc;
-            {
-                GpdeGemmArgs g = gemm0();
-                g.A = gT; g.lda = GP_W; g.a_kcontig = 0; g.B = Z; g.ldb = GP_W * K2P; g.b_kcontig = 0;
-                g.C = F(P.off_dw3p); g.ldc = K2P; g.M = GP_W; g.N = K2P; g.K = nn; g.accumulate = 1;
-                g.batches = GP_W; g.strideA = 0; g.strideB = K2P; g.strideC = (size_t)GP_W * K2P;
-                // narrow kernels (the MGKN levels: K2P = 128 / 256) give 64 - 128 workgroups that each walk all nn nodes (365 us at
-                // nn = 4525): split the node range (ordered partial reduction: deterministic) until ~512 workgroups are busy.  The
-                // partials live in the chunk's dZ buffer - nn x 64 x K2P floats that are written only by the next GEMM below, and
-                // sp <= nn / 128 of these 64 x 64 x K2P images always fit
-                int sp = 1;
-                const int wgs = GP_W * ((K2P + 127) / 128);
-                while (sp < 16 && wgs * sp < 512 && nn / (sp * 2) >= 64) sp *= 2;
-                if (sp > 1) {
-                    g.C = dZ; g.accumulate = 0; g.splits = sp; g.strideSplit = w3n;
-                    if ((rc = gpde_launch_gemm(g, st)) != GPDE_OK) return rc;
-                    if ((rc = gpde_launch_reduce_splits(dZ, w3n, sp, w3n, F(P.off_dw3p), 1, st)) != GPDE_OK) return rc;
-                } else if ((rc = gpde_launch_gemm(g, st)) != GPDE_OK) return rc;
-            }
-            // dZ[i][c][k] = sum_o gT[i][o] W3[c*64+o][k] ;  dS[i][c] = sum_o gT[i][o] b3[c*64+o]
-            {
-                GpdeGemmArgs g = gemm0();
-                g.A = gT; g.lda = GP_W; g.B = F(P.off_w3p); g.ldb = K2P; g.b_kcontig = 0;
-                g.C = dZ; g.ldc = GP_W * K2P; g.M = nn; g.N = K2P; g.K = GP_W;
-                g.batches = GP_W; g.strideA = 0; g.strideB = (size_t)GP_W * K2P; g.strideC = K2P;
-                if ((rc = gpde_launch_gemm(g, st)) != GPDE_OK) return rc;
-                GpdeGemmArgs s2 = gemm0();
-                s2.A = gT; s2.lda = GP_W; s2.B = F(P.off_b3); s2.ldb = GP_W; s2.C = dS; s2.ldc = GP_W;
-                s2.M = nn; s2.N = GP_W; s2.K = GP_W;
-                if ((rc = gpde_launch_gemm(s2, st)) != GPDE_OK) return rc;
-            }
-            // per-edge backward through the aggregation -> dU_{n-1}, dx_j
-            float* dUc = phase == BWD_FULL ? F(P.off_dU[0]) : light ? nullptr : grad_hidden_out + (size_t)e0 * K2P;   // light: dx only
-            const bool ordered = src_rowptr && src_slots;
-            EdgeBwdArgs ea{x, rowptr, src, dst, dZ, dS, Hlast, dUc, dx, e0, e1, na, K2P, ordered ? F(P.off_dxe) : nullptr};
-            const size_t lds = (size_t)4 * (32 * EB_XS + 32 * EB_HS) * 4;
-            const size_t lds2 = (size_t)(2 * EB2_DZ + 4 * 2 * EB2_H) * 4 + 4 * 64 * 4;
-            static GpdeLdsOnce once;
-            if (int rc_ = once.ensure(gpde_edge_bwd_kernel, gpde_edge_bwd2_kernel)) return rc_;
-            if (!dx) { gpde_set_error("gpde_nnconv_bwd: grad_x must be provided"); return GPDE_EINVAL; }
-            // staged kernel where a 128-slot group rarely spans more than two destinations
-            const int force = SW.edge_bwd;                     // GPDE_EDGE_BWD = 1 / 2 / 3: force a variant (tests, A/B)
-            // (accumulating dL/dU lives in the split-f16 kernel: it is correct for any in-degree, the host asks for it on dense graphs)
-            const bool gh_acc = gh_accumulate && phase == BWD_CONV;
-            // (round 6: from mean in-degree 4 - the split-f16 kernel is correct for any in-degree and measured faster on the MGKN
-            // levels of in-degree 6 - 22 too: 1.4 ms of a 30 ms training step of config 4)
-            const bool staged = force ? force >= 2 : (gh_acc || (int64_t)rows >= (int64_t)(K2P % 32 == 0 ? 4 : 32) * nn);
-            du_pre = false;
-            if (staged && force != 2 && K2P % 32 == 0) {      // split-f16 MFMA (default); GPDE_EDGE_BWD=2: the fp32-MFMA staged kernel
-                trs(GPDE_BWD_TRACE_EDGE_KERNEL, 3);
-                if ((rc = gpde_launch_dz_split(dZ, nn, K2P, F(P.off_dzun), st)) != GPDE_OK) return rc;
-                GpdeEdgeBwd3Args e3{x, src, dst, dZ, F(P.off_dzun), dS, Hlast, dUc, dx, ordered ? F(P.off_dxe) : nullptr, e0, e1, na, K2P};
-                e3.du_accumulate = gh_acc;
-                // full backward on the split GEMMs: the kernel also leaves what the dW_2 GEMM's pass over dU_2 would form
-                // (mlp_backward's tn_split && du_one_pass case)
-                if (phase == BWD_FULL && n == 3 && f16s_dw2 && f16s_du1 && rows >= 8192) {
-                    e3.dUt = gpde_gemm_f16s_tn_at(F(P.off_tnws), rows, tn_ksplits(rows, P.KP[2], P.KP[1]), &e3.ldt);
-                    e3.row_sc = F(P.off_rowsc); e3.row_isc = F(P.off_rowsc) + rows;
-                    e3.csum_part = F(P.off_tcs); e3.cmax_part = (unsigned*)F(P.off_tcm);
-                    du_pre = true;
-                    trs(GPDE_BWD_TRACE_DU_PRE, 1);
-                }
-                if ((rc = gpde_launch_edge_bwd3(e3, st)) != GPDE_OK) return rc;
-            } else if (gh_acc) {
-                gpde_set_error("gpde_nnconv_bwd: GPDE_BWD_ACCUMULATE_GRAD_HIDDEN is built into the split-f16 per-edge kernel only "
-                               "(GPDE_EDGE_BWD=2 forces the other one)");
-                return GPDE_EUNSUPPORTED;
-            } else if (staged) {
-                trs(GPDE_BWD_TRACE_EDGE_KERNEL, 2);
-                hipLaunchKernelGGL(gpde_edge_bwd2_kernel, dim3(((rows + 127) / 128 + 7) / 8 * 8), dim3(T), lds2, st, ea);
-            } else {
-                trs(GPDE_BWD_TRACE_EDGE_KERNEL, 1);
-                hipLaunchKernelGGL(gpde_edge_bwd_kernel, dim3((rows + 127) / 128), dim3(T), lds, st, ea);
-            }
-            if (ordered) trs(GPDE_BWD_TRACE_ORDERED, 1);
-            if (ordered) hipLaunchKernelGGL(k_dx_reduce, dim3((N + 3) / 4), dim3(T), 0, st, F(P.off_dxe), src_rowptr, src_slots, N, e0, e1, dx, 1, (size_t)0, 0);
-            // MLP backward over the chunk's edges
-            if (phase == BWD_FULL) { mlp_e0 = e0; if ((rc = mlp_backward(dUc, rows)) != GPDE_OK) return rc; }
-        }
-        tr_emit();
-        na = nb;
+        if (l == 1) tr.set(GPDE_BWD_TRACE_H1, 1);
+        GpdeGemmArgs g = gemm0();
+        g.A = F(P.off_H[l - 1]); g.lda = P.KP[l - 1]; g.B = F(P.off_wp[l]); g.ldb = P.KP[l - 1];
+        g.C = F(P.off_H[l]); g.ldc = P.KP[l]; g.M = rows; g.N = P.KP[l]; g.K = P.KP[l - 1];
+        g.bias = F(P.off_bp[l]); g.relu = 1;
+        int rc = gpde_launch_gemm(g, st);
+        if (rc != GPDE_OK) return rc;
     }
-    GP_LAUNCH_CHECK("gpde_nnconv_bwd kernels");
+    return GPDE_OK;
+}
 
-    // ---- node-side terms of update(): dx += g root^T, droot = X^T g, dbias = colsum g ----------------------
-    if (do_conv && (rc = bwd_node_terms(x, N, root, grad_out, dx, grad_root, grad_bias, F(P.off_part), P.part_floats, st)) != GPDE_OK) return rc;
-    // ---- un-pad the weight gradients into torch layout -------------------------------------------------------
-    for (int l = 1; l < n && do_mlp; ++l) {
-        if (grad_W && grad_W[l - 1])
-            hipLaunchKernelGGL(k_unpad_mat, dim3(nblk((size_t)dims[l] * dims[l - 1])), dim3(T), 0, st, F(P.off_dwp[l]),
-                               dims[l], dims[l - 1], P.KP[l - 1], grad_W[l - 1]);
-        if (grad_b && grad_b[l - 1])
-            GP_HIP_CHECK(gpde_copy_async(grad_b[l - 1], F(P.off_dbp[l]), (size_t)dims[l] * 4, st));
+// MLP backward over the chunk's rows: dU_last given (read only), activations H[0 .. n-2] in the workspace
+int BwdCall::mlp_backward(const Chunk& c, const float* dUlast) {
+    const int32_t* dims = a.dims;
+    const int rows = c.rows;
+    const float* dUc = dUlast;
+    float* bufs[2] = {F(P.off_dU[0]), F(P.off_dU[1])};
+    // The layer GEMMs below read every row of dU_l from all their column-slice workgroups and write dU_{l-1}
+    // rows of the same indices: the output must never be the buffer the input lives in.  In the FULL phase
+    // dU_last IS bufs[0] (the per-edge kernel wrote it there), so the first output goes to bufs[1].  (Rounds 1-2
+    // started at bufs[0]: a workgroup that finished its tile early overwrote rows a sibling slice was still
+    // reading - the intermittent 1e-3 error in grad_W1)
+    int nb = dUlast == bufs[0] ? 1 : 0;
+    bool fl_in_kernel = false;           // the dW_2 GEMM of this chunk generated H_1 itself (round 6 plan)
+    bool dw1_done = false;               // the dU_1 GEMM's epilogue formed dW_1 / db_1 (k_dw_first has nothing left to do)
+    for (int l = n - 1; l >= 1; --l) {
+        const int Kl = P.KP[l], Kin = P.KP[l - 1];
+        int rc;
+        if (l == 1 && a.grad_attr) {       // dU_1 is complete here: the gradient of the attributes through W_1
+            tr.set(GPDE_BWD_TRACE_GRAD_ATTR, 1);
+            hipLaunchKernelGGL(k_grad_attr, dim3((rows + 3) / 4), dim3(T), 0, st, dUc, Kl, F(P.off_wp[1]), Kin, a.perm, c.e0, rows,
+                               dims[0], a.grad_attr);
+        }
+        if (l == 1 && dw1_done) continue;
+        if (l == 1 && dims[0] <= 8 && Kin >= 8 && Kin % 4 == 0 && Kl % 4 == 0 && rows >= 1024) {
+            // dW_1 and db_1 from one pass over dU_1 (k_dw_first; attribute slots beyond k0 are zero columns of H_0)
+            const int cb = (Kl + 255) / 256;
+            int splits = 1; while (splits < 256 && cb * splits < 1024 && rows / (splits * 2) >= 64) splits *= 2;
+            while (splits > 1 && (size_t)splits * Kl * 9 > P.part_floats) splits /= 2;
+            if ((size_t)splits * Kl * 9 <= P.part_floats) {
+                tr.set(GPDE_BWD_TRACE_DW1, 2);
+                hipLaunchKernelGGL(k_dw_first, dim3(cb, splits), dim3(T), 0, st, dUc, F(P.off_H[0]), Kin, rows, Kl, splits, F(P.off_part));
+                hipLaunchKernelGGL(k_dw_first_reduce, dim3(nblk((size_t)Kl * 9)), dim3(T), 0, st, F(P.off_part), splits, Kl, Kin,
+                                   F(P.off_dwp[l]), F(P.off_dbp[l]));
+                continue;      // l == 1 is the last layer of the loop: nothing below it to back-propagate into
+            }
+        }
+        const bool tn_split = l == 2 && f16s_dw2 && rows >= 8192;
+        // one pass over dU_2 for its transposed copy, db_2, and the row scales of the dU_1 GEMM
+        const bool du_one_pass = tn_split && f16s_du1;
+        unsigned* du_bits = tn_split ? (unsigned*)F(P.off_dubits) : nullptr;
+        if (!du_one_pass) {   // db_l = column sums of dU_l; the same pass collects the column maxima the split dW_2 GEMM scales with
+            const int cb = (Kl + 255) / 256;
+            int splits = 1; while (splits < 512 && cb * splits < 2048 && rows / (splits * 2) >= 64) splits *= 2;
+            while (splits > 1 && (size_t)splits * Kl > P.part_floats) splits /= 2;
+            if (du_bits) GP_HIP_CHECK(gpde_zero_async(du_bits, (size_t)Kl * 4, st));
+            hipLaunchKernelGGL(k_colsum, dim3(cb, splits), dim3(T), 0, st, dUc, rows, Kl, Kl, splits, F(P.off_part), du_bits);
+            if ((rc = gpde_launch_reduce_splits(F(P.off_part), Kl, splits, Kl, F(P.off_dbp[l]), 1, st)) != GPDE_OK) return rc;
+        }
+        if (tn_split) {
+            // dW_2 += dU_2^T . H_1 on the split-f16 GEMM (contraction over the edges: both operands transposed)
+            tr.set(GPDE_BWD_TRACE_DW2, 1);
+            const int ks = tn_ksplits(rows, P.KP[2], P.KP[1]);
+            GpdeFirstLayerSpec fl{F(P.off_H[0]), P.KP[0], F(P.off_wp[1]), P.KP[0], F(P.off_bp[1]), (uint32_t*)F(P.off_maskbits), dims[0],
+                                  call_amax ? (const unsigned*)F(P.off_amax8) : nullptr};
+            fl_in_kernel = skip_h1(rows) && gpde_first_layer_in_kernel(fl, rows, ks);
+            if (fl_in_kernel) tr.set(GPDE_BWD_TRACE_H1, 3);
+            GpdeDuStats dst_{F(P.off_dbp[l]), F(P.off_rowsc), F(P.off_rowsc) + rows,
+                             c.du_pre ? F(P.off_tcs) : nullptr, c.du_pre ? (const unsigned*)F(P.off_tcm) : nullptr};
+            if ((rc = gpde_launch_gemm_f16s_tn(dUc, Kl, Kl, F(P.off_H[l - 1]), Kin, Kin, rows, ks, F(P.off_tnws), F(P.off_part), st,
+                                                du_one_pass ? nullptr : du_bits, skip_h1(rows) ? &fl : nullptr,
+                                                du_one_pass ? &dst_ : nullptr)) != GPDE_OK) return rc;
+            if ((rc = gpde_launch_reduce_splits(F(P.off_part), (size_t)Kl * Kin, ks, (size_t)Kl * Kin, F(P.off_dwp[l]), 1, st)) != GPDE_OK) return rc;
+        } else {
+            if (l == 2) tr.set(GPDE_BWD_TRACE_DW2, 2);
+            if (l == 1) tr.set(GPDE_BWD_TRACE_DW1, 3);
+            if ((rc = gemm_tn_acc(dUc, Kl, Kl, F(P.off_H[l - 1]), Kin, Kin, rows, F(P.off_dwp[l]), F(P.off_part), P.part_floats, 1, st)) != GPDE_OK) return rc;
+        }
+        if (l == 2 && f16s_du1 && rows >= 64) {
+            tr.set(GPDE_BWD_TRACE_DU1, 1);
+            float* dUo = bufs[nb]; nb ^= 1;
+            GpdeGemmF16sArgs g{};
+            g.A = dUc; g.lda = Kl; g.M = rows; g.bsplit = F(P.off_w2ts); g.ucol = F(P.off_ucol2);
+            g.mask = F(P.off_H[l - 1]); g.ldmask = Kin; g.C = dUo; g.ldc = Kin; g.K = Kl; g.N = Kin;
+            if (tn_split && skip_h1(rows)) { g.mask = nullptr; g.ldmask = 0; g.maskbits = (const uint32_t*)F(P.off_maskbits); g.ldmb = Kin / 32; }
+            if (tn_split && fl_in_kernel && dims[0] <= 7 && !a.grad_attr &&
+                gpde_gemm_f16s_dw_part_floats(rows, Kin) <= (size_t)rows * Kin) {
+                // round 6: this GEMM's epilogue forms dW_1 / db_1 from the tile in its registers: dU_1 (4 KiB per edge) is neither
+                // written nor read back by k_dw_first - unless the attribute gradient wants the tensor.  Scratch of the tile partials: the dU_1 buffer itself (512 bytes per row of its 4 KiB)
+                g.fl_mode = 2; g.fl_attr = F(P.off_H[0]); g.fl_ld0 = P.KP[0]; g.fl_rows = rows;
+                g.fl_dw_part = dUo; g.fl_dw_out = F(P.off_dwp[1]); g.fl_dw_ld = P.KP[0]; g.fl_db_out = F(P.off_dbp[1]);
+                g.fl_skip_store = 1;
+                dw1_done = true;
+                tr.set(GPDE_BWD_TRACE_DW1, 1);
+            }
+            // (row scales: a pass over dU_2, 3.9 ms at s=121.  Collecting the row maxima inside gpde_edge_bwd2_kernel was
+            // tried in round 3: 16 more registers spill 15 VGPRs of a kernel that sits at its 256-register limit, +5 ms.)
+            if (du_one_pass) {                    // row scales left in off_rowsc by the transposing pass above
+                g.sc = F(P.off_rowsc); g.isc = F(P.off_rowsc) + rows;
+                if ((rc = gpde_launch_gemm_f16s_nt(g, nullptr, st)) != GPDE_OK) return rc;
+            } else if ((rc = gpde_launch_gemm_f16s_nt(g, F(P.off_rowsc), st)) != GPDE_OK) return rc;
+            dUc = dUo;
+        } else if (l > 1) {
+            if (l == 2) tr.set(GPDE_BWD_TRACE_DU1, 2);
+            float* dUo = bufs[nb]; nb ^= 1;
+            GpdeGemmArgs g = gemm0();
+            g.A = dUc; g.lda = Kl; g.B = F(P.off_wp[l]); g.ldb = Kin; g.b_kcontig = 0;
+            g.C = dUo; g.ldc = Kin; g.M = rows; g.N = Kin; g.K = Kl;
+            g.mask = F(P.off_H[l - 1]); g.ldmask = Kin;
+            if ((rc = gpde_launch_gemm(g, st)) != GPDE_OK) return rc;
+            dUc = dUo;
+        }
     }
-    if (do_conv && grad_W && grad_W[n - 1])
+    return GPDE_OK;
+}
+
+// the node chunk that starts at `na`: the largest nb with (nb - na) <= Nc and edges <= Ec (at least one node)
+int BwdCall::next_chunk(int na, Chunk* c) {
+    const int32_t* rowptr_host = a.rowptr_host;
+    int lo = na + 1, hi = (int)((int64_t)na + P.Nc < N ? na + P.Nc : N);
+    const bool from_h = a.hpart && na < a.hpart_nodes;
+    if (from_h && hi > a.hpart_nodes) hi = (int)a.hpart_nodes;        // a chunk never straddles the end of the given H
+    const int64_t ebase = rowptr_host[na];
+    if (phase == BWD_CONV) P.Ec = a.n_edges;       // H and dU live outside the workspace: no edge limit
+    if (rowptr_host[lo] - ebase > P.Ec) {
+        gpde_set_error("gpde_nnconv_bwd: node %d has in-degree %d > %lld edges per chunk; give more workspace",
+                       na, (int)(rowptr_host[lo] - ebase), (long long)P.Ec);
+        return GPDE_EWORKSPACE;
+    }
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (rowptr_host[mid] - ebase <= P.Ec) lo = mid; else hi = mid - 1;
+    }
+    const int e0 = (int)ebase;
+    *c = Chunk{na, lo, e0, rowptr_host[lo] - e0, from_h ? a.hpart + (size_t)e0 * K2P : nullptr, false};
+    return GPDE_OK;
+}
+
+// BWD_DEFER: dU_2 of the chunk's edges from the stacked layer inputs and output gradients, then ONE MLP backward
+int BwdCall::defer_chunk(const Chunk& c) {
+    if (c.rows == 0) return GPDE_OK;
+    const int nn = c.nb - c.na, rows = c.rows;
+    float* gT = F(P.off_gT);
+    int rc;
+    if ((rc = recompute(c, n - 1)) != GPDE_OK) return rc;
+    const float* H2 = c.h ? c.h : F(P.off_H[n - 1]);
+    // dZ^(l)[i][c][k] = sum_o gT^(l)[i][o] W3[c*64+o][k] of every deferred layer, then the nodes' split images
+    const size_t dzl = (size_t)P.Nc * GP_W * K2P;
+    for (int l = 0; l < P.L; ++l) {
+        hipLaunchKernelGGL(k_scale_g, dim3((nn + 3) / 4), dim3(T), 0, st, a.g_stack + (size_t)l * N * GP_W, a.rowptr, a.aggr, c.na, nn, gT);
+        GpdeGemmArgs g = gemm0();
+        g.A = gT; g.lda = GP_W; g.B = F(P.off_w3p); g.ldb = K2P; g.b_kcontig = 0;
+        g.C = F(P.off_dzstack) + (size_t)l * dzl; g.ldc = GP_W * K2P; g.M = nn; g.N = K2P; g.K = GP_W;
+        g.batches = GP_W; g.strideA = 0; g.strideB = (size_t)GP_W * K2P; g.strideC = K2P;
+        if ((rc = gpde_launch_gemm(g, st)) != GPDE_OK) return rc;
+    }
+    if ((rc = gpde_launch_dz_image(F(P.off_dzstack), dzl, P.L, P.Lp, nn, K2P, (unsigned*)F(P.off_nbits), F(P.off_nscale),
+                                   F(P.off_nscale) + P.Nc, F(P.off_dzimg), st)) != GPDE_OK) return rc;
+    const int ntiles = gpde_tile_count(a.rowptr_host, c.na, c.nb);
+    int32_t* tiles = (int32_t*)F(P.off_tiles);
+    if ((rc = gpde_launch_tile_list(a.rowptr, c.na, nn, c.e0, tiles, st)) != GPDE_OK) return rc;
+    // dU_2 of the chunk's edges: (sum over the layers of x_j . dZ_i) masked by the recomputed H_2 > 0
+    float* dU2 = F(P.off_dU[0]);
+    if ((rc = gpde_launch_gemm_f16s_gather(a.x_stack, (size_t)N * GP_W, P.Lp, F(P.off_xsc), F(P.off_xsc) + N, a.src + c.e0, rows, tiles, ntiles,
+                                           F(P.off_dzimg), F(P.off_nscale) + P.Nc, H2, K2P, dU2, K2P, K2P, st)) != GPDE_OK) return rc;
+    return mlp_backward(c, dU2);
+}
+
+// Z of the chunk's nodes: kept by the forward (gpde_nnconv_fwd_keepz), else re-aggregated from the recomputed / given activations
+int BwdCall::chunk_z(const Chunk& c, const float* Hlast, const float** Z) {
+    if (a.z_saved) { *Z = a.z_saved + (size_t)c.na * GP_W * K2P; tr.set(GPDE_BWD_TRACE_Z, 1); return GPDE_OK; }
+    float* Zc = F(P.off_Z);
+    *Z = Zc;
+    GP_HIP_CHECK(gpde_zero_async(Zc, (size_t)(c.nb - c.na) * GP_W * K2P * 4, st));
+    GpdeFusedArgs f{};
+    f.x = a.x; f.attr = a.edge_attr; f.rowptr = a.rowptr; f.src = a.src; f.dst = a.dst; f.perm = a.perm;
+    f.hbuf = Hlast; f.zbuf = Zc; f.k0 = a.dims[0]; f.K1P = 32; f.K2P = K2P;
+    f.nc0 = c.na; f.nc1 = c.nb; f.e_chunk0 = c.e0;
+    tr.set(GPDE_BWD_TRACE_Z, 2);
+    if (zagg16) { f.xs = (const unsigned*)F(P.off_xs); f.scal = (const unsigned*)F(P.off_scal); f.hmax = (const unsigned*)F(P.off_scal) + 2; tr.set(GPDE_BWD_TRACE_Z, 3); }
+    f.n_groups = gpde_fused_groups(K2P, gpde_group_cap_bwd_chunk(c.rows));
+    return gpde_launch_zagg(f, st);
+}
+
+// gradients of the last Linear from the chunk's nodes, and what the per-edge stage reads: dZ (workspace off_dZ), dS (off_dS)
+int BwdCall::last_layer_grads(const Chunk& c, const float* Z) {
+    const int nn = c.nb - c.na;
+    const size_t w3n = (size_t)GP_W * GP_W * K2P;
+    float* gT = F(P.off_gT); float* S = F(P.off_S); float* dZ = F(P.off_dZ);
+    int rc;
+    hipLaunchKernelGGL(k_nbr_sum, dim3(nn), dim3(T), 0, st, a.x, a.rowptr, a.src, c.na, nn, S);
+    // db3[c][o] += S^T gT ;  dW3[c][o][k] += gT^T Z[:, c, :]
+    if ((rc = gemm_tn_acc(S, GP_W, GP_W, gT, GP_W, GP_W, nn, F(P.off_db3), F(P.off_part), P.part_floats, 1, st)) != GPDE_OK) return rc;
+    GpdeGemmArgs g = gemm0();
+    g.A = gT; g.lda = GP_W; g.a_kcontig = 0; g.B = Z; g.ldb = GP_W * K2P; g.b_kcontig = 0;
+    g.C = F(P.off_dw3p); g.ldc = K2P; g.M = GP_W; g.N = K2P; g.K = nn; g.accumulate = 1;
+    g.batches = GP_W; g.strideA = 0; g.strideB = K2P; g.strideC = (size_t)GP_W * K2P;
+    // narrow kernels (the MGKN levels: K2P = 128 / 256) give 64 - 128 workgroups that each walk all nn nodes (365 us at
+    // nn = 4525): split the node range (ordered partial reduction: deterministic) until ~512 workgroups are busy.  The
+    // partials live in the chunk's dZ buffer - nn x 64 x K2P floats that are written only by the next GEMM below, and
+    // sp <= nn / 128 of these 64 x 64 x K2P images always fit
+    int sp = 1;
+    const int wgs = GP_W * ((K2P + 127) / 128);
+    while (sp < 16 && wgs * sp < 512 && nn / (sp * 2) >= 64) sp *= 2;
+    if (sp > 1) {
+        g.C = dZ; g.accumulate = 0; g.splits = sp; g.strideSplit = w3n;
+        if ((rc = gpde_launch_gemm(g, st)) != GPDE_OK) return rc;
+        if ((rc = gpde_launch_reduce_splits(dZ, w3n, sp, w3n, F(P.off_dw3p), 1, st)) != GPDE_OK) return rc;
+    } else if ((rc = gpde_launch_gemm(g, st)) != GPDE_OK) return rc;
+    // dZ[i][c][k] = sum_o gT[i][o] W3[c*64+o][k] ;  dS[i][c] = sum_o gT[i][o] b3[c*64+o]
+    GpdeGemmArgs z = gemm0();
+    z.A = gT; z.lda = GP_W; z.B = F(P.off_w3p); z.ldb = K2P; z.b_kcontig = 0;
+    z.C = dZ; z.ldc = GP_W * K2P; z.M = nn; z.N = K2P; z.K = GP_W;
+    z.batches = GP_W; z.strideA = 0; z.strideB = (size_t)GP_W * K2P; z.strideC = K2P;
+    if ((rc = gpde_launch_gemm(z, st)) != GPDE_OK) return rc;
+    GpdeGemmArgs s2 = gemm0();
+    s2.A = gT; s2.lda = GP_W; s2.B = F(P.off_b3); s2.ldb = GP_W; s2.C = F(P.off_dS); s2.ldc = GP_W;
+    s2.M = nn; s2.N = GP_W; s2.K = GP_W;
+    return gpde_launch_gemm(s2, st);
+}
+
+// Which per-edge kernel serves the chunk: 1 gpde_edge_bwd_kernel, 2 gpde_edge_bwd2_kernel (staged, fp32 MFMA), 3 the split-f16
+// gpde_edge_bwd3_kernel; 0: none can (accumulating dL/dU lives in the split-f16 kernel: it is correct for any in-degree, the
+// host asks for it on dense graphs).  Staged kernels where a 128-slot group rarely spans more than two destinations
+// (round 6: from mean in-degree 4 - the split-f16 kernel is correct for any in-degree and measured faster on the MGKN
+// levels of in-degree 6 - 22 too: 1.4 ms of a 30 ms training step of config 4)
+int BwdCall::edge_kernel(const Chunk& c, bool gh_acc) const {
+    const int force = SW.edge_bwd;                     // GPDE_EDGE_BWD = 1 / 2 / 3: force a variant (tests, A/B)
+    const bool staged = force ? force >= 2 : (gh_acc || (int64_t)c.rows >= (int64_t)(K2P % 32 == 0 ? 4 : 32) * (c.nb - c.na));
+    if (staged && force != 2 && K2P % 32 == 0) return 3;      // split-f16 MFMA (default); GPDE_EDGE_BWD=2: the fp32-MFMA staged kernel
+    if (gh_acc) return 0;
+    return staged ? 2 : 1;
+}
+
+// per-edge backward through the aggregation -> dU_{n-1} (dUc; null: dx only), dx_j
+int BwdCall::edge_backward(Chunk& c, const float* Hlast, float* dUc) {
+    const int nn = c.nb - c.na, e0 = c.e0, e1 = c.e0 + c.rows, rows = c.rows;
+    float* dZ = F(P.off_dZ); float* dS = F(P.off_dS); float* dx = a.grad_x;
+    int rc;
+    const bool ordered = a.src_rowptr && a.src_slots;
+    EdgeBwdArgs ea{a.x, a.rowptr, a.src, a.dst, dZ, dS, Hlast, dUc, dx, e0, e1, c.na, K2P, ordered ? F(P.off_dxe) : nullptr};
+    const size_t lds = (size_t)4 * (32 * EB_XS + 32 * EB_HS) * 4;
+    const size_t lds2 = (size_t)(2 * EB2_DZ + 4 * 2 * EB2_H) * 4 + 4 * 64 * 4;
+    static GpdeLdsOnce once;
+    if ((rc = once.ensure(gpde_edge_bwd_kernel, gpde_edge_bwd2_kernel))) return rc;
+    if (!dx) { gpde_set_error("gpde_nnconv_bwd: grad_x must be provided"); return GPDE_EINVAL; }
+    const bool gh_acc = a.gh_accumulate && phase == BWD_CONV;
+    const int kernel = edge_kernel(c, gh_acc);
+    if (!kernel) {
+        gpde_set_error("gpde_nnconv_bwd: GPDE_BWD_ACCUMULATE_GRAD_HIDDEN is built into the split-f16 per-edge kernel only "
+                       "(GPDE_EDGE_BWD=2 forces the other one)");
+        return GPDE_EUNSUPPORTED;
+    }
+    tr.set(GPDE_BWD_TRACE_EDGE_KERNEL, kernel);
+    if (kernel == 3) {
+        if ((rc = gpde_launch_dz_split(dZ, nn, K2P, F(P.off_dzun), st)) != GPDE_OK) return rc;
+        GpdeEdgeBwd3Args e3{a.x, a.src, a.dst, dZ, F(P.off_dzun), dS, Hlast, dUc, dx, ordered ? F(P.off_dxe) : nullptr, e0, e1, c.na, K2P};
+        e3.du_accumulate = gh_acc;
+        // full backward on the split GEMMs: the kernel also leaves what the dW_2 GEMM's pass over dU_2 would form
+        // (mlp_backward's tn_split && du_one_pass case)
+        if (phase == BWD_FULL && n == 3 && f16s_dw2 && f16s_du1 && rows >= 8192) {
+            e3.dUt = gpde_gemm_f16s_tn_at(F(P.off_tnws), rows, tn_ksplits(rows, P.KP[2], P.KP[1]), &e3.ldt);
+            e3.row_sc = F(P.off_rowsc); e3.row_isc = F(P.off_rowsc) + rows;
+            e3.csum_part = F(P.off_tcs); e3.cmax_part = (unsigned*)F(P.off_tcm);
+            c.du_pre = true;
+            tr.set(GPDE_BWD_TRACE_DU_PRE, 1);
+        }
+        if ((rc = gpde_launch_edge_bwd3(e3, st)) != GPDE_OK) return rc;
+    } else if (kernel == 2) {
+        hipLaunchKernelGGL(gpde_edge_bwd2_kernel, dim3(((rows + 127) / 128 + 7) / 8 * 8), dim3(T), lds2, st, ea);
+    } else {
+        hipLaunchKernelGGL(gpde_edge_bwd_kernel, dim3((rows + 127) / 128), dim3(T), lds, st, ea);
+    }
+    if (ordered) tr.set(GPDE_BWD_TRACE_ORDERED, 1);
+    if (ordered) hipLaunchKernelGGL(k_dx_reduce, dim3((N + 3) / 4), dim3(T), 0, st, F(P.off_dxe), a.src_rowptr, a.src_slots, N, e0, e1, dx, 1, (size_t)0, 0);
+    return GPDE_OK;
+}
+
+// BWD_FULL / CONV / LIGHT: the conv side of a node chunk, then (FULL) the MLP backward over its edges
+int BwdCall::conv_chunk(Chunk& c) {
+    const int nn = c.nb - c.na;
+    int rc;
+    hipLaunchKernelGGL(k_scale_g, dim3((nn + 3) / 4), dim3(T), 0, st, a.grad_out, a.rowptr, a.aggr, c.na, nn, F(P.off_gT));
+    if (c.rows == 0) return GPDE_OK;
+    // hidden activations of the chunk's edges: recomputed, or rows of the given cache
+    const bool recomputes = phase == BWD_FULL || light;
+    if (recomputes && (rc = recompute(c, n - 1)) != GPDE_OK) return rc;
+    const float* Hlast = c.h ? c.h : recomputes ? F(P.off_H[n - 1]) : nullptr;
+    if (!Hlast) { Hlast = a.hidden + (size_t)c.e0 * K2P; tr.set(GPDE_BWD_TRACE_HLAST, 1); tr.set(GPDE_BWD_TRACE_FROM_H, 1); }
+    const float* Z = nullptr;
+    if ((rc = chunk_z(c, Hlast, &Z)) != GPDE_OK) return rc;
+    if ((rc = last_layer_grads(c, Z)) != GPDE_OK) return rc;
+    float* dUc = phase == BWD_FULL ? F(P.off_dU[0]) : light ? nullptr : a.grad_hidden_out + (size_t)c.e0 * K2P;   // light: dx only
+    if ((rc = edge_backward(c, Hlast, dUc)) != GPDE_OK) return rc;
+    return phase == BWD_FULL ? mlp_backward(c, dUc) : GPDE_OK;
+}
+
+// node-side terms of update(), then the weight gradients un-padded into torch layout
+int BwdCall::finish() {
+    const int32_t* dims = a.dims;
+    int rc;
+    // dx += g root^T, droot = X^T g, dbias = colsum g
+    if (do_conv && (rc = bwd_node_terms(a.x, N, a.root, a.grad_out, a.grad_x, a.grad_root, a.grad_bias, F(P.off_part), P.part_floats, st)) != GPDE_OK) return rc;
+    for (int l = 1; l < n && do_mlp; ++l) {
+        if (a.grad_W && a.grad_W[l - 1])
+            hipLaunchKernelGGL(k_unpad_mat, dim3(nblk((size_t)dims[l] * dims[l - 1])), dim3(T), 0, st, F(P.off_dwp[l]),
+                               dims[l], dims[l - 1], P.KP[l - 1], a.grad_W[l - 1]);
+        if (a.grad_b && a.grad_b[l - 1])
+            GP_HIP_CHECK(gpde_copy_async(a.grad_b[l - 1], F(P.off_dbp[l]), (size_t)dims[l] * 4, st));
+    }
+    if (do_conv && a.grad_W && a.grad_W[n - 1])
         hipLaunchKernelGGL(k_unpad_mat, dim3(nblk((size_t)GP_W * GP_W * dims[n - 1])), dim3(T), 0, st, F(P.off_dw3p),
-                           GP_W * GP_W, dims[n - 1], K2P, grad_W[n - 1]);
-    if (do_conv && grad_b && grad_b[n - 1])
-        GP_HIP_CHECK(gpde_copy_async(grad_b[n - 1], F(P.off_db3), GP_W * GP_W * 4, st));
+                           GP_W * GP_W, dims[n - 1], K2P, a.grad_W[n - 1]);
+    if (do_conv && a.grad_b && a.grad_b[n - 1])
+        GP_HIP_CHECK(gpde_copy_async(a.grad_b[n - 1], F(P.off_db3), GP_W * GP_W * 4, st));
     GP_LAUNCH_CHECK("gpde_nnconv_bwd epilogue kernels");
     return GPDE_OK;
 }
 
+int BwdCall::run() {
+    int rc = setup();
+    if (rc != GPDE_OK) return rc;
+    if (phase == BWD_MLP) {
+        // plain edge chunks: nothing here depends on the destination structure
+        for (int64_t e0 = 0; e0 < a.n_edges; e0 += P.Ec) {
+            const Chunk c{-1, -1, (int)e0, (int)((a.n_edges - e0) < P.Ec ? (a.n_edges - e0) : P.Ec), nullptr, false};
+            tr.begin(c);
+            // activations below the last hidden layer are recomputed; the last one is needed only as
+            // the ReLU mask, which the incoming dL/dU already carries
+            if ((rc = recompute(c, n - 2)) != GPDE_OK) return rc;
+            if ((rc = mlp_backward(c, a.grad_hidden_in + (size_t)e0 * K2P)) != GPDE_OK) return rc;
+            tr.emit();
+        }
+        GP_LAUNCH_CHECK("gpde_hidden_bwd kernels");
+    }
+    // ---- node-aligned chunks ----------------------------------------------------------------------------------
+    if (phase == BWD_DEFER && a.n_edges > 0)
+        if ((rc = gpde_launch_xstack_scales(a.x_stack, (size_t)N * GP_W, P.L, N, F(P.off_xsc), F(P.off_xsc) + N, st)) != GPDE_OK) return rc;
+    int na = 0;
+    while ((do_conv || phase == BWD_DEFER) && na < N && a.n_edges > 0) {
+        Chunk c;
+        if ((rc = next_chunk(na, &c)) != GPDE_OK) return rc;
+        tr.begin(c);
+        if ((rc = phase == BWD_DEFER ? defer_chunk(c) : conv_chunk(c)) != GPDE_OK) return rc;
+        tr.emit();
+        na = c.nb;
+    }
+    GP_LAUNCH_CHECK("gpde_nnconv_bwd kernels");
+    return finish();
+}
+
+int bwd_impl(BwdPhase phase, const BwdArgs& a) { return BwdCall(phase, a).run(); }
+
 }  // namespace
+
 
 extern "C" int gpde_nnconv_bwd_plan(int64_t n_nodes, int64_t n_edges, int n_layers, const int32_t* dims, size_t ws_bytes,
                                     int n_defer, int h_given, int64_t* edges_per_chunk, int64_t* nodes_per_chunk) {
@@ -1837,26 +1948,21 @@ extern "C" int gpde_nnconv_bwd(const float* x, int64_t n_nodes, const float* edg
         gpde_set_error("gpde_nnconv_bwd: GPDE_BWD_ACCUMULATE_GRAD_HIDDEN belongs to the `hidden` form (grad_hidden given)");
         return GPDE_EINVAL;
     }
-    hipStream_t st = (hipStream_t)stream_;
-    const float* hk = h_kept ? hidden : nullptr;
-    const int64_t hk_nodes = h_kept ? n_nodes : 0;
+    BwdArgs a = bwd_common(n_edges, n_layers, dims, W, b, grad_W, grad_b, ws, ws_bytes, stream_);
+    bwd_graph(a, n_nodes, rowptr, src, dst, rowptr_host, aggr);
+    a.x = x; a.root = root; a.grad_out = grad_out; a.grad_x = grad_x; a.grad_root = grad_root; a.grad_bias = grad_bias;
+    a.src_rowptr = src_rowptr; a.src_slots = src_slots; a.z_saved = z_saved;
     if (hidden && !h_kept) {
         if (n_edges > 0 && !grad_hidden) { gpde_set_error("gpde_nnconv_bwd: grad_hidden is null"); return GPDE_EINVAL; }
-        return bwd_impl(BWD_CONV, x, n_nodes, nullptr, n_edges, rowptr, src, dst, nullptr, rowptr_host, n_layers, dims, W, b, root,
-                        aggr, grad_out, grad_x, grad_W, grad_b, grad_root, grad_bias, hidden, grad_hidden, nullptr, ws, ws_bytes,
-                        st, src_rowptr, src_slots, z_saved, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr,
-                        (flags & GPDE_BWD_ACCUMULATE_GRAD_HIDDEN) != 0);
+        a.hidden = hidden; a.grad_hidden_out = grad_hidden; a.gh_accumulate = (flags & GPDE_BWD_ACCUMULATE_GRAD_HIDDEN) != 0;
+        return bwd_impl(BWD_CONV, a);
     }
-    if (node_attr) {
-        if (!na_ok(node_attr, dims, "gpde_nnconv_bwd")) return GPDE_EINVAL;
-        return bwd_impl(BWD_FULL, x, n_nodes, node_attr->table, n_edges, rowptr, src, dst, nullptr, rowptr_host, n_layers, dims, W, b, root,
-                        aggr, grad_out, grad_x, grad_W, grad_b, grad_root, grad_bias, nullptr, nullptr, nullptr, ws, ws_bytes, st,
-                        src_rowptr, src_slots, z_saved, 0, nullptr, nullptr, hk, hk_nodes, node_attr->stride, node_attr->sel);
-    }
-    if (n_edges > 0 && (!edge_attr || !perm)) { gpde_set_error("gpde_nnconv_bwd: edge_attr / perm is null"); return GPDE_EINVAL; }
-    return bwd_impl(BWD_FULL, x, n_nodes, edge_attr, n_edges, rowptr, src, dst, perm, rowptr_host, n_layers, dims, W, b, root, aggr,
-                    grad_out, grad_x, grad_W, grad_b, grad_root, grad_bias, nullptr, nullptr, nullptr, ws, ws_bytes, st,
-                    src_rowptr, src_slots, z_saved, 0, nullptr, nullptr, hk, hk_nodes, 0, nullptr, n_edges > 0 ? grad_edge_attr : nullptr);
+    if (node_attr && !na_ok(node_attr, dims, "gpde_nnconv_bwd")) return GPDE_EINVAL;
+    if (!node_attr && n_edges > 0 && (!edge_attr || !perm)) { gpde_set_error("gpde_nnconv_bwd: edge_attr / perm is null"); return GPDE_EINVAL; }
+    bwd_attr_source(a, edge_attr, perm, node_attr);
+    if (h_kept) { a.hpart = hidden; a.hpart_nodes = n_nodes; }
+    if (!node_attr && n_edges > 0) a.grad_attr = grad_edge_attr;
+    return bwd_impl(BWD_FULL, a);
 }
 
 // ---- depth-deferred backward: a module applied `depth` times with the same edge_attr and weights ----------------------
@@ -1869,9 +1975,7 @@ extern "C" int gpde_nnconv_bwd_deferred_supported(int n_layers, const int32_t* d
     GpdePackLayout PL;
     if (!dims || n_layers != 3 || make_bwd_plan(1, 1, n_layers, dims, 0, true, &P, 2) != GPDE_OK) return 0;
     if (!(P.f16s_du1 && P.f16s_dw2 && P.pack_bytes) || dims[0] > 7 || gpde_pack_layout(n_layers, dims, &PL) != GPDE_OK || PL.mode != 1) return 0;
-    GpdeFusedArgs probe{};
-    probe.k0 = PL.k0; probe.K1P = PL.K1P; probe.K2P = PL.K2P;
-    return gpde_fused_store_supported(probe) ? 1 : 0;
+    return gpde_fused_store_supported(gpde_fused_probe(PL)) ? 1 : 0;
 }
 
 extern "C" size_t gpde_nnconv_bwd_deferred_workspace_bytes(int64_t n_nodes, int64_t n_edges, int n_layers, const int32_t* dims,
@@ -1900,11 +2004,13 @@ extern "C" int gpde_nnconv_bwd_light(const float* x, int64_t n_nodes, const floa
     float* gW[GPDE_MAX_LAYERS] = {};
     float* gb[GPDE_MAX_LAYERS] = {};
     gW[n_layers - 1] = grad_w_last; gb[n_layers - 1] = grad_b_last;
-    return bwd_impl(BWD_LIGHT, x, n_nodes, node_attr ? node_attr->table : edge_attr, n_edges, rowptr, src, dst, node_attr ? nullptr : perm,
-                    rowptr_host, n_layers, dims, W, b, root, aggr,
-                    grad_out, grad_x, gW, gb, grad_root, grad_bias, nullptr, nullptr, nullptr, ws, ws_bytes, (hipStream_t)stream_,
-                    src_rowptr, src_slots, z_saved, 0, nullptr, nullptr, hidden_nodes > 0 ? hidden_part : nullptr, hidden_nodes,
-                    node_attr ? node_attr->stride : 0, node_attr ? node_attr->sel : nullptr);
+    BwdArgs a = bwd_common(n_edges, n_layers, dims, W, b, gW, gb, ws, ws_bytes, stream_);
+    bwd_graph(a, n_nodes, rowptr, src, dst, rowptr_host, aggr);
+    bwd_attr_source(a, edge_attr, perm, node_attr);
+    a.x = x; a.root = root; a.grad_out = grad_out; a.grad_x = grad_x; a.grad_root = grad_root; a.grad_bias = grad_bias;
+    a.src_rowptr = src_rowptr; a.src_slots = src_slots; a.z_saved = z_saved;
+    a.hpart = hidden_nodes > 0 ? hidden_part : nullptr; a.hpart_nodes = hidden_nodes;
+    return bwd_impl(BWD_LIGHT, a);
 }
 
 extern "C" int gpde_nnconv_bwd_deferred(const float* x_stack, const float* grad_out_stack, int n_defer, int64_t n_nodes,
@@ -1922,12 +2028,12 @@ extern "C" int gpde_nnconv_bwd_deferred(const float* x_stack, const float* grad_
     }
     if (node_attr && !na_ok(node_attr, dims, "gpde_nnconv_bwd_deferred")) return GPDE_EINVAL;
     if (aggr != GPDE_AGGR_ADD && aggr != GPDE_AGGR_MEAN) { gpde_set_error("gpde_nnconv_bwd_deferred: aggr %d", aggr); return GPDE_EUNSUPPORTED; }
-    return bwd_impl(BWD_DEFER, nullptr, n_nodes, node_attr ? node_attr->table : edge_attr, n_edges, rowptr, src, dst, node_attr ? nullptr : perm,
-                    rowptr_host, n_layers, dims, W, b, nullptr,
-                    aggr, nullptr, nullptr, grad_W, grad_b, nullptr, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes,
-                    (hipStream_t)stream_, nullptr, nullptr, nullptr, n_defer, x_stack, grad_out_stack,
-                    hidden_nodes > 0 ? hidden_part : nullptr, hidden_nodes, node_attr ? node_attr->stride : 0,
-                    node_attr ? node_attr->sel : nullptr);
+    BwdArgs a = bwd_common(n_edges, n_layers, dims, W, b, grad_W, grad_b, ws, ws_bytes, stream_);
+    bwd_graph(a, n_nodes, rowptr, src, dst, rowptr_host, aggr);
+    bwd_attr_source(a, edge_attr, perm, node_attr);
+    a.n_defer = n_defer; a.x_stack = x_stack; a.g_stack = grad_out_stack;
+    a.hpart = hidden_nodes > 0 ? hidden_part : nullptr; a.hpart_nodes = hidden_nodes;
+    return bwd_impl(BWD_DEFER, a);
 }
 
 extern "C" int gpde_hidden_bwd(const float* edge_attr, const GpdeNodeAttr* node_attr, int64_t n_edges, const int32_t* perm,
@@ -1940,15 +2046,12 @@ extern "C" int gpde_hidden_bwd(const float* edge_attr, const GpdeNodeAttr* node_
         gpde_set_error("gpde_hidden_bwd: null/negative argument");
         return GPDE_EINVAL;
     }
-    if (node_attr) {
-        if (!na_ok(node_attr, dims, "gpde_hidden_bwd")) return GPDE_EINVAL;
-        return bwd_impl(BWD_MLP, nullptr, 0, node_attr->table, n_edges, nullptr, src, dst, nullptr, nullptr, n_layers, dims, W, b, nullptr,
-                        GPDE_AGGR_ADD, nullptr, nullptr, grad_W, grad_b, nullptr, nullptr, nullptr, nullptr, grad_hidden, ws, ws_bytes,
-                        (hipStream_t)stream_, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, node_attr->stride, node_attr->sel);
-    }
-    return bwd_impl(BWD_MLP, nullptr, 0, edge_attr, n_edges, nullptr, nullptr, nullptr, perm, nullptr, n_layers, dims,
-                    W, b, nullptr, GPDE_AGGR_ADD, nullptr, nullptr, grad_W, grad_b, nullptr, nullptr, nullptr, nullptr,
-                    grad_hidden, ws, ws_bytes, (hipStream_t)stream_);
+    if (node_attr && !na_ok(node_attr, dims, "gpde_hidden_bwd")) return GPDE_EINVAL;
+    BwdArgs a = bwd_common(n_edges, n_layers, dims, W, b, grad_W, grad_b, ws, ws_bytes, stream_);
+    bwd_attr_source(a, edge_attr, perm, node_attr);
+    if (node_attr) { a.src = src; a.dst = dst; }         // (the attribute tensor is read through perm alone)
+    a.grad_hidden_in = grad_hidden;
+    return bwd_impl(BWD_MLP, a);
 }
 
 
@@ -1978,47 +2081,29 @@ extern "C" int gpde_hidden_fwd(const float* edge_attr, const GpdeNodeAttr* node_
     }
     if (node_attr && !na_ok(node_attr, dims, "gpde_hidden_fwd")) return GPDE_EINVAL;
     if (hidden_absmax) GP_HIP_CHECK(gpde_zero_async(hidden_absmax, sizeof(float), st));
-    if (node_attr) {          // attributes from node data: the one-wave-per-SIMD store kernel reads the table
-        const GpdeNodeAttr* na = node_attr;
-        if (n_edges == 0) return GPDE_OK;
-        GpdePackLayout L;
-        int rc = gpde_pack_layout(n_layers, dims, &L);
-        if (rc != GPDE_OK) return rc;
-        if (!(flags & GPDE_FWD_F16SPLIT) || L.mode != 1) { gpde_set_error("gpde_hidden_fwd (node_attr): 3-Linear kernel MLPs on the split-f16 kernel only"); return GPDE_EUNSUPPORTED; }
-        const float* pk = (const float*)packed;
-        GpdeFusedArgs f{};
-        f.attr = na->table; f.rowptr = rowptr; f.src = src; f.dst = dst; f.kt = na->stride;
-        for (int d = 0; d < 8; ++d) f.sel[d] = na->sel[d < dims[0] ? d : dims[0] - 1];
-        f.w1 = pk + L.off_w1; f.w2t = pk + L.off_w2t; f.b2 = pk + L.off_b2;
-        f.w2h = pk + L.off_w2h; f.ucol = pk + L.off_ucol; f.w1h = pk + L.off_w1h; f.fcol = pk + L.off_fcol;
-        f.hout = hidden; f.hmax_out = (unsigned*)hidden_absmax; f.k0 = L.k0; f.K1P = L.K1P; f.K2P = L.K2P;
-        f.nc0 = 0; f.nc1 = (int)n_nodes; f.e_chunk0 = 0;
-        const int ns = L.K2P / GP_TN;
-        int groups = gpde_num_cus() / ns; if (groups < 1) groups = 1;
-        const int64_t gcap = ((n_edges + GP_TE - 1) / GP_TE + GP_WAVES - 1) / GP_WAVES;
-        if (groups > gcap) groups = (int)gcap;
-        f.n_groups = groups;
-        if (!gpde_fused_f16v6_supported(f)) { gpde_set_error("gpde_hidden_fwd (node_attr): kernel MLP outside the one-wave-per-SIMD store kernel (>= 8 k1 chunks)"); return GPDE_EUNSUPPORTED; }
-        return gpde_launch_fused_f16v6(f, st);
-    }
     if (n_edges == 0) return GPDE_OK;
     GpdePackLayout L;
     int rc = gpde_pack_layout(n_layers, dims, &L);
     if (rc != GPDE_OK) return rc;
-    // fast path: the f16-split fused kernel with a store epilogue instead of the aggregation
-    if (packed && (flags & GPDE_FWD_F16SPLIT) && L.mode == 1) {
-        const float* pk = (const float*)packed;
+    const bool f16 = (flags & GPDE_FWD_F16SPLIT) && L.mode == 1;
+    if (node_attr && !f16) { gpde_set_error("gpde_hidden_fwd (node_attr): 3-Linear kernel MLPs on the split-f16 kernel only"); return GPDE_EUNSUPPORTED; }
+    // fast path: the f16-split fused kernel with a store epilogue instead of the aggregation (attributes from node data: the
+    // one-wave-per-SIMD store kernel reads the table, and is the only path)
+    if (node_attr || (packed && f16)) {
         GpdeFusedArgs f{};
-        f.attr = edge_attr; f.rowptr = rowptr; f.perm = perm;
-        f.w1 = pk + L.off_w1; f.w2t = pk + L.off_w2t; f.b2 = pk + L.off_b2;
-        f.w2h = pk + L.off_w2h; f.ucol = pk + L.off_ucol; f.w1h = pk + L.off_w1h; f.fcol = pk + L.off_fcol;
-        f.hout = hidden; f.hmax_out = (unsigned*)hidden_absmax; f.k0 = L.k0; f.K1P = L.K1P; f.K2P = L.K2P;
+        f.rowptr = rowptr;
+        if (node_attr) {
+            f.attr = node_attr->table; f.src = src; f.dst = dst; f.kt = node_attr->stride;
+            for (int d = 0; d < 8; ++d) f.sel[d] = node_attr->sel[d < dims[0] ? d : dims[0] - 1];
+        } else { f.attr = edge_attr; f.perm = perm; }
+        gpde_fused_set_pack(f, (const float*)packed, L);
+        f.hout = hidden; f.hmax_out = (unsigned*)hidden_absmax;
         f.nc0 = 0; f.nc1 = (int)n_nodes; f.e_chunk0 = 0;
-        const int ns = L.K2P / GP_TN;
-        int groups = gpde_num_cus() / ns; if (groups < 1) groups = 1;
-        const int64_t gcap = ((n_edges + GP_TE - 1) / GP_TE + GP_WAVES - 1) / GP_WAVES;
-        if (groups > gcap) groups = (int)gcap;
-        f.n_groups = groups;
+        f.n_groups = gpde_fused_groups(L.K2P, gpde_group_cap_fwd(n_edges));
+        if (node_attr) {
+            if (!gpde_fused_f16v6_supported(f)) { gpde_set_error("gpde_hidden_fwd (node_attr): kernel MLP outside the one-wave-per-SIMD store kernel (>= 8 k1 chunks)"); return GPDE_EUNSUPPORTED; }
+            return gpde_launch_fused_f16v6(f, st);
+        }
         if (gpde_fused_store_supported(f)) return gpde_launch_fused_store(f, st);
     }
     // general path (any layer count, exact fp32): chunks of edges through the dense GEMM

@@ -194,6 +194,29 @@ int gpde_launch_fused_store(const GpdeFusedArgs& a, hipStream_t stream);
 // one wave per SIMD, 64 x 128 wave tile, 512 registers (gpde_fused_f16v6.hip): the default from 32768 edges on
 bool gpde_fused_f16v6_supported(const GpdeFusedArgs& a);
 int gpde_launch_fused_f16v6(const GpdeFusedArgs& a, hipStream_t stream);
+int gpde_num_cus();
+// The packed-MLP side of a GpdeFusedArgs: operand pointers into the image `pk` of gpde_mlp_pack, and the widths
+static inline void gpde_fused_set_pack(GpdeFusedArgs& f, const float* pk, const GpdePackLayout& L) {
+    f.w1 = pk + L.off_w1; f.w2t = pk + L.off_w2t; f.b2 = pk + L.off_b2;
+    f.w2h = pk + L.off_w2h; f.ucol = pk + L.off_ucol; f.w1h = pk + L.off_w1h; f.fcol = pk + L.off_fcol;
+    f.k0 = L.k0; f.K1P = L.K1P; f.K2P = L.K2P;
+}
+// the widths alone: what the *_supported checks read before any operand exists
+static inline GpdeFusedArgs gpde_fused_probe(const GpdePackLayout& L) {
+    GpdeFusedArgs probe{};
+    probe.k0 = L.k0; probe.K1P = L.K1P; probe.K2P = L.K2P;
+    return probe;
+}
+// Edge groups (workgroups per column slice) of a store / zagg launch: about one workgroup per CU, at most `cap`.  The cap is
+// the caller's: the forward entry points count whole 4-wave tile sets of all edges, the backward's chunks one more than the full
+// ones - the two differ where the row count is a multiple of GP_TE * GP_WAVES, and each keeps the grid it was measured with
+static inline int64_t gpde_group_cap_fwd(int64_t n_edges) { return ((n_edges + GP_TE - 1) / GP_TE + GP_WAVES - 1) / GP_WAVES; }
+static inline int64_t gpde_group_cap_bwd_chunk(int rows) { return (rows / GP_TE + GP_WAVES) / GP_WAVES; }
+static inline int gpde_fused_groups(int K2P, int64_t cap) {
+    int groups = gpde_num_cus() / (K2P / GP_TN);
+    if (groups < 1) groups = 1;
+    return groups > cap ? (int)cap : groups;
+}
 
 struct GpdeGemm3Args {
     const float* zbuf;     // [nn][64*K2P]
