@@ -7,23 +7,33 @@
 //   H1 = relu((W1|b1) . attr)  ->  H2 = relu(W2 . H1 + b2)  ->  Z_dst[c][k] += x_src[c] * H2[k]
 // with the k1 x k2 layer and the aggregation on 2-term split f16 MFMA, fp32 accumulation.
 //
-// Why this shape (scripts/ubench/kloop_model_v6.hip, measured on MI355X: the K loop below runs at 85 %
-// matrix-pipe occupancy = 1.73 PFLOP/s chip-wide, which is what a bare MFMA stream sustains under the
-// chip's power limit; the 8-wave v3 kernel sits at 51 %):
+// Why this shape (scripts/ubench/kloop_model_v6.hip, measured on MI355X; DESIGN.md §3d has the figures; the 8-wave v3
+// kernel sits at 51 % matrix-pipe occupancy):
 //   * the v3 kernel's two waves per SIMD both convert the same H1 tile, share the SIMD's issue port and
 //     lose ~40 % of the loop to conversions, barrier waits and staging.  One wave per SIMD with a wave
-//     tile twice as tall halves conversions, W2 fragment reads, DMA pieces and barriers per MFMA
-//     (2.9 non-MFMA instructions per MFMA, spread so that no gap holds more than 4);
+//     tile twice as tall halves conversions, W2 fragment reads, DMA pieces and barriers per MFMA;
 //   * 512 registers: accumulators (128) and Z (128) live in AGPRs for the whole kernel, nothing spills
 //     (v3: 256 registers, 50 spilled);
+//   * every MFMA is v_mfma_f32_16x16x32_f16.  Under load this chip holds its clock down, and how far depends on the MFMA
+//     shape: the K loop on 32x32x16 ran at 1.9-2.0 GHz, the same tile and the same FLOP on 16x16x32 run at 2.36 GHz (the
+//     model's bare streams: 1.6 against 2.05 GHz).  Layout: lane l = (l15 = l % 16, g = l / 16).  A and B operands: row /
+//     column l15, k slots 8g .. 8g+7;  C / D: column l15, rows 4g .. 4g+3.  acc = 4 edge blocks x 8 column blocks of
+//     f32x4, Z = 4 channel blocks x 8 column blocks.  The W2 chunk image of gpde_pack.hip is read as it is (lane group g
+//     takes unit g: one ds_read_b128 for hi, one for lo, conflict-free within 16 lanes); H1 takes ONE MFMA per 16 rows x
+//     16 edges, its three split terms in the lane groups of K = 32, with the (W1|b1) rows picked by LDS address so that
+//     the result is the hidden layer's A operand without a cross-lane move; the aggregation covers a 32-edge half with
+//     one K = 32 MFMA, whose k slots are the C layout of two edge blocks;
+//   * a k1 chunk is four batches of two column blocks (fragments: two sets of 16 registers, the next batch's set read
+//     during the current one) x four edge blocks x 6 MFMAs.  The A operands are single-buffered: the next chunk's edge
+//     block e is converted into the registers of edge block e behind its last MFMA (schedule at the loop);
 //   * MFMA order is pinned by an empty asm on the accumulator ("+a") after every MFMA plus
 //     sched_barrier(0): hipcc otherwise sinks the MFMAs of a step below its conversions;
-//   * H1 is produced by an asm MFMA with a VGPR destination (the builtin lands in AGPRs in a 512-register
+//   * H1 is produced by asm MFMAs with a VGPR destination (the builtin lands in AGPRs in a 512-register
 //     kernel: one v_accvgpr_read per value) and converted by asm pairs (relu, rtz16 hi, rn16 lo) - hipcc
-//     pads no hazards for asm operands, so the producer is placed >= 2 MFMAs before the first consumer;
+//     pads no hazards for asm operands, so the producer is placed >= 2 MFMAs before the first consumer (it is 30);
 //   * W2 chunk images (16 KiB, pre-swizzled) stream through a 3-slot LDS ring by LDS-DMA: chunk c + 2 is
 //     issued during chunk c (4 pieces per wave, one address + immediate offsets), retired by the
-//     s_waitcnt vmcnt(0) + s_barrier that ends chunk c; fragments are read half a chunk ahead, in place.
+//     s_waitcnt vmcnt(0) + s_barrier that ends chunk c; fragments are read a batch ahead, in place.
 #include "gpde_common.h"
 #include <cstdlib>
 #include <type_traits>
@@ -33,8 +43,8 @@ namespace {
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+__device__ __forceinline__ f32x4 mfma32k(h8 a, h8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 #define GPDE_GLDS(g, l, off)                                                                       \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g),         \
@@ -57,7 +67,7 @@ __device__ unsigned long long gpde_v6_tm[8];      // prologue, K loop, post, til
 
 constexpr int NS = 3;                      // W2 ring slots
 constexpr int TILE_B = GP_TN * 128;        // 16 KiB per W2 chunk image: [128 columns][hi 64 B | lo 64 B]
-constexpr int TE = 64;                     // edges per wave tile (two MFMA row blocks)
+constexpr int TE = 64;                     // edges per wave tile (four MFMA row blocks of 16)
 constexpr int NW = 4;                      // waves per workgroup
 
 // WRITE_H: the store variant (gpde_hidden_fwd, the backward's recompute of H_2, the per-edge path of gpde_api.hip): the
@@ -77,12 +87,13 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
     unsigned* Xs_all = (unsigned*)(w1s + (size_t)a.K1P * 32);        // [4 waves][64 rows][64 words]
     float* Es_all = (float*)(Xs_all + NW * TE * GP_W);               // [4][64]
     int* red = (int*)(Es_all + NW * TE);                             // [2][4]
+    float* colc = (float*)(red + 16);                                // [2][128]: scaled b2 | un-scale factor of the slice's columns
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31;
-    const int h = lane >> 5;
+    const int l15 = lane & 15;                // MFMA row (A) / column (B, C, D) of this lane
+    const int g = lane >> 4;                  // lane group: k slots 8g .. 8g+7 (A, B), rows 4g .. 4g+3 (C, D)
     float* Es = Es_all + wave * TE;
     unsigned* Xs = Xs_all + wave * TE * GP_W;
 
@@ -147,22 +158,20 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
     };
 
     // constants of the un-scaling: h <= max|b2| + max_k ||W2_k||_1 * max_e B_e (pack-time constants in fcol[8..9])
-    float b2v[4] = {0.f, 0.f, 0.f, 0.f}, ucv[4] = {0.f, 0.f, 0.f, 0.f};
+    // (per column, read back per column block after the K loop: 16 registers would not fit beside the K loop's)
     float z_unscale = 1.f;
     if constexpr (WRITE_H) {
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-            b2v[nb] = a.b2[slice * GP_TN + nb * 32 + l31];
-            ucv[nb] = a.ucol[slice * GP_TN + nb * 32 + l31];
+        if (tid < GP_TN) {
+            colc[tid] = a.b2[slice * GP_TN + tid];
+            colc[GP_TN + tid] = a.ucol[slice * GP_TN + tid];
         }
     } else {
         const float sx = gpde_pow2_to_2p13(__uint_as_float(a.scal[0]));
         const float hb = a.fcol[8] + a.fcol[9] * __uint_as_float(a.scal[1]);
         const float sh = gpde_pow2_to_2p13(hb);
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-            b2v[nb] = a.b2[slice * GP_TN + nb * 32 + l31] * sh;          // exact: sh is a power of two
-            ucv[nb] = a.ucol[slice * GP_TN + nb * 32 + l31] * sh;
+        if (tid < GP_TN) {
+            colc[tid] = a.b2[slice * GP_TN + tid] * sh;                  // exact: sh is a power of two
+            colc[GP_TN + tid] = a.ucol[slice * GP_TN + tid] * sh;
         }
         z_unscale = (1.f / sx) * (1.f / sh);      // two exact reciprocals: sx * sh may exceed the float range
     }
@@ -172,13 +181,22 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
         wmx8[d] = a.w1[(size_t)a.K1P * 8 + (d & 1) * 4 + (d >> 1)];
         fcol8[d] = a.fcol[d];
     }
-    const int sw = (l31 >> 1) & 7;
-    const int boff[2] = {l31 * 128 + (((0 + h) ^ sw) << 4), l31 * 128 + (((2 + h) ^ sw) << 4)};
+    // W2 fragment of column 16 nb + l15: chunk-image row = column (128 B: units 0-3 hi, 4-7 lo; unit u = 2m + h holds, at
+    // position j, k = 16m + 8 (j >> 2) + 4h + (j & 3) of the chunk - gpde_pack.hip), unit position swizzled by
+    // (column >> 1) & 7; lane group g reads unit g (hi) and 4 + g (lo = position ^ 64).  A column block is 16 rows = 2 KiB.
+    // Within 16 lanes the sixteen 16-byte positions are distinct (8 (c & 1) + (c >> 1) mod 16)
+    const int bo = l15 * 128 + ((g ^ ((l15 >> 1) & 7)) << 4);
+    // (W1|b1) row of H1 row l15 in the chunk's first 16-row half (second half: 8 rows = 256 B on).  D row i = 4g' + r of
+    // half hf comes from W1 row k(g', 4 hf + r) = 16 (g' >> 1) + 8 hf + 4 (g' & 1) + r, so that after both halves lane
+    // group g holds, at position j = 4 hf + r, exactly the k of unit g's position j - the A operand of the hidden-layer
+    // MFMA without a cross-lane move.  Lane groups 0, 1 read the row's hi 16 bytes, 2 its lo 16 bytes, 3 the hi again
+    // (finite; its attribute operand is zero)
+    const int w1o = (16 * (l15 >> 3) + 4 * ((l15 >> 2) & 1) + (l15 & 3)) * 32 + (g == 2 ? 16 : 0);
 
     // ---- per-tile side loads ----------------------------------------------------------------------------
     const int e_clamp = max(e_hi - 1, 0);
     // lane l owns edge (tile start + l): its edge id, source node and 8 attribute slots; the MFMA operand
-    // layout needs edge 32 b + (l & 31) in BOTH lane halves - exchanged by v_permlane32_swap in the prologue
+    // layout needs edge 16 b + (l & 15) in ALL FOUR lane groups - broadcast by ds_bpermute in the prologue
     int perm_n = 0;
     [[maybe_unused]] int dst_n = 0;     // NODEATTR: perm_n holds the SOURCE node of the next tile's edge, dst_n its destination
     int src_l = 0;                      // source node of edge (tile start + lane), for the x_j row DMA
@@ -228,10 +246,16 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
         conv_a(v0, v1, ph, t0_, t1_);
         conv_b(ph, t0_, t1_, pl);
     };
-    // the leading s_nop covers a VALU write of an operand right in front of the statement
-    auto h1gen = [&](f32x16& dd, h8 a1, h8 a2, h8 b1, h8 b2) {
-        asm volatile("s_nop 4\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(dd) : "v"(a1), "v"(b1));
-        asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(dd) : "v"(a2), "v"(b2));
+    // ONE MFMA per 16 H1 rows x 16 edges: K = 32 holds the three split terms, by lane group W1hi x attr_hi |
+    // W1hi x attr_lo | W1lo x attr_hi | (anything) x 0.  The leading s_nop covers a VALU write of an operand right in
+    // front of the statement
+    auto h1gen = [&](f32x4 (&dd)[4][2], h8 w1r0, h8 w1r1, const h8 (&at)[4]) {      // the 8 MFMAs of a chunk
+        asm volatile("s_nop 4");
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(dd[e][0]) : "v"(w1r0), "v"(at[e]));
+            asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(dd[e][1]) : "v"(w1r1), "v"(at[e]));
+        }
     };
 
     // ---- prologue: chunks 0 and 1 of the W2 slice, the first tile's edges and attributes ---------------
@@ -248,42 +272,46 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    f32x16 acc[2][4], Z[2][4];
+    // acc[edge block][column block]: edge 16 e + 4g + r, column 16 nb + l15;  Z[channel block][column block]: channel
+    // 16 cb + 4g + r, column 16 nb + l15
+    f32x4 acc[4][8], Z[4][8];
 #pragma unroll
-    for (int e = 0; e < 2; ++e)
+    for (int e = 0; e < 4; ++e)
 #pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
+        for (int nb = 0; nb < 8; ++nb)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[e][nb][r] = 0.f; Z[e][nb][r] = 0.f; }
+            for (int r = 0; r < 4; ++r) { acc[e][nb][r] = 0.f; Z[e][nb][r] = 0.f; }
     int cur = -1;
     [[maybe_unused]] float hmax_run = 0.f;      // WRITE_H: running maximum of the stored activations (>= 0)
 
     // one plain-store flush per (node, slice): the row base is wave-uniform (scalar address arithmetic), the lane
-    // part of the address is ONE tile-invariant offset - 32 per-row vector addresses would be hoisted out of the
-    // tile loop and spilled
-    const int z_loff = 4 * h * a.K2P + l31;
+    // part of the address is ONE offset - 16 per-row vector addresses would be hoisted out of the tile loop and spilled
     auto flush = [&](int node) {
         float* zb = a.zbuf + ((size_t)(node - a.nc0) * GP_W) * a.K2P + slice * GP_TN;
+        int zl = lane;
+        asm volatile("" : "+v"(zl));            // opaque: the lane offset is computed here (a few VALU per node), not kept
+        const int z_loff = 4 * (zl >> 4) * a.K2P + (zl & 15);       // across the tile loop in two more registers
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
+        for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-            for (int nb = 0; nb < 4; ++nb) asm volatile("" : "+a"(Z[cb][nb]));
+            for (int nb = 0; nb < 8; ++nb) asm volatile("" : "+a"(Z[cb][nb]));
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
+        for (int cb = 0; cb < 4; ++cb) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float* rp = zb + (size_t)(cb * 32 + (r & 3) + 8 * (r >> 2)) * a.K2P;
+            for (int r = 0; r < 4; ++r) {
+                float* rp = zb + (size_t)(cb * 16 + r) * a.K2P;
 #pragma unroll
-                for (int nb = 0; nb < 4; ++nb) {
-                    rp[z_loff + nb * 32] = Z[cb][nb][r] * z_unscale;
+                for (int nb = 0; nb < 8; ++nb) {
+                    rp[z_loff + nb * 16] = Z[cb][nb][r] * z_unscale;      // 64-byte runs (16 lanes x 4 B)
                     Z[cb][nb][r] = 0.f;
                 }
-                if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);      // 16 values in flight, not 128
+                if ((r & 1) == 1) __builtin_amdgcn_sched_barrier(0);      // 16 values in flight, not 128
             }
+        }
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
+        for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-            for (int nb = 0; nb < 4; ++nb) asm volatile("" : "+a"(Z[cb][nb]));
+            for (int nb = 0; nb < 8; ++nb) asm volatile("" : "+a"(Z[cb][nb]));
     };
 
     int slot = 0;           // ring slot of the current chunk
@@ -313,23 +341,20 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
         ++n_rounds;
 
         // ---- attributes of this lane's two edges: validity, bias slot, per-edge scale, f16 split ------------
-        h8 B1[2], B2[2];        // H1 MFMA operands: B1 = h ? attr_lo : attr_hi ; B2 = h ? 0 : attr_hi
+        h8 B1[4];               // H1 MFMA operand per edge block, by lane group: attr_hi | attr_lo | attr_hi | 0
         {
-            float av[2][8];     // [edge block][slot]: attributes of edge 32 b + l31 in both lane halves
 #pragma unroll
-            for (int d = 0; d < 8; ++d) {
-                const auto r2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(attr_n[d]), __float_as_uint(attr_n[d]), false, false);
-                av[0][d] = __uint_as_float(r2[0]);      // [lower | lower]
-                av[1][d] = __uint_as_float(r2[1]);      // [upper | upper]
-            }
+            for (int b = 0; b < 4; ++b) {
+                float av[8];    // attributes of edge 16 b + l15, in all four lane groups
 #pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const bool valid = (e0 + 32 * b + l31) < eb;
+                for (int d = 0; d < 8; ++d)
+                    av[d] = __int_as_float(__builtin_amdgcn_ds_bpermute((16 * b + l15) * 4, __float_as_int(attr_n[d])));
+                const bool valid = (e0 + 16 * b + l15) < eb;
                 float v[8];
                 float bnd = 0.f;
 #pragma unroll
                 for (int d = 0; d < 8; ++d) {
-                    float q = (valid && d < a.k0) ? av[b][d] : 0.f;
+                    float q = (valid && d < a.k0) ? av[d] : 0.f;
                     if (valid && d == a.k0) q = 1.f;
                     v[d] = q;
                     bnd = fmaf(wmx8[d], fabsf(q), bnd);
@@ -338,42 +363,42 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
                 const bool okb = (ebits >= 20) && (ebits <= 230);
                 const float sc = okb ? __int_as_float((267 - ebits) << 23) : 1.f;     // 2^(13 - E(B))
                 const float isc = okb ? __int_as_float((ebits - 13) << 23) : 1.f;
-                if (h == 0) Es[32 * b + l31] = isc;
+                if (g == 0) Es[16 * b + l15] = isc;
 #pragma unroll
                 for (int d = 0; d < 8; ++d) {
                     const float s_ = v[d] * fcol8[d] * sc;
                     const _Float16 hi = (_Float16)s_;
                     const _Float16 lo = (_Float16)(s_ - (float)hi);
-                    B1[b][d] = h ? lo : hi;
-                    B2[b][d] = h ? (_Float16)0.f : hi;
+                    B1[b][d] = g == 1 ? lo : (g == 3 ? (_Float16)0.f : hi);
                 }
             }
         }
-        // W2 fragments of step (0, 0) (within the tile they are read half a chunk ahead, in place; not carried
-        // across the aggregation phase: 32 registers)
-        h8 bhi[4], blo[4];
+        // W2 fragments of the chunk's first batch (column blocks 0, 1).  A chunk is four batches of two column blocks;
+        // the 32 fragment registers are two sets, the next batch's set is read during the current batch (not carried
+        // across the aggregation phase)
+        h8 bhi[2][2], blo[2][2];
 #pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-            bhi[nb] = *(const h8*)(ring + slot * TILE_B + nb * 4096 + boff[0]);
-            blo[nb] = *(const h8*)(ring + slot * TILE_B + nb * 4096 + (boff[0] ^ 64));
+        for (int nb = 0; nb < 2; ++nb) {
+            bhi[0][nb] = *(const h8*)(ring + slot * TILE_B + nb * 2048 + bo);
+            blo[0][nb] = *(const h8*)(ring + slot * TILE_B + nb * 2048 + (bo ^ 64));
         }
-        // ---- raw H1 of chunk 0 and the operands of step (0, 0) -------------------------------------------
-        f32x16 d[2];
-        u4 ahi[2][2], alo[2][2];          // [operand buffer = step parity][edge block]
+        // ---- raw H1 of chunk 0 and the operands of chunk 0 -----------------------------------------------
+        // d[e][half][r]: H1 of edge 16 e + l15, operand position j = 4 half + r of lane group g;  ahi / alo[e]: j = 0..7 as f16 pairs
+        f32x4 d[4][2];
+        u4 ahi[4], alo[4];                // single-buffered: see the conversion schedule in the K loop
         {
-            const char* wp = w1s + (size_t)l31 * 32;
-            const h8 A1 = *(const h8*)wp, A2 = *(const h8*)(wp + 16);
-            h1gen(d[0], A1, A2, B1[0], B2[0]);
-            h1gen(d[1], A1, A2, B1[1], B2[1]);
+            const char* wp = w1s + w1o;
+            const h8 A1 = *(const h8*)wp, A2 = *(const h8*)(wp + 256);
+            h1gen(d, A1, A2, B1);
             asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");           // MFMA result -> VALU read (asm operands are not padded)
 #pragma unroll
-            for (int e = 0; e < 2; ++e)
+            for (int e = 0; e < 4; ++e)
 #pragma unroll
                 for (int jp = 0; jp < 4; ++jp) {
                     unsigned ph, pl;
-                    conv_pair(d[e][2 * jp], d[e][2 * jp + 1], ph, pl);
-                    ahi[0][e][jp] = ph;
-                    alo[0][e][jp] = pl;
+                    conv_pair(d[e][jp >> 1][2 * (jp & 1)], d[e][jp >> 1][2 * (jp & 1) + 1], ph, pl);
+                    ahi[e][jp] = ph;
+                    alo[e][jp] = pl;
                 }
         }
         // destination of the first / last edge of the two 32-edge halves: loaded with the other side loads at the
@@ -381,11 +406,6 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
         int nf_v[2] = {0, 0}, nl_v[2] = {0, 0};
         unsigned cph = 0, ct0 = 0, ct1 = 0;
         h8 A1, A2;
-        {
-            const char* wp = w1s + (size_t)(GP_BK + l31) * 32;           // (W1|b1) rows of chunk 1
-            A1 = *(const h8*)wp;
-            A2 = *(const h8*)(wp + 16);
-        }
 
         // One k1 chunk.  The first seven chunks of a tile are peeled (PH = compile-time phase) so that the side
         // loads are straight-line code: inside a runtime `if (c == ..)` hipcc copies the loaded registers into
@@ -412,88 +432,100 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
             char* ldst = ring + slot2 * TILE_B + wave * 4096;
             const char* rb0 = ring + slot * TILE_B;
             const char* rb1 = ring + slot1 * TILE_B;
-            int c1 = c + 2;                                               // (W1|b1) rows read in this chunk: chunk c + 2
+            int c1 = c + 1;                                               // (W1|b1) rows read in this chunk: chunk c + 1
             if (c1 >= NKC) c1 -= NKC;
-            const char* w1n = w1s + (size_t)(c1 * GP_BK + l31) * 32;
+            const char* w1n = w1s + (size_t)c1 * GP_BK * 32 + w1o;
+            // 96 MFMAs: batch bt = column blocks 2 bt, 2 bt + 1; per batch the edge blocks 0..3, six MFMAs each (three split
+            // products x two column blocks, product-major so that consecutive MFMAs go to different accumulators).
+            // n = MFMA index in the chunk; what rides in the gap behind MFMA n:
+            //   conversions   the next chunk's operands are converted INTO the registers of this chunk's (single buffer): edge
+            //                 block ce from the gap behind its last MFMA (n = 77 + 6 ce) on, eight gaps each (pair p: first
+            //                 part, then second part), wrapping into the next chunk's gaps 0..13 - edge block ce is first
+            //                 read there at n = 6 ce.  At a tile's first chunk the wrapped part re-converts chunk 0's edge
+            //                 blocks 2, 3 from the unchanged raw H1 (same values); at its last the early part converts the
+            //                 unused H1 below
+            //   fragments     n = 24 bt + 6 .. + 9: the next batch's four reads, into the other set
+            //   (W1|b1)       n = 25, 27;  W2 ring pieces n = 29, 35, 41, 47;  raw H1 of chunk c + 1 behind n = 47
+            //   side loads    n >= 48, one per gap, i.e. behind the four W2 pieces
 #pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                const int cbuf = m;                                       // operand buffer of this step
-                const char* rn = (m == 0) ? rb0 : rb1;                    // where the NEXT step's fragments live
-                const int bo = boff[m ^ 1];
+            for (int bt = 0; bt < 4; ++bt) {
+                const int fs = bt & 1;                                    // fragment set of this batch
+                const char* rn = (bt < 3) ? rb0 + (2 * bt + 2) * 2048 : rb1;      // where the NEXT batch's fragments live
 #pragma unroll
-                for (int nb = 0; nb < 4; ++nb) {
+                for (int e = 0; e < 4; ++e) {
 #pragma unroll
                     for (int j = 0; j < 6; ++j) {
-                        const int tt = j >> 1, e = j & 1;                 // tt: 0 = hi x lo, 1 = hi x hi, 2 = lo x hi
-                        const int i = nb * 6 + j;
+                        const int tt = j >> 1, nb = j & 1;                // tt: 0 = hi x lo, 1 = hi x hi, 2 = lo x hi
+                        const int cb = 2 * bt + nb;
+                        const int n = bt * 24 + e * 6 + j;
 #ifdef GPDE_ABL_2MFMA      // ablation build ONLY (scripts/gpu/clock_evidence.sh; WRONG results): two of the three split products, to
                            // measure how time and clock answer to a third less matrix work per edge
                         if (tt != 2)
 #endif
-                        acc[e][nb] = mfma16(__builtin_bit_cast(h8, tt == 2 ? alo[cbuf][e] : ahi[cbuf][e]),
-                                            tt == 0 ? blo[nb] : bhi[nb], acc[e][nb]);
-                        asm volatile("" : "+a"(acc[e][nb]));
-                        // conversion pair p of the NEXT step's operands: first part after MFMA 3p, second after
-                        // 3p + 1; in step 1 (raw H1 of the next chunk issued at the end of step 0) one MFMA later
+                        acc[e][cb] = mfma32k(__builtin_bit_cast(h8, tt == 2 ? alo[e] : ahi[e]),
+                                             tt == 0 ? blo[fs][nb] : bhi[fs][nb], acc[e][cb]);
+                        asm volatile("" : "+a"(acc[e][cb]));
                         {
-                            const int q = m == 0 ? i : i - 1;
-                            if (q >= 0 && q % 3 == 0 && q / 3 < 8)
-                                conv_a(d[(q / 3) >> 2][8 * (m ^ 1) + 2 * ((q / 3) & 3)],
-                                       d[(q / 3) >> 2][8 * (m ^ 1) + 2 * ((q / 3) & 3) + 1], cph, ct0, ct1);
-                            if (q >= 0 && q % 3 == 1 && q / 3 < 8) {
-                                unsigned pl;
-                                conv_b(cph, ct0, ct1, pl);
-                                ahi[cbuf ^ 1][(q / 3) >> 2][(q / 3) & 3] = cph;
-                                alo[cbuf ^ 1][(q / 3) >> 2][(q / 3) & 3] = pl;
-                                asm volatile("" ::"v"(ahi[cbuf ^ 1][(q / 3) >> 2]), "v"(alo[cbuf ^ 1][(q / 3) >> 2]));
+                            const int k = n >= 78 ? n - 78 : n + 18;
+                            if (k < 32) {
+                                const int ce = k >> 3, jp = (k & 7) >> 1;
+                                if ((k & 1) == 0)
+                                    conv_a(d[ce][jp >> 1][2 * (jp & 1)], d[ce][jp >> 1][2 * (jp & 1) + 1], cph, ct0, ct1);
+                                else {
+                                    unsigned pl;
+                                    conv_b(cph, ct0, ct1, pl);
+                                    ahi[ce][jp] = cph;
+                                    alo[ce][jp] = pl;
+                                    asm volatile("" ::"v"(ahi[ce]), "v"(alo[ce]));
+                                }
                             }
                         }
-                        if (j == 1) blo[nb] = *(const h8*)(rn + nb * 4096 + (bo ^ 64));
-                        if (j == 5) bhi[nb] = *(const h8*)(rn + nb * 4096 + bo);
-                        if (m == 0) {
-                            if (i == 2) GPDE_GLDS(gsrc, ldst, 0);
-                            if (i == 8) GPDE_GLDS(gsrc, ldst, 1024);
-                            if (i == 14) GPDE_GLDS(gsrc, ldst, 2048);
-                            if (i == 20) GPDE_GLDS(gsrc, ldst, 3072);
+                        if (e == 1) {
+                            if (j == 0) blo[fs ^ 1][0] = *(const h8*)(rn + (bo ^ 64));
+                            if (j == 1) blo[fs ^ 1][1] = *(const h8*)(rn + 2048 + (bo ^ 64));
+                            if (j == 2) bhi[fs ^ 1][0] = *(const h8*)(rn + bo);
+                            if (j == 3) bhi[fs ^ 1][1] = *(const h8*)(rn + 2048 + bo);
                         }
-                        // The tile's side loads, ONE PER MFMA GAP of step 1 - i.e. behind the chunk's four W2 pieces, so
-                        // that the counted wait at the chunk end retires exactly those (round 3: issued as one block after
-                        // the last MFMA they cost ~570 cycles in each of the six peeled chunks, the matrix pipe idling
-                        // while ~60 address / load instructions went out).  The x_j row addresses (ds_bpermute of the
-                        // source ids loaded two chunks earlier) go into the gaps of step 0.
+                        if (n == 37) A1 = *(const h8*)w1n;
+                        if (n == 39) A2 = *(const h8*)(w1n + 256);
+                        if (n == 29) GPDE_GLDS(gsrc, ldst, 0);
+                        if (n == 35) GPDE_GLDS(gsrc, ldst, 1024);
+                        if (n == 41) GPDE_GLDS(gsrc, ldst, 2048);
+                        if (n == 47) GPDE_GLDS(gsrc, ldst, 3072);
+                        // The tile's side loads, ONE PER MFMA GAP of the chunk's second half - i.e. behind the chunk's four W2
+                        // pieces, so that the counted wait at the chunk end retires exactly those (round 3: issued as one
+                        // block after the last MFMA they cost ~570 cycles in each of the six peeled chunks, the matrix pipe
+                        // idling while ~60 address / load instructions went out).  The x_j row addresses (ds_bpermute of the
+                        // source ids loaded two chunks earlier) go into gaps of the first half.
                         if constexpr (MODE == 0 && PH == 0) {
-                            if (m == 1) {
-                                if (i == 2) load_perm(e0n);
-                                if (i == 5) src_l = a.src[min(e0 + lane, e_clamp)];
-                                if (i == 8) nf_v[0] = a.dst[min(e0, e_clamp)];
-                                if (i == 11) nl_v[0] = a.dst[min(max(min(e0 + 32, eb) - 1, e0), e_clamp)];
-                                if (i == 14) nf_v[1] = a.dst[min(e0 + 32, e_clamp)];
-                                if (i == 17) nl_v[1] = a.dst[min(max(min(e0 + 64, eb) - 1, e0 + 32), e_clamp)];
-                            }
+                            if (n == 52) load_perm(e0n);
+                            if (n == 58) src_l = a.src[min(e0 + lane, e_clamp)];
+                            if (n == 64) nf_v[0] = a.dst[min(e0, e_clamp)];
+                            if (n == 70) nl_v[0] = a.dst[min(max(min(e0 + 32, eb) - 1, e0), e_clamp)];
+                            if (n == 76) nf_v[1] = a.dst[min(e0 + 32, e_clamp)];
+                            if (n == 82) nl_v[1] = a.dst[min(max(min(e0 + 64, eb) - 1, e0 + 32), e_clamp)];
                         } else if constexpr (WRITE_H && PH == 0) {
-                            if (m == 1 && i == 2) load_perm(e0n);
+                            if (n == 52) load_perm(e0n);
                         }
                         if constexpr (PH == 2) {
-                            if (m == 1 && (i & 1) == 1 && i < 16) load_attr_d(i >> 1);
+                            if (n >= 50 && n < 82 && ((n - 50) & 3) == 0) load_attr_d((n - 50) >> 2);
                         }
                         if constexpr (!WRITE_H && PH >= 2 && PH <= 5) {
-                            if (m == 0 && (i == 1 || i == 4 || i == 7 || i == 10)) x_addr1(4 * (PH - 2), (i - 1) / 3);
+                            if (n == 2 || n == 8 || n == 14 || n == 20) x_addr1(4 * (PH - 2), (n - 2) / 6);
                             if constexpr (PH == 2) {
-                                if (m == 1 && (i == 17 || i == 19 || i == 21 || i == 23)) x_issue1(0, (i - 17) / 2);
+                                if (n == 83 || n == 87 || n == 91 || n == 95) x_issue1(0, (n - 83) / 4);
                             } else {
-                                if (m == 1 && (i == 3 || i == 9 || i == 15 || i == 21)) x_issue1(4 * (PH - 2), (i - 3) / 6);
+                                if (n == 54 || n == 66 || n == 78 || n == 90) x_issue1(4 * (PH - 2), (n - 54) / 12);
                             }
                         }
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
-                if (m == 0) {
-                    // raw H1 of chunk c + 1 (single-buffered: its last reader ran two MFMAs ago); at the last
-                    // chunk this is chunk 0 with THIS tile's attributes - unused, the next tile starts afresh
-                    h1gen(d[0], A1, A2, B1[0], B2[0]);
-                    h1gen(d[1], A1, A2, B1[1], B2[1]);
-                    A1 = *(const h8*)w1n;
-                    A2 = *(const h8*)(w1n + 16);
+                if (bt == 1) {
+                    // raw H1 of chunk c + 1 (single-buffered: its last reader, edge block 3's conversion, ran in gaps 6..13
+                    // of this chunk; the first reader is 30 MFMAs on); at the last chunk this is chunk 0 with THIS tile's
+                    // attributes - unused, the next tile starts afresh
+                    h1gen(d, A1, A2, B1);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -525,27 +557,21 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
 
         TM_MARK(tm_loop);
         if constexpr (WRITE_H) {
-            // ---- un-scale + bias + ReLU, store the tile's hidden activations (128-byte runs along the columns) ----
+            // ---- un-scale + bias + ReLU, store the tile's hidden activations (64-byte runs along the columns) ----
 #pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                float ie[16];
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    const f32x4 t4 = *(const f32x4*)&Es[32 * b + 8 * q4 + 4 * h];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) ie[4 * q4 + j] = t4[j];
-                }
+            for (int b = 0; b < 4; ++b) {
+                const f32x4 ie = *(const f32x4*)&Es[16 * b + 4 * g];      // per-edge un-scale of this block's 4 accumulator rows
                 auto store_rows = [&](auto full_tag) {
                     constexpr bool FULL = decltype(full_tag)::value;
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int e = e0 + 32 * b + (r & 3) + 8 * (r >> 2) + 4 * h;
-                        float* hp = a.hout + (size_t)(e - a.e_chunk0) * a.K2P + slice * GP_TN + l31;
+                    for (int r = 0; r < 4; ++r) {
+                        const int e = e0 + 16 * b + 4 * g + r;
+                        float* hp = a.hout + (size_t)(e - a.e_chunk0) * a.K2P + slice * GP_TN + l15;
 #pragma unroll
-                        for (int nb = 0; nb < 4; ++nb) {
-                            const float y = fmaxf(fmaf(acc[b][nb][r], ie[r] * ucv[nb], b2v[nb]), 0.f);
+                        for (int nb = 0; nb < 8; ++nb) {
+                            const float y = fmaxf(fmaf(acc[b][nb][r], ie[r] * colc[GP_TN + nb * 16 + l15], colc[nb * 16 + l15]), 0.f);
                             acc[b][nb][r] = 0.f;
-                            if (FULL || e < eb) { hp[nb * 32] = y; hmax_run = fmaxf(hmax_run, y); }
+                            if (FULL || e < eb) { hp[nb * 16] = y; hmax_run = fmaxf(hmax_run, y); }
                         }
                     }
                 };
@@ -555,30 +581,33 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
         } else
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            u4 g2hi[4][2], g2lo[4][2];
-            float ie[16];           // per-edge un-scale of this half's 16 accumulator rows: four 16-byte LDS reads
+            // H2 of the half's 32 edges as the aggregation's B operand: k slot (g, t) <-> edge 16 (t / 4) + 4g + t % 4 of the
+            // half, which is the C layout of edge blocks 2b (t < 4) and 2b + 1 - the converted pairs are the operand as they are
+            u4 g2hi[8], g2lo[8];
+            float ie[8];            // per-edge un-scale of this half's 8 accumulator rows: two 16-byte LDS reads
 #pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const f32x4 t4 = *(const f32x4*)&Es[32 * b + 8 * q4 + 4 * h];
+            for (int q4 = 0; q4 < 2; ++q4) {
+                const f32x4 t4 = *(const f32x4*)&Es[32 * b + 16 * q4 + 4 * g];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) ie[4 * q4 + j] = t4[j];
             }
 #pragma unroll
-            for (int nb = 0; nb < 4; ++nb) {
-                float y[16];
+            for (int nb = 0; nb < 8; ++nb) {
+                float y[8];
+                const float b2v = colc[nb * 16 + l15], ucv = colc[GP_TN + nb * 16 + l15];
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    y[r] = fmaf(acc[b][nb][r], ie[r] * ucv[nb], b2v[nb]);
-                    acc[b][nb][r] = 0.f;
+                for (int r = 0; r < 8; ++r) {
+                    y[r] = fmaf(acc[2 * b + (r >> 2)][nb][r & 3], ie[r] * ucv, b2v);
+                    acc[2 * b + (r >> 2)][nb][r & 3] = 0.f;
                 }
 #pragma unroll
-                for (int p_ = 0; p_ < 8; ++p_) {
+                for (int p_ = 0; p_ < 4; ++p_) {
                     unsigned ph, pl;
                     conv_pair(y[2 * p_], y[2 * p_ + 1], ph, pl);
-                    g2hi[nb][p_ >> 2][p_ & 3] = ph;
-                    g2lo[nb][p_ >> 2][p_ & 3] = pl;
+                    g2hi[nb][p_] = ph;
+                    g2lo[nb][p_] = pl;
                 }
-                __builtin_amdgcn_sched_barrier(0);      // one column block at a time: 16 live values, not 64
+                if (nb & 1) __builtin_amdgcn_sched_barrier(0);      // two column blocks at a time: 16 live values, not 64
             }
             const int s0 = e0 + 32 * b;
             const int s_end = min(s0 + 32, e_end);
@@ -591,32 +620,32 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
                     if (cur >= 0) flush(cur);
                     cur = node;
                 }
-                const int lo = e_seg - s0 - 4 * h, hi = seg_end - s0 - 4 * h;
+                const int lo = e_seg - s0 - 4 * g, hi = seg_end - s0 - 4 * g;
                 const bool full = (e_seg == s0) && (seg_end == s0 + 32);       // the whole half is one segment (scalar)
                 const unsigned* xu = Xs + 32 * b * GP_W;
-                // four operand groups g = (cb, m): 8 x_j words each (k slot tq <-> edge er(8m + tq) + 4h), read one
-                // group ahead of the 12 MFMAs that use them.  The loads are unconditional and materialised by an asm
-                // before the masks: hipcc otherwise sinks each load into its mask's branch and waits per word.
+                // four operand groups = channel blocks cb: 8 x_j words each (k slot tq <-> edge 16 (tq / 4) + tq % 4 + 4g of
+                // the half, channel 16 cb + l15), read one group ahead of the 24 MFMAs that use them; ONE K = 32 MFMA covers
+                // the half.  (The four lane groups read rows 4 apart = the same banks: a 2-way conflict on these 32 reads
+                // per segment, against 96 MFMAs.)  The loads are unconditional and materialised by an asm before the masks:
+                // hipcc otherwise sinks each load into its mask's branch and waits per word.
                 unsigned wq[2][8];
-                auto ldx = [&](int g, unsigned (&w)[8]) {
-                    const int cb = g >> 1, m = g & 1;
+                auto ldx = [&](int cb, unsigned (&w)[8]) {
 #pragma unroll
                     for (int tq = 0; tq < 8; ++tq) {
-                        const int er = ((8 * m + tq) & 3) + 8 * ((8 * m + tq) >> 2);
-                        w[tq] = xu[(er + 4 * h) * GP_W + cb * 32 + l31];
+                        const int er = 16 * (tq >> 2) + (tq & 3);
+                        w[tq] = xu[(er + 4 * g) * GP_W + cb * 16 + l15];
                     }
                 };
                 ldx(0, wq[0]);
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int cb = g >> 1, m = g & 1;
-                    unsigned (&w)[8] = wq[g & 1];
-                    if (g + 1 < 4) ldx(g + 1, wq[(g + 1) & 1]);
+                for (int cb = 0; cb < 4; ++cb) {
+                    unsigned (&w)[8] = wq[cb & 1];
+                    if (cb + 1 < 4) ldx(cb + 1, wq[(cb + 1) & 1]);
                     asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]), "+v"(w[6]), "+v"(w[7]));
                     if (!full) {
 #pragma unroll
                         for (int tq = 0; tq < 8; ++tq) {
-                            const int er = ((8 * m + tq) & 3) + 8 * ((8 * m + tq) >> 2);
+                            const int er = 16 * (tq >> 2) + (tq & 3);
                             const unsigned keep = (er >= lo && er < hi) ? 0xffffffffu : 0u;
                             w[tq] &= keep;
                         }
@@ -629,11 +658,11 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
                     }
                     const h8 xhi = __builtin_bit_cast(h8, ah), xlo = __builtin_bit_cast(h8, al);
 #pragma unroll
-                    for (int nb = 0; nb < 4; ++nb) {
-                        const h8 gh = __builtin_bit_cast(h8, g2hi[nb][m]), gl = __builtin_bit_cast(h8, g2lo[nb][m]);
-                        Z[cb][nb] = mfma16(xhi, gh, Z[cb][nb]);
-                        Z[cb][nb] = mfma16(xhi, gl, Z[cb][nb]);
-                        Z[cb][nb] = mfma16(xlo, gh, Z[cb][nb]);
+                    for (int nb = 0; nb < 8; ++nb) {
+                        const h8 gh = __builtin_bit_cast(h8, g2hi[nb]), gl = __builtin_bit_cast(h8, g2lo[nb]);
+                        Z[cb][nb] = mfma32k(xhi, gh, Z[cb][nb]);
+                        Z[cb][nb] = mfma32k(xhi, gl, Z[cb][nb]);
+                        Z[cb][nb] = mfma32k(xlo, gh, Z[cb][nb]);
                         asm volatile("" : "+a"(Z[cb][nb]));      // Z stays in AGPRs (else: 128 copies per segment)
                     }
                 }
@@ -643,9 +672,9 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
         }
         if constexpr (MODE == 0)
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
+        for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-            for (int nb = 0; nb < 4; ++nb) asm volatile("" : "+a"(Z[cb][nb]));
+            for (int nb = 0; nb < 8; ++nb) asm volatile("" : "+a"(Z[cb][nb]));
         TM_MARK(tm_post);
         // ---- advance ---------------------------------------------------------------------------------------
         if (last_in_blk) {
@@ -680,7 +709,7 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
 
 size_t v6_lds_bytes(int K1P) {
     return (size_t)NS * TILE_B + (size_t)K1P * 32 + (size_t)NW * TE * GP_W * 4 + (size_t)NW * TE * 4 + 64 +
-           2 * GP_TN * 4;       // (+ 1 KiB the retired one-pass backward mode used: kept, so that the covered shapes stay the same)
+           2 * GP_TN * 4;       // (+ 1 KiB: the per-column bias and un-scale factor of the slice, `colc`)
 }
 
 }  // namespace

@@ -1,8 +1,11 @@
 // Model of the v6 K loop: FOUR waves per workgroup (one per SIMD, up to 512 registers each), wave tile
-// 64 edges x 128 hidden columns.  Per 32-wide k chunk and wave: 48 f16 MFMAs (2 edge blocks x 4 column
-// blocks x 2 k16 steps x 3 split products) + 4 H1 MFMAs, 16 ds_read_b128 of W2 fragments, 2 of (W1|b1),
-// 16 conversion pairs (5 VALU each), 4 LDS-DMA pieces of the next W2 chunk image, one s_barrier.
-// Flags ablate the parts; the result is cycles per chunk (ideal 52 x 32 = 1664) and chip TFLOP/s.
+// 64 edges x 128 hidden columns, in two MFMA shapes (template parameter SHAPE).
+// SHAPE 0, v_mfma_f32_32x32x16_f16 (the kernel up to the shape change).  Per 32-wide k chunk and wave: 48 f16 MFMAs
+// (2 edge blocks x 4 column blocks x 2 k16 steps x 3 split products) + 4 H1 MFMAs, 16 ds_read_b128 of W2 fragments,
+// 2 of (W1|b1), 16 conversion pairs (5 VALU each), 4 LDS-DMA pieces of the next W2 chunk image, one s_barrier.
+// SHAPE 1, v_mfma_f32_16x16x32_f16 (the kernel now): 96 + 8 MFMAs of half the size, everything else the same (body16).
+// Flags ablate the parts; the result is cycles per chunk (ideal 52 x 32 = 104 x 16 = 1664), the shader clock and chip
+// TFLOP/s.  The run ends with the shape A/B: bare stream and full model of both shapes, alternating, in long launches.
 //   hipcc --offload-arch=gfx950 -O3 -o kloop_model_v6 kloop_model_v6.hip && ./kloop_model_v6
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -10,6 +13,7 @@
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void dma16(const void* gsrc, void* lds) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
@@ -25,9 +29,7 @@ constexpr int TILE_B = 16384;
 //        32 keep 128 extra accumulator registers (Z) live across the loop, 64 H1 MFMAs by asm into VGPRs
 // NS: ring slots (3: DMA one chunk ahead, vmcnt(0) per chunk; 4: two chunks ahead, vmcnt(4))
 template <int FLAGS, int NS>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void kern(long* out, const char* gsrc, float seed, int iters) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+__device__ __forceinline__ void body32(char* smem, long* out, const char* gsrc, float seed, int iters) {
     char* ring = smem;
     char* w1s = smem + NS * TILE_B;           // 32 KiB
     for (int i = threadIdx.x; i < (NS * TILE_B + 32768) / 4; i += 256) ((float*)smem)[i] = (float)((i * 2654435761u) >> 20) * 1e-3f;
@@ -198,6 +200,200 @@ void kern(long* out, const char* gsrc, float seed, int iters) {
     if (s == 1234.5f) out[1] = 1;
 }
 
+// The same K loop on v_mfma_f32_16x16x32_f16 (SHAPE 1; since the kernel moved to this shape, the one it runs): same 64 x 128 wave
+// tile as 4 edge blocks x 8 column blocks of f32x4, ONE k32 step per chunk.  A chunk is four batches of two column blocks,
+// per batch the edge blocks 0..3 with 2 column blocks x 3 split products = 6 MFMAs each: 96 product MFMAs + 8 H1 MFMAs
+// (one per edge block and 16-row half: the three split terms of H1 sit in the lane groups of one K = 32 MFMA).  The 32
+// fragment registers are two sets of one batch (hi + lo of two column blocks); the next batch's set is read during the
+// current batch.  The operands are SINGLE-buffered (32 registers): the next chunk's edge block e is converted into the
+// registers of edge block e from the gap behind its last MFMA on, eight gaps each, wrapping into the next chunk's first
+// 14 gaps.  Same 16 ds_read_b128 of W2 fragments (unit g = lane / 16 of the unchanged chunk image), 2 of (W1|b1), 16
+// conversion pairs, 4 DMA pieces, one s_barrier; at most 4 non-MFMA instructions per gap.  Ideal 104 x 16 = 1664 cycles
+// per chunk, as for the 32x32 loop.  (A first form with two batches of four column blocks, the next batch's fragments
+// re-read in place during the batch's last edge block, measured 2241 cycles per chunk against this one's 2224.)
+template <int FLAGS, int NS>
+__device__ __forceinline__ void body16(char* smem, long* out, const char* gsrc, float seed, int iters) {
+    char* ring = smem;
+    char* w1s = smem + NS * TILE_B;           // 32 KiB
+    for (int i = threadIdx.x; i < (NS * TILE_B + 32768) / 4; i += 256) ((float*)smem)[i] = (float)((i * 2654435761u) >> 20) * 1e-3f;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, l15 = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // chunk image row = hidden column (128 B: units 0-3 hi k 0-7 | 8-15 | 16-23 | 24-31, units 4-7 lo), unit position
+    // swizzled by (column >> 1) & 7; a column block is 16 rows = 2 KiB
+    const int bo = l15 * 128 + ((g ^ ((l15 >> 1) & 7)) << 4);
+    // (W1|b1) row of D row l15 for half 0 (half 1: 8 rows on; the k order of the pack's units); lane group 2 reads the lo
+    // 16 bytes, the others the hi
+    const int w1o = (16 * (l15 >> 3) + 4 * ((l15 >> 2) & 1) + (l15 & 3)) * 32 + (g == 2 ? 16 : 0);
+
+    u4 ahi[4], alo[4];
+    h8 bhi[2][2], blo[2][2], B1[4];
+    f32x4 d[4][2], acc[4][8], Z[4][8];
+    for (int e = 0; e < 4; ++e)
+        for (int j = 0; j < 4; ++j) {
+            // the same pseudo-random f16 pairs as the 32x32 body
+            unsigned r_ = (unsigned)(lane * 2654435761u) ^ (unsigned)((e * 4 + j + 1) * 40503u) ^ (unsigned)(blockIdx.x * 97u);
+            r_ = r_ * 1664525u + 1013904223u;
+            const unsigned h0 = 0x3000u + ((r_ >> 4) & 0x0fffu) + ((r_ >> 1) & 0x8000u), h1 = 0x3000u + ((r_ >> 18) & 0x0fffu) + ((r_ << 3) & 0x8000u);
+            ahi[e][j] = h0 | (h1 << 16);
+            alo[e][j] = (0x0400u + ((r_ >> 9) & 0x0fffu)) | ((0x0400u + ((r_ >> 13) & 0x0fffu) + ((r_ << 7) & 0x8000u)) << 16);
+        }
+    // attributes: hi | lo | hi | zero by lane group
+    for (int e = 0; e < 4; ++e)
+        for (int j = 0; j < 8; ++j) B1[e][j] = g == 3 ? (_Float16)0.f : (_Float16)(g == 1 ? (seed - j * 0.1f) * 4.8828125e-4f : seed + j * 0.1f + e);
+    for (int e = 0; e < 4; ++e)
+        for (int nb = 0; nb < 8; ++nb)
+            for (int r = 0; r < 4; ++r) { acc[e][nb][r] = 0.f; Z[e][nb][r] = seed * (r + 4 * (nb & 3)); }
+    for (int e = 0; e < 4; ++e)
+        for (int hf = 0; hf < 2; ++hf)
+            for (int r = 0; r < 4; ++r) d[e][hf][r] = seed * (4 * hf + r + 1) * 0.01f;
+    for (int nb = 0; nb < 2; ++nb) { bhi[0][nb] = *(const h8*)(ring + nb * 2048 + bo); blo[0][nb] = *(const h8*)(ring + nb * 2048 + (bo ^ 64)); bhi[1][nb] = bhi[0][nb]; blo[1][nb] = blo[0][nb]; }
+
+    const unsigned long long gbase = (unsigned long long)gsrc + (size_t)(blockIdx.x % 8) * 32 * TILE_B + wave * 4096;
+    const unsigned lane16 = lane * 16;
+    auto issue_w2 = [&](int chunk, int slot, int piece) {
+        unsigned long long gb = gbase + (size_t)chunk * TILE_B;
+        asm volatile("" : "+s"(gb));
+        const char* gp = (const char*)(gb + lane16);
+        char* l = ring + slot * TILE_B + wave * 4096;
+        if (piece == 0) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
+        if (piece == 1) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp, (__attribute__((address_space(3))) void*)l, 16, 1024, 0);
+        if (piece == 2) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp, (__attribute__((address_space(3))) void*)l, 16, 2048, 0);
+        if (piece == 3) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp, (__attribute__((address_space(3))) void*)l, 16, 3072, 0);
+    };
+    // the conversion pair of the 32x32 body.  After the two halves a lane holds k = 8g .. 8g+7 of its edge (half hf gives
+    // k = 8g + 4 hf + r): pair jp = values 2 jp, 2 jp + 1 = d[e][jp >> 1][2 (jp & 1) ..]
+    auto conv_a = [&](float v0, float v1, unsigned& ph, unsigned& t0_, unsigned& t1_) {
+        asm("v_max_i32 %1, 0, %3\n\t"
+            "v_max_i32 %2, 0, %4\n\t"
+            "v_cvt_pkrtz_f16_f32 %0, %1, %2"
+            : "=&v"(ph), "=&v"(t0_), "=&v"(t1_) : "v"(v0), "v"(v1));
+    };
+    auto conv_b = [&](int jp, unsigned ph, unsigned t0_, unsigned t1_, u4& hi, u4& lo) {
+        unsigned pl;
+        asm("v_fma_mixlo_f16 %0, %1, 1.0, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
+            "v_fma_mixhi_f16 %0, %2, 1.0, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
+            : "=&v"(pl) : "v"(t0_), "v"(t1_), "v"(ph));
+        hi[jp] = ph;
+        lo[jp] = pl;
+    };
+    // ONE H1 MFMA per edge block and half: K = 32 carries W1hi x attr_hi + W1hi x attr_lo + W1lo x attr_hi
+    auto h1gen = [&](f32x4& dd, h8 a, h8 b) {
+        if (FLAGS & 64) {
+            asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(dd) : "v"(a), "v"(b));
+        } else {
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            dd = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, z, 0, 0, 0);
+        }
+    };
+
+    if (FLAGS & 4) {
+        for (int p = 0; p < 4; ++p) issue_w2(1, 1, p);
+        if (NS == 4) for (int p = 0; p < 4; ++p) issue_w2(2, 2, p);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    if (FLAGS & 32) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int nb = 0; nb < 8; ++nb) asm volatile("" : "+a"(Z[e][nb]));
+    }
+    int slot = 0;
+    unsigned cph = 0, ct0 = 0, ct1 = 0;
+    h8 A1 = *(const h8*)(w1s + w1o), A2 = *(const h8*)(w1s + w1o + 256);
+    long t0 = clock64();
+    for (int it = 0; it < iters; ++it) {
+        int slot1 = slot + 1 == NS ? 0 : slot + 1;            // next chunk's slot
+        int slot2 = slot1 + 1 == NS ? 0 : slot1 + 1;
+        int slot3 = slot2 + 1 == NS ? 0 : slot2 + 1;
+        const int dslot = NS == 3 ? slot2 : slot3;            // DMA target: chunk it+2 (3 slots) / it+3 (4 slots)
+        const int dchunk = (it + (NS == 3 ? 2 : 3)) & 31;
+        const char* rb0 = ring + slot * TILE_B;
+        const char* rb1 = ring + slot1 * TILE_B;
+        const char* w1n = w1s + (size_t)(((it + 1) & 31) * 32) * 32 + w1o;
+#pragma unroll
+        for (int bt = 0; bt < 4; ++bt) {
+            const int fs = bt & 1;                  // fragment set of this batch; the next batch's goes into fs ^ 1
+            // the NEXT batch's fragments: column blocks 2 bt + 2, 2 bt + 3 of this chunk, then 0, 1 of the next chunk
+            const char* rn = (bt < 3) ? rb0 + (2 * bt + 2) * 2048 : rb1;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+#pragma unroll
+                for (int i = 0; i < 6; ++i) {
+                    const int t = i >> 1, nb = i & 1;       // product-major: consecutive MFMAs go to different accumulators
+                    const int cbk = 2 * bt + nb;
+                    const int n = bt * 24 + e * 6 + i;      // MFMA index in the chunk
+                    if (!((FLAGS & 128) && t == 2))
+                        acc[e][cbk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, t == 2 ? alo[e] : ahi[e]), t == 0 ? blo[fs][nb] : bhi[fs][nb], acc[e][cbk], 0, 0, 0);
+                    asm volatile("" : "+a"(acc[e][cbk]));
+                    // conversions of the next chunk's operands: edge block ce from the gap behind its last MFMA (n = 77 + 6 ce)
+                    // on, 8 gaps each (pair p: first part, then second part), wrapping into the next chunk's first 14 gaps -
+                    // edge block ce is first read there at n = 6 ce
+                    {
+                        const int k = n >= 78 ? n - 78 : n + 18;
+                        if ((FLAGS & 1) && k < 32) {
+                            const int ce = k >> 3, jp = (k & 7) >> 1;
+                            if ((k & 1) == 0) conv_a(d[ce][jp >> 1][2 * (jp & 1)], d[ce][jp >> 1][2 * (jp & 1) + 1], cph, ct0, ct1);
+                            else {
+                                conv_b(jp, cph, ct0, ct1, ahi[ce], alo[ce]);
+                                asm volatile("" ::"v"(ahi[ce]), "v"(alo[ce]));
+                            }
+                        }
+                    }
+                    if ((FLAGS & 16) && e == 1) {           // the other set's last reader was the previous batch
+                        if (i == 0) blo[fs ^ 1][0] = *(const h8*)(rn + (bo ^ 64));
+                        if (i == 1) blo[fs ^ 1][1] = *(const h8*)(rn + 2048 + (bo ^ 64));
+                        if (i == 2) bhi[fs ^ 1][0] = *(const h8*)(rn + bo);
+                        if (i == 3) bhi[fs ^ 1][1] = *(const h8*)(rn + 2048 + bo);
+                    }
+                    if ((FLAGS & 4) && bt == 1 && i == 5) issue_w2(dchunk, dslot, e);
+                    if ((FLAGS & 8) && bt == 1 && e == 0 && i == 1) A1 = *(const h8*)w1n;
+                    if ((FLAGS & 8) && bt == 1 && e == 0 && i == 3) A2 = *(const h8*)(w1n + 256);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            if (bt == 1 && (FLAGS & 8)) {
+                // H1 of the next chunk (single-buffered raw H1: its last reader, edge block 3's conversion, ran in the first
+                // 14 gaps of this chunk; the first reader is 30 MFMAs on)
+#pragma unroll
+                for (int e1 = 0; e1 < 4; ++e1) { h1gen(d[e1][0], A1, B1[e1]); h1gen(d[e1][1], A2, B1[e1]); }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (FLAGS & 4) {
+            if (NS == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        }
+        if (FLAGS & 2) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        slot = slot1;
+    }
+    long t1 = clock64();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (FLAGS & 32) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int nb = 0; nb < 8; ++nb) asm volatile("" : "+a"(Z[e][nb]));
+    }
+    float s = 0;
+    for (int e = 0; e < 4; ++e)
+        for (int nb = 0; nb < 8; ++nb)
+            for (int r = 0; r < 4; ++r) s += acc[e][nb][r] + ((FLAGS & 32) ? Z[e][nb][r] : 0.f);
+    if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = t1 - t0;
+    if (s == 1234.5f) out[1] = 1;
+}
+
+// SHAPE 0: v_mfma_f32_32x32x16_f16 (the production kernel's), 1: v_mfma_f32_16x16x32_f16
+template <int FLAGS, int NS, int SHAPE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
+void kern(long* out, const char* gsrc, float seed, int iters) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (SHAPE == 0) body32<FLAGS, NS>(smem, out, gsrc, seed, iters);
+    else body16<FLAGS, NS>(smem, out, gsrc, seed, iters);
+}
+
 // Does the immediate offset of global_load_lds advance BOTH the global address and the LDS address?
 __global__ void dma_offset_test(const unsigned* g, unsigned* out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -212,30 +408,33 @@ __global__ void dma_offset_test(const unsigned* g, unsigned* out) {
     for (int i = threadIdx.x; i < 2048; i += 64) out[i] = ((unsigned*)smem)[i];
 }
 
-template <int FLAGS, int NS>
-void run(long* d, const char* src, const char* what) {
+template <int FLAGS, int NS, int SHAPE = 0>
+double run(long* d, const char* src, const char* what, int iters = 2048) {
     const int lds = NS * TILE_B + 32768;
-    const int iters = 2048;
-    hipFuncSetAttribute((const void*)kern<FLAGS, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipLaunchKernelGGL((kern<FLAGS, NS>), dim3(256), dim3(256), lds, 0, d, src, 1.0f, 64);
+    hipFuncSetAttribute((const void*)kern<FLAGS, NS, SHAPE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipLaunchKernelGGL((kern<FLAGS, NS, SHAPE>), dim3(256), dim3(256), lds, 0, d, src, 1.0f, 64);
     hipDeviceSynchronize();
     hipEvent_t a, b;
     hipEventCreate(&a); hipEventCreate(&b);
     hipEventRecord(a, 0);
-    hipLaunchKernelGGL((kern<FLAGS, NS>), dim3(256), dim3(256), lds, 0, d, src, 1.0f, iters);
+    hipLaunchKernelGGL((kern<FLAGS, NS, SHAPE>), dim3(256), dim3(256), lds, 0, d, src, 1.0f, iters);
     hipEventRecord(b, 0);
     hipEventSynchronize(b);
     float ms = 0;
     hipEventElapsedTime(&ms, a, b);
+    hipEventDestroy(a); hipEventDestroy(b);
     long hcyc;
     hipMemcpy(&hcyc, d, 8, hipMemcpyDeviceToHost);
+    // MFMA work in units of one 32x32x16 (= two 16x16x32: the same FLOP and the same 32 matrix-pipe cycles)
     const int nm = ((FLAGS & 128) ? 32 : 48) + ((FLAGS & 8) ? 4 : 0);
     const double tf = 256.0 * 4 * iters * nm * 32768.0 / (ms * 1e-3) / 1e12;
     // shader clock over the run: the K loop's clock64() cycles of one wave / the kernel's event time (prologue / epilogue of
     // the kernel are < 1 % of 2048 iterations); matrix pipe occupancy = MFMA cycles issued / cycles elapsed
     const double ghz = (double)hcyc / (ms * 1e-3) / 1e9;
-    printf("NS %d flags %3d %-46s: %6.0f cycles/chunk (MFMA %d = %4.1f %% of the cycles)  clock %.3f GHz  %7.1f TFLOP/s  %.2f ms  err=%s\n", NS, FLAGS, what,
+    printf("%s NS %d flags %3d %-46s: %6.0f cycles/chunk (MFMA %d = %4.1f %% of the cycles)  clock %.3f GHz  %7.1f TFLOP/s  %.2f ms  err=%s\n",
+           SHAPE ? "16x16x32" : "32x32x16", NS, FLAGS, what,
            (double)hcyc / iters, nm * 32, 100.0 * nm * 32 * iters / (double)hcyc, ghz, tf, ms, hipGetErrorString(hipGetLastError()));
+    return tf;
 }
 
 int main() {
@@ -278,5 +477,31 @@ int main() {
     run<64 | 16 | 8 | 1 | 32 | 2 | 4, 4>(d, src, "FULL, 4 slots, H1 MFMA into VGPRs (asm)");
     run<128, 3>(d, src, "32 MFMA only (2 of 3 split products)");
     run<128 | 64 | 16 | 8 | 1 | 32 | 2 | 4, 3>(d, src, "FULL, 3 slots, asm H1, 2 of 3 split products");
+
+    // the same ladder on v_mfma_f32_16x16x32_f16
+    run<0, 3, 1>(d, src, "96 MFMA only");
+    run<16, 3, 1>(d, src, "+ 16 W2 fragment reads");
+    run<16 | 8, 3, 1>(d, src, "+ H1 (8 MFMA, 2 LDS reads)");
+    run<16 | 8 | 1, 3, 1>(d, src, "+ conversions");
+    run<16 | 8 | 1 | 32, 3, 1>(d, src, "+ 128 live Z registers");
+    run<16 | 8 | 1 | 32 | 2, 3, 1>(d, src, "+ s_barrier per chunk");
+    run<16 | 8 | 1 | 32 | 2 | 4, 3, 1>(d, src, "+ DMA ring, wait per chunk (FULL, 3 slots)");
+    run<64 | 16 | 8 | 1 | 32 | 2 | 4, 3, 1>(d, src, "FULL, 3 slots, H1 MFMA into VGPRs (asm)");
+
+    // Shape A/B: bare stream and full model (the production configuration: 3 slots, asm H1) of both shapes, alternating,
+    // at 16 x the iterations (launches of tens of ms, so the clock the chip settles at is the one measured)
+    const int REPS = 4, LONG = 32768;
+    double worst_bare = 1e9, worst_full = 1e9;
+    for (int r = 0; r < REPS; ++r) {
+        printf("shape A/B repetition %d\n", r);
+        const double b32 = run<0, 3, 0>(d, src, "bare stream", LONG);
+        const double b16 = run<0, 3, 1>(d, src, "bare stream", LONG);
+        const double f32_ = run<64 | 16 | 8 | 1 | 32 | 2 | 4, 3, 0>(d, src, "FULL model", LONG);
+        const double f16_ = run<64 | 16 | 8 | 1 | 32 | 2 | 4, 3, 1>(d, src, "FULL model", LONG);
+        printf("  16x16x32 / 32x32x16 FLOP/s: bare %.4f  full %.4f\n", b16 / b32, f16_ / f32_);
+        if (b16 / b32 < worst_bare) worst_bare = b16 / b32;
+        if (f16_ / f32_ < worst_full) worst_full = f16_ / f32_;
+    }
+    printf("shape A/B lowest ratio over %d repetitions: bare %.4f  full %.4f\n", REPS, worst_bare, worst_full);
     return 0;
 }
