@@ -23,17 +23,24 @@
 //     16 edges, its three split terms in the lane groups of K = 32, with the (W1|b1) rows picked by LDS address so that
 //     the result is the hidden layer's A operand without a cross-lane move; the aggregation covers a 32-edge half with
 //     one K = 32 MFMA, whose k slots are the C layout of two edge blocks;
-//   * a k1 chunk is four batches of two column blocks (fragments: two sets of 16 registers, the next batch's set read
-//     during the current one) x four edge blocks x 6 MFMAs.  The A operands are single-buffered: the next chunk's edge
-//     block e is converted into the registers of edge block e behind its last MFMA (schedule at the loop);
+//   * a k1 chunk runs HALF-CHUNK-MAJOR: edge blocks {0, 1} over all eight column blocks (48 MFMAs), then edge blocks {2, 3}
+//     (48 MFMAs); a half is four batches of two column blocks (fragments: two sets of 16 registers, the next batch's set
+//     read during the current one - every fragment twice per chunk, 32 ds_read_b128, one per three MFMA gaps) x two edge
+//     blocks x 6 MFMAs.  An MFMA of this shape leaves the SIMD's issue port free for about half of its 16 cycles, i.e. for
+//     two vector instructions, so the K loop is LEVELLED: no gap of the steady chunk carries more than two vector / LDS /
+//     DMA instructions (three where hipcc adds an address add).  The A operands are single-buffered: while a half runs,
+//     the other half's 16 operand registers are free, and the next operands are converted into them ONE instruction per
+//     gap (40 per half over 48 gaps; schedule at the loop);
 //   * MFMA order is pinned by an empty asm on the accumulator ("+a") after every MFMA plus
 //     sched_barrier(0): hipcc otherwise sinks the MFMAs of a step below its conversions;
 //   * H1 is produced by asm MFMAs with a VGPR destination (the builtin lands in AGPRs in a 512-register
-//     kernel: one v_accvgpr_read per value) and converted by asm pairs (relu, rtz16 hi, rn16 lo) - hipcc
-//     pads no hazards for asm operands, so the producer is placed >= 2 MFMAs before the first consumer (it is 30);
+//     kernel: one v_accvgpr_read per value), in two halves of four per chunk, and converted by single-instruction asm
+//     statements (relu, relu, rtz16 hi, rn16 lo low / high half) - hipcc pads no hazards for asm operands, so each producer
+//     is placed >= 2 MFMAs before its first consumer, and a converted register is written a whole gap or more ahead of
+//     the first MFMA that reads it;
 //   * W2 chunk images (16 KiB, pre-swizzled) stream through a 3-slot LDS ring by LDS-DMA: chunk c + 2 is
-//     issued during chunk c (4 pieces per wave, one address + immediate offsets), retired by the
-//     s_waitcnt vmcnt(0) + s_barrier that ends chunk c; fragments are read a batch ahead, in place.
+//     issued during chunk c (4 pieces per wave, one address + immediate offsets, in gaps that carry nothing else), retired
+//     by the s_waitcnt vmcnt(0) + s_barrier that ends chunk c; fragments are read a batch ahead, in place.
 #include "gpde_common.h"
 #include <cstdlib>
 #include <type_traits>
@@ -246,16 +253,29 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
         conv_a(v0, v1, ph, t0_, t1_);
         conv_b(ph, t0_, t1_, pl);
     };
+    // One conversion instruction (step 0..4 of a pair: relu, relu, hi = rtz16, lo = rn16(y - hi) low / high half), as a statement
+    // of its own: the K loop issues ONE per MFMA gap.  The same five instructions as conv_a + conv_b
+    auto conv_step = [&](int step, float v0, float v1, unsigned& ph, unsigned& t0_, unsigned& t1_, unsigned& pl) {
+        if (step == 0) asm("v_max_i32 %0, 0, %1" : "=v"(t0_) : "v"(v0));
+        if (step == 1) asm("v_max_i32 %0, 0, %1" : "=v"(t1_) : "v"(v1));
+        if (step == 2) asm("v_cvt_pkrtz_f16_f32 %0, %1, %2" : "=v"(ph) : "v"(t0_), "v"(t1_));
+        if (step == 3) asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(pl) : "v"(t0_), "v"(ph));
+        if (step == 4) asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(pl) : "v"(t1_), "v"(ph));
+    };
     // ONE MFMA per 16 H1 rows x 16 edges: K = 32 holds the three split terms, by lane group W1hi x attr_hi |
     // W1hi x attr_lo | W1lo x attr_hi | (anything) x 0.  The leading s_nop covers a VALU write of an operand right in
     // front of the statement
-    auto h1gen = [&](f32x4 (&dd)[4][2], h8 w1r0, h8 w1r1, const h8 (&at)[4]) {      // the 8 MFMAs of a chunk
+    auto h1gen_half = [&](f32x4 (&dd)[4][2], int e0, h8 w1r0, h8 w1r1, const h8 (&at)[4]) {      // edge blocks e0, e0 + 1: 4 MFMAs
         asm volatile("s_nop 4");
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
+        for (int e = e0; e < e0 + 2; ++e) {
             asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(dd[e][0]) : "v"(w1r0), "v"(at[e]));
             asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(dd[e][1]) : "v"(w1r1), "v"(at[e]));
         }
+    };
+    auto h1gen = [&](f32x4 (&dd)[4][2], h8 w1r0, h8 w1r1, const h8 (&at)[4]) {      // the 8 MFMAs of a chunk (tile prologue)
+        h1gen_half(dd, 0, w1r0, w1r1, at);
+        h1gen_half(dd, 2, w1r0, w1r1, at);
     };
 
     // ---- prologue: chunks 0 and 1 of the W2 slice, the first tile's edges and attributes ---------------
@@ -404,7 +424,7 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
         // destination of the first / last edge of the two 32-edge halves: loaded with the other side loads at the
         // end of chunk 0 (all lanes the same address), made scalar after the K loop
         int nf_v[2] = {0, 0}, nl_v[2] = {0, 0};
-        unsigned cph = 0, ct0 = 0, ct1 = 0;
+        unsigned cph = 0, ct0 = 0, ct1 = 0, cpl = 0;
         h8 A1, A2;
 
         // One k1 chunk.  The first seven chunks of a tile are peeled (PH = compile-time phase) so that the side
@@ -435,98 +455,108 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
             int c1 = c + 1;                                               // (W1|b1) rows read in this chunk: chunk c + 1
             if (c1 >= NKC) c1 -= NKC;
             const char* w1n = w1s + (size_t)c1 * GP_BK * 32 + w1o;
-            // 96 MFMAs: batch bt = column blocks 2 bt, 2 bt + 1; per batch the edge blocks 0..3, six MFMAs each (three split
-            // products x two column blocks, product-major so that consecutive MFMAs go to different accumulators).
-            // n = MFMA index in the chunk; what rides in the gap behind MFMA n:
-            //   conversions   the next chunk's operands are converted INTO the registers of this chunk's (single buffer): edge
-            //                 block ce from the gap behind its last MFMA (n = 77 + 6 ce) on, eight gaps each (pair p: first
-            //                 part, then second part), wrapping into the next chunk's gaps 0..13 - edge block ce is first
-            //                 read there at n = 6 ce.  At a tile's first chunk the wrapped part re-converts chunk 0's edge
-            //                 blocks 2, 3 from the unchanged raw H1 (same values); at its last the early part converts the
-            //                 unused H1 below
-            //   fragments     n = 24 bt + 6 .. + 9: the next batch's four reads, into the other set
-            //   (W1|b1)       n = 25, 27;  W2 ring pieces n = 29, 35, 41, 47;  raw H1 of chunk c + 1 behind n = 47
-            //   side loads    n >= 48, one per gap, i.e. behind the four W2 pieces
+            // 96 MFMAs in HALF-CHUNK-MAJOR order: edge blocks {0, 1} over all eight column blocks (n = 0..47), then edge blocks
+            // {2, 3} (n = 48..95).  A half is four batches of two column blocks, a batch 12 MFMAs: edge block 2 hf, then 2 hf + 1,
+            // six each (three split products x two column blocks, product-major so that consecutive MFMAs go to different
+            // accumulators; every accumulator still receives hi x lo, hi x hi, lo x hi of a chunk in that order).  The fragment
+            // set alternates per batch (g8 & 1: eight batches, so the sets line up from chunk to chunk), and a batch's fragments
+            // are read during the batch before it - twice per chunk, since both halves need all eight column blocks.
+            // n = MFMA index in the chunk, q = n % 12 its index in the batch; what rides in the gap behind MFMA n - at most TWO
+            // vector / LDS / DMA instructions in the steady chunk, because an MFMA of this shape leaves the SIMD's issue port
+            // free for about 8 of its 16 cycles ("The levelled K loop"):
+            //   conversions   a half never reads the OTHER half's operand registers (single buffer), so they are converted
+            //                 there: this chunk's edge blocks {2, 3} in n = 0..46, the next chunk's {0, 1} in n = 48..94.
+            //                 ONE instruction per gap (conv_step: relu, relu, hi, lo-low, lo-high of a pair), batch bt does
+            //                 pairs 2 bt, 2 bt + 1 of the half's eight in q = 0..4 and 6..10; q = 5 and 11 carry none.
+            //                 A converted register is written at least a whole gap ahead of its first MFMA reader (n = 46
+            //                 before n = 54; n = 94 before the next chunk's n = 6), so no hazard pad is needed between them.
+            //                 At a tile's first chunk the first half re-converts chunk 0's edge blocks {2, 3} from the unchanged
+            //                 raw H1 (same values); at its last the second half converts the unused H1 below
+            //   fragments     q = 0, 3, 6, 9: the next batch's four reads (lo 0, lo 1, hi 0, hi 1), into the other set
+            //   W2 ring       the four pieces at n = 5, 11, 17, 23
+            //   (W1|b1)       n = 25, 31 (rows of chunk c + 1)
+            //   raw H1        of chunk c + 1 in two halves of four MFMAs: edge blocks {0, 1} behind n = 45, {2, 3} behind
+            //                 n = 93 - each behind the last conversion that read these registers (n = 94 of the chunk before,
+            //                 n = 46) and two product MFMAs ahead of the first that reads the new values (n = 48, n = 0)
+            //   side loads    peeled chunks only, in the conversion-free gaps n = 6 k + 5 behind the four W2 pieces (n >= 29), so
+            //                 that the counted wait at the chunk end retires exactly the pieces; the ds_bpermute of the x_j
+            //                 row addresses at n = 1, 7, 13, 19
 #pragma unroll
-            for (int bt = 0; bt < 4; ++bt) {
-                const int fs = bt & 1;                                    // fragment set of this batch
-                const char* rn = (bt < 3) ? rb0 + (2 * bt + 2) * 2048 : rb1;      // where the NEXT batch's fragments live
+            for (int g8 = 0; g8 < 8; ++g8) {
+                const int hf = g8 >> 2, bt = g8 & 3, fs = g8 & 1;         // half, batch of the half, fragment set
+                // where the NEXT batch's fragments live: the next column blocks of this chunk (0, 1 again behind the first
+                // half), behind the last batch 0, 1 of the next chunk
+                const char* rn = (g8 < 7) ? rb0 + (2 * ((bt + 1) & 3)) * 2048 : rb1;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                    for (int j = 0; j < 6; ++j) {
-                        const int tt = j >> 1, nb = j & 1;                // tt: 0 = hi x lo, 1 = hi x hi, 2 = lo x hi
-                        const int cb = 2 * bt + nb;
-                        const int n = bt * 24 + e * 6 + j;
+                for (int q = 0; q < 12; ++q) {
+                    const int e = 2 * hf + q / 6, j = q % 6;
+                    const int tt = j >> 1, nb = j & 1;                    // tt: 0 = hi x lo, 1 = hi x hi, 2 = lo x hi
+                    const int cb = 2 * bt + nb;
+                    const int n = g8 * 12 + q;
 #ifdef GPDE_ABL_2MFMA      // ablation build ONLY (scripts/gpu/clock_evidence.sh; WRONG results): two of the three split products, to
                            // measure how time and clock answer to a third less matrix work per edge
-                        if (tt != 2)
+                    if (tt != 2)
 #endif
-                        acc[e][cb] = mfma32k(__builtin_bit_cast(h8, tt == 2 ? alo[e] : ahi[e]),
-                                             tt == 0 ? blo[fs][nb] : bhi[fs][nb], acc[e][cb]);
-                        asm volatile("" : "+a"(acc[e][cb]));
-                        {
-                            const int k = n >= 78 ? n - 78 : n + 18;
-                            if (k < 32) {
-                                const int ce = k >> 3, jp = (k & 7) >> 1;
-                                if ((k & 1) == 0)
-                                    conv_a(d[ce][jp >> 1][2 * (jp & 1)], d[ce][jp >> 1][2 * (jp & 1) + 1], cph, ct0, ct1);
-                                else {
-                                    unsigned pl;
-                                    conv_b(cph, ct0, ct1, pl);
-                                    ahi[ce][jp] = cph;
-                                    alo[ce][jp] = pl;
-                                    asm volatile("" ::"v"(ahi[ce]), "v"(alo[ce]));
-                                }
-                            }
+                    acc[e][cb] = mfma32k(__builtin_bit_cast(h8, tt == 2 ? alo[e] : ahi[e]),
+                                         tt == 0 ? blo[fs][nb] : bhi[fs][nb], acc[e][cb]);
+                    asm volatile("" : "+a"(acc[e][cb]));
+                    if (q != 5 && q != 11) {
+                        const int v = q < 5 ? q : q - 1, pr = 2 * bt + v / 5, step = v % 5;
+                        const int ce = 2 * (1 - hf) + (pr >> 2), jp = pr & 3;
+                        conv_step(step, d[ce][jp >> 1][2 * (jp & 1)], d[ce][jp >> 1][2 * (jp & 1) + 1], cph, ct0, ct1, cpl);
+                        if (step == 4) {
+                            ahi[ce][jp] = cph;
+                            alo[ce][jp] = cpl;
                         }
-                        if (e == 1) {
-                            if (j == 0) blo[fs ^ 1][0] = *(const h8*)(rn + (bo ^ 64));
-                            if (j == 1) blo[fs ^ 1][1] = *(const h8*)(rn + 2048 + (bo ^ 64));
-                            if (j == 2) bhi[fs ^ 1][0] = *(const h8*)(rn + bo);
-                            if (j == 3) bhi[fs ^ 1][1] = *(const h8*)(rn + 2048 + bo);
-                        }
-                        if (n == 37) A1 = *(const h8*)w1n;
-                        if (n == 39) A2 = *(const h8*)(w1n + 256);
-                        if (n == 29) GPDE_GLDS(gsrc, ldst, 0);
-                        if (n == 35) GPDE_GLDS(gsrc, ldst, 1024);
-                        if (n == 41) GPDE_GLDS(gsrc, ldst, 2048);
-                        if (n == 47) GPDE_GLDS(gsrc, ldst, 3072);
-                        // The tile's side loads, ONE PER MFMA GAP of the chunk's second half - i.e. behind the chunk's four W2
-                        // pieces, so that the counted wait at the chunk end retires exactly those (round 3: issued as one
-                        // block after the last MFMA they cost ~570 cycles in each of the six peeled chunks, the matrix pipe
-                        // idling while ~60 address / load instructions went out).  The x_j row addresses (ds_bpermute of the
-                        // source ids loaded two chunks earlier) go into gaps of the first half.
-                        if constexpr (MODE == 0 && PH == 0) {
-                            if (n == 52) load_perm(e0n);
-                            if (n == 58) src_l = a.src[min(e0 + lane, e_clamp)];
-                            if (n == 64) nf_v[0] = a.dst[min(e0, e_clamp)];
-                            if (n == 70) nl_v[0] = a.dst[min(max(min(e0 + 32, eb) - 1, e0), e_clamp)];
-                            if (n == 76) nf_v[1] = a.dst[min(e0 + 32, e_clamp)];
-                            if (n == 82) nl_v[1] = a.dst[min(max(min(e0 + 64, eb) - 1, e0 + 32), e_clamp)];
-                        } else if constexpr (WRITE_H && PH == 0) {
-                            if (n == 52) load_perm(e0n);
-                        }
+                    } else {
+                        // pins the pairs converted so far in their operand registers.  NOT in the gap of a pair's last
+                        // instruction: hipcc pads an s_nop between that write and an asm statement reading it
+                        const int ce = 2 * (1 - hf) + (bt >> 1);
+                        asm volatile("" ::"v"(ahi[ce]), "v"(alo[ce]));
+                    }
+                    if (q == 0) blo[fs ^ 1][0] = *(const h8*)(rn + (bo ^ 64));
+                    if (q == 3) blo[fs ^ 1][1] = *(const h8*)(rn + 2048 + (bo ^ 64));
+                    if (q == 6) bhi[fs ^ 1][0] = *(const h8*)(rn + bo);
+                    if (q == 9) bhi[fs ^ 1][1] = *(const h8*)(rn + 2048 + bo);
+                    if (n == 5) GPDE_GLDS(gsrc, ldst, 0);
+                    if (n == 11) GPDE_GLDS(gsrc, ldst, 1024);
+                    if (n == 17) GPDE_GLDS(gsrc, ldst, 2048);
+                    if (n == 23) GPDE_GLDS(gsrc, ldst, 3072);
+                    if (n == 25) A1 = *(const h8*)w1n;
+                    if (n == 31) A2 = *(const h8*)(w1n + 256);
+                    // The tile's side loads, ONE PER conversion-free gap behind the chunk's four W2 pieces, so that the counted
+                    // wait at the chunk end retires exactly those (round 3: issued as one block after the last MFMA they cost
+                    // ~570 cycles in each of the six peeled chunks, the matrix pipe idling while ~60 address / load
+                    // instructions went out).  The x_j row addresses (ds_bpermute of the source ids loaded two chunks earlier)
+                    // go into gaps of the first half.
+                    if constexpr (MODE == 0 && PH == 0) {
+                        if (n == 53) load_perm(e0n);
+                        if (n == 59) src_l = a.src[min(e0 + lane, e_clamp)];
+                        if (n == 65) nf_v[0] = a.dst[min(e0, e_clamp)];
+                        if (n == 71) nl_v[0] = a.dst[min(max(min(e0 + 32, eb) - 1, e0), e_clamp)];
+                        if (n == 77) nf_v[1] = a.dst[min(e0 + 32, e_clamp)];
+                        if (n == 83) nl_v[1] = a.dst[min(max(min(e0 + 64, eb) - 1, e0 + 32), e_clamp)];
+                    } else if constexpr (WRITE_H && PH == 0) {
+                        if (n == 53) load_perm(e0n);
+                    }
+                    if constexpr (PH == 2) {
+                        if (n >= 29 && n < 77 && (n - 29) % 6 == 0) load_attr_d((n - 29) / 6);
+                    }
+                    if constexpr (!WRITE_H && PH >= 2 && PH <= 5) {
+                        if (n == 1 || n == 7 || n == 13 || n == 19) x_addr1(4 * (PH - 2), (n - 1) / 6);
                         if constexpr (PH == 2) {
-                            if (n >= 50 && n < 82 && ((n - 50) & 3) == 0) load_attr_d((n - 50) >> 2);
+                            if (n == 77 || n == 83 || n == 89 || n == 95) x_issue1(0, (n - 77) / 6);
+                        } else {
+                            if (n == 53 || n == 65 || n == 77 || n == 89) x_issue1(4 * (PH - 2), (n - 53) / 12);
                         }
-                        if constexpr (!WRITE_H && PH >= 2 && PH <= 5) {
-                            if (n == 2 || n == 8 || n == 14 || n == 20) x_addr1(4 * (PH - 2), (n - 2) / 6);
-                            if constexpr (PH == 2) {
-                                if (n == 83 || n == 87 || n == 91 || n == 95) x_issue1(0, (n - 83) / 4);
-                            } else {
-                                if (n == 54 || n == 66 || n == 78 || n == 90) x_issue1(4 * (PH - 2), (n - 54) / 12);
-                            }
-                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (n == 45 || n == 93) {
+                        // raw H1 of chunk c + 1, edge blocks {0, 1} / {2, 3}; at the last chunk this is chunk 0 with THIS
+                        // tile's attributes - unused, the next tile starts afresh
+                        h1gen_half(d, n == 45 ? 0 : 2, A1, A2, B1);
                         __builtin_amdgcn_sched_barrier(0);
                     }
-                }
-                if (bt == 1) {
-                    // raw H1 of chunk c + 1 (single-buffered: its last reader, edge block 3's conversion, ran in gaps 6..13
-                    // of this chunk; the first reader is 30 MFMAs on); at the last chunk this is chunk 0 with THIS tile's
-                    // attributes - unused, the next tile starts afresh
-                    h1gen(d, A1, A2, B1);
-                    __builtin_amdgcn_sched_barrier(0);
                 }
             }
             // closing wait: the chunk's W2 pieces are retired, its side loads (issued behind them, above) stay in flight

@@ -4,8 +4,10 @@
 // (2 edge blocks x 4 column blocks x 2 k16 steps x 3 split products) + 4 H1 MFMAs, 16 ds_read_b128 of W2 fragments,
 // 2 of (W1|b1), 16 conversion pairs (5 VALU each), 4 LDS-DMA pieces of the next W2 chunk image, one s_barrier.
 // SHAPE 1, v_mfma_f32_16x16x32_f16 (the kernel now): 96 + 8 MFMAs of half the size, everything else the same (body16).
+// SHAPE 2: the same MFMAs in the kernel's LEVELLED schedule (body16<.., LV = 1>: half-chunk-major, one conversion instruction per gap).
 // Flags ablate the parts; the result is cycles per chunk (ideal 52 x 32 = 104 x 16 = 1664), the shader clock and chip
-// TFLOP/s.  The run ends with the shape A/B: bare stream and full model of both shapes, alternating, in long launches.
+// TFLOP/s.  The run ends with the shape A/B (bare stream and full model of both shapes, alternating, in long launches) and
+// the schedule A/B (full model, SHAPE 1 against SHAPE 2).
 //   hipcc --offload-arch=gfx950 -O3 -o kloop_model_v6 kloop_model_v6.hip && ./kloop_model_v6
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -211,7 +213,16 @@ __device__ __forceinline__ void body32(char* smem, long* out, const char* gsrc, 
 // conversion pairs, 4 DMA pieces, one s_barrier; at most 4 non-MFMA instructions per gap.  Ideal 104 x 16 = 1664 cycles
 // per chunk, as for the 32x32 loop.  (A first form with two batches of four column blocks, the next batch's fragments
 // re-read in place during the batch's last edge block, measured 2241 cycles per chunk against this one's 2224.)
-template <int FLAGS, int NS>
+//
+// LV 1, the LEVELLED schedule (half-chunk-major): edge blocks {0, 1} run over all eight column blocks (MFMAs 0..47), then edge
+// blocks {2, 3} (48..95); inside a half the same four batches of two column blocks, so every accumulator still receives hi x lo,
+// hi x hi, lo x hi in that order.  A half leaves the other half's operand registers free for 48 gaps: the next operands of edge
+// blocks {2, 3} are converted in gaps 0..46, those of {0, 1} in gaps 48..94, ONE conversion instruction per gap (five
+// single-instruction asm statements per pair).  The W2 fragments are read twice per chunk (32 ds_read_b128, one per three gaps,
+// into the other set as before); gaps 5, 11, .. (two per batch) carry no conversion and take the DMA pieces (5, 11, 17, 23);
+// the (W1|b1) reads ride in gaps 25, 31.  Raw H1 comes in two halves of four MFMAs: edge blocks {0, 1} of the next chunk behind
+// MFMA 45, {2, 3} behind MFMA 93, each two MFMAs ahead of its first conversion.  No gap carries more than two instructions.
+template <int FLAGS, int NS, int LV = 0>
 __device__ __forceinline__ void body16(char* smem, long* out, const char* gsrc, float seed, int iters) {
     char* ring = smem;
     char* w1s = smem + NS * TILE_B;           // 32 KiB
@@ -286,6 +297,14 @@ __device__ __forceinline__ void body16(char* smem, long* out, const char* gsrc, 
             dd = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, z, 0, 0, 0);
         }
     };
+    // LV 1: the conversion pair as five statements of one instruction (step 0..4), one per MFMA gap
+    auto conv_step = [&](int step, float v0, float v1, unsigned& ph, unsigned& t0_, unsigned& t1_, unsigned& pl) {
+        if (step == 0) asm("v_max_i32 %0, 0, %1" : "=v"(t0_) : "v"(v0));
+        if (step == 1) asm("v_max_i32 %0, 0, %1" : "=v"(t1_) : "v"(v1));
+        if (step == 2) asm("v_cvt_pkrtz_f16_f32 %0, %1, %2" : "=v"(ph) : "v"(t0_), "v"(t1_));
+        if (step == 3) asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(pl) : "v"(t0_), "v"(ph));
+        if (step == 4) asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(pl) : "v"(t1_), "v"(ph));
+    };
 
     if (FLAGS & 4) {
         for (int p = 0; p < 4; ++p) issue_w2(1, 1, p);
@@ -300,7 +319,7 @@ __device__ __forceinline__ void body16(char* smem, long* out, const char* gsrc, 
             for (int nb = 0; nb < 8; ++nb) asm volatile("" : "+a"(Z[e][nb]));
     }
     int slot = 0;
-    unsigned cph = 0, ct0 = 0, ct1 = 0;
+    unsigned cph = 0, ct0 = 0, ct1 = 0, cpl = 0;
     h8 A1 = *(const h8*)(w1s + w1o), A2 = *(const h8*)(w1s + w1o + 256);
     long t0 = clock64();
     for (int it = 0; it < iters; ++it) {
@@ -312,6 +331,68 @@ __device__ __forceinline__ void body16(char* smem, long* out, const char* gsrc, 
         const char* rb0 = ring + slot * TILE_B;
         const char* rb1 = ring + slot1 * TILE_B;
         const char* w1n = w1s + (size_t)(((it + 1) & 31) * 32) * 32 + w1o;
+        if constexpr (LV == 1) {
+            unsigned long long gb_c = gbase + (size_t)dchunk * TILE_B;
+            asm volatile("" : "+s"(gb_c));
+            const char* gp_c = (const char*)(gb_c + lane16);
+#pragma unroll
+            for (int g8 = 0; g8 < 8; ++g8) {            // batch of the chunk: half hf, column blocks 2 bt, 2 bt + 1
+                const int hf = g8 >> 2, bt = g8 & 3, fs = g8 & 1;
+                // the NEXT batch's fragments: the next column blocks of this chunk (0, 1 again behind the first half), then 0, 1 of
+                // the next chunk
+                const char* rn = (g8 < 7) ? rb0 + (2 * ((bt + 1) & 3)) * 2048 : rb1;
+#pragma unroll
+                for (int q = 0; q < 12; ++q) {
+                    const int e = 2 * hf + q / 6, i = q % 6;
+                    const int t = i >> 1, nb = i & 1;
+                    const int cbk = 2 * bt + nb;
+                    const int n = g8 * 12 + q;              // MFMA index in the chunk
+                    if (!((FLAGS & 128) && t == 2))
+                        acc[e][cbk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, t == 2 ? alo[e] : ahi[e]), t == 0 ? blo[fs][nb] : bhi[fs][nb], acc[e][cbk], 0, 0, 0);
+                    asm volatile("" : "+a"(acc[e][cbk]));
+                    // conversions of the OTHER half's edge blocks (first half: this chunk's {2, 3}, second half: the next chunk's
+                    // {0, 1}): batch bt converts pairs 2 bt, 2 bt + 1 of the eight, one instruction per gap, none in gaps 5 and 11
+                    if ((FLAGS & 1) && q != 5 && q != 11) {
+                        const int v = q < 5 ? q : q - 1, pr = 2 * bt + v / 5, step = v % 5;
+                        const int ce = 2 * (1 - hf) + (pr >> 2), jp = pr & 3;
+                        conv_step(step, d[ce][jp >> 1][2 * (jp & 1)], d[ce][jp >> 1][2 * (jp & 1) + 1], cph, ct0, ct1, cpl);
+                        if (step == 4) {
+                            ahi[ce][jp] = cph;
+                            alo[ce][jp] = cpl;
+                        }
+                    } else if (FLAGS & 1) {
+                        // keeps the converted registers live in the model; a gap behind their last write (read by an asm in
+                        // the same gap as the write, hipcc pads an s_nop in front of the next MFMA)
+                        const int ce = 2 * (1 - hf) + (bt >> 1);
+                        asm volatile("" ::"v"(ahi[ce]), "v"(alo[ce]));
+                    }
+                    if (FLAGS & 16) {                       // the other set's last reader was the previous batch
+                        if (q == 0) blo[fs ^ 1][0] = *(const h8*)(rn + (bo ^ 64));
+                        if (q == 3) blo[fs ^ 1][1] = *(const h8*)(rn + 2048 + (bo ^ 64));
+                        if (q == 6) bhi[fs ^ 1][0] = *(const h8*)(rn + bo);
+                        if (q == 9) bhi[fs ^ 1][1] = *(const h8*)(rn + 2048 + bo);
+                    }
+                    if ((FLAGS & 4) && n < 24 && q % 6 == 5) {           // one address per chunk (gp_c), immediate offsets
+                        char* l = ring + dslot * TILE_B + wave * 4096;
+                        if (n == 5) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp_c, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
+                        if (n == 11) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp_c, (__attribute__((address_space(3))) void*)l, 16, 1024, 0);
+                        if (n == 17) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp_c, (__attribute__((address_space(3))) void*)l, 16, 2048, 0);
+                        if (n == 23) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp_c, (__attribute__((address_space(3))) void*)l, 16, 3072, 0);
+                    }
+                    if ((FLAGS & 8) && n == 25) A1 = *(const h8*)w1n;
+                    if ((FLAGS & 8) && n == 31) A2 = *(const h8*)(w1n + 256);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if ((FLAGS & 8) && (n == 45 || n == 93)) {
+                        // raw H1 of the next chunk, edge blocks {0, 1} / {2, 3}: the last reader of these registers (the
+                        // conversions of the other half) ran a gap earlier, the first reader is two MFMAs on
+                        const int e0 = n == 45 ? 0 : 2;
+                        h1gen(d[e0][0], A1, B1[e0]); h1gen(d[e0][1], A2, B1[e0]);
+                        h1gen(d[e0 + 1][0], A1, B1[e0 + 1]); h1gen(d[e0 + 1][1], A2, B1[e0 + 1]);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+            }
+        } else
 #pragma unroll
         for (int bt = 0; bt < 4; ++bt) {
             const int fs = bt & 1;                  // fragment set of this batch; the next batch's goes into fs ^ 1
@@ -385,13 +466,15 @@ __device__ __forceinline__ void body16(char* smem, long* out, const char* gsrc, 
     if (s == 1234.5f) out[1] = 1;
 }
 
-// SHAPE 0: v_mfma_f32_32x32x16_f16 (the production kernel's), 1: v_mfma_f32_16x16x32_f16
+// SHAPE 0: v_mfma_f32_32x32x16_f16, 1: v_mfma_f32_16x16x32_f16 (batch-major: the kernel up to the levelled K loop), 2: the same
+// MFMAs in the levelled, half-chunk-major schedule
 template <int FLAGS, int NS, int SHAPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void kern(long* out, const char* gsrc, float seed, int iters) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (SHAPE == 0) body32<FLAGS, NS>(smem, out, gsrc, seed, iters);
-    else body16<FLAGS, NS>(smem, out, gsrc, seed, iters);
+    else if (SHAPE == 1) body16<FLAGS, NS, 0>(smem, out, gsrc, seed, iters);
+    else body16<FLAGS, NS, 1>(smem, out, gsrc, seed, iters);
 }
 
 // Does the immediate offset of global_load_lds advance BOTH the global address and the LDS address?
@@ -409,7 +492,7 @@ __global__ void dma_offset_test(const unsigned* g, unsigned* out) {
 }
 
 template <int FLAGS, int NS, int SHAPE = 0>
-double run(long* d, const char* src, const char* what, int iters = 2048) {
+double run(long* d, const char* src, const char* what, int iters = 2048, double* cyc_out = nullptr) {
     const int lds = NS * TILE_B + 32768;
     hipFuncSetAttribute((const void*)kern<FLAGS, NS, SHAPE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipLaunchKernelGGL((kern<FLAGS, NS, SHAPE>), dim3(256), dim3(256), lds, 0, d, src, 1.0f, 64);
@@ -432,8 +515,9 @@ double run(long* d, const char* src, const char* what, int iters = 2048) {
     // the kernel are < 1 % of 2048 iterations); matrix pipe occupancy = MFMA cycles issued / cycles elapsed
     const double ghz = (double)hcyc / (ms * 1e-3) / 1e9;
     printf("%s NS %d flags %3d %-46s: %6.0f cycles/chunk (MFMA %d = %4.1f %% of the cycles)  clock %.3f GHz  %7.1f TFLOP/s  %.2f ms  err=%s\n",
-           SHAPE ? "16x16x32" : "32x32x16", NS, FLAGS, what,
+           SHAPE == 2 ? "16x16 lv" : SHAPE ? "16x16x32" : "32x32x16", NS, FLAGS, what,
            (double)hcyc / iters, nm * 32, 100.0 * nm * 32 * iters / (double)hcyc, ghz, tf, ms, hipGetErrorString(hipGetLastError()));
+    if (cyc_out) *cyc_out = (double)hcyc / iters;
     return tf;
 }
 
@@ -503,5 +587,24 @@ int main() {
         if (f16_ / f32_ < worst_full) worst_full = f16_ / f32_;
     }
     printf("shape A/B lowest ratio over %d repetitions: bare %.4f  full %.4f\n", REPS, worst_bare, worst_full);
+
+    // Schedule A/B on 16x16x32: the ladder of the levelled schedule, then the full model batch-major against levelled,
+    // alternating, four repetitions.  The gate for a kernel change: levelled lower by >= 100 cycles per chunk in EVERY repetition
+    run<16, 3, 2>(d, src, "+ 32 W2 fragment reads");
+    run<16 | 8, 3, 2>(d, src, "+ H1 (8 MFMA, 2 LDS reads)");
+    run<64 | 16 | 8 | 1, 3, 2>(d, src, "+ conversions, one per gap (asm H1)");
+    run<64 | 16 | 8 | 1 | 32, 3, 2>(d, src, "+ 128 live Z registers");
+    run<64 | 16 | 8 | 1 | 32 | 2, 3, 2>(d, src, "+ s_barrier per chunk");
+    run<64 | 16 | 8 | 1 | 32 | 2 | 4, 3, 2>(d, src, "+ DMA ring, wait per chunk (FULL)");
+    double least = 1e9;
+    for (int r = 0; r < REPS; ++r) {
+        printf("schedule A/B repetition %d\n", r);
+        double ca = 0, cb = 0;
+        const double fa = run<64 | 16 | 8 | 1 | 32 | 2 | 4, 3, 1>(d, src, "FULL model, batch-major", LONG, &ca);
+        const double fb = run<64 | 16 | 8 | 1 | 32 | 2 | 4, 3, 2>(d, src, "FULL model, levelled", LONG, &cb);
+        printf("  cycles per chunk saved %.0f   levelled / batch-major FLOP/s %.4f\n", ca - cb, fb / fa);
+        if (ca - cb < least) least = ca - cb;
+    }
+    printf("schedule A/B least saving over %d repetitions: %.0f cycles per chunk (gate: 100)\n", REPS, least);
     return 0;
 }
