@@ -902,3 +902,305 @@ extern "C" int gpde_radius_csr_batched_fill(const double* pos_src, int64_t n_src
     GP_LAUNCH_CHECK("gpde_radius_csr_batched_fill kernels");
     return GPDE_OK;
 }
+
+// ---- sampled arm: gpde_gaussian_csr_* -------------------------------------------------------------------------------------------
+// The reference's SECOND connectivity (gaussian_connectivity, graph-neural-operator/utilities.py:257-263, 372-378;
+// multipole-graph-neural-operator/utilities.py:283-289, 419-425): every ordered pair is kept independently with probability
+// exp(-d^2 / sigma^2).  Here the draw is a pure function of (seed, destination id, source id) - the counter-based hash of
+// gpde_edge_keys_hash - so COUNT and FILL evaluate the same predicate and the graph depends on positions, sigma and seed only:
+//     edge j -> i  iff  u(seed, i, j) < exp(-(d2 / (sigma * sigma)))          (float64, round to nearest, contraction off)
+//     u   = ((double)(key >> 10) + 0.5) * 2^-53,   key = the value gpde_edge_keys_hash gives for (seed, dst = i, src = j)
+//     d2  = the value gpde_edge_keys_sqdist gives for the edge, bit for bit: open axes d = x_dst - x_src, periodic axes
+//           d = x_src - x_dst, d -= L rint(d / L) on the RAW coordinates; squares summed in axis order.
+// u >= 2^-54, so a pair with exp(-d2 / sigma^2) <= 2^-54 is never kept: the graph lies inside the radius graph of
+// r_support = sigma sqrt(54 ln 2), and a cell list of that edge (or of the optional cutoff, if smaller) is exact.  The walk is
+// the periodic builder's (an open box is the case "no axis wraps"); the cells only ENUMERATE candidates - on a periodic axis they
+// bin the reduced coordinates while the distance is taken from the raw ones, a few ulp apart, far inside the 2^-20 slack of the
+// cell edge.  The candidate graph is never formed: at sigma = 0.1 on the 241^2 lattice it would hold 2.13e9 edges, the kept one 9.4e7.
+//   exp       is evaluated only where it decides.  With u in [2^e, 2^(e+1)) and p = 2^-t (t = d2 / sigma^2 * log2 e): t > -e means
+//             p < 2^e <= u (dropped), t < -e - 1 means p > 2^(e+1) > u (kept); both with a margin of 1e-6 in t, six orders
+//             above the rounding of t, so the shortcut never contradicts the predicate.  On the oracle's inputs 2 - 4 % of
+//             the pairs inside the support reach exp at small sigma, a quarter when sigma spans the box.
+//   geometry  optional, fill pass: the periodic builder's values (pos_src[j] - image(pos_dst[i]) on the coordinates reduced into
+//             the period, and its norm, rounded once to float32) - the rows radius_csr(..., return_geometry=True) gives the edge.
+namespace {
+
+constexpr double GAUSS_LOG2E = 1.4426950408889634;
+constexpr double GAUSS_Q_MAX = 37.5;                    // exp(-37.5) < 2^-54 = min u: no draw can keep the pair
+
+struct GaussTest {
+    double s2, cut2;            // sigma * sigma; cutoff^2 (+inf: no cutoff)
+    uint64_t seed_term;         // seed * GPDE_HASH_SEED_MUL
+};
+
+template <bool PERIODIC>
+__device__ __forceinline__ double gauss_d2(const PeriodicGrid& g, const double* __restrict__ ps, int j, const double (&xd)[3]) {
+    const int dim = g.cells.dim;
+    double d2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (k < dim) {
+            const double xs = ps[(size_t)j * dim + k];
+            double d;
+            if (PERIODIC && g.per[k] > 0.0) {
+                d = xs - xd[k];
+                d = d - g.per[k] * rint(d / g.per[k]);
+            } else {
+                d = xd[k] - xs;
+            }
+            d2 += d * d;
+        }
+    return d2;
+}
+
+__device__ __forceinline__ bool gauss_keep(const GaussTest& gt, double d2, int i, int j) {
+    if (d2 > gt.cut2) return false;
+    const double q = d2 / gt.s2;
+    if (!(q <= GAUSS_Q_MAX)) return false;
+    uint64_t z = gt.seed_term + (((uint64_t)(uint32_t)i << 32) | (uint64_t)(uint32_t)j);
+    z = (z ^ (z >> 30)) * GPDE_HASH_MUL1;
+    z = (z ^ (z >> 27)) * GPDE_HASH_MUL2;
+    z ^= z >> 31;
+    const double u = ((double)(z >> 11) + 0.5) * 0x1p-53;              // key >> 10 = z >> 11
+    const int e = (int)((__double_as_longlong(u) >> 52) & 0x7ff) - 1023;     // u in [2^e, 2^(e+1)), normal
+    const double t = q * GAUSS_LOG2E;
+    if (t > (double)(-e) + 1e-6) return false;
+    if (t < (double)(-e - 1) - 1e-6) return true;
+    return u < exp(-q);
+}
+
+template <bool PERIODIC>
+__device__ __forceinline__ void gauss_geom(const PeriodicGrid& g, const double* __restrict__ ps, int j, const double (&pc)[3], float* gs) {
+    const int dim = g.cells.dim;
+    double d2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (k < dim) {
+            const double x = ps[(size_t)j * dim + k];
+            const double dk = (PERIODIC && g.wrap[k]) ? nearest_image_diff(reduce_into_period(x, g.cells.lo[k], g.per[k]), pc[k], g.per[k], g.half[k])
+                                                      : x - pc[k];
+            gs[k] = (float)dk;
+            d2 += dk * dk;
+        }
+    gs[dim] = (float)sqrt(d2);
+}
+
+template <bool PERIODIC>
+__global__ void k_gauss_cell_ids(const double* __restrict__ pos, int n, PeriodicGrid g, uint32_t* __restrict__ cell, uint32_t* __restrict__ id) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int dim = g.cells.dim;
+    double p[3] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < dim; ++k) {
+        const double x = pos[(size_t)j * dim + k];
+        p[k] = PERIODIC ? reduce_into_period(x, g.cells.lo[k], g.per[k]) : x;
+    }
+    int c[3];
+    cell_of(g.cells, p, c);
+    cell[j] = (uint32_t)((c[2] * g.cells.nc[1] + c[1]) * g.cells.nc[0] + c[0]);
+    id[j] = (uint32_t)j;
+}
+
+template <bool FILL, bool PERIODIC>
+__global__ __launch_bounds__(256) void k_gauss_neighbors(const double* __restrict__ ps, const double* __restrict__ pd, int nd, PeriodicGrid g,
+                                                         GaussTest gt, const int32_t* __restrict__ cell_start,
+                                                         const uint32_t* __restrict__ order, int32_t* __restrict__ deg,
+                                                         const int32_t* __restrict__ rowptr, int32_t* __restrict__ src,
+                                                         int32_t* __restrict__ dst, float* __restrict__ geom, int64_t n_edges, int sort_cap) {
+    extern __shared__ uint32_t sbuf[];                  // FILL: [4 waves][sort_cap], sort_cap a power of two in 64 .. CG_SORT_MAX
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int i = blockIdx.x * 4 + wave;
+    if (i >= nd) return;
+    const int dim = g.cells.dim;
+    double pr[3] = {0.0, 0.0, 0.0}, pc[3] = {0.0, 0.0, 0.0};     // the destination: raw (the distance), reduced (its cell, the geometry)
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (k < dim) {
+            pr[k] = pd[(size_t)i * dim + k];
+            pc[k] = PERIODIC ? reduce_into_period(pr[k], g.cells.lo[k], g.per[k]) : pr[k];
+        }
+    int ci[3];
+    cell_of(g.cells, pc, ci);
+    const int r0 = FILL ? rowptr[i] : 0;
+    const int n_row = FILL ? rowptr[i + 1] - r0 : 0;
+    if (FILL && (r0 < 0 || n_row < 0 || (int64_t)r0 + n_row > n_edges)) return;      // not a rowptr of n_edges slots: nothing is written
+    const bool in_lds = FILL && n_row <= sort_cap;
+    const bool want_geom = FILL && geom != nullptr;
+    uint32_t* row = sbuf + wave * sort_cap;
+    const AxisWalk wx = axis_walk(g, 0, ci[0]), wy = axis_walk(g, 1, ci[1]), wz = axis_walk(g, 2, ci[2]);
+    int count = 0;
+    for (int tz = wz.a0; tz <= wz.a1 + (wz.extra >= 0 ? 1 : 0); ++tz) {
+        const int cz = tz > wz.a1 ? wz.extra : tz;
+        for (int ty = wy.a0; ty <= wy.a1 + (wy.extra >= 0 ? 1 : 0); ++ty) {
+            const int cy = ty > wy.a1 ? wy.extra : ty;
+            const int base = (cz * g.cells.nc[1] + cy) * g.cells.nc[0];
+            for (int tx = 0; tx <= (wx.extra >= 0 ? 1 : 0); ++tx) {
+                const int cx0 = tx ? wx.extra : wx.a0, cx1 = tx ? wx.extra : wx.a1;
+                const int p0 = cell_start[base + cx0], p1 = cell_start[base + cx1 + 1];
+                for (int q0 = p0; q0 < p1; q0 += 64) {
+                    const int q = q0 + lane;
+                    bool hit = false;
+                    int j = 0;
+                    if (q < p1) {
+                        j = (int)order[q];
+                        hit = gauss_keep(gt, gauss_d2<PERIODIC>(g, ps, j, pr), i, j);
+                    }
+                    const unsigned long long m = __ballot(hit);
+                    if (FILL && hit) {
+                        const int slot = count + __popcll(m & ((1ull << lane) - 1ull));
+                        if (slot < n_row) {
+                            if (in_lds) row[slot] = (uint32_t)j;
+                            else {                            // very long rows: cell order (deterministic, not ascending)
+                                src[r0 + slot] = j;
+                                if (want_geom) gauss_geom<PERIODIC>(g, ps, j, pc, geom + (size_t)(r0 + slot) * (dim + 1));
+                            }
+                        }
+                    }
+                    count += __popcll(m);
+                }
+            }
+        }
+    }
+    if (!FILL) {
+        if (lane == 0) deg[i] = count;
+        return;
+    }
+    if (in_lds) {
+        sort_row_by_source(row, n_row, lane);
+        for (int t = lane; t < n_row; t += 64) {
+            const int j = (int)row[t];
+            src[r0 + t] = j;
+            if (want_geom) gauss_geom<PERIODIC>(g, ps, j, pc, geom + (size_t)(r0 + t) * (dim + 1));
+        }
+    }
+    for (int t = lane; t < n_row; t += 64) dst[r0 + t] = i;
+}
+
+struct GaussPlan {
+    PeriodicGrid g;
+    GaussTest gt;
+    int64_t ncells;
+    bool periodic;
+};
+
+double gauss_support_radius(double sigma) { return sigma * sqrt(54.0 * 0.6931471805599453); }
+
+// Every refusal the scalars and the host arrays show, then the grid: cells of edge >= min(r_support, cutoff).
+int gauss_plan(const char* what, int dim, double sigma, double cutoff, int64_t seed, const double* lo, const double* hi,
+               const double* origin, const double* period, GaussPlan* p) {
+    if (dim < 1 || dim > 3) { gpde_set_error("%s: dim must be 1..3 (got %d)", what, dim); return GPDE_EUNSUPPORTED; }
+    if (!(sigma > 0.0) || !isfinite(sigma) || !(sigma * sigma > 0.0) || !isfinite(sigma * sigma)) {
+        gpde_set_error("%s: sigma = %g must be positive and finite (and so must sigma^2)", what, sigma);
+        return GPDE_EINVAL;
+    }
+    if (!(cutoff >= 0.0) || !isfinite(cutoff)) { gpde_set_error("%s: cutoff = %g must be positive and finite, or 0 (none)", what, cutoff); return GPDE_EINVAL; }
+    double r = gauss_support_radius(sigma);
+    if (cutoff > 0.0 && cutoff < r) r = cutoff;
+    if (!isfinite(r)) { gpde_set_error("%s: the support radius of sigma = %g is not finite", what, sigma); return GPDE_EINVAL; }
+    p->periodic = false;
+    double per[3] = {0.0, 0.0, 0.0}, org[3] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < dim; ++k) {
+        per[k] = period ? period[k] : 0.0;
+        org[k] = origin ? origin[k] : 0.0;
+        if (!(per[k] >= 0.0) || !isfinite(per[k]) || !isfinite(org[k])) {
+            gpde_set_error("%s: period[%d] must be >= 0 (0 = open axis) and origin[%d] finite", what, k, k);
+            return GPDE_EINVAL;
+        }
+        if (per[k] > 0.0) {
+            p->periodic = true;
+            if (!(2.0 * r < per[k])) {
+                gpde_set_error("%s: 2 min(r_support, cutoff) = %g >= period[%d] = %g: a pair would have more than one image in reach (pass a cutoff)",
+                               what, 2.0 * r, k, per[k]);
+                return GPDE_EINVAL;
+            }
+        }
+    }
+    if (int rc = make_periodic_grid(what, dim, r, lo, hi, org, per, &p->g, &p->ncells)) return rc;
+    p->gt.s2 = sigma * sigma;
+    p->gt.cut2 = cutoff > 0.0 ? cutoff * cutoff : INFINITY;
+    p->gt.seed_term = (uint64_t)seed * GPDE_HASH_SEED_MUL;
+    return GPDE_OK;
+}
+
+int gauss_check_points(const char* what, const double* ps, int64_t ns, const double* pd, int64_t nd) {
+    if (ns < 0 || nd < 0 || ns > 0x7fffffff || nd > 0x7fffffff) { gpde_set_error("%s: point counts must be 0 .. 2^31 - 1", what); return GPDE_EINVAL; }
+    if (!ps || !pd) { gpde_set_error("%s: pos_src / pos_dst is null", what); return GPDE_EINVAL; }
+    return GPDE_OK;
+}
+
+}  // namespace
+
+extern "C" size_t gpde_gaussian_csr_workspace_bytes(int64_t n_src, int dim, double sigma, double cutoff, const double* lo,
+                                                    const double* hi, const double* origin, const double* period) {
+    const char* what = "gpde_gaussian_csr_workspace_bytes";
+    GaussPlan p;
+    if (n_src < 0 || n_src > 0x7fffffff) { gpde_set_error("%s: n_src out of range", what); return 0; }
+    if (gauss_plan(what, dim, sigma, cutoff, 0, lo, hi, origin, period, &p) != GPDE_OK) return 0;
+    return carve(nullptr, n_src, p.ncells).total + 256;
+}
+
+extern "C" int gpde_gaussian_csr_count(const double* pos_src, int64_t n_src, const double* pos_dst, int64_t n_dst, int dim, double sigma,
+                                       double cutoff, int64_t seed, const double* lo, const double* hi, const double* origin,
+                                       const double* period, int32_t* deg, void* ws, size_t ws_bytes, void* stream_) {
+    const char* what = "gpde_gaussian_csr_count";
+    hipStream_t st = (hipStream_t)stream_;
+    GaussPlan p;
+    if (int rc = gauss_check_points(what, pos_src, n_src, pos_dst, n_dst)) return rc;
+    if (!deg || !ws) { gpde_set_error("%s: deg / ws is null", what); return GPDE_EINVAL; }
+    if (int rc = gauss_plan(what, dim, sigma, cutoff, seed, lo, hi, origin, period, &p)) return rc;
+    CellWs w = carve(ws, n_src, p.ncells);
+    if (ws_bytes < w.total) { gpde_set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, w.total); return GPDE_EWORKSPACE; }
+    if (n_dst == 0) return GPDE_OK;
+    const int T = 256;
+    if (n_src > 0) {
+        const dim3 grid((unsigned)((n_src + T - 1) / T));
+        if (p.periodic) hipLaunchKernelGGL((k_gauss_cell_ids<true>), grid, dim3(T), 0, st, pos_src, (int)n_src, p.g, w.cell, w.id);
+        else hipLaunchKernelGGL((k_gauss_cell_ids<false>), grid, dim3(T), 0, st, pos_src, (int)n_src, p.g, w.cell, w.id);
+        GP_HIP_CHECK(rocprim::radix_sort_pairs(w.temp, w.temp_bytes, w.cell, w.cell_sorted, w.id, w.order, (size_t)n_src, 0,
+                                               sort_bits_for(p.ncells), st));
+    }
+    hipLaunchKernelGGL(k_cell_start, dim3((unsigned)((p.ncells + 1 + T - 1) / T)), dim3(T), 0, st, w.cell_sorted, (int)n_src, (int)p.ncells, w.start);
+    const dim3 grid((unsigned)((n_dst + 3) / 4)), block(256);
+    if (p.periodic)
+        hipLaunchKernelGGL((k_gauss_neighbors<false, true>), grid, block, 0, st, pos_src, pos_dst, (int)n_dst, p.g, p.gt, w.start, w.order, deg,
+                           (const int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (float*)nullptr, (int64_t)0, 0);
+    else
+        hipLaunchKernelGGL((k_gauss_neighbors<false, false>), grid, block, 0, st, pos_src, pos_dst, (int)n_dst, p.g, p.gt, w.start, w.order, deg,
+                           (const int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (float*)nullptr, (int64_t)0, 0);
+    GP_LAUNCH_CHECK("gpde_gaussian_csr_count kernels");
+    return GPDE_OK;
+}
+
+// `ws` must still hold what gpde_gaussian_csr_count left there (same arguments); rowptr = exclusive scan of its `deg`.
+// max_in_degree (0: not known) sizes the LDS row sort: the walk waits on gathers and on float64 division, so the waves in flight
+// decide its speed, and 4 rows of CG_SORT_MAX slots (64 KiB) leave two workgroups per CU where the registers would allow seven.
+extern "C" int gpde_gaussian_csr_fill(const double* pos_src, int64_t n_src, const double* pos_dst, int64_t n_dst, int dim, double sigma,
+                                      double cutoff, int64_t seed, const double* lo, const double* hi, const double* origin,
+                                      const double* period, const int32_t* rowptr, int32_t* src, int32_t* dst, float* geom,
+                                      int64_t n_edges, int64_t max_in_degree, void* ws, size_t ws_bytes, void* stream_) {
+    const char* what = "gpde_gaussian_csr_fill";
+    hipStream_t st = (hipStream_t)stream_;
+    GaussPlan p;
+    if (int rc = gauss_check_points(what, pos_src, n_src, pos_dst, n_dst)) return rc;
+    if (n_edges < 0 || n_edges > 0x7fffffff - 64) { gpde_set_error("%s: n_edges = %lld outside an int32 CSR (0 .. 2^31 - 65)", what, (long long)n_edges); return GPDE_EINVAL; }
+    if (max_in_degree < 0) { gpde_set_error("%s: max_in_degree = %lld must be >= 0 (0: not known)", what, (long long)max_in_degree); return GPDE_EINVAL; }
+    if (!rowptr || !ws || (n_edges > 0 && (!src || !dst))) { gpde_set_error("%s: null rowptr / src / dst / ws", what); return GPDE_EINVAL; }
+    if (int rc = gauss_plan(what, dim, sigma, cutoff, seed, lo, hi, origin, period, &p)) return rc;
+    CellWs w = carve(ws, n_src, p.ncells);
+    if (ws_bytes < w.total) { gpde_set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, w.total); return GPDE_EWORKSPACE; }
+    if (n_dst == 0 || n_edges == 0) return GPDE_OK;
+    const dim3 grid((unsigned)((n_dst + 3) / 4)), block(256);
+    int sort_cap = CG_SORT_MAX;                          // rows up to this many edges are sorted: the smallest power of two that holds
+    if (max_in_degree > 0)                               // the longest row, from one wave step (64) up to CG_SORT_MAX
+        for (sort_cap = 64; sort_cap < max_in_degree && sort_cap < CG_SORT_MAX;) sort_cap <<= 1;
+    const size_t lds = (size_t)4 * sort_cap * 4;
+    if (p.periodic)
+        hipLaunchKernelGGL((k_gauss_neighbors<true, true>), grid, block, lds, st, pos_src, pos_dst, (int)n_dst, p.g, p.gt, w.start, w.order,
+                           (int32_t*)nullptr, rowptr, src, dst, geom, n_edges, sort_cap);
+    else
+        hipLaunchKernelGGL((k_gauss_neighbors<true, false>), grid, block, lds, st, pos_src, pos_dst, (int)n_dst, p.g, p.gt, w.start, w.order,
+                           (int32_t*)nullptr, rowptr, src, dst, geom, n_edges, sort_cap);
+    GP_LAUNCH_CHECK("gpde_gaussian_csr_fill kernels");
+    return GPDE_OK;
+}

@@ -727,6 +727,43 @@ GPDE_API int gpde_edge_keys_sqdist(const double* pos_src, const double* pos_dst,
 GPDE_API int gpde_edge_keys_hash(const int32_t* src_ids, const int32_t* dst_ids, int64_t n_edges, int64_t seed,
                         int64_t* keys, void* stream);
 
+/* SAMPLED GRAPHS: the reference's second connectivity, gaussian_connectivity (graph-neural-operator utilities.py:257-263,
+ * 372-378; multipole-graph-neural-operator utilities.py:283-289, 419-425), built natively as the destination CSR (the sampled
+ * arm of gpde_cellgraph.hip).  The edge j -> i (j in pos_src, i in pos_dst; level-local ids) is kept iff
+ *       u(seed, i, j) < exp(-(d2 / (sigma * sigma)))                          float64, round to nearest, nothing fused
+ *   u   ((double)(key >> 10) + 0.5) * 2^-53 with key = what gpde_edge_keys_hash gives for (seed, dst = i, src = j): the 53 top
+ *       bits of the mix, at the centre of their cell (the sum is rounded like any float64 sum); 2^-54 <= u.
+ *   d2  what gpde_edge_keys_sqdist gives for the edge, bit for bit (open axes d = x_dst - x_src; periodic axes d = x_src - x_dst,
+ *       d -= L rint(d / L) on the raw coordinates; squares summed in axis order).
+ * The graph is a pure function of positions, sigma and seed - not of cells, waves or call history; the two directions of a pair
+ * are independent draws; a pair at d = 0 (a point with itself) has p = 1 and is kept.  Since u >= 2^-54 no pair with
+ * exp(-d2 / sigma^2) <= 2^-54 is kept: the graph lies inside the radius graph of r_support = sigma sqrt(54 ln 2) ~ 6.118 sigma, and
+ * the cell list (cells of edge >= min(r_support, cutoff)) is exact.  The kernel skips exp where the binary exponent of u
+ * against d2 / sigma^2 decides; the kept set is the predicate's.  A host that follows the formula differs only where its exp and
+ * the device's differ in the last places AND u lies between them.
+ *   cutoff   0: none.  > 0: additionally drops every pair with d2 > cutoff * cutoff - a TRUNCATED Gaussian, another graph.
+ *   origin / period   HOST arrays [dim] as in gpde_radius_csr_periodic_* (NULL: origin 0 / no periodic axis).  A periodic axis needs
+ *            2 min(r_support, cutoff) < period[k].  lo / hi: HOST arrays [dim], a bounding box of both point sets, read on open axes.
+ *   geom (fill, nullable)   float32 [E][dim + 1] by CSR slot, the values of gpde_radius_csr_periodic_fill for the edge.
+ *   max_in_degree (fill)    the largest entry of COUNT's `deg`, or 0 when the caller does not know it.  It only sizes the LDS row
+ *            sort (the smallest power of two >= it, 64 .. 4096 slots per wave; 0: 4096) and with it the waves in flight; a value
+ *            below the true one leaves the rows longer than that power of two in cell order instead of ascending.
+ * Two passes with the caller's scan between them, `ws` untouched in between, like the radius builders; rows in ascending source
+ * order (rows longer than 4096 edges keep cell order); no atomics, COUNT and FILL evaluate the same predicate.  Before any device
+ * call: GPDE_EUNSUPPORTED for dim outside 1..3; GPDE_EINVAL for sigma (or sigma^2) not positive and finite, a negative or
+ * non-finite cutoff, a bad period / origin, the periodic rule, NULL positions / deg / rowptr / src / dst / ws, negative sizes and
+ * n_edges outside an int32 CSR; GPDE_EWORKSPACE for a short workspace; the workspace query returns 0 for what it can see.
+ * Additions to the ABI: GPDE_VERSION is unchanged. */
+GPDE_API size_t gpde_gaussian_csr_workspace_bytes(int64_t n_src, int dim, double sigma, double cutoff, const double* lo,
+                                         const double* hi, const double* origin, const double* period);
+GPDE_API int gpde_gaussian_csr_count(const double* pos_src, int64_t n_src, const double* pos_dst, int64_t n_dst, int dim,
+                            double sigma, double cutoff, int64_t seed, const double* lo, const double* hi, const double* origin,
+                            const double* period, int32_t* deg, void* ws, size_t ws_bytes, void* stream);
+GPDE_API int gpde_gaussian_csr_fill(const double* pos_src, int64_t n_src, const double* pos_dst, int64_t n_dst, int dim,
+                           double sigma, double cutoff, int64_t seed, const double* lo, const double* hi, const double* origin,
+                           const double* period, const int32_t* rowptr, int32_t* src, int32_t* dst, float* geom,
+                           int64_t n_edges, int64_t max_in_degree, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * GCNConv (gpde_gcn.hip): the graph convolution of Kipf & Welling, the baseline network of the multipole paper
  * (multipole-graph-neural-operator/neurips4_GCN.py:28-31 `GCNConv(width, width)`, applied 16 times per forward), on the
