@@ -15,7 +15,7 @@
 // Same two arithmetics as gpde_graph.hip (exact float64 sum of squares; GPDE_RADIUS_REFERENCE_TIES = scikit-learn's
 // dot-product expansion operation by operation).  Edge attributes are addressed by CSR slot (`perm` = identity):
 // generated in CSR order (synth / NodeAttr), or read from node data inside the kernel (row f3).
-#include "gpde_common.h"
+#include "gpde_cells.h"      // CellGrid, cell_of, sort_row_by_source: shared with gpde_knn.hip
 #include <math.h>
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -24,23 +24,6 @@
 namespace {
 
 constexpr int CG_SORT_MAX = 4096;    // rows up to this many edges are sorted by source id in LDS
-
-struct CellGrid {
-    double lo[3], inv[3];
-    int nc[3];
-    int dim;
-};
-
-__device__ __forceinline__ void cell_of(const CellGrid& g, const double* p, int (&c)[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        c[k] = 0;
-        if (k < g.dim) {
-            int v = (int)floor((p[k] - g.lo[k]) * g.inv[k]);
-            c[k] = v < 0 ? 0 : (v >= g.nc[k] ? g.nc[k] - 1 : v);
-        }
-    }
-}
 
 __global__ void k_cell_ids(const double* __restrict__ pos, int n, CellGrid g, uint32_t* __restrict__ cell, uint32_t* __restrict__ id) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -63,28 +46,6 @@ __global__ void k_cell_start(const uint32_t* __restrict__ sorted_cell, int n, in
         if (sorted_cell[mid] < (uint32_t)c) lo = mid + 1; else hi = mid;
     }
     start[c] = lo;
-}
-
-// One wave's row in LDS, sorted by source id (distinct keys): bitonic, padded with sentinels to a power of two.
-__device__ __forceinline__ void sort_row_by_source(uint32_t* row, int n_row, int lane) {
-    int np2 = 64;
-    while (np2 < n_row) np2 <<= 1;
-    for (int t = n_row + lane; t < np2; t += 64) row[t] = 0xffffffffu;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // LDS operations of one wave execute in order: a
-    __builtin_amdgcn_wave_barrier();                             // compiler fence is all the exchange between lanes needs
-    for (int k = 2; k <= np2; k <<= 1)
-        for (int jj = k >> 1; jj > 0; jj >>= 1) {
-            for (int t = lane; t < np2; t += 64) {
-                const int p = t ^ jj;
-                if (p > t) {
-                    const uint32_t a = row[t], b = row[p];
-                    const bool up = (t & k) == 0;
-                    if ((a > b) == up) { row[t] = b; row[p] = a; }
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
 }
 
 template <bool FILL, bool TIES>
@@ -411,6 +372,25 @@ int check(const char* what, const double* ps, int64_t ns, const double* pd, int6
 
 }  // namespace
 
+// The open cell list on its own (gpde_cells.h): what gpde_radius_csr_count does before its walk, for gpde_knn.hip.
+size_t gpde_cell_list_ws_bytes(int64_t n_src, int64_t ncells) { return carve(nullptr, n_src, ncells).total + 256; }
+
+int gpde_cell_list_build(const char* what, const double* pos_src, int64_t n_src, const CellGrid& g, int64_t ncells, void* ws,
+                         size_t ws_bytes, hipStream_t st, GpdeCellList* out) {
+    CellWs w = carve(ws, n_src, ncells);
+    if (ws_bytes < w.total) { gpde_set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, w.total); return GPDE_EWORKSPACE; }
+    const int T = 256;
+    if (n_src > 0) {
+        hipLaunchKernelGGL(k_cell_ids, dim3((unsigned)((n_src + T - 1) / T)), dim3(T), 0, st, pos_src, (int)n_src, g, w.cell, w.id);
+        GP_HIP_CHECK(rocprim::radix_sort_pairs(w.temp, w.temp_bytes, w.cell, w.cell_sorted, w.id, w.order, (size_t)n_src, 0,
+                                               sort_bits_for(ncells), st));
+    }
+    hipLaunchKernelGGL(k_cell_start, dim3((unsigned)((ncells + 1 + T - 1) / T)), dim3(T), 0, st, w.cell_sorted, (int)n_src, (int)ncells, w.start);
+    out->start = w.start;
+    out->order = w.order;
+    return GPDE_OK;
+}
+
 extern "C" size_t gpde_radius_csr_workspace_bytes(int64_t n_src, int dim, double r, const double* lo, const double* hi) {
     CellGrid g;
     int64_t ncells = 0;
@@ -430,13 +410,8 @@ extern "C" int gpde_radius_csr_count(const double* pos_src, int64_t n_src, const
     CellWs w = carve(ws, n_src, ncells);
     if (ws_bytes < w.total) { gpde_set_error("gpde_radius_csr_count: workspace %zu < %zu bytes", ws_bytes, w.total); return GPDE_EWORKSPACE; }
     if (n_dst == 0) return GPDE_OK;
-    const int T = 256;
-    if (n_src > 0) {
-        hipLaunchKernelGGL(k_cell_ids, dim3((unsigned)((n_src + T - 1) / T)), dim3(T), 0, st, pos_src, (int)n_src, g, w.cell, w.id);
-        GP_HIP_CHECK(rocprim::radix_sort_pairs(w.temp, w.temp_bytes, w.cell, w.cell_sorted, w.id, w.order, (size_t)n_src, 0,
-                                               sort_bits_for(ncells), st));
-    }
-    hipLaunchKernelGGL(k_cell_start, dim3((unsigned)((ncells + 1 + T - 1) / T)), dim3(T), 0, st, w.cell_sorted, (int)n_src, (int)ncells, w.start);
+    GpdeCellList cl;
+    if (int rc = gpde_cell_list_build("gpde_radius_csr_count", pos_src, n_src, g, ncells, ws, ws_bytes, st, &cl)) return rc;
     const int same = pos_src == pos_dst && n_src == n_dst;
     const dim3 grid((unsigned)((n_dst + 3) / 4)), block(256);
     if (flags & GPDE_RADIUS_REFERENCE_TIES)

@@ -727,6 +727,43 @@ GPDE_API int gpde_edge_keys_sqdist(const double* pos_src, const double* pos_dst,
 GPDE_API int gpde_edge_keys_hash(const int32_t* src_ids, const int32_t* dst_ids, int64_t n_edges, int64_t seed,
                         int64_t* keys, void* stream);
 
+/* EXACT K-NEAREST-NEIGHBOUR GRAPHS as the destination CSR (gpde_knn.hip): the counterpart of PyG's knn_graph / knn, built
+ * without a radius - the selection above needs a ball that holds k sources around EVERY destination, formed in full first.
+ * Sources pos_src float64 [n_src][dim], destinations pos_dst float64 [n_dst][dim], dim 1..3 (device arrays).  ONE point set is
+ * the call with pos_src == pos_dst and n_src == n_dst.  Row i holds the k_eff sources j with the smallest (d2_bits(j, i), j) in
+ * lexicographic order:
+ *   d2_bits   the int64 bit pattern of the float64 squared distance in the open-axis arithmetic of gpde_edge_keys_sqdist:
+ *             d = pos_dst[i][a] - pos_src[j][a], d2 += d * d in axis order, contraction off.  Ties go to the smaller source id;
+ *   loop      0 on one point set: the pair j == i is excluded BY ID (another point at distance 0 is an ordinary candidate);
+ *             1, or two point sets: nothing is excluded;
+ *   k_eff     min(k, n_src); with loop = 0 on one point set min(k, n_src - 1).  It is the same for every row:
+ *             rowptr[i] = i * k_eff (written by the call), n_edges = n_dst * k_eff - the caller sizes src / dst (int32 [n_edges])
+ *             and geom before the call, and nothing has to be read back;
+ *   rows      ascending source id inside a row (the Csr convention: it fixes the operator's summation order); perm = identity.
+ * That is gpde_csr_select_k applied to the complete bipartite graph under gpde_edge_keys_sqdist keys (self pairs dropped first
+ * for loop = 0).  The graph is a pure function of the positions, k and loop: not of the cell edge, the box, the launch geometry
+ * or call history; no atomics; two calls give identical bits.  Non-finite positions give unspecified edges (valid ids, no
+ * out-of-bounds access, no unbounded loop).
+ *   lo / hi   HOST arrays [dim]: the box the cell grid covers.  Points outside it are binned into the border cells: any finite
+ *             box with hi >= lo gives the same graph, a box around both point sets the fastest build.
+ *   cell      the cell edge; 0: automatic - a mean occupancy of max(2, k / 2) sources per cell, over the axes that have extent
+ *             (gpde_knn.hip knn_auto_cell).  Edges that give more than 2^16 cells on an axis or 2^24 in all are doubled until
+ *             they fit.  It changes the speed, never the result.
+ *   geom      nullable; float32 [n_edges][dim + 1] by CSR slot: pos_src[src] - pos_dst[dst] per axis and its norm, float64
+ *             rounded once - the values of gpde_radius_csr_periodic_fill on open axes for the same edge.
+ *   ws        gpde_knn_csr_workspace_bytes(...) bytes (host arithmetic only; 0 and gpde_last_error() for what it can refuse).
+ * gpde_knn_csr launches on `stream`, never synchronises and never allocates.  Before any device call: GPDE_EUNSUPPORTED for dim
+ * outside 1..3; GPDE_EINVAL for k < 1, k > GPDE_KNN_MAX_K, loop not 0 or 1, point counts outside 0 .. 2^31 - 1,
+ * n_dst * k_eff outside an int32 CSR, a cell that is negative, not finite or has no finite reciprocal, NULL lo / hi, a box that is not finite or has hi < lo, NULL
+ * positions of a non-empty set, NULL rowptr / ws, NULL src / dst with n_edges > 0; GPDE_EWORKSPACE for a short workspace.
+ * Zero sources and zero destinations are valid calls.  Additions to the ABI: GPDE_VERSION is unchanged. */
+#define GPDE_KNN_MAX_K 256
+GPDE_API size_t gpde_knn_csr_workspace_bytes(int64_t n_src, int64_t n_dst, int dim, int64_t k, double cell, const double* lo,
+                                    const double* hi);
+GPDE_API int gpde_knn_csr(const double* pos_src, int64_t n_src, const double* pos_dst, int64_t n_dst, int dim, int64_t k,
+                 int loop, double cell, const double* lo, const double* hi, int32_t* rowptr, int32_t* src, int32_t* dst,
+                 float* geom, void* ws, size_t ws_bytes, void* stream);
+
 /* SAMPLED GRAPHS: the reference's second connectivity, gaussian_connectivity (graph-neural-operator utilities.py:257-263,
  * 372-378; multipole-graph-neural-operator utilities.py:283-289, 419-425), built natively as the destination CSR (the sampled
  * arm of gpde_cellgraph.hip).  The edge j -> i (j in pos_src, i in pos_dst; level-local ids) is kept iff
