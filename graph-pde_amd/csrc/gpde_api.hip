@@ -142,7 +142,8 @@ struct Plan {
     int64_t nodes_per_chunk;
     int n_chunks;
     int n_groups;        // fused-kernel edge groups (workgroups per hidden slice)
-    size_t off_part, off_z, off_ha, off_hb, off_xs, off_scal, off_blk;
+    size_t off_part, off_z, off_ha, off_hb, off_xs, off_scal, off_blk, off_img;
+    bool attr_image;     // the attribute operand image of the f16v6 kernel has its place at off_img
     int nblk_max;        // f16v6 work queue: block-bound slots (0: no queue)
     size_t h_floats;     // mode 2: floats per ping-pong activation buffer
 };
@@ -156,8 +157,17 @@ int pick_splits(int64_t nn) {
     return s;
 }
 
+// Whether a forward call with these flags runs the f16v6 kernel on the attribute operand image (defined below, next to
+// choose_fused)
+bool attr_image_eligible(const GpdePackLayout& L, uint32_t flags, int64_t n_edges, int kt);
+
+// `flags`, `kt`, `attr_given`: what decides whether the call can use the attribute operand image (sizing and the plan
+// queries without flags: the default precision's).  Sizing sets its bytes aside wherever the forward would choose the
+// f16v6 kernel; a plan for a given workspace takes the image only if, with those bytes set aside, it still gets the
+// nodes per chunk that sizing recommends - otherwise it is the plan without the image, exactly
 int make_plan(int64_t N, int64_t E, int n_layers, const int32_t* dims, size_t ws_bytes, bool sizing,
-              Plan* P, size_t* needed, bool hidden_given = false) {
+              Plan* P, size_t* needed, bool hidden_given = false, uint32_t flags = GPDE_FWD_F16SPLIT, int kt = 0,
+              bool attr_given = true) {
     int rc = gpde_pack_layout(n_layers, dims, &P->L);
     if (rc != GPDE_OK) return rc;
     const GpdePackLayout& L = P->L;
@@ -179,31 +189,47 @@ int make_plan(int64_t N, int64_t E, int n_layers, const int32_t* dims, size_t ws
     P->nblk_max = (L.mode == 1 && E < ((int64_t)1 << 31) - GP_QBLOCK) ? (int)(E / GP_QBLOCK + E / 8 / (GP_QBLOCK / 8)) + 10 : 0;
     const size_t blk_bytes = P->nblk_max ? align_up(((size_t)P->nblk_max + 2 + 64) * 4) : 0;
     fixed += blk_bytes;
-    int64_t npc;
-    if (sizing) {
-        // recommended: all nodes if Z fits 4 GiB, else 4 GiB worth of nodes (at least one tile)
-        int64_t cap = (int64_t)(((size_t)4 << 30) / zrow);
-        if (cap < 64) cap = 64;
-        npc = N < cap ? N : cap;
-        if (npc < 1) npc = 1;
-    } else {
-        if (ws_bytes < fixed + 2 * kAlign) {
-            gpde_set_error("gpde_nnconv_fwd: workspace %zu bytes cannot hold the %zu-byte hidden "
-                           "activation buffers", ws_bytes, fixed);
+    const size_t img_bytes = (attr_given && !hidden_given && attr_image_eligible(L, flags, E, kt)) ? gpde_attr_image_bytes(E) : 0;
+    // recommended: all nodes if Z fits 4 GiB, else 4 GiB worth of nodes (at least one tile)
+    int64_t npc_rec = (int64_t)(((size_t)4 << 30) / zrow);
+    if (npc_rec < 64) npc_rec = 64;
+    if (npc_rec > N) npc_rec = N;
+    if (npc_rec < 1) npc_rec = 1;
+    // nodes per chunk of a given workspace with `fx` bytes outside the node chunks
+    auto nodes_for = [&](size_t fx, bool quiet, int64_t* out) {
+        if (ws_bytes < fx + 2 * kAlign) {
+            if (!quiet) gpde_set_error("gpde_nnconv_fwd: workspace %zu bytes cannot hold the %zu-byte hidden "
+                                       "activation buffers", ws_bytes, fx);
             return GPDE_EWORKSPACE;
         }
-        npc = (int64_t)((ws_bytes - fixed - 2 * kAlign) / (zrow + prow));
+        int64_t n_ = (int64_t)((ws_bytes - fx - 2 * kAlign) / (zrow + prow));
         // the whole graph in one chunk whenever it fits exactly (the estimate above gives up two
         // alignment units, which used to split a graph sized with the recommended workspace)
-        if (N > 0 && align_up((size_t)N * prow) + align_up((size_t)N * zrow) + fixed <= ws_bytes) npc = N;
-        if (npc > N) npc = N;
+        if (N > 0 && align_up((size_t)N * prow) + align_up((size_t)N * zrow) + fx <= ws_bytes) n_ = N;
+        if (n_ > N) n_ = N;
         const int64_t min_nodes = N < 64 ? N : 64;
-        if (npc < min_nodes || (N > 0 && npc < 1)) {
-            gpde_set_error("gpde_nnconv_fwd: workspace %zu bytes holds %lld destination nodes, need >= %lld "
-                           "(%zu bytes per node)", ws_bytes, (long long)npc, (long long)min_nodes, zrow + prow);
+        if (n_ < min_nodes || (N > 0 && n_ < 1)) {
+            if (!quiet) gpde_set_error("gpde_nnconv_fwd: workspace %zu bytes holds %lld destination nodes, need >= %lld "
+                                       "(%zu bytes per node)", ws_bytes, (long long)n_, (long long)min_nodes, zrow + prow);
             return GPDE_EWORKSPACE;
         }
-        if (npc < N && npc > 64) npc = npc / 64 * 64;
+        if (n_ < N && n_ > 64) n_ = n_ / 64 * 64;
+        *out = n_;
+        return GPDE_OK;
+    };
+    int64_t npc;
+    P->attr_image = false;
+    if (sizing) {
+        npc = npc_rec;
+        P->attr_image = img_bytes != 0;
+    } else {
+        int64_t npc_img = 0;
+        if (img_bytes && nodes_for(fixed + img_bytes, true, &npc_img) == GPDE_OK && npc_img >= npc_rec) {
+            npc = npc_img;
+            P->attr_image = true;
+        } else if ((rc = nodes_for(fixed, false, &npc)) != GPDE_OK) {
+            return rc;
+        }
     }
     if (npc < 1) npc = 1;
     P->nodes_per_chunk = npc;
@@ -217,6 +243,7 @@ int make_plan(int64_t N, int64_t E, int n_layers, const int32_t* dims, size_t ws
     P->off_xs = off;   off += xs_bytes ? xs_bytes - kAlign : 0;
     P->off_scal = off; off += xs_bytes ? kAlign : 0;
     P->off_blk = off;  off += blk_bytes;
+    P->off_img = off;  off += P->attr_image ? img_bytes : 0;
     if (needed) *needed = off;
     // fused-kernel grid: ~one workgroup per CU, never more edge groups than 4-wave tile sets
     const int ns = L.K2P / GP_TN;
@@ -253,6 +280,12 @@ FusedChoice choose_fused(const GpdePackLayout& L, int mode, uint32_t flags, int6
     return c;
 }
 
+bool attr_image_eligible(const GpdePackLayout& L, uint32_t flags, int64_t n_edges, int kt) {
+    if ((flags & GPDE_FWD_NO_ATTR_IMAGE) || n_edges >= ((int64_t)1 << 31) - GP_QBLOCK) return false;
+    if (choose_fused(L, L.mode, flags, n_edges, kt).kind != FK_V6) return false;
+    return gpde_fused_f16v6_image_supported(gpde_fused_probe(L));
+}
+
 // Whether a forward call takes the per-edge last layer (fwd_impl's low in-degree branch) -- ONE place, used by fwd_impl
 // and by the query gpde_nnconv_fwd_edge_path.  `hidden`: the last hidden activations are given (with their maximum:
 // `hidden_absmax`); `mixed` / `kt`: the mixed and node-table forwards, which never take it.
@@ -287,9 +320,19 @@ extern "C" int gpde_nnconv_fwd_edge_path(int64_t n_nodes, int64_t n_edges, int n
                                          size_t ws_bytes) {
     Plan P;
     if (!dims || n_nodes < 0 || n_edges < 0) { gpde_set_error("gpde_nnconv_fwd_edge_path: null/negative argument"); return GPDE_EINVAL; }
-    int rc = make_plan(n_nodes, n_edges, n_layers, dims, ws_bytes, false, &P, nullptr);
+    int rc = make_plan(n_nodes, n_edges, n_layers, dims, ws_bytes, false, &P, nullptr, false, flags);
     if (rc != GPDE_OK) return rc;
     return takes_edge_path(P, flags, n_nodes, n_edges, false, false, false, 0) ? 1 : 0;
+}
+
+extern "C" int gpde_nnconv_fwd_attr_image(int64_t n_nodes, int64_t n_edges, int n_layers, const int32_t* dims, uint32_t flags,
+                                          size_t ws_bytes, int32_t* n_chunks) {
+    Plan P;
+    if (!dims || n_nodes < 0 || n_edges < 0) { gpde_set_error("gpde_nnconv_fwd_attr_image: null/negative argument"); return GPDE_EINVAL; }
+    int rc = make_plan(n_nodes, n_edges, n_layers, dims, ws_bytes, false, &P, nullptr, false, flags);
+    if (rc != GPDE_OK) return rc;
+    if (n_chunks) *n_chunks = P.n_chunks;
+    return (P.attr_image && !takes_edge_path(P, flags, n_nodes, n_edges, false, false, false, 0)) ? 1 : 0;
 }
 
 extern "C" size_t gpde_nnconv_fwd_workspace_bytes(int64_t n_nodes, int64_t n_edges, int n_layers,
@@ -371,7 +414,8 @@ int fwd_impl(const FwdArgs& a) {
     if (a.n_nodes == 0) return GPDE_OK;
     if (!a.ws) { gpde_set_error("gpde_nnconv_fwd: workspace is null"); return GPDE_EWORKSPACE; }
     Plan P;
-    int rc = make_plan(a.n_nodes, a.n_edges, a.n_layers, a.dims, a.ws_bytes, false, &P, nullptr, a.hidden != nullptr && !mixed);
+    int rc = make_plan(a.n_nodes, a.n_edges, a.n_layers, a.dims, a.ws_bytes, false, &P, nullptr, a.hidden != nullptr && !mixed,
+                       a.flags, a.kt, a.hidden == nullptr);
     if (rc != GPDE_OK) return rc;
     const GpdePackLayout& L = P.L;
     const int mode = (a.hidden && !mixed) ? 2 : L.mode;
@@ -444,6 +488,7 @@ int fwd_impl(const FwdArgs& a) {
 
     const unsigned* xs = nullptr;
     const unsigned* scal = nullptr;
+    GpdeAttrImage img{nullptr, nullptr, nullptr, nullptr};
     const FusedChoice fc = choose_fused(L, mode, a.flags, a.n_edges, a.kt);
     if (a.kt && fc.kind == FK_GENERIC) {
         gpde_set_error("gpde_nnconv_fwd_mixed_keepz (node_attr): built for 3-Linear kernel MLPs on the f16-split kernel only");
@@ -456,6 +501,13 @@ int fwd_impl(const FwdArgs& a) {
         if (rc != GPDE_OK) return rc;
         xs = (const unsigned*)(w + P.off_xs);
         scal = (const unsigned*)(w + P.off_scal);
+        if (P.attr_image && fc.kind == FK_V6) {
+            // the f16v6 kernel's attribute operands, once per call instead of per tile, column slice and lane group
+            img = gpde_attr_image_at(w + P.off_img, a.n_edges);
+            rc = gpde_launch_attr_image(a.edge_attr, a.perm, a.n_edges, L.k0, pk + L.off_w1 + (size_t)L.K1P * 8, pk + L.off_fcol,
+                                        img, a.stream, a.kt, a.sel, a.src, a.dst);
+            if (rc != GPDE_OK) return rc;
+        }
     }
 
     // hidden activations given together with their maximum: the streaming aggregation on split f16
@@ -483,6 +535,7 @@ int fwd_impl(const FwdArgs& a) {
             f.kt = a.kt; f.hmax = (from_h && xs) ? (const unsigned*)a.hidden_absmax : nullptr;
             for (int d = 0; d < 8; ++d) f.sel[d] = (a.kt && a.sel) ? a.sel[d < L.k0 ? d : L.k0 - 1] : 0;
             f.nc0 = (int)nc0; f.nc1 = (int)nc1; f.e_chunk0 = 0; f.n_groups = P.n_groups;
+            f.img_rec = img.rec; f.img_hi = img.hi; f.img_lo = img.lo; f.img_isc = img.isc;
             {
                 ProfScope ps(GPDE_PROF_FUSED, a.stream);
                 if (!from_h && fc.kind == FK_V6 && P.nblk_max && L.K2P / GP_TN <= 64 && !(a.flags & GPDE_FWD_STATIC_RANGES)) {

@@ -162,6 +162,13 @@ struct GpdeFusedArgs {
     int n_groups;          // edge groups (workgroups per slice)
     int kernarg_pad_;      // unused: the struct must extend past 0xfb so that the store kernels can fetch k0 .. n_groups
                            // (0xdc - 0xf7) with one 32-byte scalar load - without it the compiler splits that load
+    // f16v6, attribute operand image (gpde_launch_attr_image; nullptr = attributes from a.attr): per CSR slot the H1 MFMA's
+    // attribute operand as the kernel's tile prologue forms it - hi / lo planes of 8 f16, the per-edge un-scale - and one
+    // constant record (16 zero bytes, then 1.0f) that lanes without an edge read
+    const void* img_hi;    // [E][8] f16
+    const void* img_lo;    // [E][8] f16
+    const float* img_isc;  // [E]
+    const void* img_rec;   // 16 zero bytes | 1.0f
 };
 int gpde_launch_fused(int mode, bool f16split, const GpdeFusedArgs& a, hipStream_t stream);
 // pre-passes of the f16-split aggregation (gpde_prep.hip): scal[0..1], xs [n_nodes][64]
@@ -169,6 +176,22 @@ int gpde_launch_g2_prep(const float* x, int64_t n_nodes, const float* attr, int6
                         const float* wmax8, unsigned* scal, unsigned* xs, hipStream_t stream,
                         int kt = 0, const int* sel = nullptr, const int32_t* src = nullptr,
                         const int32_t* dst = nullptr);
+// The attribute operand image of gpde_fused_f16v6_kernel (gpde_prep.hip): one region [constant record | hi plane | lo plane
+// | isc], every part aligned to 256 bytes.  Built once per forward call from the attributes in CSR slot order (tensor
+// through `perm`, or node table through src / dst / sel when kt != 0) with the arithmetic of the kernel's tile prologue.
+struct GpdeAttrImage { void* rec; void* hi; void* lo; float* isc; };
+static inline size_t gpde_attr_image_bytes(int64_t n_edges) {
+    const size_t e = (size_t)(n_edges > 0 ? n_edges : 0);
+    return 256 + 2 * ((e * 16 + 255) / 256 * 256) + (e * 4 + 255) / 256 * 256;
+}
+static inline GpdeAttrImage gpde_attr_image_at(void* base, int64_t n_edges) {
+    const size_t e = (size_t)(n_edges > 0 ? n_edges : 0), plane = (e * 16 + 255) / 256 * 256;
+    char* b = (char*)base;
+    return GpdeAttrImage{b, b + 256, b + 256 + plane, (float*)(b + 256 + 2 * plane)};
+}
+int gpde_launch_attr_image(const float* attr, const int32_t* perm, int64_t n_edges, int k0, const float* wmax8,
+                           const float* fcol, const GpdeAttrImage& img, hipStream_t stream, int kt = 0,
+                           const int* sel = nullptr, const int32_t* src = nullptr, const int32_t* dst = nullptr);
 // block bounds + queue counters of the f16v6 work queue (gpde_prep.hip): blk [nblk_max + 1], qn [1], qctr [n_slices]
 constexpr int GP_QBLOCK = 4096;    // edges per big block (node-aligned: a block holds whole destination nodes); the
                                    // last 1/8 of the edges is cut into blocks of GP_QBLOCK / 8
@@ -194,6 +217,7 @@ int gpde_launch_fused_store(const GpdeFusedArgs& a, hipStream_t stream);
 // one wave per SIMD, 64 x 128 wave tile, 512 registers (gpde_fused_f16v6.hip): the default from 32768 edges on
 bool gpde_fused_f16v6_supported(const GpdeFusedArgs& a);
 int gpde_launch_fused_f16v6(const GpdeFusedArgs& a, hipStream_t stream);
+bool gpde_fused_f16v6_image_supported(const GpdeFusedArgs& a);      // shapes of its attribute-image variant (a.img_hi set)
 int gpde_num_cus();
 // The packed-MLP side of a GpdeFusedArgs: operand pointers into the image `pk` of gpde_mlp_pack, and the widths
 static inline void gpde_fused_set_pack(GpdeFusedArgs& f, const float* pk, const GpdePackLayout& L) {

@@ -40,7 +40,10 @@
 //     the first MFMA that reads it;
 //   * W2 chunk images (16 KiB, pre-swizzled) stream through a 3-slot LDS ring by LDS-DMA: chunk c + 2 is
 //     issued during chunk c (4 pieces per wave, one address + immediate offsets, in gaps that carry nothing else), retired
-//     by the s_waitcnt vmcnt(0) + s_barrier that ends chunk c; fragments are read a batch ahead, in place.
+//     by the s_waitcnt vmcnt(0) + s_barrier that ends chunk c; fragments are read a batch ahead, in place;
+//   * the forward's aggregation runs on the attribute operand image where the workspace holds one (ASRC_IMAGE, at the
+//     kernel's template): no per-tile prologue, the tile boundary lies inside the tile's last chunk (DESIGN.md §3d,
+//     "The tile boundary").
 #include "gpde_common.h"
 #include <cstdlib>
 #include <type_traits>
@@ -84,10 +87,20 @@ constexpr int NW = 4;                      // waves per workgroup
 // (j -> i) is table[(sel[d] >> 8 ? i : j) * kt + (sel[d] & 255)], read from the node table (a.attr) with the tile's
 // source / destination ids (the reference builds the [E, 6] tensor from node data, utilities.py:274-277).  No `perm`,
 // no per-edge attribute traffic: the table (N x kt floats) lives in L2.
-template <int MODE, bool NODEATTR = false>
+// ASRC 2, the attribute operand IMAGE (aggregation variant only; gpde_launch_attr_image built it for this call): B1 and the
+// per-edge un-scale are not formed per tile but fetched - the next tile's 64 rows of the hi plane, the lo plane and isc by
+// three LDS-DMA in the tile's chunk 2, into a per-wave staging area and the other parity of a double-buffered `Es`.  The
+// tile boundary moves into the tile's LAST chunk (peeled, PH 7): it reads the next tile's B1 from the staging area in its
+// first gaps, its two H1 halves are the next tile's chunk-0 raw H1 (c1 wraps to the chunk-0 rows of (W1|b1)) and the
+// conversions of its second half the next tile's operands of edge blocks {0, 1}.  What is left between two tiles is
+// the round flags with their barrier and the first fragment reads; only a wave's first tile forms its operands up front.
+enum { ASRC_TENSOR = 0, ASRC_NODES = 1, ASRC_IMAGE = 2 };
+template <int MODE, int ASRC = ASRC_TENSOR>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
     constexpr bool WRITE_H = MODE == 1;       // store variant
+    constexpr bool NODEATTR = ASRC == ASRC_NODES, IMAGE = ASRC == ASRC_IMAGE;
+    static_assert(!(IMAGE && WRITE_H), "the store variant forms its attribute operands itself");
     extern __shared__ __attribute__((aligned(16))) char smem[];     // ONE LDS object (cdna guide, glds trap a)
     char* ring = smem;                                               // [3][16 KiB]
     char* w1s = smem + NS * TILE_B;                                  // [K1P][hi 16 B | lo 16 B]
@@ -103,6 +116,15 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
     const int g = lane >> 4;                  // lane group: k slots 8g .. 8g+7 (A, B), rows 4g .. 4g+3 (C, D)
     float* Es = Es_all + wave * TE;
     unsigned* Xs = Xs_all + wave * TE * GP_W;
+    // IMAGE: red[8..11] is a zeroed 16-byte slot (lane group 3's attribute operand); behind colc a staging area per wave
+    // ([hi rows 1 KiB | lo rows 1 KiB] of the next tile's 64 edges) and the second parity of Es, [4][64].  `Es` is the
+    // current tile's parity, Es_n the one the next tile's isc is fetched into; they swap per tile
+    char* stage = nullptr;
+    float* Es_n = nullptr;
+    if constexpr (IMAGE) {
+        stage = (char*)(colc + 2 * GP_TN) + wave * 2048;
+        Es_n = (float*)((char*)(colc + 2 * GP_TN) + NW * 2048) + wave * TE;
+    }
 
     const int ns = a.K2P / GP_TN;
     const int slice = blockIdx.x % ns;
@@ -152,6 +174,9 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
     }
     // red[parity][wave]: "this wave has no tile" flags of the current tile round (double-buffered by parity)
     if (lane == 0) { red[wave] = have ? 0 : 1; red[4 + wave] = 0; }
+    if constexpr (IMAGE) {
+        if (tid < 4) red[8 + tid] = 0;
+    }
     __syncthreads();
     if (red[0] + red[1] + red[2] + red[3] == 4) return;
 
@@ -226,6 +251,33 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
 #pragma unroll
         for (int d = 0; d < 8; ++d) load_attr_d(d);
     };
+    // IMAGE: the three LDS-DMA of a tile that starts at CSR slot e0t in a block that ends at ebt (0: no tile) - lane l
+    // fetches edge e0t + l's row of the hi plane, of the lo plane (16 bytes each, to the staging area) and its isc (4 bytes,
+    // to `es_to`).  A lane without an edge fetches the constant record (zeros | 1.0f): masking is one address select, and
+    // no lane reads past the image
+    [[maybe_unused]] auto img_issue = [&](int which, int e0t, int ebt, float* es_to) {
+        const int e = e0t + lane;
+        const bool ok = e < ebt;
+        if (which == 0) {
+            const char* p = ok ? (const char*)a.img_hi + (size_t)e * 16 : (const char*)a.img_rec;
+            GPDE_GLDS(p, stage, 0);
+        } else if (which == 1) {
+            const char* p = ok ? (const char*)a.img_lo + (size_t)e * 16 : (const char*)a.img_rec;
+            GPDE_GLDS(p, stage + 1024, 0);      // (an immediate offset would move the global side too)
+        } else {
+            const char* p = ok ? (const char*)(a.img_isc + e) : (const char*)a.img_rec + 16;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)p,
+                                             (__attribute__((address_space(3))) void*)es_to, 4, 0, 0);
+        }
+    };
+    // where lane (l15, g) reads B1 of edge block b from the staging area: block 0's address and the stride per block -
+    // lane group 1 the lo rows, groups 0 and 2 the hi rows, group 3 the zeroed slot (stride 0)
+    const char* b1p = nullptr;
+    int b1s = 0;
+    if constexpr (IMAGE) {
+        b1p = g == 3 ? (const char*)(red + 8) : stage + l15 * 16 + (g == 1 ? 1024 : 0);
+        b1s = g == 3 ? 0 : 256;
+    }
     // x_j rows of this tile: piece i = rows 4i .. 4i+3 (lane >> 4 picks the row, lane & 15 its 16-byte unit).
     // The source node comes from the lane that loaded that edge's src (ds_bpermute) at the START of a chunk,
     // the four DMA are issued at its END, behind the chunk's W2 pieces (see the K loop).
@@ -287,8 +339,13 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
         char* l1 = ring + TILE_B + wave * 4096;
         GPDE_GLDS(g1, l1, 0); GPDE_GLDS(g1, l1, 1024); GPDE_GLDS(g1, l1, 2048); GPDE_GLDS(g1, l1, 3072);
     }
-    load_perm(have ? blk_a : e_hi);
-    load_attr();
+    if constexpr (IMAGE) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) img_issue(i, have ? blk_a : e_hi, have ? blk_b : 0, Es);
+    } else {
+        load_perm(have ? blk_a : e_hi);
+        load_attr();
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
@@ -341,6 +398,31 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
 #endif
     int e0 = have ? blk_a : e_hi;
     int n_rounds = 0;
+    // B1[e]: H1 MFMA operand per edge block, by lane group: attr_hi | attr_lo | attr_hi | 0
+    // d[e][half][r]: H1 of edge 16 e + l15, operand position j = 4 half + r of lane group g;  ahi / alo[e]: j = 0..7 as f16 pairs
+    // (IMAGE: B1, d[2..3] and ahi / alo[0..1] are carried from a tile's last chunk into the next tile)
+    h8 B1[4];
+    f32x4 d[4][2];
+    u4 ahi[4], alo[4];                // single-buffered: see the conversion schedule in the K loop
+    if constexpr (IMAGE) {
+        // cold start, once per wave and launch: the first tile's operands from the staging area, raw H1 of chunk 0, the
+        // operands of edge blocks {0, 1} (chunk 0 converts {2, 3} in its first half)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) B1[b] = *(const h8*)(b1p + b * b1s);
+        const char* wp = w1s + w1o;
+        const h8 A1 = *(const h8*)wp, A2 = *(const h8*)(wp + 256);
+        h1gen(d, A1, A2, B1);
+        asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");           // MFMA result -> VALU read (asm operands are not padded)
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+#pragma unroll
+            for (int jp = 0; jp < 4; ++jp) {
+                unsigned ph, pl;
+                conv_pair(d[e][jp >> 1][2 * (jp & 1)], d[e][jp >> 1][2 * (jp & 1) + 1], ph, pl);
+                ahi[e][jp] = ph;
+                alo[e][jp] = pl;
+            }
+    }
     for (int t = 0;; ++t) {
         // ---- this tile, and where the NEXT one starts (its edge ids / attributes are prefetched during this one) ----
         const int eb = have ? blk_b : e0;                        // no tile: everything below is masked out
@@ -350,6 +432,7 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
         bool have_n = have && !last_in_blk;
         if (last_in_blk && queue) have_n = draw_block(na_, nb_);      // drawn ONE tile ahead: no block is held in reserve
         const int e0n = !have ? e_hi : (last_in_blk ? (have_n ? na_ : e_hi) : e0 + TE);
+        [[maybe_unused]] const int ebn = !have ? 0 : (last_in_blk ? (have_n ? nb_ : 0) : blk_b);     // its block's end (0: no next tile)
         if (t > 0) {
             // all four waves out of tiles -> done.  Flags of this round were written before the barrier; the other
             // parity is rewritten two rounds later, behind at least one K loop of barriers
@@ -361,8 +444,8 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
         ++n_rounds;
 
         // ---- attributes of this lane's two edges: validity, bias slot, per-edge scale, f16 split ------------
-        h8 B1[4];               // H1 MFMA operand per edge block, by lane group: attr_hi | attr_lo | attr_hi | 0
-        {
+        // (IMAGE: the tile's last chunk read them from the staging area, its isc is in Es)
+        if constexpr (!IMAGE) {
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 float av[8];    // attributes of edge 16 b + l15, in all four lane groups
@@ -403,10 +486,8 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
             blo[0][nb] = *(const h8*)(ring + slot * TILE_B + nb * 2048 + (bo ^ 64));
         }
         // ---- raw H1 of chunk 0 and the operands of chunk 0 -----------------------------------------------
-        // d[e][half][r]: H1 of edge 16 e + l15, operand position j = 4 half + r of lane group g;  ahi / alo[e]: j = 0..7 as f16 pairs
-        f32x4 d[4][2];
-        u4 ahi[4], alo[4];                // single-buffered: see the conversion schedule in the K loop
-        {
+        // (IMAGE: the last chunk of the tile before produced them, or the cold start)
+        if constexpr (!IMAGE) {
             const char* wp = w1s + w1o;
             const h8 A1 = *(const h8*)wp, A2 = *(const h8*)(wp + 256);
             h1gen(d, A1, A2, B1);
@@ -439,6 +520,12 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
         //   PH 2: next tile's attributes (8 loads) + x_j rows 0..15 (4 DMA)                        -> vmcnt(12)
         //   PH 3/4/5: x_j rows 16..31 / 32..47 / 48..63 (4 DMA each)                               -> vmcnt(4)
         //   PH 6: steady state                                                                     -> vmcnt(0)
+        // IMAGE (no edge ids, no attribute loads; the tile's LAST chunk is peeled too):
+        //   PH 0: this tile's source nodes, 4 segment-end nodes (5 loads)                          -> vmcnt(5)
+        //   PH 1: nothing                                                                          -> vmcnt(0)
+        //   PH 2: next tile's hi rows, lo rows, isc (3 DMA) + x_j rows 0..15 (4 DMA)               -> vmcnt(7)
+        //   PH 3/4/5, PH 6: as above (PH 3's wait retires the three image DMA)                     -> vmcnt(4), vmcnt(0)
+        //   PH 7: the last chunk: next tile's B1 from the staging area, its chunk-0 raw H1 and operands {0, 1} -> vmcnt(0)
         TM_MARK(tm_pro);
         auto chunk = [&](auto ph_tag, int c) {
             constexpr int PH = decltype(ph_tag)::value;
@@ -530,7 +617,9 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
                     // instructions went out).  The x_j row addresses (ds_bpermute of the source ids loaded two chunks earlier)
                     // go into gaps of the first half.
                     if constexpr (MODE == 0 && PH == 0) {
-                        if (n == 53) load_perm(e0n);
+                        if constexpr (!IMAGE) {
+                            if (n == 53) load_perm(e0n);
+                        }
                         if (n == 59) src_l = a.src[min(e0 + lane, e_clamp)];
                         if (n == 65) nf_v[0] = a.dst[min(e0, e_clamp)];
                         if (n == 71) nl_v[0] = a.dst[min(max(min(e0 + 32, eb) - 1, e0), e_clamp)];
@@ -539,8 +628,18 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
                     } else if constexpr (WRITE_H && PH == 0) {
                         if (n == 53) load_perm(e0n);
                     }
-                    if constexpr (PH == 2) {
+                    if constexpr (PH == 2 && IMAGE) {
+                        if (n == 29 || n == 35 || n == 41) img_issue((n - 29) / 6, e0n, ebn, Es_n);
+                    } else if constexpr (PH == 2) {
                         if (n >= 29 && n < 77 && (n - 29) % 6 == 0) load_attr_d((n - 29) / 6);
+                    }
+                    if constexpr (PH == 7) {
+                        // the next tile's B1: this tile's last reader of B1 was the H1 half behind n = 93 of the chunk before;
+                        // gaps that carry one conversion and nothing else
+                        if (n == 1) B1[0] = *(const h8*)b1p;
+                        if (n == 2) B1[1] = *(const h8*)(b1p + b1s);
+                        if (n == 4) B1[2] = *(const h8*)(b1p + 2 * b1s);
+                        if (n == 7) B1[3] = *(const h8*)(b1p + 3 * b1s);
                     }
                     if constexpr (!WRITE_H && PH >= 2 && PH <= 5) {
                         if (n == 1 || n == 7 || n == 13 || n == 19) x_addr1(4 * (PH - 2), (n - 1) / 6);
@@ -553,7 +652,8 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
                     __builtin_amdgcn_sched_barrier(0);
                     if (n == 45 || n == 93) {
                         // raw H1 of chunk c + 1, edge blocks {0, 1} / {2, 3}; at the last chunk this is chunk 0 with THIS
-                        // tile's attributes - unused, the next tile starts afresh
+                        // tile's attributes - unused, the next tile starts afresh (IMAGE, PH 7: with the NEXT tile's
+                        // attributes - the next tile's chunk-0 raw H1)
                         h1gen_half(d, n == 45 ? 0 : 2, A1, A2, B1);
                         __builtin_amdgcn_sched_barrier(0);
                     }
@@ -565,7 +665,9 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
             else if constexpr (WRITE_H && PH == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             else if constexpr (WRITE_H) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             else if constexpr (PH == 0 && NODEATTR) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
+            else if constexpr (PH == 0 && IMAGE) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
             else if constexpr (PH == 0) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            else if constexpr (PH == 2 && IMAGE) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
             else if constexpr (PH == 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
             else if constexpr (PH >= 3 && PH <= 5) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -582,8 +684,8 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
 #ifdef GPDE_V6_TIMING
         tm_peel += clock64() - tm0_;
 #endif
-        for (int c = 6; c < NKC; ++c) chunk(std::integral_constant<int, 6>{}, c);
-
+        for (int c = 6; c < (IMAGE ? NKC - 1 : NKC); ++c) chunk(std::integral_constant<int, 6>{}, c);
+        if constexpr (IMAGE) chunk(std::integral_constant<int, 7>{}, NKC - 1);
 
         TM_MARK(tm_loop);
         if constexpr (WRITE_H) {
@@ -707,6 +809,11 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
             for (int nb = 0; nb < 8; ++nb) asm volatile("" : "+a"(Z[cb][nb]));
         TM_MARK(tm_post);
         // ---- advance ---------------------------------------------------------------------------------------
+        if constexpr (IMAGE) {
+            float* es_t = Es;
+            Es = Es_n;
+            Es_n = es_t;
+        }
         if (last_in_blk) {
             have = have_n;
             blk_a = na_;
@@ -741,6 +848,8 @@ size_t v6_lds_bytes(int K1P) {
     return (size_t)NS * TILE_B + (size_t)K1P * 32 + (size_t)NW * TE * GP_W * 4 + (size_t)NW * TE * 4 + 64 +
            2 * GP_TN * 4;       // (+ 1 KiB: the per-column bias and un-scale factor of the slice, `colc`)
 }
+// the image variant: + a 2 KiB staging area and a second `Es` per wave
+size_t v6_image_lds_bytes(int K1P) { return v6_lds_bytes(K1P) + (size_t)NW * 2048 + (size_t)NW * TE * 4; }
 
 }  // namespace
 
@@ -762,20 +871,36 @@ bool gpde_fused_f16v6_supported(const GpdeFusedArgs& a) {
            (a.hout != nullptr || a.xs != nullptr);
 }
 
+// The image variant's shapes: the kernel's, with room for its staging areas (K1P up to 1152).  Wider ones keep the
+// per-tile prologue - the same kernel, not the 8-wave one
+bool gpde_fused_f16v6_image_supported(const GpdeFusedArgs& a) {
+    GpdeFusedArgs p = a;
+    if (!p.xs) p.xs = (const unsigned*)(uintptr_t)8;      // "will be present"
+    p.hout = nullptr;
+    return gpde_fused_f16v6_supported(p) && v6_image_lds_bytes(a.K1P) <= 160 * 1024;
+}
+
 int gpde_launch_fused_f16v6(const GpdeFusedArgs& a, hipStream_t stream) {
     const int ns = a.K2P / GP_TN;
     const dim3 grid(a.n_groups * ns), block(256);
     const size_t lds = v6_lds_bytes(a.K1P);
     static GpdeLdsOnce once;
-    if (int rc = once.ensure(gpde_fused_f16v6_kernel<0, false>, gpde_fused_f16v6_kernel<1, false>, gpde_fused_f16v6_kernel<0, true>,
-                             gpde_fused_f16v6_kernel<1, true>)) return rc;
+    if (int rc = once.ensure(gpde_fused_f16v6_kernel<0, ASRC_TENSOR>, gpde_fused_f16v6_kernel<1, ASRC_TENSOR>,
+                             gpde_fused_f16v6_kernel<0, ASRC_NODES>, gpde_fused_f16v6_kernel<1, ASRC_NODES>,
+                             gpde_fused_f16v6_kernel<0, ASRC_IMAGE>)) return rc;
     if (a.hout) {
         GpdeFusedArgs b = a;
         b.blk = nullptr; b.qn = nullptr; b.qctr = nullptr;             // rows are independent: static ranges
-        if (a.kt) hipLaunchKernelGGL((gpde_fused_f16v6_kernel<1, true>), grid, block, lds, stream, b);     // row f3 in training
-        else hipLaunchKernelGGL((gpde_fused_f16v6_kernel<1, false>), grid, block, lds, stream, b);
-    } else if (a.kt) hipLaunchKernelGGL((gpde_fused_f16v6_kernel<0, true>), grid, block, lds, stream, a);
-    else hipLaunchKernelGGL((gpde_fused_f16v6_kernel<0, false>), grid, block, lds, stream, a);
+        if (a.kt) hipLaunchKernelGGL((gpde_fused_f16v6_kernel<1, ASRC_NODES>), grid, block, lds, stream, b);     // row f3 in training
+        else hipLaunchKernelGGL((gpde_fused_f16v6_kernel<1, ASRC_TENSOR>), grid, block, lds, stream, b);
+    } else if (a.img_hi) {
+        if (!a.img_lo || !a.img_isc || !a.img_rec || !gpde_fused_f16v6_image_supported(a)) {
+            gpde_set_error("gpde_fused_f16v6_kernel: attribute image incomplete or K1P = %d beyond the image variant", a.K1P);
+            return GPDE_EINVAL;
+        }
+        hipLaunchKernelGGL((gpde_fused_f16v6_kernel<0, ASRC_IMAGE>), grid, block, v6_image_lds_bytes(a.K1P), stream, a);
+    } else if (a.kt) hipLaunchKernelGGL((gpde_fused_f16v6_kernel<0, ASRC_NODES>), grid, block, lds, stream, a);
+    else hipLaunchKernelGGL((gpde_fused_f16v6_kernel<0, ASRC_TENSOR>), grid, block, lds, stream, a);
     GP_LAUNCH_CHECK("gpde_fused_f16v6_kernel");
     return GPDE_OK;
 }

@@ -7,6 +7,8 @@
 //   k_absmax_x      scal[0] = max |x|            (atomicMax on the bit pattern; scal zeroed by memset)
 //   k_attr_bound    scal[1] = max_e sum_d max_k|W1b[k][d]| |attr_e[d]|   (bias slot d = k0 counts as 1)
 //   k_split_x       xs[i][c] = (lo16 << 16) | hi16 of x[i][c] * 2^sx,  hi = rtz16, lo = rn16(rest)
+// and, where the one-wave-per-SIMD kernel runs and the workspace has room (gpde_api.hip make_plan), once per call
+//   k_attr_image    per CSR slot the H1 MFMA's attribute operand (two f16 terms of the scaled slots) and the per-edge un-scale
 #include "gpde_common.h"
 
 namespace {
@@ -57,6 +59,59 @@ __global__ void k_attr_bound_nodes(const float* __restrict__ table, int kt, SelA
     if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(scal + 1, __float_as_uint(m));
 }
 
+// The attribute operand image of gpde_fused_f16v6_kernel: per CSR slot what that kernel's tile prologue forms from the
+// edge's attributes, with the same arithmetic in the same order - slots d < k0 the attribute, slot k0 the bias 1, the rest
+// 0; bnd = the fmaf chain over d = 0..7; the per-edge power-of-two scale and its reciprocal from bnd's exponent bits; the
+// scaled slots split into two f16 terms.  NODES: the attributes come from a node table (row f3), else through `perm`.
+typedef _Float16 h8v __attribute__((ext_vector_type(8)));
+template <bool NODES>
+__global__ void k_attr_image(const float* __restrict__ attr, const int32_t* __restrict__ perm, int kt, SelArr sel,
+                             const int32_t* __restrict__ src, const int32_t* __restrict__ dst, int64_t E, int k0,
+                             const float* __restrict__ wmax8, const float* __restrict__ fcol, h8v* __restrict__ hi8,
+                             h8v* __restrict__ lo8, float* __restrict__ isc_out, unsigned* __restrict__ rec) {
+    float wmx8[8], fcol8[8];
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+        wmx8[d] = wmax8[(d & 1) * 4 + (d >> 1)];
+        fcol8[d] = fcol[d];
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 5) rec[threadIdx.x] = threadIdx.x == 4 ? __float_as_uint(1.f) : 0u;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
+        float v[8];
+        if constexpr (NODES) {
+            const int s_ = src[e], t_ = dst[e];
+#pragma unroll
+            for (int d = 0; d < 8; ++d)
+                v[d] = d < k0 ? attr[(size_t)((sel.v[d] >> 8) ? t_ : s_) * kt + (sel.v[d] & 255)] : 0.f;
+        } else {
+            const size_t row = (size_t)perm[e] * k0;
+#pragma unroll
+            for (int d = 0; d < 8; ++d) v[d] = d < k0 ? attr[row + d] : 0.f;
+        }
+        float bnd = 0.f;
+#pragma unroll
+        for (int d = 0; d < 8; ++d) {
+            if (d == k0) v[d] = 1.f;
+            bnd = fmaf(wmx8[d], fabsf(v[d]), bnd);
+        }
+        const int ebits = (__float_as_int(bnd) >> 23) & 0xff;
+        const bool okb = (ebits >= 20) && (ebits <= 230);
+        const float sc = okb ? __int_as_float((267 - ebits) << 23) : 1.f;     // 2^(13 - E(B))
+        const float isc = okb ? __int_as_float((ebits - 13) << 23) : 1.f;
+        h8v hi, lo;
+#pragma unroll
+        for (int d = 0; d < 8; ++d) {
+            const float s_ = v[d] * fcol8[d] * sc;
+            const _Float16 h = (_Float16)s_;
+            hi[d] = h;
+            lo[d] = (_Float16)(s_ - (float)h);
+        }
+        hi8[e] = hi;
+        lo8[e] = lo;
+        isc_out[e] = isc;
+    }
+}
+
 __global__ void k_split_x(const float* __restrict__ x, size_t n, const unsigned* __restrict__ scal,
                           unsigned* __restrict__ xs) {
     const float sc = gpde_pow2_to_2p13(__uint_as_float(scal[0]));
@@ -102,6 +157,24 @@ int gpde_launch_block_bounds(const int32_t* rowptr, int nc0, int nc1, int nblk_m
     hipLaunchKernelGGL(k_block_bounds, dim3((threads + 255) / 256), dim3(256), 0, stream, rowptr, nc0, nc1, nblk_max, blk, qn,
                        qctr, n_slices);
     GP_LAUNCH_CHECK("k_block_bounds");
+    return GPDE_OK;
+}
+
+int gpde_launch_attr_image(const float* attr, const int32_t* perm, int64_t n_edges, int k0, const float* wmax8,
+                           const float* fcol, const GpdeAttrImage& img, hipStream_t stream, int kt, const int* sel,
+                           const int32_t* src, const int32_t* dst) {
+    if (k0 < 1 || k0 > 7 || (kt ? (!sel || !src || !dst) : !perm)) {
+        gpde_set_error("gpde_launch_attr_image: k0 = %d (1..7) or a missing attribute source", k0);
+        return GPDE_EINVAL;
+    }
+    const unsigned ge = (unsigned)((n_edges + 255) / 256 < 8192 ? (n_edges + 255) / 256 : 8192);
+    SelArr sa;
+    for (int d = 0; d < 8; ++d) sa.v[d] = kt ? sel[d] : 0;
+    if (kt) hipLaunchKernelGGL(k_attr_image<true>, dim3(ge ? ge : 1), dim3(256), 0, stream, attr, perm, kt, sa, src, dst, n_edges,
+                               k0, wmax8, fcol, (h8v*)img.hi, (h8v*)img.lo, img.isc, (unsigned*)img.rec);
+    else hipLaunchKernelGGL(k_attr_image<false>, dim3(ge ? ge : 1), dim3(256), 0, stream, attr, perm, kt, sa, src, dst, n_edges,
+                            k0, wmax8, fcol, (h8v*)img.hi, (h8v*)img.lo, img.isc, (unsigned*)img.rec);
+    GP_LAUNCH_CHECK("k_attr_image");
     return GPDE_OK;
 }
 

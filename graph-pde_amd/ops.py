@@ -699,8 +699,16 @@ _PRECISION = {"f32": _lib.GPDE_FWD_DEFAULT, "f16split": _lib.GPDE_FWD_F16SPLIT,
               "f16split_static": _lib.GPDE_FWD_F16SPLIT | _lib.GPDE_FWD_STATIC_RANGES,  # v6 with static per-wave ranges instead of the block queue
               "f16split_agg16": _lib.GPDE_FWD_F16SPLIT | _lib.GPDE_FWD_AGG_F16,  # aggregation on split f16 regardless of size
               "f16split_agg32": _lib.GPDE_FWD_F16SPLIT | _lib.GPDE_FWD_AGG_F32,  # aggregation on fp32 MFMA regardless of size
-              "f16split_noedge": _lib.GPDE_FWD_F16SPLIT | _lib.GPDE_FWD_NO_EDGE_PATH}  # never the per-edge last layer of low in-degree graphs
+              "f16split_noedge": _lib.GPDE_FWD_F16SPLIT | _lib.GPDE_FWD_NO_EDGE_PATH,  # never the per-edge last layer of low in-degree graphs
+              "f16split_noimage": _lib.GPDE_FWD_F16SPLIT | _lib.GPDE_FWD_NO_ATTR_IMAGE}  # v6 forms its attribute operands per tile, not from the per-call image
+# Names that choose no arithmetic of their own: "f16split_noimage" gives the bytes of "f16split" by construction (it only moves
+# where the kernel's attribute operands are formed).  It is accepted, and left out of the choices an error message offers.
+_SAME_BYTES_SWITCHES = ("f16split_noimage",)
 DEFAULT_PRECISION = os.environ.get("GPDE_PRECISION", "f16split")
+
+
+def _precision_choices() -> list:
+    return sorted(k for k in _PRECISION if k not in _SAME_BYTES_SWITCHES)
 # The per-edge last layer of low in-degree graphs forms W_e = W3 h_e on split-f16 operands (2^-22 of a block's
 # largest magnitude where fp32 carries 2^-24): each message carries ~4 x the reference's rounding, and a node that sums many of
 # them cancels it up.  Measured on the MI355X (mean in-degree <= 4, the in-edges gathered on a few destinations, no root / bias):
@@ -715,7 +723,7 @@ def _fwd_flags(csr: "Csr", precision: Optional[str]) -> int:
     has more than EDGE_PATH_MAX_IN_DEGREE in-edges."""
     name = DEFAULT_PRECISION if precision is None else precision
     if name not in _PRECISION:
-        raise ValueError(f"precision must be one of {sorted(_PRECISION)}, got {name!r}")
+        raise ValueError(f"precision must be one of {_precision_choices()}, got {name!r}")
     flags = _PRECISION[name]
     if precision is None and (flags & _lib.GPDE_FWD_F16SPLIT) and csr.n_edges > 0 and csr.max_in_degree > EDGE_PATH_MAX_IN_DEGREE:
         flags |= _lib.GPDE_FWD_NO_EDGE_PATH
@@ -1110,8 +1118,9 @@ def forward_route(csr: Csr, pm: PackedMlp, aggr: str = "mean", precision: Option
     """How NNConvFunction's forward of this graph runs (host-side queries, no device work): "association" is
     "per_edge" (per_edge_association) or "node" (the fused operator); for the latter "kernel" names the fused edge
     kernel, "edge_path" says whether the per-edge last layer of low in-degree graphs runs instead, "n_chunks" is
-    the node chunking of the plan for `ws_bytes` (default: the recommended workspace).  `precision` None: the default
-    precision with its routing (EDGE_PATH_MAX_IN_DEGREE), as nnconv_forward_raw applies it."""
+    the node chunking of the plan for `ws_bytes` (default: the recommended workspace), "attr_image" whether the fused
+    kernel reads the per-call attribute operand image.  `precision` None: the default precision with its routing
+    (EDGE_PATH_MAX_IN_DEGREE), as nnconv_forward_raw applies it."""
     if per_edge_association(csr, pm.dims, aggr):
         return {"association": "per_edge"}
     flags = _fwd_flags(csr, precision)
@@ -1121,8 +1130,12 @@ def forward_route(csr: Csr, pm: PackedMlp, aggr: str = "mean", precision: Option
     rc = _lib.lib().gpde_nnconv_fwd_edge_path(n, e, len(pm.dims) - 1, pm.dims_c, flags, ws_bytes)
     if rc < 0:
         _lib.check(rc, "gpde_nnconv_fwd_edge_path")
+    nch = ctypes.c_int32()
+    img = _lib.lib().gpde_nnconv_fwd_attr_image(n, e, len(pm.dims) - 1, pm.dims_c, flags, ws_bytes, ctypes.byref(nch))
+    if img < 0:
+        _lib.check(img, "gpde_nnconv_fwd_attr_image")
     return {"association": "node", "kernel": fused_kernel_name(n, e, pm, precision), "edge_path": rc == 1,
-            "n_chunks": launch_plan(n, e, pm, ws_bytes)["n_chunks"]}
+            "n_chunks": nch.value, "attr_image": img == 1}
 
 
 def launch_plan(n_nodes: int, n_edges: int, pm: PackedMlp, ws_bytes: int):
@@ -1132,8 +1145,9 @@ def launch_plan(n_nodes: int, n_edges: int, pm: PackedMlp, ws_bytes: int):
                                   ctypes.byref(nch), ctypes.byref(npc), ctypes.byref(wgs),
                                   ctypes.byref(mode))
     _lib.check(rc, "gpde_nnconv_fwd_plan")
+    img = lib.gpde_nnconv_fwd_attr_image(n_nodes, n_edges, len(pm.dims) - 1, pm.dims_c, _PRECISION[DEFAULT_PRECISION], ws_bytes, None)
     return {"n_chunks": nch.value, "nodes_per_chunk": npc.value, "fused_workgroups": wgs.value,
-            "mode": mode.value}
+            "mode": mode.value, "attr_image": img == 1}
 
 
 def fused_kernel_name(n_nodes: int, n_edges: int, pm: PackedMlp, precision: Optional[str] = None) -> str:
@@ -1315,7 +1329,7 @@ def hidden_forward_raw(csr: Csr, edge_attr: torch.Tensor, pm: PackedMlp,
     _require_cuda(edge_attr, "edge_attr")
     precision = DEFAULT_PRECISION if precision is None else precision
     if precision not in _PRECISION:
-        raise ValueError(f"precision must be one of {sorted(_PRECISION)}, got {precision!r}")
+        raise ValueError(f"precision must be one of {_precision_choices()}, got {precision!r}")
     e, dev, nl, flags = csr.n_edges, edge_attr.device, len(pm.dims) - 1, _PRECISION[precision]
     is_na = isinstance(edge_attr, NodeAttr)
     if not is_na and (edge_attr.dtype != torch.float32 or edge_attr.dim() != 2 or edge_attr.size(0) != e or

@@ -63,9 +63,12 @@ enum {
     GPDE_FWD_AGG_F16 = 16,       /* with F16SPLIT: aggregation x_j (x) h_e on split-f16 MFMA too, also for small
                                     graphs (default: from 32768 edges on; three tiny pre-pass launches) */
     GPDE_FWD_AGG_F32 = 32,       /* with F16SPLIT: keep the aggregation on fp32 MFMA (A/B) */
-    GPDE_FWD_NO_EDGE_PATH = 64   /* never take the per-edge last layer of low in-degree graphs (mean in-degree <= 4,
+    GPDE_FWD_NO_EDGE_PATH = 64,  /* never take the per-edge last layer of low in-degree graphs (mean in-degree <= 4,
                                   * >= 4096 edges, k2 >= 256: W_e = W3 . h_e on the split-f16 GEMM, contracted with x_j
                                   * in its epilogue) - A/B against the re-associated path */
+    GPDE_FWD_NO_ATTR_IMAGE = 128 /* gpde_fused_f16v6_kernel: form the attribute operands of the first hidden layer in every
+                                  * tile's prologue instead of reading the per-call attribute operand image (A/B, parity
+                                  * tests; same bytes out) */
 };
 
 #define GPDE_MAX_LAYERS 8
@@ -198,6 +201,13 @@ GPDE_API const char* gpde_nnconv_fwd_kernel(int64_t n_edges, int n_layers, const
  * it does not; < 0 (GpdeStatus) on invalid arguments or a workspace too small for the call.  Host only, no device work. */
 GPDE_API int gpde_nnconv_fwd_edge_path(int64_t n_nodes, int64_t n_edges, int n_layers, const int32_t* dims, uint32_t flags,
                                        size_t ws_bytes);
+
+/* 1 when that call runs gpde_fused_f16v6_kernel on the attribute operand image (36 bytes per edge of the workspace, built
+ * once per call: gpde_nnconv_fwd_workspace_bytes counts them wherever the default flags choose that kernel; a smaller
+ * workspace, GPDE_FWD_NO_ATTR_IMAGE or k1 above 1152 keep the operands in the kernel's tile prologue); 0 when it does
+ * not; < 0 as above.  `n_chunks` (nullable): the node chunks of the call's plan under these flags.  Host only. */
+GPDE_API int gpde_nnconv_fwd_attr_image(int64_t n_nodes, int64_t n_edges, int n_layers, const int32_t* dims, uint32_t flags,
+                                        size_t ws_bytes, int32_t* n_chunks);
 
 /* ---------------------------------------------------------------------------------------------
  * Backward of the fused NNConv (what autograd computes through nn_conv.py:267-282,

@@ -10,7 +10,10 @@
 #   phases  scripts/v6_timing.py g241 on the -DGPDE_V6_TIMING builds of both, where they exist next to the libraries
 #           (libgpde_T6base.so / libgpde_T6.so under scripts/ubench/lib/).
 # Arguments: the reference build and the build under test, relative to the repo root, the output directory (default: a
-# directory under TMPDIR) and the parts to run (default: all five).  Every step runs under its own time limit and the first
+# directory under TMPDIR) and the parts to run (default: all five).  A build is a library, run through this checkout's
+# Python (GPDE_LIB), or - where the two differ in their entry points - a directory that holds another checkout with its
+# own library built: then its own bench.py runs (phases: libgpde_T6base.so with that checkout's scripts/v6_timing.py).
+# Every step runs under its own time limit and the first
 # failure ends the job; nothing is tried twice.  scripts/pmc_summary.py reduces the counter tables.
 set -o pipefail
 BASE=${1:-scripts/ubench/lib/libgpde_base.so}
@@ -20,7 +23,9 @@ O=${3:-${TMPDIR:-/tmp}/fwd_kloop}
 PARTS=${4:-model bits ab pmc phases}
 case $O in /*) ;; *) O=$R/$O ;; esac
 mkdir -p $O
-B="python $R/bench.py --no-cpu-baseline --no-alt --no-mgkn --no-reuse-probe --no-backward-probe"
+BOPT="--no-cpu-baseline --no-alt --no-mgkn --no-reuse-probe --no-backward-probe"
+tree() { if [ -d $R/$1 ]; then echo $R/$1; else echo $R; fi; }                  # the checkout a build runs in
+libof() { if [ -d $R/$1 ]; then echo $R/$1/graph-pde_amd/libgpde.so; else echo $R/$1; fi; }
 has() { case " $PARTS " in *" $1 "*) return 0 ;; *) return 1 ;; esac; }
 
 if has model; then
@@ -32,7 +37,7 @@ if has bits; then
   : > $O/bits.txt
   dump() {      # tag, library, bench arguments...
     local tag=$1 lib=$2; shift 2
-    GPDE_LIB=$R/$lib timeout -k 10 400 $B --steps 2 --warmup 1 --dump-outputs $O/dump_$tag "$@" > $O/dump_$tag.log 2>&1 || return 1
+    GPDE_LIB=$(libof $lib) timeout -k 10 400 python $(tree $lib)/bench.py $BOPT --steps 2 --warmup 1 --dump-outputs $O/dump_$tag "$@" > $O/dump_$tag.log 2>&1 || return 1
   }
   same() {      # two dump directories: every array byte for byte
     python - $O/dump_$1 $O/dump_$2 <<'EOF' | tee -a $O/bits.txt
@@ -63,7 +68,7 @@ fi
 if has ab; then
   : > $O/ab.txt
   one() {
-    GPDE_LIB=$R/$1 timeout -k 10 240 $B --steps 6 --warmup 2 2>/dev/null | tail -1 > $O/_line.json || return 1
+    GPDE_LIB=$(libof $1) timeout -k 10 240 python $(tree $1)/bench.py $BOPT --steps 6 --warmup 2 2>/dev/null | tail -1 > $O/_line.json || return 1
     python -c "import json; d=json.load(open('$O/_line.json')); print('$1', d['value'], d['roofline']['frac'], d['roofline']['avg_launch_ms'], d['roofline']['kernel'])" | tee -a $O/ab.txt
   }
   for rep in 1 2 3; do
@@ -85,7 +90,7 @@ if has pmc; then
   cd /tmp && export TMPDIR=/tmp
   pmc() {      # tag, library, counters...
     local tag=$1 lib=$2; shift 2
-    GPDE_LIB=$R/$lib timeout -k 10 300 rocprofv3 --output-format csv --pmc "$@" --kernel-trace -d $O/pmc_$tag -o run -- $B --steps 2 --warmup 1 > $O/pmc_$tag.log 2>&1 || return 1
+    GPDE_LIB=$(libof $lib) timeout -k 10 300 rocprofv3 --output-format csv --pmc "$@" --kernel-trace -d $O/pmc_$tag -o run -- python $(tree $lib)/bench.py $BOPT --steps 2 --warmup 1 > $O/pmc_$tag.log 2>&1 || return 1
   }
   pmc clock_base $BASE GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES || exit 1
   pmc clock_new $NEW GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES || exit 1
@@ -97,8 +102,9 @@ fi
 
 if has phases; then
   for t in T6base T6; do
+    T=$R; [ $t = T6base ] && T=$(tree $BASE)
     if [ -f $R/scripts/ubench/lib/libgpde_$t.so ]; then
-      GPDE_LIB=$R/scripts/ubench/lib/libgpde_$t.so timeout -k 10 400 python scripts/v6_timing.py g241 2>/dev/null | sed "s/^/$t: /" | tee -a $O/phases.txt || exit 1
+      GPDE_LIB=$R/scripts/ubench/lib/libgpde_$t.so timeout -k 10 400 python $T/scripts/v6_timing.py g241 2>/dev/null | sed "s/^/$t: /" | tee -a $O/phases.txt || exit 1
     fi
   done
 fi
