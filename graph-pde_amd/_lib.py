@@ -22,6 +22,7 @@ GPDE_WECONV_MAX_GROUP = 16
 GPDE_WECONV_ANY_MAX_WIDTH = 256      # include/gpde.h: widths of the gpde_nnconv_*_edgeweights_any entry points
 GPDE_REASSOC_ANY_MAX_HIDDEN = 4096    # include/gpde.h: last hidden width of the gpde_nnconv_*_hidden_any entry points
 GPDE_RADIUS_BATCHED_REC_BYTES = 96    # include/gpde.h: one graph's record of the gpde_radius_csr_batched_* table
+GPDE_KNN_BATCHED_REC_BYTES = 128      # include/gpde.h: one graph's record of the gpde_knn_csr_batched table
 GPDE_FWD_DEFAULT, GPDE_FWD_F16SPLIT = 0, 1
 # the other forward flags of include/gpde.h (A/B switches; tests/test_abi.py checks these values against the header)
 GPDE_FWD_F16SPLIT_8WAVE, GPDE_FWD_STATIC_RANGES, GPDE_FWD_AGG_F16, GPDE_FWD_AGG_F32, GPDE_FWD_NO_EDGE_PATH = 2, 4, 16, 32, 64

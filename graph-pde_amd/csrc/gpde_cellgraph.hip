@@ -375,20 +375,34 @@ int check(const char* what, const double* ps, int64_t ns, const double* pd, int6
 // The open cell list on its own (gpde_cells.h): what gpde_radius_csr_count does before its walk, for gpde_knn.hip.
 size_t gpde_cell_list_ws_bytes(int64_t n_src, int64_t ncells) { return carve(nullptr, n_src, ncells).total + 256; }
 
-int gpde_cell_list_build(const char* what, const double* pos_src, int64_t n_src, const CellGrid& g, int64_t ncells, void* ws,
-                         size_t ws_bytes, hipStream_t st, GpdeCellList* out) {
+int gpde_cell_list_slots(const char* what, int64_t n_src, int64_t ncells, void* ws, size_t ws_bytes, GpdeCellSlots* out) {
+    CellWs w = carve(ws, n_src, ncells);
+    if (ws_bytes < w.total) { gpde_set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, w.total); return GPDE_EWORKSPACE; }
+    out->cell = w.cell;
+    out->id = w.id;
+    return GPDE_OK;
+}
+
+int gpde_cell_list_finish(const char* what, int64_t n_src, int64_t ncells, void* ws, size_t ws_bytes, hipStream_t st, GpdeCellList* out) {
     CellWs w = carve(ws, n_src, ncells);
     if (ws_bytes < w.total) { gpde_set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, w.total); return GPDE_EWORKSPACE; }
     const int T = 256;
-    if (n_src > 0) {
-        hipLaunchKernelGGL(k_cell_ids, dim3((unsigned)((n_src + T - 1) / T)), dim3(T), 0, st, pos_src, (int)n_src, g, w.cell, w.id);
+    if (n_src > 0)
         GP_HIP_CHECK(rocprim::radix_sort_pairs(w.temp, w.temp_bytes, w.cell, w.cell_sorted, w.id, w.order, (size_t)n_src, 0,
                                                sort_bits_for(ncells), st));
-    }
     hipLaunchKernelGGL(k_cell_start, dim3((unsigned)((ncells + 1 + T - 1) / T)), dim3(T), 0, st, w.cell_sorted, (int)n_src, (int)ncells, w.start);
     out->start = w.start;
     out->order = w.order;
     return GPDE_OK;
+}
+
+int gpde_cell_list_build(const char* what, const double* pos_src, int64_t n_src, const CellGrid& g, int64_t ncells, void* ws,
+                         size_t ws_bytes, hipStream_t st, GpdeCellList* out) {
+    GpdeCellSlots s;
+    if (int rc = gpde_cell_list_slots(what, n_src, ncells, ws, ws_bytes, &s)) return rc;
+    if (n_src > 0)
+        hipLaunchKernelGGL(k_cell_ids, dim3((unsigned)((n_src + 255) / 256)), dim3(256), 0, st, pos_src, (int)n_src, g, s.cell, s.id);
+    return gpde_cell_list_finish(what, n_src, ncells, ws, ws_bytes, st, out);
 }
 
 extern "C" size_t gpde_radius_csr_workspace_bytes(int64_t n_src, int dim, double r, const double* lo, const double* hi) {
@@ -778,6 +792,10 @@ int check_batched_call(const char* what, const double* ps, int64_t ns, const dou
 }
 
 }  // namespace
+
+int gpde_batch_check_ptr(const char* what, const char* name, const int64_t* ptr, int64_t n_graphs, int64_t n) {
+    return check_ptr(what, name, ptr, n_graphs, n);
+}
 
 // HOST ONLY.  bounds [B][2][dim] (lo then hi of graph b; not read for a graph without sources), ptr_src / ptr_dst [B + 1]
 // (ptr_dst NULL: one point set), r [B].  table (nullable: a query) receives B records.

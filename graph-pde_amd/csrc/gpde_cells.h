@@ -44,6 +44,37 @@ __device__ __forceinline__ void sort_row_by_source(uint32_t* row, int n_row, int
         }
 }
 
+// One wave's exchange through LDS: its LDS operations execute in order, a compiler fence is all the lanes need between them.
+__device__ __forceinline__ void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// ascending bitonic sort of np2 (a power of two >= 64) pairs by (key, id): the k-best buffer of the nearest-neighbour arms
+__device__ __forceinline__ void sort_pairs(int64_t* key, uint32_t* id, int np2, int lane) {
+    wave_lds_fence();
+    for (int k = 2; k <= np2; k <<= 1)
+        for (int jj = k >> 1; jj > 0; jj >>= 1) {
+            for (int t = lane; t < np2; t += 64) {
+                const int p = t ^ jj;
+                if (p > t) {
+                    const int64_t ka = key[t], kb = key[p];
+                    const uint32_t ia = id[t], ib = id[p];
+                    const bool up = (t & k) == 0;
+                    const bool a_after_b = ka > kb || (ka == kb && ia > ib);
+                    if (a_after_b == up) { key[t] = kb; key[p] = ka; id[t] = ib; id[p] = ia; }
+                }
+            }
+            wave_lds_fence();
+        }
+}
+
+// What the nearest-neighbour arms (gpde_knn.hip, gpde_knn_arms.hip) share on the host: the limits of a grid and the automatic
+// cell edge (defined in gpde_knn.hip).
+constexpr int KNN_NC_MAX = 1 << 16;                     // cells per axis: bounds the ring loop
+constexpr int64_t KNN_CELLS_MAX = (int64_t)1 << 24;     // cells in all (the cap of the other builders)
+double knn_auto_cell(int dim, int64_t n_src, int k, const double* lo, const double* hi);
+
 // The cell list of `n_src` points in grid `g` (ncells = nc[0] nc[1] nc[2] <= 2^24), built on `st` inside `ws`
 // (gpde_cell_list_ws_bytes; no allocation, no synchronisation): the members of cell c = (cz nc[1] + cy) nc[0] + cx are
 // order[start[c] .. start[c + 1]), ascending point id inside a cell.  Defined in gpde_cellgraph.hip.
@@ -54,3 +85,11 @@ struct GpdeCellList {
 size_t gpde_cell_list_ws_bytes(int64_t n_src, int64_t ncells);
 int gpde_cell_list_build(const char* what, const double* pos_src, int64_t n_src, const CellGrid& g, int64_t ncells, void* ws,
                          size_t ws_bytes, hipStream_t st, GpdeCellList* out);
+// The same in two steps, for a caller that bins by a rule of its own (a batch's per-graph grids, reduced periodic
+// coordinates): _slots carves `ws` and hands out cell[n_src] / id[n_src] for the caller's kernel to fill on `st` (id[j] = j);
+// _finish sorts them by cell and writes the first position of every cell.
+struct GpdeCellSlots { uint32_t* cell; uint32_t* id; };
+int gpde_cell_list_slots(const char* what, int64_t n_src, int64_t ncells, void* ws, size_t ws_bytes, GpdeCellSlots* out);
+int gpde_cell_list_finish(const char* what, int64_t n_src, int64_t ncells, void* ws, size_t ws_bytes, hipStream_t st, GpdeCellList* out);
+// ptr[0] = 0 <= ptr[1] <= ... <= ptr[B] = n <= 2^31 - 1 (n < 0: the end is not compared): the rule of every batched builder
+int gpde_batch_check_ptr(const char* what, const char* name, const int64_t* ptr, int64_t n_graphs, int64_t n);

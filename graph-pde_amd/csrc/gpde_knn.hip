@@ -33,40 +33,33 @@
 
 #pragma clang fp contract(off)      // the key is defined by where it rounds
 
-namespace {
+// The automatic cell edge: the mean occupancy of a cell is m = max(2, k / 2) sources, so that the k nearest of a destination in a
+// uniform cloud lie within about one ring.  The cloud's dimension is taken from its box: with the extents sorted descending,
+// h = max over d' = 1 .. dim of (m e_1 .. e_d' / n_src)^(1 / d') - a flat or line-like box gets the spacing of the axes that
+// have extent, not a fine grid across the thin ones.  A box without extent: h = 1 (one cell).
+double knn_auto_cell(int dim, int64_t n_src, int k, const double* lo, const double* hi) {
+    double e[3] = {0.0, 0.0, 0.0};
+    for (int a = 0; a < dim; ++a) e[a] = hi[a] - lo[a];
+    for (int a = 0; a < 3; ++a)
+        for (int b = a + 1; b < 3; ++b)
+            if (e[b] > e[a]) { const double t = e[a]; e[a] = e[b]; e[b] = t; }
+    const double m = k / 2 > 2 ? (double)(k / 2) : 2.0, n = n_src > 0 ? (double)n_src : 1.0;
+    double h = 0.0, prod = 1.0;
+    for (int d = 1; d <= dim; ++d) {
+        prod *= e[d - 1];
+        const double c = pow(m * prod / n, 1.0 / d);
+        if (c > h && isfinite(c)) h = c;
+    }
+    return h > 0.0 && isfinite(1.0 / h) ? h : 1.0;
+}
 
-constexpr int KNN_NC_MAX = 1 << 16;                     // cells per axis: bounds the ring loop
-constexpr int64_t KNN_CELLS_MAX = (int64_t)1 << 24;     // cells in all (the cap of the other builders)
+namespace {
 
 struct KnnGrid {
     CellGrid cells;
     double h;                   // cell edge; cells.inv = 1 / h
     double mag[3];              // |lo| + (nc + 1) h per axis: the slack of the stopping rule, before the destination's share
 };
-
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// ascending bitonic sort of np2 (a power of two >= 64) pairs by (key, id)
-__device__ __forceinline__ void sort_pairs(int64_t* key, uint32_t* id, int np2, int lane) {
-    wave_lds_fence();
-    for (int k = 2; k <= np2; k <<= 1)
-        for (int jj = k >> 1; jj > 0; jj >>= 1) {
-            for (int t = lane; t < np2; t += 64) {
-                const int p = t ^ jj;
-                if (p > t) {
-                    const int64_t ka = key[t], kb = key[p];
-                    const uint32_t ia = id[t], ib = id[p];
-                    const bool up = (t & k) == 0;
-                    const bool a_after_b = ka > kb || (ka == kb && ia > ib);
-                    if (a_after_b == up) { key[t] = kb; key[p] = ka; id[t] = ib; id[p] = ia; }
-                }
-            }
-            wave_lds_fence();
-        }
-}
 
 __global__ __launch_bounds__(256) void k_knn_rowptr(int32_t* __restrict__ rowptr, int n_dst, int k_eff) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -233,26 +226,6 @@ struct KnnPlan {
     int skip_self;
     int cap;                    // pairs per wave in LDS
 };
-
-// The automatic cell edge: the mean occupancy of a cell is m = max(2, k / 2) sources, so that the k nearest of a destination in a
-// uniform cloud lie within about one ring.  The cloud's dimension is taken from its box: with the extents sorted descending,
-// h = max over d' = 1 .. dim of (m e_1 .. e_d' / n_src)^(1 / d') - a flat or line-like box gets the spacing of the axes that
-// have extent, not a fine grid across the thin ones.  A box without extent: h = 1 (one cell).
-double knn_auto_cell(int dim, int64_t n_src, int k, const double* lo, const double* hi) {
-    double e[3] = {0.0, 0.0, 0.0};
-    for (int a = 0; a < dim; ++a) e[a] = hi[a] - lo[a];
-    for (int a = 0; a < 3; ++a)
-        for (int b = a + 1; b < 3; ++b)
-            if (e[b] > e[a]) { const double t = e[a]; e[a] = e[b]; e[b] = t; }
-    const double m = k / 2 > 2 ? (double)(k / 2) : 2.0, n = n_src > 0 ? (double)n_src : 1.0;
-    double h = 0.0, prod = 1.0;
-    for (int d = 1; d <= dim; ++d) {
-        prod *= e[d - 1];
-        const double c = pow(m * prod / n, 1.0 / d);
-        if (c > h && isfinite(c)) h = c;
-    }
-    return h > 0.0 && isfinite(1.0 / h) ? h : 1.0;
-}
 
 // Every refusal the scalars and the host arrays show, then the grid.
 int knn_plan(const char* what, int64_t n_src, int64_t n_dst, int dim, int64_t k, int loop, int same_set, double cell, const double* lo,

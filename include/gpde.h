@@ -774,6 +774,64 @@ GPDE_API int gpde_knn_csr(const double* pos_src, int64_t n_src, const double* po
                  int loop, double cell, const double* lo, const double* hi, int32_t* rowptr, int32_t* src, int32_t* dst,
                  float* geom, void* ws, size_t ws_bytes, void* stream);
 
+/* The nearest-neighbour builder for a BATCH of independent point sets (gpde_knn_arms.hip): the block-diagonal destination CSR of
+ * B kNN graphs in one build - what a DataLoader makes of per-sample knn graphs - without one build per sample.  Graph b owns the
+ * sources ptr_src[b] .. ptr_src[b + 1] and the destinations ptr_dst[b] .. ptr_dst[b + 1] of the concatenated float64 position
+ * arrays; node ids in rowptr / src / dst are GLOBAL.  ptr_dst = NULL, or pos_dst == pos_src with n_dst == n_src (then ptr_dst must
+ * repeat ptr_src), is ONE point set per graph.
+ *   k_eff[b]  min(k, ns_b); with loop = 0 (one point set: the pair of equal id is excluded) min(k, ns_b - 1), never negative: a
+ *             graph with destinations but no usable source has empty rows.  loop = 0 with two point sets is refused (pass 1);
+ *   slots     edge_ptr[b + 1] = edge_ptr[b] + nd_b k_eff[b]; row i of graph b starts at rowptr[i] = edge_ptr[b] + (i - ptr_dst[b])
+ *             k_eff[b].  All of it is host arithmetic on the ptr arrays: n_edges = edge_ptr[B] is known before anything runs (the
+ *             plan returns it) and the call writes rowptr itself;
+ *   result    rowptr / src / dst / geom are the per-graph gpde_knn_csr results concatenated with their offsets, BIT FOR BIT: keys
+ *             and ties are the open arm's, evaluated inside the destination's own graph - a source of another graph is never a
+ *             candidate, however the graphs overlap in space.  No atomics; two calls give identical bits.
+ *   gpde_knn_csr_batched_plan   HOST ONLY, no device call.  bounds [B][2][dim]: lo then hi of a box of graph b (not read for a
+ *       graph without sources, which gets one cell, as does a graph of coincident points); `cell`: every graph's cell edge, 0 =
+ *       automatic per graph (the open arm's rule with that graph's ns_b and box).  Writes B records of
+ *       GPDE_KNN_BATCHED_REC_BYTES bytes into the host array `table` (NULL: a query) and returns the summed cell count, the
+ *       workspace bytes and n_edges.  The summed cell count is held to 2^24 by doubling every graph's cell edge: the grid
+ *       changes the speed, never the result.
+ *   gpde_knn_csr_batched   `table`: the planned records in a DEVICE buffer (the caller uploads them); n_cells, n_edges: what the
+ *       plan returned; ptr_src / ptr_dst the HOST arrays again.  Launches on `stream`; never synchronises, never allocates.  The
+ *       LDS buffer of a wave is sized by max_b k_eff[b].
+ * Before any device call: GPDE_EUNSUPPORTED for dim outside 1..3; GPDE_EINVAL for k outside 1 .. GPDE_KNN_MAX_K, loop not 0 or 1,
+ * a bad cell, n_graphs < 0, a ptr array that is NULL, does not start at 0, decreases or does not end at the point count, a box
+ * of a graph with sources that is empty or not finite, NULL arguments, n_edges that is not the plan's or lies outside the int32
+ * CSR; GPDE_EWORKSPACE for a short workspace.  n_graphs = 0 and zero points are valid calls.  GPDE_VERSION is unchanged. */
+enum { GPDE_KNN_BATCHED_REC_BYTES = 128 };
+GPDE_API int gpde_knn_csr_batched_plan(const double* bounds, const int64_t* ptr_src, const int64_t* ptr_dst, int64_t n_graphs, int dim,
+                              int64_t k, int loop, double cell, void* table, int64_t* n_cells, size_t* ws_bytes, int64_t* n_edges);
+GPDE_API int gpde_knn_csr_batched(const double* pos_src, int64_t n_src, const double* pos_dst, int64_t n_dst, int dim, int64_t k,
+                         int loop, const int64_t* ptr_src, const int64_t* ptr_dst, int64_t n_graphs, const void* table,
+                         int64_t n_cells, int32_t* rowptr, int32_t* src, int32_t* dst, float* geom, int64_t n_edges, void* ws,
+                         size_t ws_bytes, void* stream);
+
+/* The nearest-neighbour builder on a TORUS (gpde_knn_arms.hip): gpde_knn_csr with the minimum-image distance.  period / origin:
+ * HOST arrays [dim] (origin NULL: 0).  period[a] > 0: axis a wraps with that length; period[a] == 0: an open axis.  Points
+ * anywhere on the real line are legal on a periodic axis.  origin only anchors the cell grid: the graph does not depend on it.
+ *   key       the int64 bit pattern of the float64 squared distance in the periodic arithmetic of gpde_edge_keys_sqdist: on a
+ *             periodic axis d = pos_src[j][a] - pos_dst[i][a], d -= L rint(d / L) on the RAW coordinates (half to even); on an
+ *             open axis the plain difference; squares summed in axis order, contraction off.  Ties go to the smaller source id.
+ *             Every source is a candidate once, at its minimum image: a row never holds a source twice;
+ *   k_eff, rowptr, rows, loop   as gpde_knn_csr.  There is no 2 r < period precondition: k may reach every source on the torus.
+ * That is gpde_csr_select_k on the complete bipartite graph under gpde_edge_keys_sqdist(period) keys - a pure function of the
+ * positions, k, loop and period: not of origin, the cell edge, lo / hi or call history.
+ *   geom      nullable; float32 [n_edges][dim + 1]: the per-axis d of the key (source minus target, on an open axis
+ *             pos_src - pos_dst) and sqrt of their squares' sum, float64 rounded once.  NOT the arithmetic of
+ *             gpde_radius_csr_periodic_fill, which reduces both points into the box first and is undefined at separations of
+ *             period / 2 and beyond; the two agree up to their last bits where both exist;
+ *   lo / hi   read on OPEN axes only (NULL when every axis is periodic); cell: as gpde_knn_csr - a periodic axis is tiled by
+ *             floor(period / cell) cells.
+ * Refusals as gpde_knn_csr, and GPDE_EINVAL for a NULL period, a negative or non-finite period (or one without a finite
+ * reciprocal) and a non-finite origin.  Never synchronises, never allocates.  GPDE_VERSION is unchanged. */
+GPDE_API size_t gpde_knn_csr_periodic_workspace_bytes(int64_t n_src, int64_t n_dst, int dim, int64_t k, double cell, const double* lo,
+                                             const double* hi, const double* origin, const double* period);
+GPDE_API int gpde_knn_csr_periodic(const double* pos_src, int64_t n_src, const double* pos_dst, int64_t n_dst, int dim, int64_t k,
+                          int loop, double cell, const double* lo, const double* hi, const double* origin, const double* period,
+                          int32_t* rowptr, int32_t* src, int32_t* dst, float* geom, void* ws, size_t ws_bytes, void* stream);
+
 /* SAMPLED GRAPHS: the reference's second connectivity, gaussian_connectivity (graph-neural-operator utilities.py:257-263,
  * 372-378; multipole-graph-neural-operator utilities.py:283-289, 419-425), built natively as the destination CSR (the sampled
  * arm of gpde_cellgraph.hip).  The edge j -> i (j in pos_src, i in pos_dst; level-local ids) is kept iff
