@@ -496,6 +496,47 @@ class HiddenAnyFunction(torch.autograd.Function):
         return gxs, gxd, (gh if need[2] else None), gwl, gbl, None, groot, gbias, None
 
 
+class ChainAnyFunction(torch.autograd.Function):
+    """The STREAMED any-width operator (gpde_nnconv_fwd_chain_any / gpde_nnconv_bwd_chain_any): from the edge attributes and the
+    weights of a Linear / ReLU chain, the hidden rows generated by block of destination nodes - neither [E, K] nor [E, in * out]
+    is formed, in either direction.  Differentiable in x_src, x_dst, edge_attr, root, bias and every weight and bias of the chain.
+    `x_dst`: as WeConvAnyFunction takes it.  `edge_attr` [E, k0] comes in the CALLER's edge order and its gradient goes back in
+    that order.  Only the inputs are saved: the backward recomputes every activation block by block.
+    `params`: the chain's weights, then its biases (None for a Linear without one)."""
+
+    @staticmethod
+    def forward(ctx, x_src, x_dst, edge_attr, csr, root, bias, aggr, *params):
+        root = _root_term(x_dst, root)
+        nl = len(params) // 2
+        ctx.one, ctx.has_dst, ctx.nl = x_dst is ops._ONE_SET, torch.is_tensor(x_dst), nl
+        ctx.identity = bool(getattr(csr, "_perm_is_identity", False))
+        ea = edge_attr.detach().float().contiguous()
+        ea_s = ea if ctx.identity or csr.n_edges == 0 else ops.gather_rows(ea, csr.perm)
+        xd = ops._ONE_SET if ctx.one else x_dst.detach() if ctx.has_dst else None
+        out = ops.nnconv_forward_chain_any_raw(x_src.detach(), xd, csr, ea_s, params[:nl], params[nl:], root, bias, aggr)
+        ctx.csr, ctx.aggr, ctx.has_bias, ctx.has_root = csr, aggr, bias is not None, root is not None
+        ctx.save_for_backward(x_src, x_dst if ctx.has_dst else None, edge_attr, root, *params)
+        return out
+
+    @staticmethod
+    @once_differentiable        # the native backward is not itself differentiable: create_graph=True raises
+    def backward(ctx, grad_out):
+        x_src, x_dst, edge_attr, root, *params = ctx.saved_tensors
+        need, nl, csr = ctx.needs_input_grad, ctx.nl, ctx.csr
+        ea = edge_attr.detach().float().contiguous()
+        ea_s = ea if ctx.identity or csr.n_edges == 0 else ops.gather_rows(ea, csr.perm)
+        xd = ops._ONE_SET if ctx.one else x_dst if ctx.has_dst else None
+        gxs, gxd, gea, gw, gb, groot, gbias = ops.nnconv_backward_chain_any_raw(
+            x_src, xd, csr, ea_s, params[:nl], params[nl:], root, ctx.aggr, grad_out, need_x_src=need[0], need_x_dst=ctx.has_dst and need[1],
+            need_w=list(need[7:7 + nl]), need_b=[params[nl + l] is not None and need[7 + nl + l] for l in range(nl)],
+            need_root=ctx.has_root and need[4], need_bias=ctx.has_bias and need[5], need_edge_attr=need[2])
+        if gea is not None and not ctx.identity:            # slot order -> the caller's edge order (an edge the CSR dropped: 0)
+            gea = torch.zeros(edge_attr.shape, dtype=gea.dtype, device=gea.device).index_copy_(0, csr.perm.long(), gea)
+        if gea is not None:
+            gea = gea.to(edge_attr.dtype)
+        return (gxs, gxd, gea, None, groot, gbias, None, *gw, *gb)
+
+
 class GCNFunction(torch.autograd.Function):
     """GCNConv: out = (A x) W + bias, A = the normalised adjacency of an `ops.GcnNorm` (gpde_gcn_fwd), differentiable in x, W and
     bias.  With G = A^T grad_out (one launch of the aggregation kernel on the reversed graph): grad_x = G W^T, grad_W = x^T G

@@ -439,3 +439,31 @@ int gpde_launch_any_dx_finish(const float* dxe, const int32_t* src_rowptr, const
                               float* dx, int64_t n_nodes, int cin, int cout, int ordered, hipStream_t stream);
 int gpde_launch_any_node_grads(const float* x, const float* g, float* part, int64_t n_nodes, int cin, int cout, float* droot,
                                float* dbias, hipStream_t stream);
+
+// The re-associated any-width operator BY NODE BLOCK (gpde_reassoc_any.hip), shared with gpde_chain_any.hip, which generates the
+// hidden rows of a block of destinations just before it runs these on the block.  `hidden` is the address row 0 (CSR slot 0) would
+// have: the kernels index it by global slot, so a caller holding the rows from slot e0 on passes `buffer - e0 * K`.
+struct GpdeRaShape {
+    int cin, cout, coutP, K, KP, splits;
+    size_t zrow;           // floats of one node's Z'
+    size_t p_bytes;        // P (and dP)
+};
+GpdeRaShape gpde_ra_shape(int cin, int cout, int K);
+size_t gpde_ra_fwd_per_node(const GpdeRaShape& s);          // Z' and the split-K partials of one node
+size_t gpde_ra_bwd_per_node(const GpdeRaShape& s);          // dZ', Z' and g of one node
+int64_t gpde_ra_pref_block(const GpdeRaShape& s, int64_t n_nodes);
+int gpde_ra_check(const char* who, int cin, int in_dst, int cout, int K, int aggr);
+int gpde_ra_permute(const GpdeRaShape& s, const float* w_last, const float* b_last, float* P, hipStream_t st);
+int gpde_ra_unpermute(const GpdeRaShape& s, const float* dP, float* grad_w_last, float* grad_b_last, hipStream_t st);
+// forward of the destinations [na, na + nb): Z [nb][zrow], part [splits][nb][cout]
+int gpde_ra_fwd_block(const GpdeRaShape& s, const float* x_src, const float* x_dst, const float* hidden, const int32_t* rowptr,
+                      const int32_t* src, const float* P, const float* root, const float* bias, int aggr, int in_dst, float* out, float* Z,
+                      float* part, int na, int nb, hipStream_t st);
+// backward of the destinations [na, na + nb): dZ, Z [nb][zrow], gs [nb][coutP]; dP nullable; dxe [E][cin] by global slot, nullable
+int gpde_ra_bwd_block(const GpdeRaShape& s, const float* x_src, const float* hidden, const int32_t* rowptr, const int32_t* src, const float* P,
+                      int aggr, const float* grad_out, float* dZ, float* Z, float* gs, float* dP, int dp_accumulate, float* grad_hidden,
+                      float* dxe, int na, int nb, hipStream_t st);
+// grad_x_src / grad_x_dst / grad_root / grad_bias once every block has written its dxe rows (dxe NULL: a call without edges)
+int gpde_ra_bwd_node_side(const float* x_dst, int64_t n_src, int64_t n_nodes, const float* dxe, const int32_t* src_rowptr,
+                          const int32_t* src_slots, const float* root, const float* grad_out, float* grad_x_src, float* grad_x_dst,
+                          float* grad_root, float* grad_bias, float* ngp, int cin, int cind, int cout, bool square, hipStream_t st);

@@ -237,11 +237,7 @@ __global__ __launch_bounds__(256) void k_ra_epilogue(const float* __restrict__ p
     out[(size_t)i * cout + o] = t;
 }
 
-struct RaShape {
-    int cin, cout, coutP, K, KP, splits;
-    size_t zrow;           // floats of one node's Z'
-    size_t p_bytes;        // P (and dP)
-};
+using RaShape = GpdeRaShape;     // (gpde_common.h: gpde_chain_any.hip sizes its node blocks with it)
 
 RaShape ra_shape(int cin, int cout, int K) {
     RaShape s{};
@@ -330,6 +326,85 @@ inline char* ra_base(void* ws) { return (char*)(((uintptr_t)ws + 255) / 256 * 25
 
 namespace {
 
+// One block of destination nodes [na, na + nb) of the forward: Z' of the block, out = Z' . P, the epilogue
+int ra_fwd_block(const RaShape& s, const float* x_src, const float* x_dst, const float* hidden, const int32_t* rowptr, const int32_t* src,
+                 const float* P, const float* root, const float* bias, int aggr, int in_dst, float* out, float* Z, float* part, int na, int nb,
+                 hipStream_t st) {
+    const int cout = s.cout;
+    int rc = ra_launch_zagg(s, x_src, hidden, rowptr, src, Z, na, nb, st);
+    if (rc != GPDE_OK) return rc;
+    GpdeGemmArgs g = ra_gemm(Z, P, part, nb, cout, (int)s.zrow, (int)s.zrow, s.coutP, cout, 1, 0);     // NN: Z' . P
+    g.splits = s.splits;
+    g.strideSplit = (size_t)nb * cout;
+    rc = gpde_launch_gemm(g, st);
+    if (rc != GPDE_OK) return rc;
+    const size_t n = (size_t)nb * cout;
+    hipLaunchKernelGGL(k_ra_epilogue, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, s.splits, (size_t)nb * cout, x_dst, rowptr,
+                       root, bias, out, na, nb, in_dst, cout, aggr);
+    GP_LAUNCH_CHECK("k_ra_epilogue");
+    return GPDE_OK;
+}
+
+// One block of destination nodes of the backward: g of the block, dZ' = g . P^T, dP (+)= Z'^T . g (dP NULL: skipped), then dH and the
+// per-edge dx rows of the block's in-edges
+int ra_bwd_block(const RaShape& s, const float* x_src, const float* hidden, const int32_t* rowptr, const int32_t* src, const float* P,
+                 int aggr, const float* grad_out, float* dZ, float* Z, float* gs, float* dP, int dp_accumulate, float* grad_hidden, float* dxe,
+                 int na, int nb, hipStream_t st) {
+    const int cin = s.cin, cout = s.cout;
+    const size_t ng = (size_t)nb * s.coutP;
+    hipLaunchKernelGGL(k_ra_scale_g, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, st, grad_out, rowptr, gs, na, nb, cout, s.coutP, aggr);
+    GP_LAUNCH_CHECK("k_ra_scale_g");
+    // NT: dZ' = g . P^T
+    int rc = gpde_launch_gemm(ra_gemm(gs, P, dZ, nb, (int)s.zrow, s.coutP, s.coutP, s.coutP, (int)s.zrow, 1, 1), st);
+    if (rc != GPDE_OK) return rc;
+    if (dP) {                                                    // TN: dP (+)= Z'^T . g, Z' of the block recomputed
+        rc = ra_launch_zagg(s, x_src, hidden, rowptr, src, Z, na, nb, st);
+        if (rc != GPDE_OK) return rc;
+        GpdeGemmArgs g = ra_gemm(Z, gs, dP, (int)s.zrow, cout, nb, (int)s.zrow, s.coutP, s.coutP, 0, 0);
+        g.accumulate = dp_accumulate;
+        rc = gpde_launch_gemm(g, st);
+        if (rc != GPDE_OK) return rc;
+    }
+    hipLaunchKernelGGL(gpde_reassoc_edge_bwd_kernel, dim3((unsigned)nb, RB_SEGS), dim3(256), 0, st, x_src, hidden, rowptr, src, dZ, grad_hidden,
+                       dxe, na, cin, s.K, s.KP);
+    GP_LAUNCH_CHECK("gpde_reassoc_edge_bwd_kernel");
+    return GPDE_OK;
+}
+
+// The node-side gradients of both backwards.  With edges: grad_x_src from the per-edge rows `dxe` (ordered), on one node set with the
+// root term in the same launch.  Without (`dxe` NULL): the root term alone.  grad_root / grad_bias through `ngp`.
+int ra_bwd_node_side(const float* x_dst, int64_t n_src, int64_t n_nodes, const float* dxe, const int32_t* src_rowptr, const int32_t* src_slots,
+                     const float* root, const float* grad_out, float* grad_x_src, float* grad_x_dst, float* grad_root, float* grad_bias,
+                     float* ngp, int cin, int cind, int cout, bool square, hipStream_t st) {
+    int rc;
+    if (square) {
+        if (grad_x_src) {
+            if (!dxe) GP_HIP_CHECK(gpde_zero_async(grad_x_src, (size_t)n_nodes * cin * 4, st));          // the root term alone, added to 0
+            rc = gpde_launch_any_dx_finish(dxe, dxe ? src_rowptr : nullptr, dxe ? src_slots : nullptr, root, grad_out, grad_x_src, n_nodes, cin,
+                                           cout, dxe ? 1 : 0, st);
+            if (rc != GPDE_OK) return rc;
+        }
+    } else {
+        if (grad_x_src && !dxe && n_src > 0) GP_HIP_CHECK(gpde_zero_async(grad_x_src, (size_t)n_src * cin * 4, st));
+        if (grad_x_src && dxe) {                                 // the sources: the sum over their out-edges, no root term
+            rc = gpde_launch_any_dx_finish(dxe, src_rowptr, src_slots, nullptr, nullptr, grad_x_src, n_src, cin, cout, 1, st);
+            if (rc != GPDE_OK) return rc;
+        }
+        if (grad_x_dst) {                                        // the destinations: g . root^T
+            if (!root) GP_HIP_CHECK(gpde_zero_async(grad_x_dst, (size_t)n_nodes * cind * 4, st));
+            else {
+                rc = gpde_launch_any_dx_finish(nullptr, nullptr, nullptr, root, grad_out, grad_x_dst, n_nodes, cind, cout, 2, st);
+                if (rc != GPDE_OK) return rc;
+            }
+        }
+    }
+    if (grad_root || grad_bias) {
+        rc = gpde_launch_any_node_grads(x_dst, grad_out, ngp, n_nodes, cind, cout, grad_root, grad_bias, st);
+        if (rc != GPDE_OK) return rc;
+    }
+    return GPDE_OK;
+}
+
 // Both forwards after their argument checks.  x_src [n_src][cin] is gathered by `src`; x_dst [n_dst][cind] (nullable with root
 // == NULL) enters the epilogue's root term only; the node blocks walk the n_dst destinations.  A square call hands x twice.
 int ra_fwd_run(const char* who, const float* x_src, const float* x_dst, int64_t n_nodes, const float* hidden, int64_t n_edges, int k_hidden,
@@ -361,17 +436,8 @@ int ra_fwd_run(const char* who, const float* x_src, const float* x_dst, int64_t 
     if (rc != GPDE_OK) return rc;
     for (int64_t na = 0; na < n_nodes; na += blk) {
         const int nb = (int)(n_nodes - na < blk ? n_nodes - na : blk);
-        rc = ra_launch_zagg(s, x_src, hidden, rowptr, src, Z, (int)na, nb, st);
+        rc = ra_fwd_block(s, x_src, x_dst, hidden, rowptr, src, P, root, bias, aggr, in_dst, out, Z, part, (int)na, nb, st);
         if (rc != GPDE_OK) return rc;
-        GpdeGemmArgs g = ra_gemm(Z, P, part, nb, cout, (int)s.zrow, (int)s.zrow, s.coutP, cout, 1, 0);     // NN: Z' . P
-        g.splits = s.splits;
-        g.strideSplit = (size_t)nb * cout;
-        rc = gpde_launch_gemm(g, st);
-        if (rc != GPDE_OK) return rc;
-        const size_t n = (size_t)nb * cout;
-        hipLaunchKernelGGL(k_ra_epilogue, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, s.splits, (size_t)nb * cout, x_dst, rowptr,
-                           root, bias, out, (int)na, nb, in_dst, cout, aggr);
-        GP_LAUNCH_CHECK("k_ra_epilogue");
     }
     return GPDE_OK;
 }
@@ -388,31 +454,14 @@ int ra_bwd_run(const char* who, const float* x_src, int64_t n_src, const float* 
     const RaShape s = ra_shape(in_channels, out_channels, k_hidden);
     const int cin = s.cin, cout = s.cout, cind = in_dst;
     if (n_edges == 0) {                                          // no edge: the node-side terms alone; only grad_root / grad_bias use the workspace
-        if (square) {
-            if (grad_x_src) {
-                GP_HIP_CHECK(gpde_zero_async(grad_x_src, (size_t)n_nodes * cin * 4, st));          // the root term alone, added to 0
-                rc = gpde_launch_any_dx_finish(nullptr, nullptr, nullptr, root, grad_out, grad_x_src, n_nodes, cin, cout, 0, st);
-                if (rc != GPDE_OK) return rc;
-            }
-        } else {
-            if (grad_x_src && n_src > 0) GP_HIP_CHECK(gpde_zero_async(grad_x_src, (size_t)n_src * cin * 4, st));
-            if (grad_x_dst) {
-                if (!root) GP_HIP_CHECK(gpde_zero_async(grad_x_dst, (size_t)n_nodes * cind * 4, st));
-                else {
-                    rc = gpde_launch_any_dx_finish(nullptr, nullptr, nullptr, root, grad_out, grad_x_dst, n_nodes, cind, cout, 2, st);
-                    if (rc != GPDE_OK) return rc;
-                }
-            }
-        }
         if (grad_root || grad_bias) {
             if (!ws || ws_bytes < gpde_any_node_grads_ws_bytes(cind, cout) + 256) {
                 gpde_set_error("%s: grad_root / grad_bias need %zu bytes of workspace", who, gpde_any_node_grads_ws_bytes(cind, cout) + 256);
                 return GPDE_EINVAL;
             }
-            rc = gpde_launch_any_node_grads(x_dst, grad_out, (float*)ra_base(ws), n_nodes, cind, cout, grad_root, grad_bias, st);
-            if (rc != GPDE_OK) return rc;
         }
-        return GPDE_OK;
+        return ra_bwd_node_side(x_dst, n_src, n_nodes, nullptr, nullptr, nullptr, root, grad_out, grad_x_src, grad_x_dst, grad_root, grad_bias,
+                                (grad_root || grad_bias) ? (float*)ra_base(ws) : nullptr, cin, cind, cout, square, st);
     }
     if (ws_bytes < ra_bwd_fixed(s, n_edges, cind) + ra_bwd_per_node(s)) {
         gpde_set_error("%s: workspace of %zu bytes holds less than one node's Z' and dZ' (%zu bytes needed; %zu preferred)", who, ws_bytes,
@@ -437,24 +486,9 @@ int ra_bwd_run(const char* who, const float* x_src, int64_t n_src, const float* 
         if (rc != GPDE_OK) return rc;
         for (int64_t na = 0; na < n_nodes; na += blk) {
             const int nb = (int)(n_nodes - na < blk ? n_nodes - na : blk);
-            const size_t ng = (size_t)nb * s.coutP;
-            hipLaunchKernelGGL(k_ra_scale_g, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, st, grad_out, rowptr, gs, (int)na, nb, cout,
-                               s.coutP, aggr);
-            GP_LAUNCH_CHECK("k_ra_scale_g");
-            // NT: dZ' = g . P^T
-            rc = gpde_launch_gemm(ra_gemm(gs, P, dZ, nb, (int)s.zrow, s.coutP, s.coutP, s.coutP, (int)s.zrow, 1, 1), st);
+            rc = ra_bwd_block(s, x_src, hidden, rowptr, src, P, aggr, grad_out, dZ, Z, gs, want_dp ? dP : (float*)nullptr, na > 0 ? 1 : 0,
+                              grad_hidden, grad_x_src ? dxe : (float*)nullptr, (int)na, nb, st);
             if (rc != GPDE_OK) return rc;
-            if (want_dp) {                                       // TN: dP (+)= Z'^T . g, Z' of the block recomputed
-                rc = ra_launch_zagg(s, x_src, hidden, rowptr, src, Z, (int)na, nb, st);
-                if (rc != GPDE_OK) return rc;
-                GpdeGemmArgs g = ra_gemm(Z, gs, dP, (int)s.zrow, cout, nb, (int)s.zrow, s.coutP, s.coutP, 0, 0);
-                g.accumulate = na > 0 ? 1 : 0;
-                rc = gpde_launch_gemm(g, st);
-                if (rc != GPDE_OK) return rc;
-            }
-            hipLaunchKernelGGL(gpde_reassoc_edge_bwd_kernel, dim3((unsigned)nb, RB_SEGS), dim3(256), 0, st, x_src, hidden, rowptr, src, dZ,
-                               grad_hidden, grad_x_src ? dxe : (float*)nullptr, (int)na, cin, s.K, s.KP);
-            GP_LAUNCH_CHECK("gpde_reassoc_edge_bwd_kernel");
         }
         if (want_dp) {
             hipLaunchKernelGGL(k_ra_unpermute, dim3((s.KP + 31) / 32, (s.coutP + 31) / 32, cin), dim3(256), 0, st, dP, grad_w_last,
@@ -462,29 +496,8 @@ int ra_bwd_run(const char* who, const float* x_src, int64_t n_src, const float* 
             GP_LAUNCH_CHECK("k_ra_unpermute");
         }
     }
-    if (square) {
-        if (grad_x_src) {
-            rc = gpde_launch_any_dx_finish(dxe, src_rowptr, src_slots, root, grad_out, grad_x_src, n_nodes, cin, cout, 1, st);
-            if (rc != GPDE_OK) return rc;
-        }
-    } else {
-        if (grad_x_src) {                                        // the sources: the sum over their out-edges, no root term
-            rc = gpde_launch_any_dx_finish(dxe, src_rowptr, src_slots, nullptr, nullptr, grad_x_src, n_src, cin, cout, 1, st);
-            if (rc != GPDE_OK) return rc;
-        }
-        if (grad_x_dst) {                                        // the destinations: g . root^T
-            if (!root) GP_HIP_CHECK(gpde_zero_async(grad_x_dst, (size_t)n_nodes * cind * 4, st));
-            else {
-                rc = gpde_launch_any_dx_finish(nullptr, nullptr, nullptr, root, grad_out, grad_x_dst, n_nodes, cind, cout, 2, st);
-                if (rc != GPDE_OK) return rc;
-            }
-        }
-    }
-    if (grad_root || grad_bias) {
-        rc = gpde_launch_any_node_grads(x_dst, grad_out, ngp, n_nodes, cind, cout, grad_root, grad_bias, st);
-        if (rc != GPDE_OK) return rc;
-    }
-    return GPDE_OK;
+    return ra_bwd_node_side(x_dst, n_src, n_nodes, dxe, src_rowptr, src_slots, root, grad_out, grad_x_src, grad_x_dst, grad_root, grad_bias, ngp,
+                            cin, cind, cout, square, st);
 }
 
 int ra_check_in_dst(const char* who, int in_dst) {
@@ -641,4 +654,39 @@ extern "C" int gpde_nnconv_bwd_hidden_bip(const float* x_src, int64_t n_src, con
     return ra_bwd_run(who, x_src, n_src, x_dst, n_dst, hidden, n_edges, k_hidden, rowptr, src, w_last, b_last, root, aggr, in_src, in_dst,
                       out_channels, grad_out, grad_x_src, grad_x_dst, grad_hidden, grad_w_last, grad_b_last, grad_root, grad_bias, src_rowptr,
                       src_slots, ws, ws_bytes, false, st);
+}
+
+// ---- the node-block halves above for gpde_chain_any.hip (declared in gpde_common.h), which generates `hidden` block by block ----
+GpdeRaShape gpde_ra_shape(int cin, int cout, int K) { return ra_shape(cin, cout, K); }
+size_t gpde_ra_fwd_per_node(const GpdeRaShape& s) { return ra_fwd_per_node(s); }
+size_t gpde_ra_bwd_per_node(const GpdeRaShape& s) { return ra_bwd_per_node(s); }
+int64_t gpde_ra_pref_block(const GpdeRaShape& s, int64_t n_nodes) { return ra_pref_block(s, n_nodes); }
+int gpde_ra_check(const char* who, int cin, int in_dst, int cout, int K, int aggr) {
+    const int rc = ra_check(who, cin, cout, K, aggr);
+    return rc != GPDE_OK ? rc : ra_check_in_dst(who, in_dst);
+}
+int gpde_ra_permute(const GpdeRaShape& s, const float* w_last, const float* b_last, float* P, hipStream_t st) {
+    return ra_launch_permute(s, w_last, b_last, P, st);
+}
+int gpde_ra_unpermute(const GpdeRaShape& s, const float* dP, float* grad_w_last, float* grad_b_last, hipStream_t st) {
+    hipLaunchKernelGGL(k_ra_unpermute, dim3((s.KP + 31) / 32, (s.coutP + 31) / 32, s.cin), dim3(256), 0, st, dP, grad_w_last, grad_b_last, s.cout,
+                       s.coutP, s.K, s.KP);
+    GP_LAUNCH_CHECK("k_ra_unpermute");
+    return GPDE_OK;
+}
+int gpde_ra_fwd_block(const GpdeRaShape& s, const float* x_src, const float* x_dst, const float* hidden, const int32_t* rowptr,
+                      const int32_t* src, const float* P, const float* root, const float* bias, int aggr, int in_dst, float* out, float* Z,
+                      float* part, int na, int nb, hipStream_t st) {
+    return ra_fwd_block(s, x_src, x_dst, hidden, rowptr, src, P, root, bias, aggr, in_dst, out, Z, part, na, nb, st);
+}
+int gpde_ra_bwd_block(const GpdeRaShape& s, const float* x_src, const float* hidden, const int32_t* rowptr, const int32_t* src, const float* P,
+                      int aggr, const float* grad_out, float* dZ, float* Z, float* gs, float* dP, int dp_accumulate, float* grad_hidden,
+                      float* dxe, int na, int nb, hipStream_t st) {
+    return ra_bwd_block(s, x_src, hidden, rowptr, src, P, aggr, grad_out, dZ, Z, gs, dP, dp_accumulate, grad_hidden, dxe, na, nb, st);
+}
+int gpde_ra_bwd_node_side(const float* x_dst, int64_t n_src, int64_t n_nodes, const float* dxe, const int32_t* src_rowptr,
+                          const int32_t* src_slots, const float* root, const float* grad_out, float* grad_x_src, float* grad_x_dst,
+                          float* grad_root, float* grad_bias, float* ngp, int cin, int cind, int cout, bool square, hipStream_t st) {
+    return ra_bwd_node_side(x_dst, n_src, n_nodes, dxe, src_rowptr, src_slots, root, grad_out, grad_x_src, grad_x_dst, grad_root, grad_bias, ngp,
+                            cin, cind, cout, square, st);
 }

@@ -23,7 +23,7 @@ from torch.nn import Parameter
 
 from . import hidden_cache, ops
 from . import autograd as _ag
-from .autograd import (HiddenAnyFunction, NNConvDeferredFunction, NNConvFunction, NNConvHiddenFunction, SharedParamFunction, WeConvAnyFunction,
+from .autograd import (ChainAnyFunction, HiddenAnyFunction, NNConvDeferredFunction, NNConvFunction, NNConvHiddenFunction, SharedParamFunction, WeConvAnyFunction,
                        WeConvFunction)
 from .message_passing import MessagePassing
 
@@ -419,7 +419,8 @@ class NNConv_old(MessagePassing):
         the route of `_propagate_general_nn` at run-time widths, on ONE node set.  This front validates, builds the square CSR and
         decides the route (ops.any_width_route states the rule: the per-edge weights materialised as in the reference, or - a
         Linear / ReLU chain under add / mean that does not fit, GPDE_ANY_REASSOC=auto, or every such call, =on - the last Linear
-        re-associated); `_any_width_operator` runs it.  `residual` / `relu`: fused into the kernel's epilogue; callers pass them
+        re-associated; =streamed: every such call from the edge attributes, hidden rows by node block); `_any_width_operator` runs
+        it.  `residual` / `relu`: fused into the kernel's epilogue; callers pass them
         only when no gradient is needed.  aggr='max': the native kernel when no gradient is needed, else PyG's chain over the
         native `message()` / `update()`, as at 64."""
         self._check_width()
@@ -450,7 +451,7 @@ class NNConv_old(MessagePassing):
             raise RuntimeError(f"{self!r}: at widths other than {ops.WIDTH} -> {ops.WIDTH} the per-edge weights are materialised as in the reference "
                                f"(nn_conv.py:274) - {csr.n_edges} edges x {cin} x {cout} x 4 B = {route['bytes_materialised'] / 2**30:.2f} GiB "
                                f"(twice that with gradients), {free / 2**30:.2f} GiB free{other}")
-        return self._any_width_operator(x, ops._ONE_SET, csr, pseudo, route["route"] == "reassociated", lin, dev, needs_grad, residual, relu)
+        return self._any_width_operator(x, ops._ONE_SET, csr, pseudo, route["route"], lin, dev, needs_grad, residual, relu)
 
     def _any_width_route(self, csr, dev):
         """(ops.any_width_route of a call on `csr`, the Linear layers of `nn` when it is a Linear / ReLU chain - else None -, the free
@@ -459,9 +460,14 @@ class NNConv_old(MessagePassing):
         free, _ = ops.device_free_bytes(dev)
         lin = ops.mlp_linears(self.nn) if self._nn_is_linear_relu_chain() else None
         chain = lin is not None and lin[-1].out_features == cin * cout
-        return ops.any_width_route(csr.n_nodes, csr.n_edges, cin, cout, lin[-1].in_features if chain else None, self.aggr, chain, free), lin, free
+        dims = [lin[0].in_features] + [l.out_features for l in lin] if chain else None
+        args = (csr.n_nodes, csr.n_edges, cin, cout, lin[-1].in_features if chain else None, self.aggr, chain, free)
+        route = ops.any_width_route(*args)
+        if route["route"] == "streamed" and not ops.chain_any_supported(dims):       # a chain the library does not generate: as under `off`
+            route = ops.any_width_route(*args, mode="off")
+        return route, lin, free
 
-    def _any_width_operator(self, x_src, x_dst, csr, pseudo, reassociated, lin, dev, needs_grad, residual, relu):
+    def _any_width_operator(self, x_src, x_dst, csr, pseudo, route, lin, dev, needs_grad, residual, relu):
         """The operator of `_propagate_any_width` (`x_dst` ops._ONE_SET) and of `_propagate_rect` (`x_dst` a tensor or None) once the
         route is decided - a call on one node set is the two-set call that hands one table twice.  Rows of `pseudo` in CSR slot
         order, where the module lives; parameters and CPU tensors staged to `dev` (`.to()` is differentiable), the result back on
@@ -472,16 +478,25 @@ class NNConv_old(MessagePassing):
         Re-associated (`lin`: a Linear / ReLU chain, add / mean): H = relu(L_{n-1}(... pseudo)) [E, K] by torch, then aggregation, the
         LAST Linear per destination and update() as ONE native call (gpde_nnconv_fwd_hidden_any / _bip; dL/dH flows on through the
         earlier layers by autograd).
+        Streamed (GPDE_ANY_REASSOC=streamed; the same chains): `pseudo` and the chain's weights go to ONE native call that generates
+        the hidden rows by block of destination nodes (gpde_nnconv_fwd_chain_any; its backward recomputes them and differentiates the
+        whole chain) - no per-edge tensor wider than `pseudo` exists.
         `residual` [n_dst, out] / `relu`: the kernel's epilogue on the materialised call without a gradient, torch ops otherwise."""
         one = x_dst is ops._ONE_SET
         cin, cout = int(self._in_src()), int(self.out_channels)
-        pseudo_s = _slot_rows(csr, pseudo)              # (`nn` acts row by row, batch statistics are order-free)
+        reassociated = route == "reassociated"
+        pseudo_s = None if route == "streamed" else _slot_rows(csr, pseudo)      # (`nn` acts row by row, batch statistics are order-free)
         on_dev = lambda t: _on_dev(t, dev, needs_grad)
         root, bias = (None if x_dst is None else on_dev(self.root)), on_dev(self.bias)      # PyG: no x_dst, no root term
         xs_d = x_src.to(dev) if needs_grad else x_src.detach().to(dev)
         xd_d = x_dst if not torch.is_tensor(x_dst) else x_dst.to(dev) if needs_grad else x_dst.detach().to(dev)
         fused = False
-        if reassociated:
+        if route == "streamed":
+            # (.float(): as on the re-associated route, a float64 kernel network runs with float32 x)
+            params = [on_dev(l.weight).float() for l in lin] + [None if l.bias is None else on_dev(l.bias).float() for l in lin]
+            ea = pseudo.to(dev) if needs_grad and pseudo.requires_grad else pseudo.detach().to(dev)
+            out = ChainAnyFunction.apply(xs_d, xd_d, ea, csr, root, bias, self.aggr, *params)      # (no graph when nothing needs one)
+        elif reassociated:
             h = pseudo_s
             for l in lin[:-1]:
                 h = torch.relu(torch.nn.functional.linear(h, l.weight, l.bias))
@@ -551,7 +566,7 @@ class NNConv_old(MessagePassing):
             raise RuntimeError(f"{self!r}: a call between two node sets materialises the per-edge weights as the reference does (nn_conv.py:274) - "
                                f"{csr.n_edges} edges x {cin} x {cout} x 4 B = {route['bytes_materialised'] / 2**30:.2f} GiB (twice that with "
                                f"gradients), {free / 2**30:.2f} GiB free (GPDE_ANY_REASSOC={ops.ANY_REASSOC})")
-        return self._any_width_operator(x_src, x_dst, csr, pseudo, route["route"] == "reassociated", lin, dev, needs_grad, residual, relu)
+        return self._any_width_operator(x_src, x_dst, csr, pseudo, route["route"], lin, dev, needs_grad, residual, relu)
 
     def _propagate(self, x, edge_index, pseudo, weights, biases, root, bias, use_hidden_cache):
         """propagate() of the reference (gather, message, aggregate, update) as ONE native operator on device

@@ -113,6 +113,7 @@ class Csr:
     _flow_flipped: bool = False              # built from edge_index with its rows swapped (flow='target_to_source' of the module)
     _src_order_tag: Optional[StreamTag] = None   # where src_order was built (order_hit)
     _identity_tag: Optional[StreamTag] = None    # where _identity was built (attr_in_slot_order)
+    _chain_blocks: Optional[dict] = None         # block tables of the streamed any-width route (chain_any_blocks), host only
 
     @property
     def n_src(self) -> int:
@@ -1532,10 +1533,12 @@ def any_width_plan(in_channels: int, out_channels: int, aligned: bool = True, ag
 # ... re-associated at any width (include/gpde.h gpde_nnconv_fwd_hidden_any / gpde_nnconv_bwd_hidden_any; csrc/gpde_reassoc_any.hip):
 # the last hidden activations [E, K] instead of the per-edge weights [E, in * out]
 ANY_MAX_HIDDEN = _lib.GPDE_REASSOC_ANY_MAX_HIDDEN
-ANY_REASSOC = os.environ.get("GPDE_ANY_REASSOC", "auto")      # auto | on | off: which any-width calls take the re-associated route
+ANY_REASSOC = os.environ.get("GPDE_ANY_REASSOC", "auto")      # auto | on | off | streamed: which any-width calls take the re-associated route
 _ANY_PREF_Z_BYTES = 512 << 20        # Z' of the library's preferred node block (RA_PREF_Z_BYTES of gpde_reassoc_any.hip; tests/test_reassoc_host.py
 #                                      holds the two together through the workspace query)
 ANY_WS_FRACTION = 0.5                # a call of the re-associated route takes at most this share of the free memory as workspace
+CHAIN_ANY_MIN_LINEAR, CHAIN_ANY_MAX_LINEAR, CHAIN_ANY_MAX_K0 = 2, 5, 64      # the chains gpde_chain_any.hip generates
+CHAIN_ANY_PREF_BUDGET = 256 << 20    # per-edge buffers of one node block of the streamed route, when the free memory allows
 
 
 def _hidden_any_ws_bytes(query, n: int, e: int, cin: int, cout: int, k: int, dev) -> int:
@@ -1548,8 +1551,18 @@ def _hidden_any_ws_bytes(query, n: int, e: int, cin: int, cout: int, k: int, dev
     return max(one, min(pref, int(free * ANY_WS_FRACTION)))
 
 
+def chain_any_supported(dims) -> bool:
+    """Whether a Linear / ReLU chain of widths `dims` = [k0, K_1, .., K_{n-1}, in * out] is one the streamed route generates
+    (gpde_nnconv_*_chain_any: 2 .. 5 Linears, 1 <= k0 <= 64, hidden widths 1 .. ANY_MAX_HIDDEN)."""
+    if dims is None:
+        return False
+    dims = [int(v) for v in dims]
+    return CHAIN_ANY_MIN_LINEAR <= len(dims) - 1 <= CHAIN_ANY_MAX_LINEAR and 1 <= dims[0] <= CHAIN_ANY_MAX_K0 and \
+        all(1 <= v <= ANY_MAX_HIDDEN for v in dims[1:-1])
+
+
 def any_width_route(n_nodes: int, n_edges: int, in_channels: int, out_channels: int, k_hidden: Optional[int], aggr: str, chain: bool,
-                    free_bytes: int, mode: Optional[str] = None) -> dict:
+                    free_bytes: int, mode: Optional[str] = None, dims=None) -> dict:
     """Which route a call of a module whose widths are not (64, 64) takes.  Host arithmetic only.
 
     `materialised`: the reference's order, `nn(pseudo)` as [E, in * out] (E in out 4 bytes; the last Linear costs 2 E K in out
@@ -1562,16 +1575,20 @@ def any_width_route(n_nodes: int, n_edges: int, in_channels: int, out_channels: 
         off    materialised, or refused when it does not fit           (the behaviour before the re-associated kernels)
         auto   materialised whenever it fits - exactly the calls of `off`; only a call that `off` refuses takes the re-associated
                route, if it is eligible and fits; else refused
-        on     every eligible call is re-associated (refused when it does not fit); the others as `off`"""
+        on     every eligible call is re-associated (refused when it does not fit); the others as `off`
+        streamed   every eligible call whose chain `dims` the library generates (chain_any_supported; `dims` None: the caller checks its
+               chain itself and asks again with mode="off" for one that is not, as NNConv_old does) runs from the edge attributes,
+               hidden rows by node block (gpde_nnconv_*_chain_any: neither per-edge tensor is formed; `bytes_streamed` is what the
+               route holds besides one block of its budget); the others as `off`"""
     mode = ANY_REASSOC if mode is None else mode
-    if mode not in ("auto", "on", "off"):
+    if mode not in ("auto", "on", "off", "streamed"):
         raise ValueError(f"GPDE_ANY_REASSOC must be auto, on or off, got {mode!r}")
     n, e, cin, cout = int(n_nodes), int(n_edges), int(in_channels), int(out_channels)
     k = None if k_hidden is None else int(k_hidden)
     eligible = bool(chain) and aggr in ("add", "mean") and k is not None and 1 <= k <= ANY_MAX_HIDDEN
     bytes_m = e * cin * cout * 4
     out = {"eligible": eligible, "bytes_materialised": bytes_m, "bytes_reassociated": None, "node_block": None,
-           "flops_materialised": None if k is None else 2 * e * k * cin * cout, "flops_reassociated": None}
+           "flops_materialised": None if k is None else 2 * e * k * cin * cout, "flops_reassociated": None, "bytes_streamed": None}
     fits_m = 2 * bytes_m <= free_bytes
     fits_r = False
     if eligible:
@@ -1581,6 +1598,12 @@ def any_width_route(n_nodes: int, n_edges: int, in_channels: int, out_channels: 
         out["bytes_reassociated"] = e * k * 4 + block * zrow
         out["flops_reassociated"] = 2 * e * cin * k + 2 * n * cin * k * cout
         fits_r = 2 * out["bytes_reassociated"] <= free_bytes
+    if eligible and (dims is None or chain_any_supported(dims)):          # (`dims` not given: the caller checks its chain)
+        # what the streamed route holds whatever its block budget: the per-edge dx rows, the last Linear permuted and its gradient
+        out["bytes_streamed"] = e * cin * 4 + 2 * zrow * ((cout + 3) // 4 * 4)
+        if mode == "streamed":
+            out["route"] = "streamed"
+            return out
     if mode == "on" and eligible:
         out["route"] = "reassociated" if fits_r else "refused"
     elif fits_m:
@@ -2937,3 +2960,9 @@ def diagconv_backward_raw(x_src, x_dst, csr: Csr, edge_kernel, root, aggr: str, 
     _lib.check(rc, "gpde_diagconv_bwd")
     _lib.n_native_calls += 1
     return gxs, (gxd if need_x_dst else None), gk, groot, gbias
+
+
+# ... streamed (include/gpde.h gpde_nnconv_*_chain_any; csrc/gpde_chain_any.hip): the route's block tables and its two wrappers live in
+# chain_any.py and are reached through this module like every other entry point (imported last: chain_any.py uses the helpers above)
+from .chain_any import (ChainBlocks, chain_any_blocks, chain_any_table, nnconv_backward_chain_any_raw,      # noqa: E402,F401
+                        nnconv_forward_chain_any_raw)

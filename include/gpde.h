@@ -579,6 +579,56 @@ GPDE_API int gpde_nnconv_bwd_hidden_bip(const float* x_src, int64_t n_src, const
                                float* grad_root, float* grad_bias, const int32_t* src_rowptr, const int32_t* src_slots,
                                void* ws, size_t ws_bytes, void* stream);
 
+/* The re-associated any-width operator FROM THE EDGE ATTRIBUTES (gpde_chain_any.hip): the operator of the "hidden form" above with
+ * `hidden` replaced by its definition for a Linear / ReLU chain of n_linear = 2 .. 5 Linears,
+ *     hidden = relu(L_{n-1}(... relu(L_1(edge_attr)) ...)),     dims = [k0, K_1, .., K_{n-1}, in_src * out]     (n_linear + 1 entries)
+ *   1 <= k0 <= 64, 1 <= K_l <= GPDE_REASSOC_ANY_MAX_HIDDEN, widths and aggr as the hidden form (add / mean).  The hidden rows are
+ *   generated BY BLOCK OF CONSECUTIVE DESTINATIONS and never exist for more than one block: no caller-side tensor is [E][K] or
+ *   [E][in * out].  One entry point serves one node set (`square` != 0: x_src is the table of the root term too, x_dst / n_src /
+ *   in_dst / grad_x_dst are ignored, grad_x_src holds both terms in one ordered sum) and two (`square` == 0: the `_bip` rules).
+ *   edge_attr [E][k0] and grad_edge_attr [E][k0]: rows in CSR SLOT order (the convention `hidden` has above).
+ *   weights / biases: HOST arrays of n_linear device pointers in torch's layouts (W_l [K_l][K_{l-1}], b_l [K_l]; `biases` or any
+ *   entry of it may be NULL: no bias); grad_w / grad_b likewise (the array or any entry NULL: that gradient is not formed).
+ * The block table.  The hidden rows of the block of destinations [a, b) are the CSR slots rowptr[a] .. rowptr[b]; the host must know
+ *   that count to size buffers and grids and the library never synchronises, so the table is a HOST argument: block_nodes holds
+ *   n_blocks + 1 pairs (first node, first slot) - pair b opens block b, the last pair is (n_dst, n_edges).
+ *   gpde_nnconv_chain_any_plan   HOST ONLY, no device call.  From a host copy of rowptr: cuts consecutive destinations greedily so
+ *     that a block's per-edge buffers of the BACKWARD stay within budget_bytes.  A block is never less than one node - a row larger
+ *     than the budget is a block of its own and the sizes returned cover it -, nodes without in-edges join their neighbour's block.
+ *     block_nodes_out: room for 2 * (n_dst + 1) int32, or NULL (count and sizes only).  A block of 2^31 or more elements
+ *     (rows x widest K_l): GPDE_EUNSUPPORTED.  *ws_fwd / *ws_bwd: the workspaces the two calls need WITH THIS TABLE.
+ *   gpde_nnconv_chain_any_workspace_bytes   HOST ONLY: the same two sizes for a table the caller made.
+ *   A table that is not monotone, does not run from (0, 0) to (n_dst, n_edges) or has slots in a block without nodes: GPDE_EINVAL.
+ *   A workspace below the size the table needs: GPDE_EWORKSPACE (the message names the size).  A table whose slots disagree with the
+ *   device rowptr cannot be seen from the host: the kernels then read a copy of rowptr clipped to each block's slot range, so they
+ *   stay inside the block's buffers (the results are wrong), and *n_bad (int32 device word, nullable; cleared by the call) is set.
+ * Memory.  The workspace holds, besides the last Linear permuted (and its gradient), the buffers of ONE block: in the forward two
+ *   [E_b][max K_l] buffers; in the backward every layer's activations, dH and two dU buffers - gpde_nnconv_chain_any_plan's budget -
+ *   and Z' (dZ') of a node sub-block of at most that many bytes.  What remains O(E): the caller's edge_attr (and grad_edge_attr) and,
+ *   in the backward's workspace, the per-edge dx rows [E][in_src] of the ordered grad_x_src sum.
+ * Determinism.  fp32, no atomics.  out, grad_x_src, grad_x_dst and grad_edge_attr do not depend on the block table, bit for bit (a
+ *   hidden row's arithmetic does not depend on its block); the weight and bias gradients are summed over the blocks in order.  The
+ *   derivative of the ReLU at 0 is 0, as torch's.  A NULL gradient output leaves the bits of the others unchanged.
+ * Zero destinations and zero edges are valid calls.  Additions to the ABI: GPDE_VERSION is unchanged. */
+GPDE_API int gpde_nnconv_chain_any_plan(const int32_t* rowptr_host, int64_t n_dst, int64_t n_edges, int n_linear, const int32_t* dims,
+                               int in_src, int in_dst, int out_channels, size_t budget_bytes, int32_t* block_nodes_out,
+                               int64_t* n_blocks, size_t* ws_fwd, size_t* ws_bwd);
+GPDE_API int gpde_nnconv_chain_any_workspace_bytes(const int32_t* block_nodes, int64_t n_blocks, int64_t n_dst, int64_t n_edges,
+                                          int n_linear, const int32_t* dims, int in_src, int in_dst, int out_channels,
+                                          size_t* ws_fwd, size_t* ws_bwd);
+GPDE_API int gpde_nnconv_fwd_chain_any(const float* x_src, int64_t n_src, const float* x_dst, int64_t n_dst, int square,
+                              const float* edge_attr, int64_t n_edges, const int32_t* rowptr, const int32_t* src, int n_linear,
+                              const int32_t* dims, const float* const* weights, const float* const* biases, const float* root,
+                              const float* bias, int aggr, int in_src, int in_dst, int out_channels, const int32_t* block_nodes,
+                              int64_t n_blocks, float* out, int32_t* n_bad, void* ws, size_t ws_bytes, void* stream);
+GPDE_API int gpde_nnconv_bwd_chain_any(const float* x_src, int64_t n_src, const float* x_dst, int64_t n_dst, int square,
+                              const float* edge_attr, int64_t n_edges, const int32_t* rowptr, const int32_t* src, int n_linear,
+                              const int32_t* dims, const float* const* weights, const float* const* biases, const float* root,
+                              int aggr, int in_src, int in_dst, int out_channels, const float* grad_out, float* grad_x_src,
+                              float* grad_x_dst, float* grad_edge_attr, float* const* grad_w, float* const* grad_b, float* grad_root,
+                              float* grad_bias, const int32_t* src_rowptr, const int32_t* src_slots, const int32_t* block_nodes,
+                              int64_t n_blocks, int32_t* n_bad, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Edge attributes on the fly (opt-in): the `node_attr` argument (GpdeNodeAttr, declared at the top).
  * The reference materialises edge_attr[e] = [pos_src(2), pos_dst(2), a_src, a_dst] from node data
