@@ -14,15 +14,13 @@ aggregation and `update()` are ONE native call.  (`graph_pde_amd.NNConv` stays `
 from __future__ import annotations
 
 import torch
-from torch.nn import Parameter
 
 from . import ops
 from .autograd import DiagConvFunction
-from .message_passing import MessagePassing
-from .nn_conv import NNConv_old, _GatherRows, _on_dev, _reset, _slot_rows, _uniform
+from .nn_conv import _ConvFront, _dev_of, _front_args, _glued, _materialized, _on_dev, _rows, _slot_rows
 
 
-class NNConvDiag(MessagePassing):
+class NNConvDiag(_ConvFront):
     r"""x'_i = Theta x_i + aggr_{j in N(i)} x_j (.) h_Theta(e_ij), h_Theta emitting one value per channel and edge
     (nn_conv.py:8-96).  The source width must equal `out_channels` (`diag_embed(...).view(-1, in, out)`, nn_conv.py:84, needs it).
 
@@ -35,22 +33,13 @@ class NNConvDiag(MessagePassing):
     device and the result returns to the caller's device."""
 
     _nn_line = "nn_conv.py:84"
+    _propagate_line = "nn_conv.py:81"
 
     def __init__(self, in_channels, out_channels, nn, aggr="add", root_weight=True, bias=True, **kwargs):
         if not isinstance(nn, torch.nn.Module):
             raise NotImplementedError(f"nn must be a torch.nn.Module that maps edge attributes [E, k] to [E, out_channels] values "
                                       f"(nn_conv.py:28-32, 84), got {type(nn).__name__}")
-        flow = kwargs.pop("flow", "source_to_target")
-        if flow not in ("source_to_target", "target_to_source"):
-            raise ValueError(f"flow must be 'source_to_target' or 'target_to_source', got {flow!r}")
-        if kwargs:
-            raise TypeError(f"unexpected arguments {sorted(kwargs)}")
-        if aggr not in ("add", "mean", "max"):
-            raise ValueError(f"aggr must be 'add', 'mean' or 'max' (nn_conv.py:33-35), got {aggr!r}")
-        if isinstance(in_channels, (tuple, list)):
-            if len(in_channels) != 2:
-                raise ValueError(f"in_channels must be an int or a pair (in_src, in_dst), got {in_channels!r}")
-            in_channels = (in_channels[0], in_channels[1])
+        in_channels, flow = _front_args(in_channels, aggr, kwargs, "nn_conv.py:33-35")
         in_src = in_channels[0] if isinstance(in_channels, tuple) else in_channels
         in_dst = in_channels[1] if isinstance(in_channels, tuple) else in_channels
         if in_src != out_channels:
@@ -59,32 +48,7 @@ class NNConvDiag(MessagePassing):
         if not (ops.width_supported(in_src, out_channels) and ops.width_supported(in_dst, out_channels)):
             raise NotImplementedError(f"the MI355X diagonal operator is built for widths 1 .. {ops.ANY_MAX_WIDTH}, got "
                                       f"{in_channels}->{out_channels}")
-        super().__init__(aggr=aggr, flow=flow)
-        self.in_channels = in_channels
-        self.out_channels = out_channels
-        self.nn = nn
-        if root_weight:
-            self.root = Parameter(torch.Tensor(in_dst, out_channels))
-        else:
-            self.register_parameter("root", None)
-        if bias:
-            self.bias = Parameter(torch.Tensor(out_channels))
-        else:
-            self.register_parameter("bias", None)
-        self.reset_parameters()
-
-    # the pair / flow plumbing is NNConv_old's own (plain functions of `self`: in_channels, out_channels, flow)
-    _in_src = NNConv_old._in_src
-    _in_dst = NNConv_old._in_dst
-    _flipped = NNConv_old._flipped
-    _rect_call = NNConv_old._rect_call
-    _flow_csr = NNConv_old._flow_csr
-
-    def reset_parameters(self):                       # nn_conv.py:72-75
-        _reset(self.nn)
-        size = self._in_src()
-        _uniform(size, self.root)
-        _uniform(size, self.bias)
+        super().__init__(in_channels, out_channels, nn, aggr, root_weight, bias, flow)
 
     # ---- the per-edge kernel ----------------------------------------------------------------------------------------------
     def edge_kernel(self, pseudo):
@@ -112,30 +76,16 @@ class NNConvDiag(MessagePassing):
                 if isinstance(edge_attr, ops.NodeAttr):
                     raise NotImplementedError("ops.NodeAttr attributes on a call between two node sets are not built: a node table addresses "
                                               "ONE node set - pass the edge_attr tensor")
-                pseudo = edge_attr.unsqueeze(-1) if edge_attr.dim() == 1 else edge_attr
-                return self._propagate_two(rect[0], rect[1], rect[2], rect[3], edge_index, pseudo, residual, relu)
-            if isinstance(x, (tuple, list)):
-                x = x[0]
-            x = x.unsqueeze(-1) if x.dim() == 1 else x
+                return self._propagate_two(*rect, edge_index, _rows(edge_attr), residual, relu)
+            x = _rows(x[0] if isinstance(x, (tuple, list)) else x)
             slot_order = False
             if isinstance(edge_attr, ops.NodeAttr):
                 if self._flipped():
                     raise NotImplementedError("ops.NodeAttr attributes with flow='target_to_source' are not built - pass the edge_attr tensor")
                 # (from a CSR the rows come out in slot order already)
                 slot_order = isinstance(edge_index, ops.Csr)
-                edge_attr = edge_attr.materialize(edge_index.edge_index if slot_order else edge_index.to(edge_attr.device))
-            pseudo = edge_attr.unsqueeze(-1) if edge_attr.dim() == 1 else edge_attr
-            return self._propagate_one(x, edge_index, pseudo, residual, relu, slot_order)
-
-    def propagate(self, edge_index, size=None, **kwargs):
-        """`propagate(edge_index, x=x, pseudo=pseudo)` (nn_conv.py:81) as the native operator."""
-        if set(kwargs) != {"x", "pseudo"}:
-            raise TypeError(f"propagate() takes x= and pseudo= (nn_conv.py:81), got {sorted(kwargs)}")
-        return self.forward(kwargs["x"], edge_index, kwargs["pseudo"], size=size)
-
-    def _needs_grad(self, tensors, pseudo):
-        return torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in tensors) or
-                                            (torch.is_tensor(pseudo) and pseudo.requires_grad) or any(p.requires_grad for p in self.parameters()))
+                edge_attr = _materialized(edge_attr, edge_index)
+            return self._propagate_one(x, edge_index, _rows(edge_attr), residual, relu, slot_order)
 
     def _propagate_one(self, x, edge_index, pseudo, residual, relu, slot_order=False):
         w = int(self.out_channels)
@@ -145,19 +95,16 @@ class NNConvDiag(MessagePassing):
             raise NotImplementedError(f"the diagonal operator: float32 only (x is {x.dtype})")
         if residual is not None and tuple(residual.shape) != tuple(x.shape):
             raise ValueError(f"residual must be [N, out_channels] = {tuple(x.shape)}, got {tuple(residual.shape)}")
-        needs_grad = self._needs_grad((x, residual), pseudo)
+        needs_grad = self._needs_grad(x, residual, pseudo)
+        dev = _dev_of(x)
         if self.aggr == "max" and needs_grad:
-            out = self._max_chain(edge_index, x, pseudo, slot_order)
-            if residual is not None:
-                out = residual.to(out.device) + out
-            return torch.relu(out) if relu else out
-        dev = x.device if x.is_cuda else ops.staging_device()
+            # (`_max_detour` over the torch `message()` / `update()` below, where the call runs; a Csr's rows always go in slot order)
+            out = self._max_detour(edge_index, x.to(dev), pseudo, slot_rows=not slot_order).to(x.device)
+            return _glued(out, residual, relu)
         if self._flipped() and not (isinstance(edge_index, ops.Csr) and edge_index._flow_flipped):
             csr = self._flow_csr(edge_index, x)
-        elif isinstance(edge_index, ops.Csr):
-            csr = edge_index
         else:
-            csr = ops.csr_for(edge_index if edge_index.device == dev else ops.stage_const(edge_index, dev), x.size(0))
+            csr = self._square_csr(edge_index, x)
         if pseudo.size(0) != csr.n_edges:
             raise ValueError(f"edge_attr has {pseudo.size(0)} rows, edge_index {csr.n_edges} edges")
         return self._operator(x, ops._ONE_SET, csr, pseudo if slot_order else _slot_rows(csr, pseudo), dev, needs_grad, residual, relu)
@@ -165,24 +112,8 @@ class NNConvDiag(MessagePassing):
     def _propagate_two(self, x_src, x_dst, n_src, n_dst, edge_index, pseudo, residual, relu):
         """Between two node sets: sources x_src [n_src, out], destinations x_dst [n_dst, in_dst] or None (no root term, PyG's rule),
         edges (edge_index[0] in [0, n_src)) -> (edge_index[1] in [0, n_dst)) (rows swapped under flow='target_to_source')."""
-        tensors = [t for t in (x_src, x_dst, residual) if t is not None]
-        if any(t.dtype != torch.float32 for t in tensors):
-            raise NotImplementedError(f"a call between two node sets: float32 only (got {[str(t.dtype) for t in tensors]})")
-        needs_grad = self._needs_grad(tensors, pseudo)
-        if self.aggr == "max" and needs_grad:
-            raise NotImplementedError("aggr='max' with a gradient on a call between two node sets is not built (inference runs natively: "
-                                      "call under torch.no_grad())")
-        dev = x_src.device if x_src.is_cuda else ops.staging_device()
-        if isinstance(edge_index, ops.Csr):
-            if self._flipped() and not edge_index._flow_flipped:
-                raise NotImplementedError("flow='target_to_source' with a destination CSR (ops.Csr): a CSR has its direction built in - "
-                                          "pass the edge_index tensor")
-            csr = ops.csr_for(edge_index, n_dst, n_src=n_src)
-        else:
-            csr = ops.csr_for(edge_index if edge_index.device == dev else ops.stage_const(edge_index, dev), n_dst, n_src=n_src,
-                              flip=self._flipped())
-        if pseudo.size(0) != csr.n_edges:
-            raise ValueError(f"edge_attr has {pseudo.size(0)} rows, edge_index {csr.n_edges} edges")
+        needs_grad = self._two_sets_gate([t for t in (x_src, x_dst, residual) if t is not None], pseudo)
+        dev, csr = _dev_of(x_src), self._rect_csr(edge_index, x_src, n_src, n_dst, pseudo)
         return self._operator(x_src, x_dst, csr, _slot_rows(csr, pseudo), dev, needs_grad, residual, relu)
 
     def _operator(self, x_src, x_dst, csr, pseudo_s, dev, needs_grad, residual, relu):
@@ -195,29 +126,11 @@ class NNConvDiag(MessagePassing):
         xs_d = x_src.to(dev) if needs_grad else x_src.detach().to(dev)
         xd_d = x_dst if not torch.is_tensor(x_dst) else x_dst.to(dev) if needs_grad else x_dst.detach().to(dev)
         if needs_grad:
-            out = DiagConvFunction.apply(xs_d, xd_d, k, csr, root, bias, self.aggr)
-            if residual is not None:
-                out = residual.to(dev) + out
-            if relu:
-                out = torch.relu(out)
+            out = _glued(DiagConvFunction.apply(xs_d, xd_d, k, csr, root, bias, self.aggr), residual, relu)
         else:
             res = None if residual is None else residual.detach().to(dev)
             out = ops.diagconv_forward_raw(xs_d, xd_d, csr, k.detach(), root, bias, self.aggr, residual=res, relu=relu)
         return out.to(x_src.device)
-
-    def _max_chain(self, edge_index, x, pseudo, slot_order=False):
-        """A gradient through aggr='max' on one node set: PyG's own chain (MessagePassing.propagate applies `flow` itself) over
-        `message()` / `update()` below, x_j gathered by `_GatherRows` - grad_x is the same bits on every run."""
-        if isinstance(edge_index, ops.Csr):
-            csr = edge_index
-            edge_index = csr.edge_index
-            if not slot_order:
-                pseudo = _slot_rows(csr, pseudo)
-            if csr._flow_flipped:
-                edge_index = edge_index.flip(0)
-        dev = x.device if x.is_cuda else ops.staging_device()
-        out = MessagePassing.propagate(self, edge_index.to(dev), x=x.to(dev), pseudo=pseudo, _gather=_GatherRows.apply)
-        return out.to(x.device)
 
     def message(self, x_j, pseudo):                    # nn_conv.py:83-85
         """m_e = x_j[e] . diag(k_e) = x_j[e] * k_e."""
@@ -230,9 +143,6 @@ class NNConvDiag(MessagePassing):
         if self.bias is not None:
             aggr_out = aggr_out + self.bias.to(aggr_out.device)
         return aggr_out
-
-    def __repr__(self):                               # nn_conv.py:94-96
-        return "{}({}, {})".format(self.__class__.__name__, self.in_channels, self.out_channels)
 
 
 class NNConvGaussian(NNConvDiag):
