@@ -16,6 +16,7 @@ from .nn_conv import ECConv, NNConv, NNConv_old, nnconv_group   # noqa: F401
 from .gcn_conv import GCNConv                       # noqa: F401
 from .diag_conv import NNConvDiag, NNConvGaussian   # noqa: F401  (the reference's diagonal-kernel classes, nn_conv.py:8-194)
 from .ops import NodeAttr                           # noqa: F401  (opt-in: edge attributes from node data)
+from .ops import Sin                                # noqa: F401  (torch.sin as a module: the sine kernel network the streamed route reads)
 from .capture import capture                        # noqa: F401  (opt-in: a model function's native calls as one HIP graph)
 
-__all__ = ["NNConv_old", "NNConv", "ECConv", "NNConvDiag", "NNConvGaussian", "GCNConv", "NodeAttr", "nnconv_group", "capture", "ops", "sampled_graph", "neighbor_graph", "synth"]
+__all__ = ["NNConv_old", "NNConv", "ECConv", "NNConvDiag", "NNConvGaussian", "GCNConv", "NodeAttr", "Sin", "nnconv_group", "capture", "ops", "sampled_graph", "neighbor_graph", "synth"]

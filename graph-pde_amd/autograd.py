@@ -502,10 +502,11 @@ class ChainAnyFunction(torch.autograd.Function):
     is formed, in either direction.  Differentiable in x_src, x_dst, edge_attr, root, bias and every weight and bias of the chain.
     `x_dst`: as WeConvAnyFunction takes it.  `edge_attr` [E, k0] comes in the CALLER's edge order and its gradient goes back in
     that order.  Only the inputs are saved: the backward recomputes every activation block by block.
+    `acts`: None (a Linear / ReLU chain) or one (kind, p0, p1) per hidden layer (ops.mlp_chain: gpde_nnconv_*_chain_act), not a tensor.
     `params`: the chain's weights, then its biases (None for a Linear without one)."""
 
     @staticmethod
-    def forward(ctx, x_src, x_dst, edge_attr, csr, root, bias, aggr, *params):
+    def forward(ctx, x_src, x_dst, edge_attr, csr, root, bias, aggr, acts, *params):
         root = _root_term(x_dst, root)
         nl = len(params) // 2
         ctx.one, ctx.has_dst, ctx.nl = x_dst is ops._ONE_SET, torch.is_tensor(x_dst), nl
@@ -513,8 +514,8 @@ class ChainAnyFunction(torch.autograd.Function):
         ea = edge_attr.detach().float().contiguous()
         ea_s = ea if ctx.identity or csr.n_edges == 0 else ops.gather_rows(ea, csr.perm)
         xd = ops._ONE_SET if ctx.one else x_dst.detach() if ctx.has_dst else None
-        out = ops.nnconv_forward_chain_any_raw(x_src.detach(), xd, csr, ea_s, params[:nl], params[nl:], root, bias, aggr)
-        ctx.csr, ctx.aggr, ctx.has_bias, ctx.has_root = csr, aggr, bias is not None, root is not None
+        out = ops.nnconv_forward_chain_any_raw(x_src.detach(), xd, csr, ea_s, params[:nl], params[nl:], root, bias, aggr, acts=acts)
+        ctx.csr, ctx.aggr, ctx.has_bias, ctx.has_root, ctx.acts = csr, aggr, bias is not None, root is not None, acts
         ctx.save_for_backward(x_src, x_dst if ctx.has_dst else None, edge_attr, root, *params)
         return out
 
@@ -528,13 +529,13 @@ class ChainAnyFunction(torch.autograd.Function):
         xd = ops._ONE_SET if ctx.one else x_dst if ctx.has_dst else None
         gxs, gxd, gea, gw, gb, groot, gbias = ops.nnconv_backward_chain_any_raw(
             x_src, xd, csr, ea_s, params[:nl], params[nl:], root, ctx.aggr, grad_out, need_x_src=need[0], need_x_dst=ctx.has_dst and need[1],
-            need_w=list(need[7:7 + nl]), need_b=[params[nl + l] is not None and need[7 + nl + l] for l in range(nl)],
-            need_root=ctx.has_root and need[4], need_bias=ctx.has_bias and need[5], need_edge_attr=need[2])
+            need_w=list(need[8:8 + nl]), need_b=[params[nl + l] is not None and need[8 + nl + l] for l in range(nl)],
+            need_root=ctx.has_root and need[4], need_bias=ctx.has_bias and need[5], need_edge_attr=need[2], acts=ctx.acts)
         if gea is not None and not ctx.identity:            # slot order -> the caller's edge order (an edge the CSR dropped: 0)
             gea = torch.zeros(edge_attr.shape, dtype=gea.dtype, device=gea.device).index_copy_(0, csr.perm.long(), gea)
         if gea is not None:
             gea = gea.to(edge_attr.dtype)
-        return (gxs, gxd, gea, None, groot, gbias, None, *gw, *gb)
+        return (gxs, gxd, gea, None, groot, gbias, None, None, *gw, *gb)
 
 
 class GCNFunction(torch.autograd.Function):

@@ -293,7 +293,57 @@ struct GpdeGemmArgs {
     int batches; size_t strideA, strideB, strideC;
     int splits; size_t strideSplit; // split-K: partial s written at C + s*strideSplit
     int skew_us;                    // test hook (GPDE_DEBUG_SKEW_US): odd column tiles start this many us late
+    // The activations of gpde_chain_any.hip (GPDE_ACT_*).  All zero - what `GpdeGemmArgs g{}` leaves - is the kernel as it was: a
+    // call with any of act / preact / dact set runs the kernel's ACT instantiation, every other call the one it always ran.
+    int act; float act_p0;          // with `relu`: C = act(A . B + bias) instead of max(., 0)
+    int act_n;                      // with `act`: columns n >= act_n hold 0 whatever act(0) is (the row padding of a kept buffer)
+    float* preact; int ldpre;       // optional second output: A . B + bias before the activation, [M][ldpre]
+    int dact; float dact_p0;        // with `mask`: C = C * act'(mask) instead of the (mask > 0) select; `mask` is H for kinds whose
+                                    // derivative comes from the value, the pre-activation U for the others (gp_act_from_u)
 };
+
+// Hidden activations of the streamed any-width route (include/gpde.h GPDE_ACT_*; csrc/gpde_chain_any.hip).  fp32, the accurate device
+// functions, branches by SELECT (never value * 0/1 mask: an ELU at u = +100 would form 0 * inf).  Kinds 0 .. 4 give act' from the
+// value h = act(u), kinds 5 .. 8 need u itself.
+enum { GP_ACT_RELU = 0, GP_ACT_LEAKY_RELU = 1, GP_ACT_ELU = 2, GP_ACT_TANH = 3, GP_ACT_SIGMOID = 4, GP_ACT_GELU = 5, GP_ACT_GELU_TANH = 6,
+       GP_ACT_SILU = 7, GP_ACT_SIN = 8, GP_ACT_KINDS = 9 };
+inline bool gp_act_from_u(int kind) { return kind >= GP_ACT_GELU; }
+__device__ __forceinline__ float gp_act(int kind, float p0, float u) {
+    switch (kind) {
+    case GP_ACT_LEAKY_RELU: return u > 0.f ? u : p0 * u;
+    case GP_ACT_ELU: return u > 0.f ? u : p0 * expm1f(u);
+    case GP_ACT_TANH: return tanhf(u);
+    case GP_ACT_SIGMOID: return 1.f / (1.f + expf(-u));
+    case GP_ACT_GELU: return 0.5f * u * (1.f + erff(u * 0.70710678118654752440f));
+    case GP_ACT_GELU_TANH: {
+        const float inner = 0.79788456080286535588f * (u + 0.044715f * u * u * u);
+        return 0.5f * u * (1.f + tanhf(inner));
+    }
+    case GP_ACT_SILU: return u / (1.f + expf(-u));
+    case GP_ACT_SIN: return sinf(u);
+    default: return fmaxf(u, 0.f);
+    }
+}
+// act'(u) from s = h (kinds 0 .. 4) or s = u (kinds 5 .. 8); at the kink of RELU / LEAKY_RELU / ELU the value torch's backward takes
+__device__ __forceinline__ float gp_dact(int kind, float p0, float s) {
+    switch (kind) {
+    case GP_ACT_LEAKY_RELU: return s > 0.f ? 1.f : p0;
+    case GP_ACT_ELU: return s > 0.f ? 1.f : s + p0;
+    case GP_ACT_TANH: return 1.f - s * s;
+    case GP_ACT_SIGMOID: return s * (1.f - s);
+    case GP_ACT_GELU: return 0.5f * (1.f + erff(s * 0.70710678118654752440f)) + s * 0.39894228040143267794f * expf(-0.5f * s * s);
+    case GP_ACT_GELU_TANH: {
+        const float s2 = s * s, t = tanhf(0.79788456080286535588f * (s + 0.044715f * s * s2));
+        return 0.5f * (1.f + t) + 0.5f * s * (1.f - t * t) * 0.79788456080286535588f * (1.f + 3.f * 0.044715f * s2);
+    }
+    case GP_ACT_SILU: {
+        const float g = 1.f / (1.f + expf(-s));
+        return g * (1.f + s * (1.f - g));
+    }
+    case GP_ACT_SIN: return cosf(s);
+    default: return s > 0.f ? 1.f : 0.f;
+    }
+}
 // Test hook shared by the GEMM kernels: with GPDE_DEBUG_SKEW_US=<n> in the environment, workgroups of odd column
 // slices spin n microseconds before their first load.  Sibling slices read the same operand rows; a buffer plan that
 // lets one slice's output land in rows another slice still has to read then fails deterministically instead of once

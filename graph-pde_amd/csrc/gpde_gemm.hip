@@ -27,7 +27,9 @@ constexpr int GK = 32;       // K chunk
 constexpr int SKC = 36;      // LDS row stride, K-contiguous operand  [128][36]
 constexpr int SKS = 132;     // LDS row stride, K-strided operand     [32][132]
 
-template <bool A_KC, bool B_KC>
+// ACT: the instantiation that reads the activation fields of GpdeGemmArgs (act / act_n / preact / dact; gpde_chain_any.hip).  The
+// launcher takes it only when one of them is set, so every other call runs the code it always ran.
+template <bool A_KC, bool B_KC, bool ACT = false>
 __global__ __launch_bounds__(256) void gpde_gemm_kernel(GpdeGemmArgs g) {
     __shared__ __attribute__((aligned(16))) float As[2][A_KC ? GT * SKC : GK * SKS];
     __shared__ __attribute__((aligned(16))) float Bs[2][B_KC ? GT * SKC : GK * SKS];
@@ -175,8 +177,15 @@ __global__ __launch_bounds__(256) void gpde_gemm_kernel(GpdeGemmArgs g) {
                 const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
                 if (m >= g.M) continue;
                 float v = acc[i][j][r] + bias;
-                if (g.relu) v = fmaxf(v, 0.f);
-                if (g.mask) v = (mk[r] > 0.f) ? v : 0.f;
+                if (ACT) {
+                    // (both stores of a row follow every load of the 16 rows above: no load waits behind a store)
+                    if (g.preact) g.preact[(size_t)m * g.ldpre + n] = v;
+                    if (g.relu) v = n < g.act_n ? gp_act(g.act, g.act_p0, v) : 0.f;
+                    if (g.mask) v = g.dact ? v * gp_dact(g.dact, g.dact_p0, mk[r]) : (mk[r] > 0.f) ? v : 0.f;
+                } else {
+                    if (g.relu) v = fmaxf(v, 0.f);
+                    if (g.mask) v = (mk[r] > 0.f) ? v : 0.f;
+                }
                 if (g.accumulate) v += old[r];
                 C[(size_t)m * g.ldc + n] = v;
             }
@@ -220,8 +229,11 @@ int gpde_launch_gemm(const GpdeGemmArgs& g_in, hipStream_t stream) {
         const size_t aa = (nb * g.strideA + (g.a_kcontig ? (size_t)(g.M - 1) * g.lda + g.K : (size_t)(g.K - 1) * g.lda + g.M)) * 4;
         const size_t ba = (nb * g.strideB + (g.b_kcontig ? (size_t)(g.N - 1) * g.ldb + g.K : (size_t)(g.K - 1) * g.ldb + g.N)) * 4;
         const size_t ma = g.mask ? ((size_t)(g.M - 1) * g.ldmask + g.N) * 4 : 0;
+        const size_t pa = g.preact ? ((size_t)(g.M - 1) * g.ldpre + g.N) * 4 : 0;
         if (g.M > 0 && g.N > 0 && g.K > 0 &&
-            (gp_overlap(g.C, ca, g.A, aa) || gp_overlap(g.C, ca, g.B, ba) || gp_overlap(g.C, ca, g.mask, ma))) {
+            (gp_overlap(g.C, ca, g.A, aa) || gp_overlap(g.C, ca, g.B, ba) || gp_overlap(g.C, ca, g.mask, ma) ||
+             gp_overlap(g.preact, pa, g.A, aa) || gp_overlap(g.preact, pa, g.B, ba) || gp_overlap(g.preact, pa, g.mask, ma) ||
+             gp_overlap(g.preact, pa, g.C, ca))) {
             gpde_set_error("gpde_gemm: output overlaps an operand (internal buffer plan error)");
             return GPDE_EINVAL;
         }
@@ -230,7 +242,16 @@ int gpde_launch_gemm(const GpdeGemmArgs& g_in, hipStream_t stream) {
     static const bool log_shapes = getenv("GPDE_DEBUG_GEMM_LOG") != nullptr;      // one stderr line per launch (pairs with a rocprofv3 kernel trace)
     if (log_shapes) fprintf(stderr, "[gpde_gemm] <%d,%d> M %d N %d K %d batches %d splits %d acc %d mask %d wgs %u\n", g.a_kcontig, g.b_kcontig, g.M, g.N, g.K,
                             g.batches, g.splits, g.accumulate, g.mask != nullptr, grid.x * grid.y * grid.z);
-    if (g.a_kcontig && g.b_kcontig) hipLaunchKernelGGL((gpde_gemm_kernel<true, true>), grid, block, 0, stream, g);
+    if (g.act || g.preact || g.dact) {             // the activations of gpde_chain_any.hip: its NT (forward) and NN (backward) calls
+        if (g.batches != 1 || g.splits != 1 || g.accumulate || !g.a_kcontig || (g.act && !g.relu) || (g.dact && !g.mask) ||
+            ((g.act || g.preact) && !g.b_kcontig) || g.act < 0 || g.act >= GP_ACT_KINDS || g.dact < 0 || g.dact >= GP_ACT_KINDS) {
+            gpde_set_error("gpde_gemm: activation fields on a call they are not built for (internal error)");
+            return GPDE_EINVAL;
+        }
+        if (g.act_n <= 0) g.act_n = g.N;
+        if (g.b_kcontig) hipLaunchKernelGGL((gpde_gemm_kernel<true, true, true>), grid, block, 0, stream, g);
+        else hipLaunchKernelGGL((gpde_gemm_kernel<true, false, true>), grid, block, 0, stream, g);
+    } else if (g.a_kcontig && g.b_kcontig) hipLaunchKernelGGL((gpde_gemm_kernel<true, true>), grid, block, 0, stream, g);
     else if (g.a_kcontig && !g.b_kcontig) hipLaunchKernelGGL((gpde_gemm_kernel<true, false>), grid, block, 0, stream, g);
     else if (!g.a_kcontig && !g.b_kcontig) hipLaunchKernelGGL((gpde_gemm_kernel<false, false>), grid, block, 0, stream, g);
     else { gpde_set_error("gemm layout (A strided, B k-contiguous) not built"); return GPDE_EUNSUPPORTED; }

@@ -312,7 +312,14 @@ class NNConv_old(_ConvFront):
     Such a call runs the any-width kernels at every width (`_propagate_rect`; 64 -> 64 included).  Not built for it: a gradient
     through aggr='max', `ops.NodeAttr` attributes, the hidden / edge-weight caches and the shared launch of `nnconv_group`.
     `flow='target_to_source'` swaps the two rows of `edge_index` (read in place through a negative row stride, no copy) at every
-    width."""
+    width.
+
+    Kernel networks with other activations: `Linear, (act, Linear)+` with act one of ReLU, LeakyReLU (slope >= 0), ELU, Tanh, Sigmoid,
+    GELU (both forms), SiLU and `graph_pde_amd.Sin` per hidden layer (ops.mlp_chain) has a route that forms no per-edge tensor wider
+    than `edge_attr`: the STREAMED any-width route (gpde_nnconv_*_chain_act), taken under GPDE_ANY_REASSOC=streamed, under `auto` by
+    a call whose per-edge weights do not fit, and at 64 -> 64 on one node set by a call that `_propagate_general_nn` would refuse
+    for memory.  Calls that fit keep their route.  The reference's `DenseNet_sin` applies `torch.sin` inside its `forward`, where no
+    parser of layers sees it, and therefore keeps the general route; `DenseNet(layers, graph_pde_amd.Sin)` is the streamed form."""
 
     _propagate_line = "nn_conv.py:271"
 
@@ -437,6 +444,18 @@ class NNConv_old(_ConvFront):
         need = csr.n_edges * ops.WIDTH * ops.WIDTH * 4
         free, _ = ops.device_free_bytes(x.device)
         if 2 * need > free:
+            # the per-edge weights do not fit.  `Linear, (act, Linear)+` with an activation the library generates (ops.mlp_chain:
+            # GELU, SiLU, tanh, sin, ...) runs STREAMED instead, from the edge attributes by block of destination nodes
+            # (gpde_nnconv_*_chain_act; the any-width kernels take 64 -> 64).  A call that fits keeps its route and its bits
+            chain = ops.mlp_chain(self.nn)
+            if chain is not None:
+                lin, acts = chain
+                dims = [lin[0].in_features] + [l.out_features for l in lin]
+                route = ops.any_width_route(csr.n_nodes, csr.n_edges, ops.WIDTH, ops.WIDTH, dims[-2], self.aggr, dims[-1] == ops.WIDTH * ops.WIDTH,
+                                            free, mode="off" if ops.ANY_REASSOC == "off" else "auto", dims=dims, acts=acts)
+                if route["route"] == "streamed":
+                    return self._any_width_operator(x, ops._ONE_SET, csr, pseudo, "streamed", lin, x.device, self._needs_grad(x, pseudo), None,
+                                                    False, acts=acts)
             raise RuntimeError(f"kernel network {type(self.nn).__name__} is not a Linear / ReLU chain: its per-edge weights are materialised as in the "
                                f"reference (nn_conv.py:274) - {csr.n_edges} edges x 16 KiB = {need / 2**30:.1f} GiB (twice that with gradients), "
                                f"{free / 2**30:.1f} GiB free")
@@ -479,7 +498,7 @@ class NNConv_old(_ConvFront):
         # the route (ops.any_width_route; GPDE_ANY_REASSOC = auto | on | off): a call whose per-edge weights fit runs on them exactly
         # as before; a Linear / ReLU chain under add / mean that does not fit (auto), or every such call (on), re-associates the
         # last Linear and never forms [E, in * out]
-        route, lin, free = self._any_width_route(csr, dev)
+        route, lin, acts, free = self._any_width_route(csr, dev)
         if route["route"] == "refused":
             other = ""
             if route["eligible"] and ops.ANY_REASSOC != "off":
@@ -488,23 +507,26 @@ class NNConv_old(_ConvFront):
             raise RuntimeError(f"{self!r}: at widths other than {ops.WIDTH} -> {ops.WIDTH} the per-edge weights are materialised as in the reference "
                                f"(nn_conv.py:274) - {csr.n_edges} edges x {cin} x {cout} x 4 B = {route['bytes_materialised'] / 2**30:.2f} GiB "
                                f"(twice that with gradients), {free / 2**30:.2f} GiB free{other}")
-        return self._any_width_operator(x, ops._ONE_SET, csr, pseudo, route["route"], lin, dev, needs_grad, residual, relu)
+        return self._any_width_operator(x, ops._ONE_SET, csr, pseudo, route["route"], lin, dev, needs_grad, residual, relu, acts=acts)
 
     def _any_width_route(self, csr, dev):
-        """(ops.any_width_route of a call on `csr`, the Linear layers of `nn` when it is a Linear / ReLU chain - else None -, the free
-        bytes of `dev`)."""
+        """(ops.any_width_route of a call on `csr`, the Linear layers of `nn` when it is a Linear / ReLU chain or - ops.mlp_chain - a
+        chain with other hidden activations, else None -, those activations - None for the ReLU chain -, the free bytes of `dev`)."""
         cin, cout = int(self._in_src()), int(self.out_channels)
         free, _ = ops.device_free_bytes(dev)
-        lin = self._linears()
+        lin, acts = self._linears(), None
+        if lin is None:
+            lin, acts = ops.mlp_chain(self.nn) or (None, None)
         chain = lin is not None and lin[-1].out_features == cin * cout
         dims = [lin[0].in_features] + [l.out_features for l in lin] if chain else None
         args = (csr.n_nodes, csr.n_edges, cin, cout, lin[-1].in_features if chain else None, self.aggr, chain, free)
-        route = ops.any_width_route(*args)
+        kw = {} if acts is None else {"dims": dims, "acts": acts}      # (a Linear / ReLU chain asks exactly as it always did)
+        route = ops.any_width_route(*args, **kw)
         if route["route"] == "streamed" and not ops.chain_any_supported(dims):       # a chain the library does not generate: as under `off`
-            route = ops.any_width_route(*args, mode="off")
-        return route, lin, free
+            route = ops.any_width_route(*args, mode="off", **kw)
+        return route, lin, acts, free
 
-    def _any_width_operator(self, x_src, x_dst, csr, pseudo, route, lin, dev, needs_grad, residual, relu):
+    def _any_width_operator(self, x_src, x_dst, csr, pseudo, route, lin, dev, needs_grad, residual, relu, acts=None):
         """The operator of `_propagate_any_width` (`x_dst` ops._ONE_SET) and of `_propagate_rect` (`x_dst` a tensor or None) once the
         route is decided - a call on one node set is the two-set call that hands one table twice.  Rows of `pseudo` in CSR slot
         order, where the module lives; parameters and CPU tensors staged to `dev` (`.to()` is differentiable), the result back on
@@ -517,7 +539,8 @@ class NNConv_old(_ConvFront):
         earlier layers by autograd).
         Streamed (GPDE_ANY_REASSOC=streamed; the same chains): `pseudo` and the chain's weights go to ONE native call that generates
         the hidden rows by block of destination nodes (gpde_nnconv_fwd_chain_any; its backward recomputes them and differentiates the
-        whole chain) - no per-edge tensor wider than `pseudo` exists.
+        whole chain) - no per-edge tensor wider than `pseudo` exists.  `acts` (ops.mlp_chain): the chain's hidden activations when
+        they are not all ReLU - GELU, SiLU, tanh, sin, ... -, which only this route takes (gpde_nnconv_*_chain_act).
         `residual` [n_dst, out] / `relu`: the kernel's epilogue on the materialised call without a gradient, torch ops otherwise."""
         one = x_dst is ops._ONE_SET
         cin, cout = int(self._in_src()), int(self.out_channels)
@@ -530,7 +553,7 @@ class NNConv_old(_ConvFront):
             # (.float(): as on the re-associated route, a float64 kernel network runs with float32 x)
             params = [on_dev(l.weight).float() for l in lin] + [None if l.bias is None else on_dev(l.bias).float() for l in lin]
             ea = pseudo.to(dev) if needs_grad and pseudo.requires_grad else pseudo.detach().to(dev)
-            out = ChainAnyFunction.apply(xs_d, xd_d, ea, csr, root, bias, self.aggr, *params)      # (no graph when nothing needs one)
+            out = ChainAnyFunction.apply(xs_d, xd_d, ea, csr, root, bias, self.aggr, acts, *params)      # (no graph when nothing needs one)
         elif route == "reassociated":
             h = pseudo_s
             for l in lin[:-1]:
@@ -574,12 +597,12 @@ class NNConv_old(_ConvFront):
                                       f"{self.in_channels}->{self.out_channels}")
         needs_grad = self._two_sets_gate([t for t in (x_src, x_dst, residual) if t is not None], pseudo)
         dev, csr = _dev_of(x_src), self._rect_csr(edge_index, x_src, n_src, n_dst, pseudo)
-        route, lin, free = self._any_width_route(csr, dev)
+        route, lin, acts, free = self._any_width_route(csr, dev)
         if route["route"] == "refused":
             raise RuntimeError(f"{self!r}: a call between two node sets materialises the per-edge weights as the reference does (nn_conv.py:274) - "
                                f"{csr.n_edges} edges x {int(cin)} x {int(cout)} x 4 B = {route['bytes_materialised'] / 2**30:.2f} GiB (twice that with "
                                f"gradients), {free / 2**30:.2f} GiB free (GPDE_ANY_REASSOC={ops.ANY_REASSOC})")
-        return self._any_width_operator(x_src, x_dst, csr, pseudo, route["route"], lin, dev, needs_grad, residual, relu)
+        return self._any_width_operator(x_src, x_dst, csr, pseudo, route["route"], lin, dev, needs_grad, residual, relu, acts=acts)
 
     def _propagate_64(self, x, edge_index, pseudo, weights, biases, root, bias, use_hidden_cache, residual=None, relu=False):
         """The 64 -> 64 operator of a Linear / ReLU chain on device tensors: gather, message, aggregate, update of the reference as

@@ -622,6 +622,95 @@ def mlp_linears(mlp: torch.nn.Module) -> List[torch.nn.Linear]:
     return lin
 
 
+class Sin(torch.nn.Module):
+    """`torch.sin` as a module: `DenseNet(layers, graph_pde_amd.Sin)` is the sine kernel network `mlp_chain` reads (the reference's
+    `DenseNet_sin` applies torch.sin inside its forward, which no parser of layers can see)."""
+
+    def forward(self, x):
+        return torch.sin(x)
+
+
+# GPDE_ACT_* of include/gpde.h: the hidden activations of the streamed any-width route (csrc/gpde_chain_any.hip)
+ACT_RELU, ACT_LEAKY_RELU, ACT_ELU, ACT_TANH, ACT_SIGMOID, ACT_GELU, ACT_GELU_TANH, ACT_SILU, ACT_SIN = range(9)
+ACT_NAMES = ("relu", "leaky_relu", "elu", "tanh", "sigmoid", "gelu", "gelu_tanh", "silu", "sin")
+ACT_FROM_U = frozenset((ACT_GELU, ACT_GELU_TANH, ACT_SILU, ACT_SIN))      # act' needs the pre-activation: the backward keeps U_l too
+
+
+def _act_of(layer) -> Optional[Tuple[int, float, float]]:
+    """(kind, p0, p1) of one activation module, or None.  Exact classes only: a subclass may override `forward`."""
+    t, nn = type(layer), torch.nn
+    if t is nn.ReLU:
+        return (ACT_RELU, 0.0, 0.0)
+    if t is nn.LeakyReLU:            # (act' is read from the value: a negative slope would make the value's sign ambiguous)
+        s = float(layer.negative_slope)
+        return (ACT_LEAKY_RELU, s, 0.0) if s >= 0.0 and s != float("inf") else None
+    if t is nn.ELU:
+        a = float(layer.alpha)
+        return (ACT_ELU, a, 0.0) if 0.0 < a < float("inf") else None
+    if t is nn.Tanh:
+        return (ACT_TANH, 0.0, 0.0)
+    if t is nn.Sigmoid:
+        return (ACT_SIGMOID, 0.0, 0.0)
+    if t is nn.GELU:
+        approx = getattr(layer, "approximate", "none")
+        return (ACT_GELU, 0.0, 0.0) if approx == "none" else (ACT_GELU_TANH, 0.0, 0.0) if approx == "tanh" else None
+    if t is nn.SiLU:
+        return (ACT_SILU, 0.0, 0.0)
+    if t is Sin:
+        return (ACT_SIN, 0.0, 0.0)
+    return None
+
+
+def mlp_chain(mlp: torch.nn.Module):
+    """(linears, acts) of a kernel network `Linear, (act, Linear)+` - a Sequential or a DenseNet-style `.layers` ModuleList -, `acts`
+    one (kind, p0, p1) per hidden layer (ACT_*; `inplace` is irrelevant); None for anything else: BatchNorm, an output nonlinearity,
+    a LeakyReLU of negative slope, an activation the library does not generate, a subclass of Linear or of an activation (it may
+    override `forward`).  The chains `mlp_linears` takes are the all-ReLU ones of these."""
+    if hasattr(mlp, "layers") and isinstance(mlp.layers, torch.nn.ModuleList):
+        layers = list(mlp.layers)
+    elif type(mlp) is torch.nn.Sequential:
+        layers = list(mlp)
+    else:
+        return None
+    if len(layers) < 3 or len(layers) % 2 == 0:
+        return None
+    lin, acts = [], []
+    for i, l in enumerate(layers):
+        if i % 2 == 0:
+            if type(l) is not torch.nn.Linear:
+                return None
+            lin.append(l)
+        else:
+            a = _act_of(l)
+            if a is None:
+                return None
+            acts.append(a)
+    if any(u.out_features != v.in_features for u, v in zip(lin[:-1], lin[1:])):
+        return None
+    return lin, acts
+
+
+def acts_all_relu(acts) -> bool:
+    return acts is None or all(int(a[0]) == ACT_RELU for a in acts)
+
+
+def acts_key(acts):
+    """`acts` as a hashable key; None for an all-ReLU chain (the `_chain_any` entry points)."""
+    return None if acts_all_relu(acts) else _acts_tuple(acts)
+
+
+def _acts_tuple(acts):
+    return tuple((int(a[0]), float(a[1]) if len(a) > 1 else 0.0, float(a[2]) if len(a) > 2 else 0.0) for a in acts)
+
+
+def acts_arrays(acts):
+    """The two host arrays of the `_chain_act` entry points: int32 kinds [n], float params [n][2]."""
+    key = _acts_tuple(acts)
+    kinds = (ctypes.c_int32 * len(key))(*[a[0] for a in key])
+    params = (ctypes.c_float * (2 * len(key)))(*[v for a in key for v in a[1:3]])
+    return kinds, params
+
+
 @dataclass
 class PackedMlp:
     dims: Tuple[int, ...]
@@ -1561,8 +1650,40 @@ def chain_any_supported(dims) -> bool:
         all(1 <= v <= ANY_MAX_HIDDEN for v in dims[1:-1])
 
 
+def chain_edge_bytes(dims, acts=None) -> int:
+    """Bytes per hidden row of a backward block of the streamed route (the plan's budget is spent in these): every kept H_l, the U_l
+    of the layers whose act' needs it, dH and two dU buffers, rows padded to 4 floats."""
+    kp = [(int(v) + 3) // 4 * 4 for v in dims[1:-1]]
+    extra = 0 if acts is None else sum(p for p, a in zip(kp, acts) if int(a[0]) in ACT_FROM_U)
+    return (sum(kp) + extra + kp[-1] + 2 * max(kp)) * 4
+
+
+def _act_chain_route(n, e, cin, cout, k, free_bytes, mode, dims, acts) -> dict:
+    """any_width_route for a chain with a hidden activation other than the ReLU (its docstring states the rule)."""
+    bytes_m = e * cin * cout * 4
+    zrow = cin * ((k + 1 + 3) // 4 * 4) * 4
+    out = {"eligible": False, "eligible_streamed": dims is None or chain_any_supported(dims), "bytes_materialised": bytes_m,
+           "bytes_reassociated": None, "node_block": None, "flops_materialised": 2 * e * k * cin * cout, "flops_reassociated": None,
+           "bytes_streamed": None}
+    fits_m = 2 * bytes_m <= free_bytes
+    if out["eligible_streamed"]:
+        out["bytes_streamed"] = e * cin * 4 + 2 * zrow * ((cout + 3) // 4 * 4)
+        if dims is not None:
+            per_edge = chain_edge_bytes(dims, acts)
+            out["bytes_streamed"] += min(e, CHAIN_ANY_PREF_BUDGET // per_edge) * (per_edge - chain_edge_bytes(dims))
+    if mode == "streamed" and out["eligible_streamed"]:
+        out["route"] = "streamed"
+    elif fits_m:
+        out["route"] = "materialised"
+    elif mode == "auto" and out["eligible_streamed"] and 2 * out["bytes_streamed"] <= free_bytes:
+        out["route"] = "streamed"
+    else:
+        out["route"] = "refused"
+    return out
+
+
 def any_width_route(n_nodes: int, n_edges: int, in_channels: int, out_channels: int, k_hidden: Optional[int], aggr: str, chain: bool,
-                    free_bytes: int, mode: Optional[str] = None, dims=None) -> dict:
+                    free_bytes: int, mode: Optional[str] = None, dims=None, acts=None) -> dict:
     """Which route a call of a module whose widths are not (64, 64) takes.  Host arithmetic only.
 
     `materialised`: the reference's order, `nn(pseudo)` as [E, in * out] (E in out 4 bytes; the last Linear costs 2 E K in out
@@ -1579,13 +1700,24 @@ def any_width_route(n_nodes: int, n_edges: int, in_channels: int, out_channels: 
         streamed   every eligible call whose chain `dims` the library generates (chain_any_supported; `dims` None: the caller checks its
                chain itself and asks again with mode="off" for one that is not, as NNConv_old does) runs from the edge attributes,
                hidden rows by node block (gpde_nnconv_*_chain_any: neither per-edge tensor is formed; `bytes_streamed` is what the
-               route holds besides one block of its budget); the others as `off`"""
+               route holds besides one block of its budget); the others as `off`
+    `acts` (ops.mlp_chain; None or all ReLU: everything above): a chain with another hidden activation (gpde_nnconv_*_chain_act) is
+    eligible for the STREAMED route only - `eligible` stays False, `eligible_streamed` says it:
+        streamed   streamed, as above
+        auto       materialised whenever that fits, as today; a call that today is refused runs streamed (refused when twice
+                   `bytes_streamed` is not free either)
+        on, off    unchanged: materialised, or refused when it does not fit
+    and `bytes_streamed` also counts the pre-activation rows U_l that the backward keeps for GELU, GELU_TANH, SILU and SIN, for a
+    block of the preferred budget (they are spent from the block budget: such a chain has fewer edges per block)."""
     mode = ANY_REASSOC if mode is None else mode
     if mode not in ("auto", "on", "off", "streamed"):
         raise ValueError(f"GPDE_ANY_REASSOC must be auto, on or off, got {mode!r}")
     n, e, cin, cout = int(n_nodes), int(n_edges), int(in_channels), int(out_channels)
     k = None if k_hidden is None else int(k_hidden)
-    eligible = bool(chain) and aggr in ("add", "mean") and k is not None and 1 <= k <= ANY_MAX_HIDDEN
+    streamable = bool(chain) and aggr in ("add", "mean") and k is not None and 1 <= k <= ANY_MAX_HIDDEN
+    eligible = streamable and acts_all_relu(acts)
+    if streamable and not eligible:
+        return _act_chain_route(n, e, cin, cout, k, free_bytes, mode, dims, acts)
     bytes_m = e * cin * cout * 4
     out = {"eligible": eligible, "bytes_materialised": bytes_m, "bytes_reassociated": None, "node_block": None,
            "flops_materialised": None if k is None else 2 * e * k * cin * cout, "flops_reassociated": None, "bytes_streamed": None}

@@ -629,6 +629,60 @@ GPDE_API int gpde_nnconv_bwd_chain_any(const float* x_src, int64_t n_src, const 
                               float* grad_bias, const int32_t* src_rowptr, const int32_t* src_slots, const int32_t* block_nodes,
                               int64_t n_blocks, int32_t* n_bad, void* ws, size_t ws_bytes, void* stream);
 
+/* The same operator for a chain whose hidden layers have OTHER ACTIVATIONS than the ReLU (gpde_chain_any.hip):
+ *     hidden = act_{n-1}(L_{n-1}(... act_1(L_1(edge_attr)) ...)),     one kind per hidden layer, mixed chains allowed.
+ *   The four entry points below mirror the `_chain_any` four argument for argument, with two more HOST arrays after `dims`:
+ *     act_kinds   n_linear - 1 entries, GPDE_ACT_* (NULL: all GPDE_ACT_RELU);
+ *     act_params  [n_linear - 1][2] floats (NULL: zeros): [l][0] is LEAKY_RELU's slope (finite, >= 0) or ELU's alpha (finite, > 0),
+ *                 [l][1] is reserved (finite).
+ *   An unknown kind: GPDE_EUNSUPPORTED; a slope < 0, an alpha <= 0 or a non-finite parameter: GPDE_EINVAL.  A table and its workspace
+ *   sizes belong to the kinds they were asked for.  The `_chain_any` entry points are the all-RELU call of the same body; an all-RELU
+ *   call here gives their sizes and their bits.
+ *     kind                   h = act(u)                                act' is computed from
+ *     GPDE_ACT_RELU          max(u, 0)                                 h   (h > 0)
+ *     GPDE_ACT_LEAKY_RELU    u > 0 ? u : slope u                       h   (h > 0 ? 1 : slope)
+ *     GPDE_ACT_ELU           u > 0 ? u : alpha (e^u - 1)               h   (h > 0 ? 1 : h + alpha)
+ *     GPDE_ACT_TANH          tanh u                                    h   (1 - h^2)
+ *     GPDE_ACT_SIGMOID       1 / (1 + e^-u)                            h   (h (1 - h))
+ *     GPDE_ACT_GELU          u (1 + erf(u / sqrt 2)) / 2               u
+ *     GPDE_ACT_GELU_TANH     torch's GELU(approximate='tanh')          u
+ *     GPDE_ACT_SILU          u / (1 + e^-u)                            u
+ *     GPDE_ACT_SIN           sin u                                     u
+ *   fp32 with the accurate device functions; branches select, so a saturated unit (|u| past expf's range) gives its finite limit.
+ *   Memory: a kind whose derivative comes from h keeps what the ReLU chain keeps; one that needs u keeps U_l next to H_l in the
+ *   backward's recompute pass - one more [block edges][K_l padded to 4] buffer per such layer, counted by the plan's budget (fewer
+ *   edges per block) and by *ws_bwd.  *ws_fwd does not depend on the kinds.  Determinism as above, for every kind.
+ * Additions to the ABI: GPDE_VERSION is unchanged. */
+#define GPDE_ACT_RELU 0
+#define GPDE_ACT_LEAKY_RELU 1
+#define GPDE_ACT_ELU 2
+#define GPDE_ACT_TANH 3
+#define GPDE_ACT_SIGMOID 4
+#define GPDE_ACT_GELU 5
+#define GPDE_ACT_GELU_TANH 6
+#define GPDE_ACT_SILU 7
+#define GPDE_ACT_SIN 8
+GPDE_API int gpde_nnconv_chain_act_plan(const int32_t* rowptr_host, int64_t n_dst, int64_t n_edges, int n_linear, const int32_t* dims,
+                               const int32_t* act_kinds, const float* act_params, int in_src, int in_dst, int out_channels,
+                               size_t budget_bytes, int32_t* block_nodes_out, int64_t* n_blocks, size_t* ws_fwd, size_t* ws_bwd);
+GPDE_API int gpde_nnconv_chain_act_workspace_bytes(const int32_t* block_nodes, int64_t n_blocks, int64_t n_dst, int64_t n_edges,
+                                          int n_linear, const int32_t* dims, const int32_t* act_kinds, const float* act_params,
+                                          int in_src, int in_dst, int out_channels, size_t* ws_fwd, size_t* ws_bwd);
+GPDE_API int gpde_nnconv_fwd_chain_act(const float* x_src, int64_t n_src, const float* x_dst, int64_t n_dst, int square,
+                              const float* edge_attr, int64_t n_edges, const int32_t* rowptr, const int32_t* src, int n_linear,
+                              const int32_t* dims, const int32_t* act_kinds, const float* act_params, const float* const* weights,
+                              const float* const* biases, const float* root, const float* bias, int aggr, int in_src, int in_dst,
+                              int out_channels, const int32_t* block_nodes, int64_t n_blocks, float* out, int32_t* n_bad, void* ws,
+                              size_t ws_bytes, void* stream);
+GPDE_API int gpde_nnconv_bwd_chain_act(const float* x_src, int64_t n_src, const float* x_dst, int64_t n_dst, int square,
+                              const float* edge_attr, int64_t n_edges, const int32_t* rowptr, const int32_t* src, int n_linear,
+                              const int32_t* dims, const int32_t* act_kinds, const float* act_params, const float* const* weights,
+                              const float* const* biases, const float* root, int aggr, int in_src, int in_dst, int out_channels,
+                              const float* grad_out, float* grad_x_src, float* grad_x_dst, float* grad_edge_attr,
+                              float* const* grad_w, float* const* grad_b, float* grad_root, float* grad_bias,
+                              const int32_t* src_rowptr, const int32_t* src_slots, const int32_t* block_nodes, int64_t n_blocks,
+                              int32_t* n_bad, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Edge attributes on the fly (opt-in): the `node_attr` argument (GpdeNodeAttr, declared at the top).
  * The reference materialises edge_attr[e] = [pos_src(2), pos_dst(2), a_src, a_dst] from node data
