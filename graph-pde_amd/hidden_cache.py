@@ -79,43 +79,65 @@ WE_SMALL_EDGES = 8192          # calls up to this many edges qualify whatever th
 stats = {"hits": 0, "builds": 0, "direct": 0, "we_hits": 0, "we_builds": 0}       # counters for tests / bench
 
 
-class _Entry:
-    __slots__ = ("key", "hidden", "token", "attr_ref", "csr", "last_key", "repeats", "hits_on_hidden", "hn", "we", "we_key",
-                 "we_refs", "big_key", "dkey", "dtoken", "dvirtual", "dcount", "drefs", "twe", "twe_key", "twe_token", "twe_h", "last_partial",
-                 "key_refs", "dkey_refs", "we_key_refs", "twe_key_refs", "tag", "dtag", "we_tag", "twe_tag")
+def _param_refs(params) -> tuple:
+    """Weak references to the parameter objects a key was built from, kept next to the key (as ops.pack_mlp does).  A key names a
+    parameter by (data_ptr, version); a NEW tensor object - `conv.nn = new_mlp.to(dev)`, the device copy ops.stage_const makes
+    again after its cache evicted the last one - starts at version 0 and often at the address the old one just freed.  A live
+    object keeps its address, a dead one fails `_same_params`: equal keys then really mean the same parameters."""
+    return tuple(None if p is None else weakref.ref(p) for p in params)
+
+
+def _same_params(refs, params) -> bool:
+    return refs is not None and len(refs) == len(params) and \
+        all((p is None) if r is None else (r() is p) for r, p in zip(refs, params))
+
+
+class _Slot(ops.Cached):
+    """One cached value of a module: the record with the `key` it was built for, `refs` - weak references to the parameter OBJECTS
+    the key names (_param_refs) - and the validity `token` its autograd node clears (None where the value has none)."""
+    __slots__ = ("key", "refs", "token")
 
     def __init__(self):
-        self.key = None
-        self.hidden = None
-        self.token = None
-        self.attr_ref = None        # strong reference: pins the memory behind `key`
-        self.csr = None
-        self.last_key = None
-        self.repeats = False        # this module has been seen repeating a key
-        self.hits_on_hidden = 0
-        self.hn = 0                 # nodes whose in-edges the cached H covers (all of them unless partial)
-        self.we = None              # per-edge weights [E, 4096] (inference) and the key they were built for
-        self.we_key = None
-        self.we_refs = None         # pins edge_attr / csr behind we_key
-        self.big_key = None         # key of the last call whose H was wanted but exceeded the budget
-        self.dkey = None            # depth-deferred backward: key, token and tensor of the current virtual H,
-        self.dtoken = None          # applications hanging on it, pinned edge_attr / csr
-        self.dvirtual = None
-        self.dcount = 0
-        self.drefs = None
-        self.twe = None             # training: W_e as an autograd node shared by the applications of a step, its key,
-        self.twe_key = None         # validity token (cleared by its backward) and the H tensor it was built from
-        self.twe_token = None
-        self.last_partial = None    # (n_edges, hn) of the last PARTIAL H built: the next build keeps that size while it still fits (see lookup)
-        self.twe_h = None
-        # weak references to the parameter OBJECTS behind key / dkey / we_key / twe_key (_param_refs): the keys name parameters by
-        # address + version, and both repeat when a replaced parameter lands on the freed address of the old one
-        self.key_refs = None
-        self.dkey_refs = None
-        self.we_key_refs = None
-        self.twe_key_refs = None
-        # where hidden / dvirtual / we / twe were built (ops.StreamTag): a hit from another stream goes through ops.order_hit
-        self.tag = self.dtag = self.we_tag = self.twe_tag = None
+        super().__init__()
+        self.key = self.refs = self.token = None
+
+    def holds(self, key, params) -> bool:        # is the value still the one for this call?
+        return self.value is not None and self.key == key and (self.token is None or self.token.valid) and \
+            _same_params(self.refs, params)
+
+    def store(self, value, key, params, pins, token=None, extra_buffers=()):
+        self.value, self.key, self.refs, self.token = value, key, _param_refs(params), token
+        self.buffers, self.pins = (value,) + tuple(extra_buffers), tuple(pins)
+        self.stamp(value.device)
+
+    def clear(self):
+        self.__init__()
+
+
+def _field(slot: str, attr: str):
+    return property(lambda ent: getattr(getattr(ent, slot), attr))
+
+
+class _Entry:
+    __slots__ = ("h", "hn", "w", "tw", "d", "dcount", "last_key", "repeats", "hits_on_hidden", "big_key", "last_partial")
+    # READ-ONLY views under the names the slots' fields had on the entry itself: the benchmark (hidden, hn) and the call-history
+    # tests read them.  Nothing is written through them - a value enters a slot through `store` alone.
+    hidden, token, we, dvirtual = _field("h", "value"), _field("h", "token"), _field("w", "value"), _field("d", "value")
+    twe, twe_token, dtoken = _field("tw", "value"), _field("tw", "token"), _field("d", "token")
+    csr = property(lambda ent: ent.h.pins[1] if ent.h.pins else None)
+
+    def __init__(self):
+        # h: H, pins (edge_attr, csr), its token's hmax is a buffer too; w: per-edge weights [E, 4096] (inference), pins (edge_attr, csr);
+        # tw: training, W_e as an autograd node shared by the applications of a step, pin: the H it was built from;
+        # d: depth-deferred backward, the current virtual H, pins (edge_attr, csr)
+        self.h, self.w, self.tw, self.d = _Slot(), _Slot(), _Slot(), _Slot()
+        # hn: nodes whose in-edges the cached H covers (all of them unless partial); dcount: applications hanging on the virtual H
+        self.hn, self.dcount = 0, 0
+        # policy state - what was learnt about the module: last_key; repeats: it has been seen repeating a key; hits_on_hidden; big_key:
+        # key of the last call whose H was wanted but exceeded the budget; last_partial: (n_edges, hn) of the last PARTIAL H built - the
+        # next build keeps that size while it still fits (see lookup)
+        self.last_key = self.big_key = self.last_partial = None
+        self.repeats, self.hits_on_hidden = False, 0
 
 
 _entries: "weakref.WeakKeyDictionary[torch.nn.Module, _Entry]" = weakref.WeakKeyDictionary()
@@ -132,15 +154,14 @@ def release_all() -> bool:
     ops._alloc_ws when a workspace does not fit.  Returns whether anything was released."""
     freed = False
     for ent in list(_entries.values()):
-        if ent.hidden is not None or ent.we is not None:
-            freed = True
-        if ent.token is not None:
-            ent.token.gh_acc, ent.token.gh_adds = None, 0
-        ent.hidden, ent.key, ent.token, ent.attr_ref, ent.csr = None, None, None, None, None
-        ent.we, ent.we_key, ent.we_refs = None, None, None
-        ent.twe, ent.twe_key, ent.twe_token, ent.twe_h = None, None, None, None     # (nodes of a live graph keep their own references)
-        if ent.dtoken is not None:
-            ent.dtoken.hpart = None          # applications still hanging on the virtual H recompute instead (same mathematics)
+        freed = freed or ent.h.value is not None or ent.w.value is not None
+        if ent.h.token is not None:
+            ent.h.token.gh_acc, ent.h.token.gh_adds = None, 0
+        # On purpose: the virtual-H node `d` stays (it owns no H of its own, only `hpart`), and no policy state is reset
+        for slot in (ent.h, ent.w, ent.tw):        # (nodes of a live graph keep their own references)
+            slot.clear()
+        if ent.d.token is not None:
+            ent.d.token.hpart = None         # applications still hanging on the virtual H recompute instead (same mathematics)
     if freed:
         stats["released"] = stats.get("released", 0) + 1
     return freed
@@ -152,38 +173,22 @@ def snapshot() -> list:
     them under it - ADVICE r5)."""
     pins = []
     for ent in list(_entries.values()):
-        pins.append((ent.hidden, ent.we, ent.twe, ent.twe_h, ent.attr_ref, ent.csr, ent.we_refs, ent.drefs, ent.dvirtual,
-                     None if ent.dtoken is None else ent.dtoken.hpart))
+        pins.extend(slot.held() for slot in (ent.h, ent.w, ent.tw, ent.d))
+        pins.append(None if ent.d.token is None else ent.d.token.hpart)
     return pins
 
 
-def _param_refs(params) -> tuple:
-    """Weak references to the parameter objects a key was built from, kept next to the key (as ops.pack_mlp does).  A key names a
-    parameter by (data_ptr, version); a NEW tensor object - `conv.nn = new_mlp.to(dev)`, the device copy ops.stage_const makes
-    again after its cache evicted the last one - starts at version 0 and often at the address the old one just freed.  A live
-    object keeps its address, a dead one fails `_same_params`: equal keys then really mean the same parameters."""
-    return tuple(None if p is None else weakref.ref(p) for p in params)
-
-
-def _same_params(refs, params) -> bool:
-    return refs is not None and len(refs) == len(params) and \
-        all((p is None) if r is None else (r() is p) for r, p in zip(refs, params))
+def _pkey(p: Optional[torch.Tensor]) -> tuple:
+    return (0, 0) if p is None else (p.data_ptr(), ops._ver(p))
 
 
 def _key(edge_attr, csr, hidden_params: List[Optional[torch.Tensor]], precision: str):
-    ops.watch(edge_attr.table if isinstance(edge_attr, ops.NodeAttr) else edge_attr, *hidden_params)
-    if isinstance(edge_attr, ops.NodeAttr):      # attributes described by node data: keyed on the table's memory + version + slots
-        tb = edge_attr.table
-        grad = torch.is_grad_enabled() and any(p is not None and p.requires_grad for p in hidden_params)
-        return (str(tb.device), tb.untyped_storage().data_ptr(), tb.storage_offset(), tuple(tb.shape), tuple(tb.stride()),
-                ops._ver(tb), tuple(edge_attr.sel), id(csr),
-                tuple((0, 0) if p is None else (p.data_ptr(), ops._ver(p)) for p in hidden_params), precision, grad)
-    st = edge_attr.untyped_storage()
+    node = isinstance(edge_attr, ops.NodeAttr)   # attributes described by node data: keyed on the table's memory + version + slots
+    t = edge_attr.table if node else edge_attr
+    ops.watch(t, *hidden_params)
     grad = torch.is_grad_enabled() and any(p is not None and p.requires_grad for p in hidden_params)
-    return (str(edge_attr.device), st.data_ptr(), edge_attr.storage_offset(), tuple(edge_attr.shape),
-            tuple(edge_attr.stride()), ops._ver(edge_attr), id(csr),
-            tuple((0, 0) if p is None else (p.data_ptr(), ops._ver(p)) for p in hidden_params),
-            precision, grad)
+    return (str(t.device),) + ops.mem_key(t) + ((tuple(edge_attr.sel),) if node else ()) + \
+        (id(csr), tuple(_pkey(p) for p in hidden_params), precision, grad)
 
 
 def lookup(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, weights, biases,
@@ -208,30 +213,31 @@ def lookup(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, weights, b
     ent = _entries.get(module)
     if ent is None:
         ent = _entries[module] = _Entry()
-    if ent.hidden is not None and ent.key == key and ent.token.valid and _same_params(ent.key_refs, hw + hb):
+    h = ent.h
+    if h.holds(key, hw + hb):
         ent.hits_on_hidden += 1
         # a backward pass that never reached the H node (input gradients only, an exception) left its running dL/dH sum on the
         # token: [E, K2P], 24 GB at s=121.  Dropped at forward time - unless this forward runs INSIDE a backward pass
         # (a checkpointed segment recomputing): the sum then belongs to the pass in flight
         if not in_backward_pass():
-            ent.token.gh_acc, ent.token.gh_adds = None, 0
+            h.token.gh_acc, h.token.gh_adds = None, 0
         if ent.hn == csr.n_nodes or allow_partial:
             stats["hits"] += 1
             if ent.hn < csr.n_nodes:
                 ent.big_key = key
-            ops.order_hit(ent.tag, "hidden", (ent.hidden, ent.token.hmax))
-            return ent.hidden, ent.token.hmax, ent.hn
+            h.hit("hidden")
+            return h.value, h.token.hmax, ent.hn
     repeated = ent.last_key == key
     if repeated:
         ent.repeats = True
-    elif ent.hidden is not None and ent.key != key and ent.hits_on_hidden == 0:
+    elif h.value is not None and h.key != key and ent.hits_on_hidden == 0:
         ent.repeats = False          # the last H was built and never reused: stop speculating
     ent.last_key = key
     row_bytes = ops.hidden_width(pm.dims) * 4
     nbytes = csr.n_edges * row_bytes
     want = mode == "on" or (mode == "auto" and ent.repeats)
     hn = csr.n_nodes
-    budget = budget_bytes(edge_attr.device, 0 if ent.hidden is None else ent.hidden.numel() * ent.hidden.element_size()) if want else 0
+    budget = budget_bytes(edge_attr.device, 0 if h.value is None else h.value.numel() * h.value.element_size()) if want else 0
     if want and nbytes > budget and PARTIAL and allow_partial and len(pm.dims) == 4:
         # the leading nodes whose in-edges fit the budget, in whole 64-node tiles; worth it from 1/8 on
         rp = csr.rowptr_host
@@ -246,14 +252,14 @@ def lookup(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, weights, b
             hn = lp[1]
         nbytes = int(rp[hn]) * row_bytes if hn >= csr.n_nodes // 8 and hn > 0 else budget + 1
     if not want or nbytes > budget or csr.n_edges == 0 or edge_attr.requires_grad:
-        ent.hidden, ent.key, ent.token, ent.attr_ref, ent.csr = None, None, None, None, None
+        h.clear()                    # (on purpose: last_partial and repeats stay, big_key is set anew)
         ent.big_key = key if (want and nbytes > budget and csr.n_edges > 0 and not edge_attr.requires_grad) else None
         stats["direct"] += 1
         return None
-    token = HiddenToken()
-    ent.hidden = None                # release the previous H before allocating the next one
-    if ent.dtoken is not None:
-        ent.dtoken.hpart = None      # ... also where a finished virtual-H node still points at it
+    token, old = HiddenToken(), h.token
+    h.clear()                        # release the previous H before allocating the next one
+    if ent.d.token is not None:
+        ent.d.token.hpart = None     # ... also where a finished virtual-H node still points at it
     try:
         if hn < csr.n_nodes:         # partial: no autograd node (inference, or training on the virtual-H node: lookup_deferred)
             hidden, token.hmax = ops.hidden_forward_raw(csr, edge_attr.detach(), pm, list(weights[:-1]) + [None],
@@ -263,16 +269,15 @@ def lookup(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, weights, b
     except torch.OutOfMemoryError:
         # the budget was measured a moment ago; another module's cache, another process or the caller's own tensors may have
         # taken the room since.  H is an optimisation: drop everything cached and run the direct path.
-        ent.hidden, ent.key, ent.token, ent.attr_ref, ent.csr = None, None, None, None, None
+        if old is not None:
+            old.gh_acc, old.gh_adds = None, 0        # (as release_all does for the token of an H still in its slot)
         release_all()
         torch.cuda.empty_cache()
         stats["oom_fallbacks"] = stats.get("oom_fallbacks", 0) + 1
         stats["direct"] += 1
         return None
-    ent.key, ent.hidden, ent.token, ent.attr_ref, ent.csr, ent.hn = key, hidden, token, edge_attr, csr, hn
-    ent.key_refs = _param_refs(hw + hb)
-    ent.tag = ops.stream_tag(hidden.device)
-    ent.hits_on_hidden = 0
+    h.store(hidden, key, hw + hb, (edge_attr, csr), token, (token.hmax,))      # (hmax: a device scalar the hidden forward reads)
+    ent.hn, ent.hits_on_hidden = hn, 0
     if hn < csr.n_nodes:
         ent.big_key = key            # the whole H does not fit: a training call shares a virtual-H node (lookup_deferred)
         ent.last_partial = (csr.n_edges, hn)
@@ -292,11 +297,11 @@ def token_of(module: torch.nn.Module, hidden: torch.Tensor, csr=None):
     (edge_weights_qualify): there W_e's backward is a second kind of consumer of H, and an application can fall from one form to the
     other when memory is short - the in-place sum wants NNConvHiddenFunction to be H's only consumer."""
     ent = _entries.get(module)
-    if ent is None or ent.hidden is not hidden or ent.token is None or not ent.token.valid:
+    if ent is None or ent.h.value is not hidden or ent.h.token is None or not ent.h.token.valid:
         return None
     if csr is not None and WE_MODE != "off" and edge_weights_qualify(csr, explicit=True):
         return None
-    return ent.token
+    return ent.h.token
 
 
 def lookup_deferred(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, weights, biases, aggr: str,
@@ -321,22 +326,23 @@ def lookup_deferred(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, w
     # the virtual node also saved the LAST Linear (its deferred pass forms dL/dH through it): a node built before a write to that
     # layer - by a forward whose backward never ran - must not serve the next step
     w_last, b_last = weights[-1], biases[-1]
-    dkey = (key, (w_last.data_ptr(), ops._ver(w_last)), (0, 0) if b_last is None else (b_last.data_ptr(), ops._ver(b_last)))
+    dkey = (key, _pkey(w_last), _pkey(b_last))
     named = hw + hb + [w_last, b_last]
-    if ent.dtoken is not None and ent.dkey == dkey and ent.dtoken.valid and _same_params(ent.dkey_refs, named):
+    d = ent.d
+    if d.holds(dkey, named):
         ent.dcount += 1
-        ent.dtoken.hpart = hpart
+        d.token.hpart = hpart
         # (not from a forward that runs inside a backward pass - a checkpointed segment: the pairs are that pass's own)
-        if not in_backward_pass() and ent.dtoken.drop_stale():      # a backward over this (still valid) node ended without its deferred pass
+        if not in_backward_pass() and d.token.drop_stale():      # a backward over this (still valid) node ended without its deferred pass
             stats["deferred_stale_dropped"] = stats.get("deferred_stale_dropped", 0) + 1
         stats["deferred_hits"] = stats.get("deferred_hits", 0) + 1
-        ops.order_hit(ent.dtag, "deferred", (ent.dvirtual,))
-        return ent.dvirtual, ent.dtoken
-    if ent.dtoken is not None and ent.dcount <= 1:
+        d.hit("deferred")
+        return d.value, d.token
+    if d.token is not None and ent.dcount <= 1:
         ent.repeats = False             # the last virtual H served a single application: stop speculating
-    if ent.dtoken is not None:
-        ent.dtoken.hpart = None
-    ent.dkey, ent.dtoken, ent.dvirtual, ent.drefs, ent.dcount = None, None, None, None, 0
+    if d.token is not None:
+        d.token.hpart = None
+    d.clear()                           # (dcount is read only while the slot holds a token: the next store sets it)
     if not ent.repeats or ent.big_key != key or not ops.deferred_supported(pm.dims):
         return None
     token = DeferredToken()
@@ -344,9 +350,8 @@ def lookup_deferred(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, w
     n = len(weights)
     virtual = DeferredHiddenFunction.apply(edge_attr, csr, aggr, token, n, *hw, w_last.detach(),
                                            *hb, None if b_last is None else b_last.detach())
-    ent.dkey, ent.dtoken, ent.dvirtual, ent.drefs, ent.dcount = dkey, token, virtual, (edge_attr, csr), 1
-    ent.dkey_refs = _param_refs(named)
-    ent.dtag = ops.stream_tag(virtual.device)
+    d.store(virtual, dkey, named, (edge_attr, csr), token)
+    ent.dcount = 1
     stats["deferred_builds"] = stats.get("deferred_builds", 0) + 1
     return virtual, token
 
@@ -370,7 +375,7 @@ def we_token_of(module: torch.nn.Module, we: torch.Tensor):
     """The token of the module's shared W_e node when `we` is that node (WeConvFunction sums the applications' gradients in place
     on it), else None."""
     ent = _entries.get(module)
-    return ent.twe_token if ent is not None and ent.twe is we else None
+    return ent.tw.token if ent is not None and ent.tw.value is we else None
 
 
 def lookup_edge_weights_train(module: torch.nn.Module, hidden: torch.Tensor, csr, pm, weights, biases):
@@ -381,20 +386,20 @@ def lookup_edge_weights_train(module: torch.nn.Module, hidden: torch.Tensor, csr
     if WE_MODE != "auto" or not edge_weights_qualify(csr) or not torch.is_grad_enabled():
         return None
     ent = _entries.get(module)
-    if ent is None or ent.hidden is not hidden:
+    if ent is None or ent.h.value is not hidden:
         return None
     w_last, b_last = weights[-1], biases[-1]
-    key = ((w_last.data_ptr(), ops._ver(w_last)), (0, 0) if b_last is None else (b_last.data_ptr(), ops._ver(b_last)))
-    if ent.twe is not None and ent.twe_h is hidden and ent.twe_key == key and ent.twe_token.valid and \
-            _same_params(ent.twe_key_refs, [w_last, b_last]):
+    key = (id(hidden), _pkey(w_last), _pkey(b_last))       # (the H it was built from: pinned by the slot, so its id names it)
+    twe = ent.tw
+    if twe.holds(key, [w_last, b_last]):
         stats["we_hits"] += 1
         # (a backward pass that never reached the W_e node left its running sums on the token; a forward inside a backward pass -
         # a checkpointed segment - leaves them alone, as `lookup` does)
         if not in_backward_pass():
-            ent.twe_token.gh_acc, ent.twe_token.gh_adds, ent.twe_token.side_acc = None, 0, None
-        ops.order_hit(ent.twe_tag, "edge_weights", (ent.twe,))
-        return ent.twe
-    ent.twe, ent.twe_key, ent.twe_token, ent.twe_h = None, None, None, None
+            twe.token.gh_acc, twe.token.gh_adds, twe.token.side_acc = None, 0, None
+        twe.hit("edge_weights")
+        return twe.value
+    twe.clear()
     # memory of the training form: W_e, one dL/dW_e per application in flight and autograd's running sum of them - 16 KiB per
     # edge each (the budget bounded W_e only).  When three of them do not fit what is free, the H path runs.
     free, _ = ops.device_free_bytes(hidden.device)
@@ -408,9 +413,7 @@ def lookup_edge_weights_train(module: torch.nn.Module, hidden: torch.Tensor, csr
         torch.cuda.empty_cache()
         stats["oom_fallbacks"] = stats.get("oom_fallbacks", 0) + 1
         return None
-    ent.twe, ent.twe_key, ent.twe_token, ent.twe_h = we, key, token, hidden
-    ent.twe_key_refs = _param_refs([w_last, b_last])
-    ent.twe_tag = ops.stream_tag(we.device)
+    twe.store(we, key, [w_last, b_last], (hidden,), token)
     stats["we_builds"] += 1
     return we
 
@@ -426,36 +429,31 @@ def lookup_edge_weights(module: torch.nn.Module, edge_attr: torch.Tensor, csr, p
     precision = ops.DEFAULT_PRECISION if precision is None else precision
     ent = _entries.get(module)
     w_last, b_last = weights[-1], biases[-1]
-    key = (_key(edge_attr, csr, list(weights[:-1]) + list(biases[:-1]), precision)[:-1],
-           (w_last.data_ptr(), ops._ver(w_last)), (0, 0) if b_last is None else (b_last.data_ptr(), ops._ver(b_last)))
+    hparams = list(weights[:-1]) + list(biases[:-1])
+    key = (_key(edge_attr, csr, hparams, precision)[:-1], _pkey(w_last), _pkey(b_last))
     params = list(weights) + list(biases)
-    if ent is not None and ent.we is not None and ent.we_key == key and _same_params(ent.we_key_refs, params):
+    if ent is not None and ent.w.holds(key, params):
         stats["we_hits"] += 1
-        ops.order_hit(ent.we_tag, "edge_weights", (ent.we,))
-        return ent.we
+        ent.w.hit("edge_weights")
+        return ent.w.value
     now = force or explicit
     if not now:
         # peek only: the H policy (who repeats, who gets built) is driven by ONE lookup() per call, made by the caller's
         # ordinary path.  W_e is derived from an H that is already there - i.e. from the call after H was built.
-        hkey = _key(edge_attr, csr, list(weights[:-1]) + list(biases[:-1]), precision)
-        if ent is None or ent.hidden is None or ent.key != hkey or not ent.token.valid or ent.hn != csr.n_nodes or \
-                not _same_params(ent.key_refs, list(weights[:-1]) + list(biases[:-1])):
+        if ent is None or not ent.h.holds(_key(edge_attr, csr, hparams, precision), hparams) or ent.hn != csr.n_nodes:
             return None
     hit = lookup(module, edge_attr, csr, pm, weights, biases, precision, mode="on" if now else None, allow_partial=False)
     ent = _entries.get(module)
+    if ent is not None:
+        ent.w.clear()                   # (a hit on H: release the previous tensor before allocating the next one)
     if hit is None or hit[2] != csr.n_nodes:
-        if ent is not None:
-            ent.we, ent.we_key, ent.we_refs = None, None, None
         return None
-    ent.we = None                       # release the previous tensor before allocating the next one
     try:
-        ent.we = ops.edge_weights_raw(hit[0].detach(), pm, w_last, b_last)
+        we = ops.edge_weights_raw(hit[0].detach(), pm, w_last, b_last)
     except torch.OutOfMemoryError:      # 16 KiB per edge: an optimisation like H - on OOM the ordinary path runs
-        ent.we, ent.we_key, ent.we_refs = None, None, None
         torch.cuda.empty_cache()
         stats["oom_fallbacks"] = stats.get("oom_fallbacks", 0) + 1
         return None
-    ent.we_key, ent.we_refs, ent.we_key_refs = key, (edge_attr, csr), _param_refs(params)
-    ent.we_tag = ops.stream_tag(ent.we.device)
+    ent.w.store(we, key, params, (edge_attr, csr))
     stats["we_builds"] += 1
-    return ent.we
+    return we

@@ -91,6 +91,81 @@ def _order_cross_stream(tag: StreamTag, stream, cache: str, buffers):
     cross_stream_hits[cache] = cross_stream_hits.get(cache, 0) + 1
 
 
+class Cached:
+    """One cached device value, declared ONCE where it is built.  `value`: what the cache hands out; `buffers`: the device tensors a
+    native call will read; `pins`: other objects kept alive only so that the key stays meaningful (the tensor or storage whose address
+    is in it, the `Csr`); `tag`: the StreamTag `stamp` makes right after the LAST build kernel was launched; `nbytes`: for byte bounds."""
+    __slots__ = ("value", "buffers", "pins", "tag", "nbytes")
+
+    def __init__(self, value=None, buffers=(), pins=(), nbytes: int = 0):
+        self.value, self.buffers, self.pins, self.tag, self.nbytes = value, buffers, pins, None, nbytes
+
+    def stamp(self, dev, synced: bool = False):
+        self.tag = stream_tag(dev, synced)
+        return self
+
+    def hit(self, cache: str):               # the only way a hit is ordered
+        tag = self.tag                       # (order_hit's own first test, made here too: on the builder's stream - every training
+        if tag is not None and _current_stream(tag.dev) != tag.stream:      # loop - the call is spared, 5 % of a csr_for hit)
+            order_hit(tag, cache, self.buffers)
+
+    def held(self) -> tuple:                 # the only thing a snapshot collects
+        return self.buffers + self.pins
+
+
+class Lru:
+    """Records by key in an insertion-ordered dict, least recently used first; `name`: what the cache is called in `cross_stream_hits`.  Over
+    `max_entries`, or over `max_bytes` in the running sum of the records' `nbytes`, the oldest go - the byte bound spares the last one."""
+
+    def __init__(self, name: str, max_entries: Optional[int] = None, max_bytes: Optional[int] = None):
+        self.name, self.max_entries, self.max_bytes = name, max_entries, max_bytes
+        self._d, self.nbytes = {}, 0
+
+    def get(self, key) -> Optional[Cached]:
+        d = self._d
+        rec = d.pop(key, None)
+        if rec is not None:
+            d[key] = rec                         # move to the MRU end
+        return rec
+
+    def put(self, key, rec: Cached):
+        self.pop(key)
+        self._d[key] = rec
+        self.nbytes += rec.nbytes
+        while (self.max_entries is not None and len(self._d) > self.max_entries) or \
+                (self.max_bytes is not None and len(self._d) > 1 and self.nbytes > self.max_bytes):
+            self.pop(next(iter(self._d)))
+
+    def pop(self, key) -> Optional[Cached]:
+        rec = self._d.pop(key, None)
+        self.nbytes -= 0 if rec is None else rec.nbytes
+        return rec
+
+    def clear(self):
+        self._d, self.nbytes = {}, 0
+
+    def __len__(self):
+        return len(self._d)
+
+    def __iter__(self):
+        return iter(self._d)
+
+    def values(self):
+        return self._d.values()
+
+
+class Pair(Cached):
+    """A record that still reads as the pair its cache held before, (pins[0], value): (source tensor, slot-ordered copy) in
+    `Csr._attr_sorted`, (weak references to the parameters, PackedMlp) in `_pack_cache`."""
+
+    def __getitem__(self, i):
+        return (self.pins[0], self.value)[i]
+
+
+def mem_key(t: torch.Tensor) -> tuple:       # the core of every cache key on a tensor's memory: where it lies, its layout, `_ver`
+    return (t.untyped_storage().data_ptr(), t.storage_offset(), t.shape, t.stride(), _ver(t))      # (Size and stride: tuples already)
+
+
 # ----------------------------------------------------------------------------------------------
 # destination-sorted CSR, cached per edge_index tensor
 # ----------------------------------------------------------------------------------------------
@@ -103,16 +178,15 @@ class Csr:
     dst: torch.Tensor      # int32 [E]  target node of each CSR slot (sorted ascending)
     perm: torch.Tensor     # int32 [E]  CSR slot -> original edge id (stable within a target)
     _rowptr_host: Optional[torch.Tensor] = None
-    _src_order: Optional[tuple] = None
+    _src_order: Optional[tuple] = None       # (src_rowptr, src_slots) - `src_order` - and the record that declares them
+    _src_order_rec: Optional[Cached] = None
     _attr_sorted: Optional[dict] = None      # edge_attr tensors gathered into CSR slot order (attr_in_slot_order)
-    _identity: Optional[torch.Tensor] = None
+    _identity: Optional[Cached] = None       # value: the identity permutation (attr_in_slot_order)
     _perm_is_identity: bool = False
     _max_in_degree: Optional[int] = None
     n_src_nodes: Optional[int] = None        # a RECTANGULAR graph: `src` indexes this many source nodes, `n_nodes` counts the destination
     #                                          rows (rowptr has n_nodes + 1 entries); None: square, one node set
     _flow_flipped: bool = False              # built from edge_index with its rows swapped (flow='target_to_source' of the module)
-    _src_order_tag: Optional[StreamTag] = None   # where src_order was built (order_hit)
-    _identity_tag: Optional[StreamTag] = None    # where _identity was built (attr_in_slot_order)
     _chain_blocks: Optional[dict] = None         # block tables of the streamed any-width route (chain_any_blocks), host only
 
     @property
@@ -147,10 +221,13 @@ class Csr:
                 rc = lib.gpde_csr_source_order(self.src.data_ptr(), self.n_edges, n_src, srp.data_ptr(),
                                                ssl.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
             _lib.check(rc, "gpde_csr_source_order")
-            self._src_order, self._src_order_tag = (srp, ssl), stream_tag(dev)
-            return self._src_order
-        order_hit(self._src_order_tag, "src_order", self._src_order)
+            self._src_order, self._src_order_rec = (srp, ssl), Cached(buffers=(srp, ssl)).stamp(dev)
+        elif self._src_order_rec is not None:        # (none: a source order that was handed in, not built here)
+            self._src_order_rec.hit("src_order")
         return self._src_order
+
+    def records(self) -> list:               # of what was built on this graph on first use (cache_snapshot)
+        return [r for r in (self._src_order_rec, self._identity, *(self._attr_sorted or {}).values()) if r is not None]
 
     @property
     def edge_index(self) -> torch.Tensor:
@@ -259,7 +336,7 @@ def staging_device() -> torch.device:
     return torch.device("cuda", torch.cuda.current_device())
 
 
-_stage_cache: "dict[tuple, tuple]" = {}        # constant inputs (edge_index, edge_attr) staged once per tensor
+_stage_cache = Lru("stage_const", max_entries=16)      # constant inputs (edge_index, edge_attr) staged once per tensor; pins: the CPU storage
 
 
 def stage_const(t: torch.Tensor, dev: torch.device) -> torch.Tensor:
@@ -267,15 +344,13 @@ def stage_const(t: torch.Tensor, dev: torch.device) -> torch.Tensor:
     storage + version so that the `depth` applications of one forward share the copy (and its CSR)."""
     if t.is_cuda:
         return t
-    st = t.untyped_storage()
-    key = (st.data_ptr(), t.storage_offset(), tuple(t.shape), tuple(t.stride()), t.dtype, _ver(t), str(dev))
-    hit = _stage_cache.pop(key, None)
+    key = mem_key(t) + (t.dtype, str(dev))
+    hit = _stage_cache.get(key)
     if hit is None:
-        hit = (st, t.detach().to(dev))
-    _stage_cache[key] = hit                     # MRU
-    while len(_stage_cache) > 16:
-        _stage_cache.pop(next(iter(_stage_cache)))
-    return hit[1]
+        copy = t.detach().to(dev)
+        hit = Cached(copy, (copy,), (t.untyped_storage(),))
+        _stage_cache.put(key, hit)
+    return hit.value
 
 
 def gather_rows(rows: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
@@ -320,31 +395,29 @@ def attr_in_slot_order(csr: "Csr", edge_attr: torch.Tensor):
     if not ATTR_SLOT_ORDER or e < _ATTR_SLOT_ORDER_MIN_EDGES or edge_attr.requires_grad or edge_attr.dtype != torch.float32:
         return edge_attr, csr.perm
     if csr._identity is None:
-        csr._identity = torch.arange(e, dtype=torch.int32, device=csr.perm.device)
-        csr._identity_tag = stream_tag(csr.perm.device, synced=True)      # (complete: the probe below waits for the device)
+        ident = torch.arange(e, dtype=torch.int32, device=csr.perm.device)
+        csr._identity = Cached(ident, (ident,)).stamp(ident.device, synced=True)      # (complete: the probe below waits for the device)
         csr._attr_sorted = {}
         # is `perm` the identity (a graph already in slot order)?  A full comparison is a pass over 95.5 M indices plus a byte mask
         # of the same length on the headline graph - 21 of the 23 ms a NEW sample's first call spent here (profiles/
         # r06_attr_reorder_probe.txt; the gather itself is 2.2 ms).  A graph in the reference's source-major order fails the
         # comparison at almost every slot: 4096 sampled slots decide it; only a sample that passes is followed by the full check.
         probe = identity_probe(e, csr.perm.device)
-        csr._perm_is_identity = bool(torch.equal(csr.perm[probe], probe.to(torch.int32))) and bool(torch.equal(csr.perm, csr._identity))
+        csr._perm_is_identity = bool(torch.equal(csr.perm[probe], probe.to(torch.int32))) and bool(torch.equal(csr.perm, ident))
     if csr._perm_is_identity:
         return edge_attr, csr.perm
-    st = edge_attr.untyped_storage()
-    key = (st.data_ptr(), edge_attr.storage_offset(), tuple(edge_attr.shape), tuple(edge_attr.stride()), _ver(edge_attr))
+    key = mem_key(edge_attr)
     hit = csr._attr_sorted.get(key)
     if hit is None:
-        src = edge_attr.detach()
-        out = gather_rows(src, csr.perm)
+        out = gather_rows(edge_attr.detach(), csr.perm)
         while len(csr._attr_sorted) >= 2:
             csr._attr_sorted.pop(next(iter(csr._attr_sorted)))
-        hit = csr._attr_sorted[key] = (edge_attr, out, stream_tag(out.device))  # the source tensor is kept alive: its address is part of the key
+        hit = csr._attr_sorted[key] = Pair(out, (out,), (edge_attr,)).stamp(out.device)  # the source tensor is kept alive: its address is part of the key
     else:
-        order_hit(hit[2], "attr_slot_order", (hit[1],))
+        hit.hit("attr_slot_order")
     # the identity permutation serves every entry of this CSR, built or hit: kept for a stream other than the one it was made on
-    order_hit(csr._identity_tag, "attr_identity", (csr._identity,))
-    return hit[1], csr._identity
+    csr._identity.hit("attr_identity")
+    return hit.value, csr._identity.value
 
 
 def _require_cuda(t, name: str):
@@ -501,9 +574,7 @@ def _build_csr_general(edge_index: torch.Tensor, n_dst: int, n_src: Optional[int
     return Csr(n_dst, e, rowptr, src, dst, perm, _max_in_degree=max_deg, n_src_nodes=n_src, _flow_flipped=flip)
 
 
-_csr_cache: "dict[tuple, tuple]" = {}      # key -> (storage kept alive, nbytes, Csr, StreamTag or None); LRU order
-_CSR_CACHE_MAX_ENTRIES = 64
-_CSR_CACHE_MAX_BYTES = 8 << 30
+_csr_cache = Lru("csr", max_entries=64, max_bytes=8 << 30)      # value: the Csr; pins: the index storage, nbytes: its size
 
 
 def csr_for(edge_index: torch.Tensor, n_nodes: int, n_src: Optional[int] = None, flip: bool = False) -> Csr:
@@ -519,25 +590,19 @@ def csr_for(edge_index: torch.Tensor, n_nodes: int, n_src: Optional[int] = None,
         if edge_index.n_src != (n_nodes if n_src is None else int(n_src)):
             raise ValueError(f"the CSR was built for {edge_index.n_src} source nodes, the call has {n_nodes if n_src is None else int(n_src)}")
         return edge_index
-    storage = edge_index.untyped_storage()
     watch(edge_index)
-    key = (str(edge_index.device), storage.data_ptr(), edge_index.storage_offset(),
-           tuple(edge_index.shape), tuple(edge_index.stride()), _ver(edge_index), n_nodes)
+    key = (str(edge_index.device), *mem_key(edge_index), n_nodes)
     if n_src is not None or flip:
         key = key + (None if n_src is None else int(n_src), bool(flip))
-    hit = _csr_cache.pop(key, None)
+    hit = _csr_cache.get(key)
     if hit is not None:
-        _csr_cache[key] = hit            # move to the MRU end
-        csr = hit[2]
-        if hit[3] is not None:               # (an entry without a tag - off the GPU - may be a stand-in without these arrays)
-            order_hit(hit[3], "csr", (csr.rowptr, csr.src, csr.dst, csr.perm))
-        return csr
+        hit.hit(_csr_cache.name)
+        return hit.value
     csr = build_csr(edge_index, n_nodes, n_src, flip)
+    storage = edge_index.untyped_storage()
     # (build_csr read the bad-edge count back: the arrays are complete - a hit from another stream only keeps them from being recycled)
-    _csr_cache[key] = (storage, storage.nbytes(), csr, stream_tag(edge_index.device, synced=int(edge_index.size(1)) > 0))
-    while len(_csr_cache) > _CSR_CACHE_MAX_ENTRIES or \
-            (len(_csr_cache) > 1 and sum(v[1] for v in _csr_cache.values()) > _CSR_CACHE_MAX_BYTES):
-        _csr_cache.pop(next(iter(_csr_cache)))
+    arrays = (csr.rowptr, csr.src, csr.dst, csr.perm) if edge_index.is_cuda else ()      # (off the GPU `csr` may be a stand-in without them)
+    _csr_cache.put(key, Cached(csr, arrays, (csr, storage), storage.nbytes()).stamp(edge_index.device, synced=int(edge_index.size(1)) > 0))
     return csr
 
 
@@ -557,14 +622,10 @@ def cache_snapshot() -> list:
     """Strong references to every device buffer the caches of this module own right now (CSRs with their source-order arrays
     and slot-ordered attribute copies, packed weights, staged constants): capture.py pins them for the lifetime of a recorded
     graph, whose kernels read those addresses whatever the LRU policies do afterwards."""
-    pins = [v for v in _csr_cache.values()] + [v[1] for v in _pack_cache.values()] + [v for v in _stage_cache.values()]
-    for v in _gcn_norm_cache.values():       # coefficients of the GCN normalisation, with the reversed graph where a backward built it
-        pins.append((v[2].csr, v[2].coef, v[2].self_coef, v[2]._reversed))
-    for v in _csr_cache.values():
-        srt = v[2]._attr_sorted
-        if srt:
-            pins.extend(srt.values())
-    return pins
+    recs = [r for cache in (_csr_cache, _pack_cache, _stage_cache, _gcn_norm_cache) for r in cache.values()]
+    for owner in [r.value for r in recs if isinstance(r.value, (Csr, GcnNorm))]:       # what a graph / a normalisation built on first use
+        recs.extend(owner.records())
+    return [r.held() for r in recs]
 
 
 def clear_param_caches():
@@ -578,11 +639,9 @@ def clear_caches():
     """Drop the CSR / packed-weight / staging caches.  REQUIRED after writing a parameter or an index tensor
     through `.data` (`p.data.add_(..)`, `p.data.clamp_()`, `dist.broadcast(p.data)`): such writes do not bump
     the version counter the cache keys are built on (tests/test_host_logic.py pins this contract)."""
-    _csr_cache.clear()
-    _pack_cache.clear()
+    for cache in (_csr_cache, _pack_cache, _stage_cache, _gcn_norm_cache):
+        cache.clear()
     _pack_by_ptr.clear()
-    _stage_cache.clear()
-    _gcn_norm_cache.clear()
     cross_stream_hits.clear()
 
 
@@ -716,12 +775,10 @@ class PackedMlp:
     dims: Tuple[int, ...]
     packed: torch.Tensor            # float32 flat buffer in libgpde layout
     dims_c: object                  # ctypes int32 array (kept alive)
-    tag: Optional[StreamTag] = None  # where pack_mlp built it (order_hit)
 
 
-_pack_cache: "dict[tuple, tuple]" = {}       # key -> (weakrefs of the parameters, PackedMlp); LRU order
+_pack_cache = Lru("pack_mlp", max_bytes=1 << 30)      # value: the PackedMlp; pins: (weak references to the parameters - a hit's liveness check,)
 _pack_by_ptr: "dict[tuple, tuple]" = {}      # parameter addresses -> current key (older versions are evicted)
-_PACK_CACHE_MAX_BYTES = 1 << 30
 
 
 def pack_mlp(weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Tensor]]) -> PackedMlp:
@@ -739,14 +796,11 @@ def pack_mlp(weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Te
     ptrs = tuple(w.data_ptr() for w in weights) + tuple(0 if b is None else b.data_ptr() for b in biases) + (dims,)
     key = tuple((w.data_ptr(), _ver(w)) for w in weights) + \
         tuple((0, 0) if b is None else (b.data_ptr(), _ver(b)) for b in biases) + (dims,)
-    hit = _pack_cache.pop(key, None)
-    if hit is not None:
-        refs, pm = hit
-        # same parameter objects still alive => the addresses were not recycled
-        if all(r() is t for r, t in zip(refs, list(weights) + [b for b in biases if b is not None])):
-            _pack_cache[key] = hit           # MRU
-            order_hit(pm.tag, "pack_mlp", (pm.packed,))
-            return pm
+    hit = _pack_cache.get(key)
+    # same parameter objects still alive => the addresses were not recycled
+    if hit is not None and all(r() is t for r, t in zip(hit.pins[0], list(weights) + [b for b in biases if b is not None])):
+        hit.hit(_pack_cache.name)
+        return hit.value
     dims_c = _lib.dims_array(dims)
     nbytes = int(lib.gpde_mlp_pack_bytes(n, dims_c))
     if nbytes == 0:
@@ -761,16 +815,11 @@ def pack_mlp(weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Te
     with torch.cuda.device(dev):
         rc = lib.gpde_mlp_pack(n, dims_c, wp, bp, packed.data_ptr(), nbytes, _stream_ptr(dev))
     _lib.check(rc, "gpde_mlp_pack")
-    pm = PackedMlp(dims, packed, dims_c, stream_tag(dev))
-    old_key = _pack_by_ptr.get(ptrs)
-    if old_key is not None:
-        _pack_cache.pop(old_key, None)       # the same parameters at an older version
-    refs = [weakref.ref(t) for t in list(weights) + [b for b in biases if b is not None]]
-    _pack_cache[key] = (refs, pm)
+    refs = tuple(weakref.ref(t) for t in list(weights) + [b for b in biases if b is not None])
+    pm = PackedMlp(dims, packed, dims_c)
+    _pack_cache.pop(_pack_by_ptr.get(ptrs))      # the same parameters at an older version, if there
+    _pack_cache.put(key, Pair(pm, (packed,), (refs,), packed.numel() * 4).stamp(dev))
     _pack_by_ptr[ptrs] = key
-    while len(_pack_cache) > 1 and sum(v[1].packed.numel() * 4 for v in _pack_cache.values()) > _PACK_CACHE_MAX_BYTES:
-        k0 = next(iter(_pack_cache))
-        _pack_cache.pop(k0)
     if len(_pack_by_ptr) > 4096:
         live = set(_pack_cache)
         for k in [k for k, v in _pack_by_ptr.items() if v not in live]:
@@ -2781,14 +2830,15 @@ class GcnNorm:
 
     def __init__(self, csr: Csr, coef: torch.Tensor, self_coef: torch.Tensor, flags: int):
         self.csr, self.coef, self.self_coef, self.flags = csr, coef, self_coef, flags
-        self._reversed = None
-        self._tag = self._reversed_tag = None       # where the coefficients / the reversed pair were built (order_hit)
+        self._rec = Cached(buffers=(coef, self_coef, csr.rowptr, csr.src, csr.dst, csr.perm))      # stamped by gcn_norm after its kernel
+        self._reversed: Optional[Cached] = None     # value: the reversed pair
 
     def order(self):
-        """A hit on this normalisation - from the cache of gcn_norm or from a module that pinned it (GCNConv(cached=True)): the
-        coefficients and the arrays of the graph they index, ordered for the current stream (order_hit)."""
-        csr = self.csr
-        order_hit(self._tag, "gcn_norm", (self.coef, self.self_coef, csr.rowptr, csr.src, csr.dst, csr.perm))
+        """A hit on this normalisation, from the cache of gcn_norm or from a module that pinned it (GCNConv(cached=True))."""
+        self._rec.hit("gcn_norm")
+
+    def records(self) -> list:
+        return [self._rec] if self._reversed is None else [self._rec, self._reversed]
 
     @property
     def reversed(self):
@@ -2799,21 +2849,19 @@ class GcnNorm:
         if self._reversed is None:
             csr = self.csr
             if csr.n_edges == 0:
-                self._reversed = (csr, self.coef)
+                self._reversed = Cached((csr, self.coef))        # (the forward arrays: nothing of its own to order)
             else:
                 rev = build_csr(csr.edge_index, csr.n_nodes, flip=True)
-                self._reversed = (rev, gather_rows(self.coef.view(-1, 1), rev.perm).view(-1))
-                self._reversed_tag = stream_tag(self.coef.device)
-                return self._reversed
-        if self._reversed_tag is not None:
-            rev, coef = self._reversed
-            order_hit(self._reversed_tag, "gcn_norm", (rev.rowptr, rev.src, rev.dst, rev.perm, coef))
-        return self._reversed
+                coef = gather_rows(self.coef.view(-1, 1), rev.perm).view(-1)
+                self._reversed = Cached((rev, coef), (rev.rowptr, rev.src, rev.dst, rev.perm, coef)).stamp(coef.device)
+        else:
+            self._reversed.hit("gcn_norm")
+        return self._reversed.value
 
 
-_gcn_norm_cache: "dict[tuple, tuple]" = {}       # key -> (Csr kept alive, edge_weight storage kept alive, GcnNorm, nbytes); LRU order
-_GCN_NORM_CACHE_MAX_ENTRIES = 64
-_GCN_NORM_CACHE_MAX_BYTES = 1 << 30                # what the entries pin: the CSR, the coefficients and - after a backward - the same again
+# value: the GcnNorm (it orders its own hits); pins: the Csr and the edge_weight storage; nbytes: what the entry keeps alive - the CSR,
+# the coefficients and - after a backward - the same again
+_gcn_norm_cache = Lru("gcn_norm", max_entries=64, max_bytes=1 << 30)
 
 
 def gcn_flags(improved: bool = False, add_self_loops: bool = True, normalize: bool = True) -> int:
@@ -2843,14 +2891,12 @@ def gcn_norm(csr: Csr, edge_weight: Optional[torch.Tensor] = None, improved: boo
         if edge_weight.requires_grad:
             raise NotImplementedError("the gradient with respect to edge_weight is not built: pass edge_weight.detach()")
         watch(edge_weight)
-        st = edge_weight.untyped_storage()
-        wkey = (st.data_ptr(), edge_weight.storage_offset(), tuple(edge_weight.shape), tuple(edge_weight.stride()), _ver(edge_weight))
+        wkey = mem_key(edge_weight)
     key = (id(csr), wkey, flags)
-    hit = _gcn_norm_cache.pop(key, None)
+    hit = _gcn_norm_cache.get(key)
     if hit is not None:
-        _gcn_norm_cache[key] = hit
-        hit[2].order()
-        return hit[2]
+        hit.value.order()
+        return hit.value
     lib = _lib.lib()
     _require_cuda(csr.rowptr, "csr")
     dev = csr.rowptr.device
@@ -2866,14 +2912,11 @@ def gcn_norm(csr: Csr, edge_weight: Optional[torch.Tensor] = None, improved: boo
     _lib.check(rc, "gpde_gcn_norm")
     _lib.n_native_calls += 1
     norm = GcnNorm(csr, coef, self_coef, flags)
-    norm._tag = stream_tag(dev)
+    norm._rec.stamp(dev)
     # bytes an entry keeps alive once the CSR cache has let go of the graph: rowptr / src / dst / perm, coef, self_coef, edge_weight -
     # counted twice, for the reversed graph a backward adds (GcnNorm.reversed)
     nbytes = 2 * (16 * e + 8 * n + 4) + (0 if edge_weight is None else 4 * e)
-    _gcn_norm_cache[key] = (csr, None if edge_weight is None else edge_weight.untyped_storage(), norm, nbytes)
-    while len(_gcn_norm_cache) > _GCN_NORM_CACHE_MAX_ENTRIES or \
-            (len(_gcn_norm_cache) > 1 and sum(v[3] for v in _gcn_norm_cache.values()) > _GCN_NORM_CACHE_MAX_BYTES):
-        _gcn_norm_cache.pop(next(iter(_gcn_norm_cache)))
+    _gcn_norm_cache.put(key, Cached(norm, (), (csr, None if edge_weight is None else edge_weight.untyped_storage()), nbytes))
     return norm
 
 

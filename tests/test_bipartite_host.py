@@ -139,7 +139,7 @@ def test_csr_with_and_without_a_source_count():
 def test_the_csr_cache_key_includes_the_source_count_and_the_flip(monkeypatch):
     built = []
     monkeypatch.setattr(ops, "build_csr", lambda ei, n, n_src=None, flip=False: built.append((n, n_src, flip)) or object())
-    monkeypatch.setattr(ops, "_csr_cache", {})
+    monkeypatch.setattr(ops, "_csr_cache", ops.Lru("csr", max_entries=64, max_bytes=8 << 30))
     ei, _ = graph(5, 5)
     a, b, c, d = ops.csr_for(ei, 5), ops.csr_for(ei, 5, n_src=5), ops.csr_for(ei, 5, n_src=9), ops.csr_for(ei, 5, flip=True)
     assert len({id(t) for t in (a, b, c, d)}) == 4 and built == [(5, None, False), (5, 5, False), (5, 9, False), (5, None, True)]

@@ -897,3 +897,85 @@ def test_two_streams_at_once():
     assert open1 and open2, "a hold ended before both steps were issued: the two modules ran one after the other"
     bad = [("NNConv", k) for k in base1 if not _bits(got1[k], base1[k])] + [("GCNConv", k) for k in base2 if not _bits(got2[k], base2[k])]
     assert not bad, bad
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# 7. what a cross-stream hit keeps, a snapshot pins
+# ---------------------------------------------------------------------------------------------------------------------------
+def _tensor_ptrs(obj, out, seen):
+    """data_ptr of every tensor reachable from `obj` through tuples, lists, dicts and the package's own objects (Csr, PackedMlp,
+    GcnNorm, the cache records)."""
+    if obj is None or id(obj) in seen:
+        return out
+    seen.add(id(obj))
+    if isinstance(obj, torch.Tensor):
+        out.add(obj.data_ptr())
+    elif isinstance(obj, dict):
+        _tensor_ptrs(list(obj.values()), out, seen)
+    elif isinstance(obj, (tuple, list, set)):
+        for o in obj:
+            _tensor_ptrs(o, out, seen)
+    elif type(obj).__module__.startswith("graph_pde_amd"):
+        names = [s for c in type(obj).__mro__ for s in getattr(c, "__slots__", ())] + list(getattr(obj, "__dict__", {}))
+        for nm in names:
+            _tensor_ptrs(getattr(obj, nm, None), out, seen)
+    return out
+
+
+def test_a_snapshot_pins_what_a_cross_stream_hit_keeps(monkeypatch):
+    """Bookkeeping only - nothing is raced, no stream is held.  Every cache is filled on the default stream: a 64 -> 64 NNConv with
+    the kernel MLP [3, 32, 32, 4096] on 256 nodes / 32,768 random edges (attr_in_slot_order engages) and a second instance of it on
+    512 nodes / 1,024 edges (the inference W_e form qualifies; one instance per graph, since a module caches one H), and a GCNConv
+    on the small graph - one training step, then two calls without gradient each.  Then the snapshots are taken and the same calls
+    run once on a side stream: every tensor a cross-stream hit hands to ops._keep_for must be reachable from the snapshots (a
+    recorded graph that pinned them reads nothing the caches could free), and every cache name but "deferred" must have counted."""
+    monkeypatch.setattr(hidden_cache, "MODE", "on")
+    ops.clear_caches()
+    hidden_cache.clear()
+    g = torch.Generator().manual_seed(71)
+    torch.manual_seed(71)
+    dims = [3, 32, 32, 4096]
+    assert 32768 >= ops._ATTR_SLOT_ORDER_MIN_EDGES and ops.ATTR_SLOT_ORDER
+    cases = []
+    for n, e in ((256, 32768), (512, 1024)):
+        ei, ea = _graph(n, e, g).to(D), torch.randn(e, dims[0], generator=g).to(D)
+        conv = gp.NNConv(64, 64, DenseNet(dims, torch.nn.ReLU), aggr="mean").to(D)
+        cases.append((conv, torch.randn(n, 64, generator=g).to(D), (lambda m, xl, ei=ei, ea=ea: m(xl, ei, ea)), torch.randn(n, 64, generator=g).to(D)))
+    ei_small = ei
+    cases.append((gp.GCNConv(16, 24).to(D), torch.randn(512, 16, generator=g).to(D), (lambda m, xl: m(xl, ei_small)),
+                  torch.randn(512, 24, generator=g).to(D)))
+
+    def calls(no_grad_calls):
+        for model, x, fwd, gout in cases:
+            _step(model, x, fwd, gout)
+        for model, x, fwd, gout in cases:
+            with torch.no_grad():
+                for _ in range(no_grad_calls):
+                    fwd(model, x)
+    calls(2)
+    torch.cuda.synchronize()
+    assert ops.cross_stream_hits == {}
+    ent_big, ent_small = hidden_cache._entries[cases[0][0]], hidden_cache._entries[cases[1][0]]
+    assert ent_big.hidden is not None and ent_small.hidden is not None, "the policy built no H"
+    pinned = _tensor_ptrs([ops.cache_snapshot(), hidden_cache.snapshot()], set(), set())
+    kept, real_keep = [], ops._keep_for
+    monkeypatch.setattr(ops, "_keep_for", lambda t, stream: (kept.append(t), real_keep(t, stream)))
+    S = stream_beside(torch.cuda.current_stream())
+    with torch.cuda.stream(S):
+        # (without gradient first: H and W_e of the default stream are still the entries; the training step then rebuilds H from
+        # the slot-ordered attributes and runs the backward over the source order and the reversed GCN graph)
+        for model, x, fwd, gout in cases:
+            with torch.no_grad():
+                fwd(model, x)
+        for model, x, fwd, gout in cases:
+            _step(model, x, fwd, gout)
+    S.synchronize()
+    torch.cuda.synchronize()
+    print("cross-stream hits:", dict(ops.cross_stream_hits), "tensors kept:", len(kept))
+    loose = [(tuple(t.shape), t.dtype) for t in kept if t.data_ptr() not in pinned]
+    print("kept by a hit but not pinned by the snapshots:", loose)
+    assert kept and not loose, loose
+    names = {"csr", "pack_mlp", "attr_slot_order", "attr_identity", "src_order", "gcn_norm", "hidden", "edge_weights"}
+    assert names <= set(ops.cross_stream_hits), sorted(names - set(ops.cross_stream_hits))
+    ops.clear_caches()
+    hidden_cache.clear()

@@ -252,7 +252,7 @@ def test_virtual_hidden_node_policy_host_logic(monkeypatch):
     with torch.no_grad():
         w[0].mul_(1.0)                                                # optimizer step; this forward applies the module once ...
     assert call() is not None
-    hidden_cache._entries[conv].dtoken.valid = False
+    hidden_cache._entries[conv].d.token.valid = False
     with torch.no_grad():
         w[0].mul_(1.0)
     assert call() is None and not hidden_cache._entries[conv].repeats  # ... so the next forward's call is a stranger again
@@ -652,7 +652,8 @@ def test_workspace_allocation_drops_the_caches_once_when_the_device_is_full(monk
         pass
     m = M()
     ent = hidden_cache._Entry()
-    ent.hidden, ent.key, ent.repeats = torch.zeros(4), ("k",), True
+    ent.h.store(torch.zeros(4), ("k",), [], ())
+    ent.repeats = True
     hidden_cache._entries[m] = ent
     real_empty, calls = torch.empty, {"n": 0}
 
@@ -665,7 +666,7 @@ def test_workspace_allocation_drops_the_caches_once_when_the_device_is_full(monk
     monkeypatch.setattr(torch.cuda, "empty_cache", lambda: None)
     ws = ops._alloc_ws(100, "cpu")
     assert ws.numel() == 100 and calls["n"] == 2
-    assert ent.hidden is None and ent.key is None and ent.repeats       # tensors gone, what was learnt about the module stays
+    assert ent.h.value is None and ent.h.key is None and ent.repeats    # tensors gone, what was learnt about the module stays
     calls["n"] = 0                                                        # nothing cached any more: the error propagates
     with pytest.raises(torch.OutOfMemoryError):
         ops._alloc_ws(100, "cpu")
@@ -750,16 +751,16 @@ def test_token_of_hands_out_the_shared_h_token_only_where_h_has_one_kind_of_cons
     small = ops.Csr(100, 3200, z32, z32, z32, z32)                 # in-degree 32 but <= WE_SMALL_EDGES edges: qualifies too
     h = torch.zeros(4, 4)
     ent = hidden_cache._Entry()
-    ent.hidden, ent.token = h, HiddenToken()
+    ent.h.store(h, ("k",), [], (), HiddenToken())
     monkeypatch.setitem(hidden_cache._entries, m, ent)
     monkeypatch.setattr(hidden_cache, "MODE", "auto")
     monkeypatch.setattr(hidden_cache, "WE_MODE", "auto")
-    assert hidden_cache.token_of(m, h, dense) is ent.token
+    assert hidden_cache.token_of(m, h, dense) is ent.h.token
     assert hidden_cache.token_of(m, torch.zeros(4, 4), dense) is None
     assert hidden_cache.token_of(m, h, sparse) is None and hidden_cache.token_of(m, h, small) is None
     monkeypatch.setattr(hidden_cache, "WE_MODE", "off")
-    assert hidden_cache.token_of(m, h, sparse) is ent.token
-    ent.token.valid = False
+    assert hidden_cache.token_of(m, h, sparse) is ent.h.token
+    ent.h.token.valid = False
     assert hidden_cache.token_of(m, h, dense) is None
     assert hidden_cache.token_of(torch.nn.Linear(2, 2), h, dense) is None
 
