@@ -25,7 +25,8 @@
 //     one K = 32 MFMA, whose k slots are the C layout of two edge blocks;
 //   * a k1 chunk runs HALF-CHUNK-MAJOR: edge blocks {0, 1} over all eight column blocks (48 MFMAs), then edge blocks {2, 3}
 //     (48 MFMAs); a half is four batches of two column blocks (fragments: two sets of 16 registers, the next batch's set
-//     read during the current one - every fragment twice per chunk, 32 ds_read_b128, one per three MFMA gaps) x two edge
+//     read during the current one - every fragment twice per chunk, 32 ds_read_b128, one per three MFMA gaps; the image
+//     variant: four resident sets, every fragment once, last item below) x two edge
 //     blocks x 6 MFMAs.  An MFMA of this shape leaves the SIMD's issue port free for about half of its 16 cycles, i.e. for
 //     two vector instructions, so the K loop is LEVELLED: no gap of the steady chunk carries more than two vector / LDS /
 //     DMA instructions (three where hipcc adds an address add).  The A operands are single-buffered: while a half runs,
@@ -43,7 +44,18 @@
 //     by the s_waitcnt vmcnt(0) + s_barrier that ends chunk c; fragments are read a batch ahead, in place;
 //   * the forward's aggregation runs on the attribute operand image where the workspace holds one (ASRC_IMAGE, at the
 //     kernel's template): no per-tile prologue, the tile boundary lies inside the tile's last chunk (DESIGN.md §3d,
-//     "The tile boundary").
+//     "The tile boundary");
+//   * the image variant (209 VGPRs with two fragment sets) keeps FOUR RESIDENT sets, 64 registers: batch bt of either half
+//     reads set bt, so every fragment is read from LDS once per chunk - 16 ds_read_b128, not 32.  Chunk c + 1's sets 0, 1, 2
+//     are read from its ring slot during chunk c's second-half batches 1, 2, 3 (behind the set's last MFMA of chunk c, two
+//     batches or more ahead of its first of chunk c + 1), its set 3 during its own second batch, two batches ahead; same
+//     gaps (q = 0, 3, 6, 9), and three batches of the first half carry no fragment read.  The 3-slot ring allows it:
+//     chunk c + 1's pieces were issued during chunk c - 1 and retired by the wait and barrier that closed it; during chunk
+//     c only the slot of chunk c + 2 is written, which was the slot of chunk c - 1 - whose last fragment read (its set 3)
+//     ran in front of that same barrier.  The sets do not live across the aggregation phase (g2hi / g2lo take their
+//     registers): a tile reads set 0 up front, as before, and sets 1, 2, 3 in the first three batches of its chunk 0, a
+//     batch ahead each; its last chunk reads nothing for a next chunk.  MFMA order and operands are those of the two-set
+//     schedule, which the other four instantiations keep line for line ("Resident fragments").
 #include "gpde_common.h"
 #include <cstdlib>
 #include <type_traits>
@@ -479,7 +491,10 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
         // W2 fragments of the chunk's first batch (column blocks 0, 1).  A chunk is four batches of two column blocks;
         // the 32 fragment registers are two sets, the next batch's set is read during the current batch (not carried
         // across the aggregation phase)
-        h8 bhi[2][2], blo[2][2];
+        // IMAGE: FOUR sets, one per batch of a half and resident for the chunk (see the header); chunk 0 reads sets 1-3 in its
+        // own first gaps
+        constexpr int NFS = IMAGE ? 4 : 2;
+        h8 bhi[NFS][2], blo[NFS][2];
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
             bhi[0][nb] = *(const h8*)(ring + slot * TILE_B + nb * 2048 + bo);
@@ -560,6 +575,7 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
             //                 At a tile's first chunk the first half re-converts chunk 0's edge blocks {2, 3} from the unchanged
             //                 raw H1 (same values); at its last the second half converts the unused H1 below
             //   fragments     q = 0, 3, 6, 9: the next batch's four reads (lo 0, lo 1, hi 0, hi 1), into the other set
+            //                 (IMAGE: the four reads of ONE resident set in four of the eight batches, see the batch loop)
             //   W2 ring       the four pieces at n = 5, 11, 17, 23
             //   (W1|b1)       n = 25, 31 (rows of chunk c + 1)
             //   raw H1        of chunk c + 1 in two halves of four MFMAs: edge blocks {0, 1} behind n = 45, {2, 3} behind
@@ -570,10 +586,26 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
             //                 row addresses at n = 1, 7, 13, 19
 #pragma unroll
             for (int g8 = 0; g8 < 8; ++g8) {
-                const int hf = g8 >> 2, bt = g8 & 3, fs = g8 & 1;         // half, batch of the half, fragment set
+                const int hf = g8 >> 2, bt = g8 & 3, fs = IMAGE ? bt : (g8 & 1);      // half, batch of the half, fragment set
                 // where the NEXT batch's fragments live: the next column blocks of this chunk (0, 1 again behind the first
-                // half), behind the last batch 0, 1 of the next chunk
+                // half), behind the last batch 0, 1 of the next chunk; they go into set rs = the other one
+                int rs = fs ^ 1;
                 const char* rn = (g8 < 7) ? rb0 + (2 * ((bt + 1) & 3)) * 2048 : rb1;
+                if constexpr (IMAGE) {
+                    // resident sets: batch bt reads set bt in both halves, so this batch's gaps carry the reads of at most ONE
+                    // set rs (none: rs < 0), each fragment once per chunk -
+                    //   second half, bt = 1, 2, 3: set bt - 1 of chunk c + 1 from its slot (rb1), behind the set's last MFMA of
+                    //     this chunk (batch bt - 1 of this half) and 2 batches or more ahead of its first of the next;
+                    //   first half, bt = 1: set 3 of THIS chunk (its last MFMA ran in the chunk before), two batches ahead
+                    //     (read in batch 0 or 2 instead, hipcc's peeled chunks carry 8 / 32 more accumulator copies);
+                    //   a tile's chunk 0 (the sets do not live across the aggregation phase; set 0 was read at the tile start):
+                    //     sets 1, 2, 3 in the first half's batches 0, 1, 2, a batch ahead each;
+                    //   a tile's last chunk: nothing for a next chunk
+                    rs = -1;
+                    if (PH == 0 && hf == 0 && bt < 3) { rs = bt + 1; rn = rb0 + (2 * (bt + 1)) * 2048; }
+                    else if (PH != 0 && g8 == 1) { rs = 3; rn = rb0 + 6 * 2048; }
+                    else if (PH != 7 && hf == 1 && bt >= 1) { rs = bt - 1; rn = rb1 + (2 * (bt - 1)) * 2048; }
+                }
 #pragma unroll
                 for (int q = 0; q < 12; ++q) {
                     const int e = 2 * hf + q / 6, j = q % 6;
@@ -601,10 +633,12 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
                         const int ce = 2 * (1 - hf) + (bt >> 1);
                         asm volatile("" ::"v"(ahi[ce]), "v"(alo[ce]));
                     }
-                    if (q == 0) blo[fs ^ 1][0] = *(const h8*)(rn + (bo ^ 64));
-                    if (q == 3) blo[fs ^ 1][1] = *(const h8*)(rn + 2048 + (bo ^ 64));
-                    if (q == 6) bhi[fs ^ 1][0] = *(const h8*)(rn + bo);
-                    if (q == 9) bhi[fs ^ 1][1] = *(const h8*)(rn + 2048 + bo);
+                    if (rs >= 0) {
+                        if (q == 0) blo[rs][0] = *(const h8*)(rn + (bo ^ 64));
+                        if (q == 3) blo[rs][1] = *(const h8*)(rn + 2048 + (bo ^ 64));
+                        if (q == 6) bhi[rs][0] = *(const h8*)(rn + bo);
+                        if (q == 9) bhi[rs][1] = *(const h8*)(rn + 2048 + bo);
+                    }
                     if (n == 5) GPDE_GLDS(gsrc, ldst, 0);
                     if (n == 11) GPDE_GLDS(gsrc, ldst, 1024);
                     if (n == 17) GPDE_GLDS(gsrc, ldst, 2048);

@@ -1,6 +1,7 @@
 #!/bin/bash
 # K-loop schedule evidence for the headline forward kernel ("The levelled K loop"), all on ONE box, one call:
-#   model   scripts/ubench/kloop_model_v6: the full K-loop model batch-major against levelled, alternating, four repetitions;
+#   model   scripts/ubench/kloop_model_v6: the full K-loop model batch-major against levelled, then levelled with two fragment sets
+#           against four resident ones, alternating, four repetitions each;
 #   bits    python bench.py --steps 2 --warmup 1 --dump-outputs of both builds at g61 and g241 (out.npy byte for byte), and
 #           of --train --config g61 (every dumped array; BASE against BASE first: the parent's own distance is the bar);
 #   ab      same-box A/B of the two builds, alternating, three pairs (python bench.py --steps 6 --warmup 2);
@@ -30,7 +31,7 @@ has() { case " $PARTS " in *" $1 "*) return 0 ;; *) return 1 ;; esac; }
 
 if has model; then
   timeout -k 10 240 scripts/ubench/kloop_model_v6 > $O/kloop_model.txt 2>&1 || exit 1
-  grep -E "schedule A/B|saved" $O/kloop_model.txt
+  grep -E "schedule A/B|fragment A/B|saved" $O/kloop_model.txt
 fi
 
 if has bits; then
