@@ -55,7 +55,14 @@
 //     ran in front of that same barrier.  The sets do not live across the aggregation phase (g2hi / g2lo take their
 //     registers): a tile reads set 0 up front, as before, and sets 1, 2, 3 in the first three batches of its chunk 0, a
 //     batch ahead each; its last chunk reads nothing for a next chunk.  MFMA order and operands are those of the two-set
-//     schedule, which the other four instantiations keep line for line ("Resident fragments").
+//     schedule, which the other four instantiations keep line for line ("Resident fragments");
+//   * the image variant's product MFMAs are asm statements with a TIED accumulator (one "+a" operand is C and D; as builtins
+//     hipcc rotated them through a[0:3] - `acc` and `Z` fill the AGPRs - and parked accumulators in VGPRs around the peeled
+//     chunks' side loads).  A tile's first product into each accumulator (chunk 0, hi x lo) takes the inline constant 0 as C:
+//     nothing zeroes `acc`.  hipcc pads no wait states around an asm MFMA, so: A operands are written a whole gap or more ahead
+//     (conversion schedule), and the only non-MFMA reader of an accumulator, the un-scale, sits behind the last chunk's
+//     barrier, 16 wait states and an opaque "+a" on every accumulator.  Same products, same order, same rounding (DESIGN.md
+//     §3d, "Tied accumulators").
 #include "gpde_common.h"
 #include <cstdlib>
 #include <type_traits>
@@ -337,6 +344,19 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
             asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(dd[e][1]) : "v"(w1r1), "v"(at[e]));
         }
     };
+    // Product MFMA of the hidden layer with a TIED accumulator (image variant): one "+a" operand is C and D, so hipcc cannot
+    // rotate the accumulators through spare registers or park them in VGPRs.  An accumulate chain into the same D needs no
+    // wait states; the A operand comes from conversions a whole gap or more ahead (K-loop schedule), the B operand from
+    // ds_read_b128 that hipcc still waits for.  Any OTHER reader of the accumulator needs the MFMA's wait states first -
+    // see the end of the K loop
+    // `first`: an accumulator's first product of a tile (chunk 0, hi x lo) takes the inline constant 0 as C and writes the
+    // accumulator as a plain output - nothing zeroes `acc`, and nothing a tile (or a round without a tile) left in it is
+    // added to.  `pad`: two wait states in front (a VALU write of the A operand at no fixed distance)
+    [[maybe_unused]] auto prod_tied = [&](f32x4& c, u4 av, h8 bv, bool first, bool pad) {
+        if (first && pad) asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=a"(c) : "v"(av), "v"(bv));
+        else if (first) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=a"(c) : "v"(av), "v"(bv));
+        else asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "v"(av), "v"(bv));
+    };
     auto h1gen = [&](f32x4 (&dd)[4][2], h8 w1r0, h8 w1r1, const h8 (&at)[4]) {      // the 8 MFMAs of a chunk (tile prologue)
         h1gen_half(dd, 0, w1r0, w1r1, at);
         h1gen_half(dd, 2, w1r0, w1r1, at);
@@ -369,7 +389,10 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
 #pragma unroll
         for (int nb = 0; nb < 8; ++nb)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { acc[e][nb][r] = 0.f; Z[e][nb][r] = 0.f; }
+            for (int r = 0; r < 4; ++r) {
+                if constexpr (!IMAGE) acc[e][nb][r] = 0.f;      // (IMAGE: chunk 0's first products take C = 0)
+                Z[e][nb][r] = 0.f;
+            }
     int cur = -1;
     [[maybe_unused]] float hmax_run = 0.f;      // WRITE_H: running maximum of the stored activations (>= 0)
 
@@ -616,9 +639,17 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
                            // measure how time and clock answer to a third less matrix work per edge
                     if (tt != 2)
 #endif
-                    acc[e][cb] = mfma32k(__builtin_bit_cast(h8, tt == 2 ? alo[e] : ahi[e]),
-                                         tt == 0 ? blo[fs][nb] : bhi[fs][nb], acc[e][cb]);
-                    asm volatile("" : "+a"(acc[e][cb]));
+                    if constexpr (IMAGE) {
+                        // tied accumulator (header, last item): D = C by construction, C = 0 in a tile's first product of
+                        // each accumulator.  A wave's first product follows the cold start's conversions of its A operand
+                        // at no fixed distance: two wait states in the string
+                        prod_tied(acc[e][cb], tt == 2 ? alo[e] : ahi[e], tt == 0 ? blo[fs][nb] : bhi[fs][nb],
+                                  PH == 0 && tt == 0, PH == 0 && n == 0);
+                    } else {
+                        acc[e][cb] = mfma32k(__builtin_bit_cast(h8, tt == 2 ? alo[e] : ahi[e]),
+                                             tt == 0 ? blo[fs][nb] : bhi[fs][nb], acc[e][cb]);
+                        asm volatile("" : "+a"(acc[e][cb]));
+                    }
                     if (q != 5 && q != 11) {
                         const int v = q < 5 ? q : q - 1, pr = 2 * bt + v / 5, step = v % 5;
                         const int ce = 2 * (1 - hf) + (pr >> 2), jp = pr & 3;
@@ -719,7 +750,17 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
         tm_peel += clock64() - tm0_;
 #endif
         for (int c = 6; c < (IMAGE ? NKC - 1 : NKC); ++c) chunk(std::integral_constant<int, 6>{}, c);
-        if constexpr (IMAGE) chunk(std::integral_constant<int, 7>{}, NKC - 1);
+        if constexpr (IMAGE) {
+            chunk(std::integral_constant<int, 7>{}, NKC - 1);
+            // The un-scale below is the first non-MFMA reader of the accumulators, and hipcc pads nothing behind an asm MFMA:
+            // 16 wait states behind the last chunk's barrier (an 8-pass MFMA needs 12 before a VALU read of its D), then every
+            // accumulator opaque, so that no v_accvgpr_read is hoisted across them into the K loop
+            asm volatile("s_nop 15" ::: "memory");
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int nb = 0; nb < 8; ++nb) asm volatile("" : "+a"(acc[e][nb]));
+        }
 
         TM_MARK(tm_loop);
         if constexpr (WRITE_H) {
@@ -764,7 +805,7 @@ void gpde_fused_f16v6_kernel(GpdeFusedArgs a) {
 #pragma unroll
                 for (int r = 0; r < 8; ++r) {
                     y[r] = fmaf(acc[2 * b + (r >> 2)][nb][r & 3], ie[r] * ucv, b2v);
-                    acc[2 * b + (r >> 2)][nb][r & 3] = 0.f;
+                    if constexpr (!IMAGE) acc[2 * b + (r >> 2)][nb][r & 3] = 0.f;
                 }
 #pragma unroll
                 for (int p_ = 0; p_ < 4; ++p_) {

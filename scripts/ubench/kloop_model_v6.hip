@@ -6,13 +6,20 @@
 // SHAPE 1, v_mfma_f32_16x16x32_f16 (the kernel now): 96 + 8 MFMAs of half the size, everything else the same (body16).
 // SHAPE 2: the same MFMAs in the kernel's LEVELLED schedule (body16<.., LV = 1>: half-chunk-major, one conversion instruction per gap).
 // SHAPE 3: the levelled schedule with FOUR RESIDENT fragment sets (body16<.., LV = 2>): every W2 fragment is read once per chunk.
+// SHAPE 4: SHAPE 3 as a PEELED chunk of the image variant (body16<.., LV = 3>): + the side loads of chunks 3-5 (four ds_bpermute of the
+//          x_j row addresses, four gather LDS-DMA of x_j rows, closing wait vmcnt(4)), accumulators tied (D = C) as everywhere in this model.
+// SHAPE 5: SHAPE 4 + the accumulator copies hipcc puts into the kernel's peeled chunks (body16<.., LV = 4>): four accumulators per chunk
+//          parked in VGPRs behind their first product (s_nop 7, 4 v_accvgpr_read_b32) and put back in front of their second
+//          (4 v_accvgpr_write_b32, s_nop 1) - 32 copies and 8 pads per chunk against the kernel's 33 and 15.
 // Flags ablate the parts; the result is cycles per chunk (ideal 52 x 32 = 104 x 16 = 1664), the shader clock and chip
 // TFLOP/s.  The run ends with the shape A/B (bare stream and full model of both shapes, alternating, in long launches) and
-// the schedule A/B (full model, SHAPE 1 against SHAPE 2) and the fragment A/B (full model, SHAPE 2 against SHAPE 3).
-//   hipcc --offload-arch=gfx950 -O3 -o kloop_model_v6 kloop_model_v6.hip && ./kloop_model_v6
+// the schedule A/B (full model, SHAPE 1 against SHAPE 2), the fragment A/B (full model, SHAPE 2 against SHAPE 3) and the copy A/B
+// (peeled chunk with side loads, SHAPE 4 against SHAPE 5: what the accumulator copies of a peeled chunk cost).
+//   hipcc --offload-arch=gfx950 -O3 -o kloop_model_v6 kloop_model_v6.hip && ./kloop_model_v6        (./kloop_model_v6 copy: the copy A/B alone)
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -228,6 +235,12 @@ __device__ __forceinline__ void body32(char* smem, long* out, const char* gsrc, 
 // fragment is read twice in a chunk (16 ds_read_b128, none in the first half but set 3).  The next chunk's sets 0, 1, 2 are read
 // from its ring slot during the second half's batches 1, 2, 3 - each behind the set's last reader of this chunk and a batch or
 // more ahead of its first reader of the next - and set 3 during the next chunk's own first batch.  Same gaps (q = 0, 3, 6, 9).
+//
+// LV 3, LV 2 as a peeled chunk of the image variant (its chunks 3, 4, 5): the x_j row addresses by ds_bpermute in gaps 1, 7, 13, 19, the
+// four gather DMA of x_j rows in gaps 53, 65, 77, 89 (behind the ring pieces), and the closing wait leaves those four in flight.
+// LV 4, LV 3 with accumulator copies as hipcc places them around the side loads: the accumulator of MFMA 48, 60, 72, 84 (the first product
+// of a batch) is read into VGPRs behind it (s_nop 7 first: MFMA result -> VALU read) and written back in the next gap, in front of the
+// second product into it (s_nop 1 behind: VALU write -> MFMA C).  The values come back unchanged.
 template <int FLAGS, int NS, int LV = 0>
 __device__ __forceinline__ void body16(char* smem, long* out, const char* gsrc, float seed, int iters) {
     char* ring = smem;
@@ -244,7 +257,7 @@ __device__ __forceinline__ void body16(char* smem, long* out, const char* gsrc, 
     const int w1o = (16 * (l15 >> 3) + 4 * ((l15 >> 2) & 1) + (l15 & 3)) * 32 + (g == 2 ? 16 : 0);
 
     u4 ahi[4], alo[4];
-    constexpr int NFS = LV == 2 ? 4 : 2;      // fragment sets
+    constexpr int NFS = LV >= 2 ? 4 : 2;      // fragment sets
     h8 bhi[NFS][2], blo[NFS][2], B1[4];
     f32x4 d[4][2], acc[4][8], Z[4][8];
     for (int e = 0; e < 4; ++e)
@@ -266,7 +279,7 @@ __device__ __forceinline__ void body16(char* smem, long* out, const char* gsrc, 
         for (int hf = 0; hf < 2; ++hf)
             for (int r = 0; r < 4; ++r) d[e][hf][r] = seed * (4 * hf + r + 1) * 0.01f;
     for (int nb = 0; nb < 2; ++nb) { bhi[0][nb] = *(const h8*)(ring + nb * 2048 + bo); blo[0][nb] = *(const h8*)(ring + nb * 2048 + (bo ^ 64)); bhi[1][nb] = bhi[0][nb]; blo[1][nb] = blo[0][nb]; }
-    if constexpr (LV == 2)
+    if constexpr (LV >= 2)
         for (int s = 2; s < 4; ++s)
             for (int nb = 0; nb < 2; ++nb) { bhi[s][nb] = *(const h8*)(ring + (2 * s + nb) * 2048 + bo); blo[s][nb] = *(const h8*)(ring + (2 * s + nb) * 2048 + (bo ^ 64)); }
 
@@ -331,6 +344,11 @@ __device__ __forceinline__ void body16(char* smem, long* out, const char* gsrc, 
     int slot = 0;
     unsigned cph = 0, ct0 = 0, ct1 = 0, cpl = 0;
     h8 A1 = *(const h8*)(w1s + w1o), A2 = *(const h8*)(w1s + w1o + 256);
+    // LV >= 3: the wave's x_j piece (4 DMA of 4 rows x 256 B) behind the (W1|b1) rows; source rows picked per lane and chunk
+    [[maybe_unused]] char* xs = smem + NS * TILE_B + 32768 + wave * 4096;
+    [[maybe_unused]] int xsidx[4] = {0, 0, 0, 0};
+    [[maybe_unused]] int src_l = (int)(lane * 2654435761u >> 18);
+    [[maybe_unused]] float pk[4];
     long t0 = clock64();
     for (int it = 0; it < iters; ++it) {
         int slot1 = slot + 1 == NS ? 0 : slot + 1;            // next chunk's slot
@@ -341,18 +359,19 @@ __device__ __forceinline__ void body16(char* smem, long* out, const char* gsrc, 
         const char* rb0 = ring + slot * TILE_B;
         const char* rb1 = ring + slot1 * TILE_B;
         const char* w1n = w1s + (size_t)(((it + 1) & 31) * 32) * 32 + w1o;
+        if constexpr (LV >= 3) src_l += 40503 * it;
         if constexpr (LV >= 1) {
             unsigned long long gb_c = gbase + (size_t)dchunk * TILE_B;
             asm volatile("" : "+s"(gb_c));
             const char* gp_c = (const char*)(gb_c + lane16);
 #pragma unroll
             for (int g8 = 0; g8 < 8; ++g8) {            // batch of the chunk: half hf, column blocks 2 bt, 2 bt + 1
-                const int hf = g8 >> 2, bt = g8 & 3, fs = LV == 2 ? bt : (g8 & 1);
+                const int hf = g8 >> 2, bt = g8 & 3, fs = LV >= 2 ? bt : (g8 & 1);
                 // the NEXT batch's fragments: the next column blocks of this chunk (0, 1 again behind the first half), then 0, 1 of
                 // the next chunk, into the other set.  LV 2: set rs, or none (rs < 0) - set 3 of this chunk in the first batch, sets
                 // bt - 1 of the next chunk in the second half's batches bt = 1, 2, 3
-                const int rs = LV != 2 ? (fs ^ 1) : (g8 == 0 ? 3 : (g8 >= 5 ? bt - 1 : -1));
-                const char* rn = LV == 2 ? (g8 == 0 ? rb0 + 6 * 2048 : rb1 + (2 * (bt - 1)) * 2048)
+                const int rs = LV < 2 ? (fs ^ 1) : (g8 == 0 ? 3 : (g8 >= 5 ? bt - 1 : -1));
+                const char* rn = LV >= 2 ? (g8 == 0 ? rb0 + 6 * 2048 : rb1 + (2 * (bt - 1)) * 2048)
                                          : ((g8 < 7) ? rb0 + (2 * ((bt + 1) & 3)) * 2048 : rb1);
 #pragma unroll
                 for (int q = 0; q < 12; ++q) {
@@ -394,6 +413,27 @@ __device__ __forceinline__ void body16(char* smem, long* out, const char* gsrc, 
                     }
                     if ((FLAGS & 8) && n == 25) A1 = *(const h8*)w1n;
                     if ((FLAGS & 8) && n == 31) A2 = *(const h8*)(w1n + 256);
+                    if constexpr (LV >= 3) {
+                        // the side loads of a peeled chunk: row i = 0..3 of this chunk's x_j piece, 4 rows of 256 B per DMA
+                        if (n == 1 || n == 7 || n == 13 || n == 19)
+                            xsidx[(n - 1) / 6] = __builtin_amdgcn_ds_bpermute((4 * ((n - 1) / 6) + (lane >> 4)) * 4, src_l);
+                        if (n == 53 || n == 65 || n == 77 || n == 89)
+                            dma16(gsrc + (size_t)(xsidx[(n - 53) / 12] & 0x3fff) * 256 + (lane & 15) * 16, xs + ((n - 53) / 12) * 1024);
+                    }
+                    if constexpr (LV == 4) {
+                        if (q == 0 && hf == 1)          // park the accumulator MFMA n has just written
+                            asm volatile("s_nop 7\n\tv_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\t"
+                                         "v_accvgpr_read_b32 %2, %6\n\tv_accvgpr_read_b32 %3, %7"
+                                         : "=&v"(pk[0]), "=&v"(pk[1]), "=&v"(pk[2]), "=&v"(pk[3])
+                                         : "a"(acc[e][cbk][0]), "a"(acc[e][cbk][1]), "a"(acc[e][cbk][2]), "a"(acc[e][cbk][3]));
+                        if (q == 1 && hf == 1) {        // and put it back in front of MFMA n + 1, its second product
+                            f32x4& ac = acc[e][2 * bt];
+                            asm volatile("v_accvgpr_write_b32 %0, %4\n\tv_accvgpr_write_b32 %1, %5\n\t"
+                                         "v_accvgpr_write_b32 %2, %6\n\tv_accvgpr_write_b32 %3, %7\n\ts_nop 1"
+                                         : "=a"(ac[0]), "=a"(ac[1]), "=a"(ac[2]), "=a"(ac[3])
+                                         : "v"(pk[0]), "v"(pk[1]), "v"(pk[2]), "v"(pk[3]));
+                        }
+                    }
                     __builtin_amdgcn_sched_barrier(0);
                     if ((FLAGS & 8) && (n == 45 || n == 93)) {
                         // raw H1 of the next chunk, edge blocks {0, 1} / {2, 3}: the last reader of these registers (the
@@ -456,7 +496,8 @@ __device__ __forceinline__ void body16(char* smem, long* out, const char* gsrc, 
             }
         }
         if (FLAGS & 4) {
-            if (NS == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (LV >= 3) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");       // the ring pieces are retired, the four x_j DMA stay in flight
+            else if (NS == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         }
         if (FLAGS & 2) __builtin_amdgcn_s_barrier();
@@ -480,7 +521,8 @@ __device__ __forceinline__ void body16(char* smem, long* out, const char* gsrc, 
 }
 
 // SHAPE 0: v_mfma_f32_32x32x16_f16, 1: v_mfma_f32_16x16x32_f16 (batch-major: the kernel up to the levelled K loop), 2: the same
-// MFMAs in the levelled, half-chunk-major schedule, 3: levelled with four resident fragment sets
+// MFMAs in the levelled, half-chunk-major schedule, 3: levelled with four resident fragment sets, 4: 3 as a peeled chunk with its side
+// loads, 5: 4 with the accumulator copies of the kernel's peeled chunks
 template <int FLAGS, int NS, int SHAPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void kern(long* out, const char* gsrc, float seed, int iters) {
@@ -488,7 +530,9 @@ void kern(long* out, const char* gsrc, float seed, int iters) {
     if (SHAPE == 0) body32<FLAGS, NS>(smem, out, gsrc, seed, iters);
     else if (SHAPE == 1) body16<FLAGS, NS, 0>(smem, out, gsrc, seed, iters);
     else if (SHAPE == 2) body16<FLAGS, NS, 1>(smem, out, gsrc, seed, iters);
-    else body16<FLAGS, NS, 2>(smem, out, gsrc, seed, iters);
+    else if (SHAPE == 3) body16<FLAGS, NS, 2>(smem, out, gsrc, seed, iters);
+    else if (SHAPE == 4) body16<FLAGS, NS, 3>(smem, out, gsrc, seed, iters);
+    else body16<FLAGS, NS, 4>(smem, out, gsrc, seed, iters);
 }
 
 // Does the immediate offset of global_load_lds advance BOTH the global address and the LDS address?
@@ -507,7 +551,7 @@ __global__ void dma_offset_test(const unsigned* g, unsigned* out) {
 
 template <int FLAGS, int NS, int SHAPE = 0>
 double run(long* d, const char* src, const char* what, int iters = 2048, double* cyc_out = nullptr) {
-    const int lds = NS * TILE_B + 32768;
+    const int lds = NS * TILE_B + 32768 + (SHAPE >= 4 ? 16384 : 0);      // SHAPE 4, 5: + 4 KiB of x_j rows per wave
     hipFuncSetAttribute((const void*)kern<FLAGS, NS, SHAPE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipLaunchKernelGGL((kern<FLAGS, NS, SHAPE>), dim3(256), dim3(256), lds, 0, d, src, 1.0f, 64);
     hipDeviceSynchronize();
@@ -529,13 +573,16 @@ double run(long* d, const char* src, const char* what, int iters = 2048, double*
     // the kernel are < 1 % of 2048 iterations); matrix pipe occupancy = MFMA cycles issued / cycles elapsed
     const double ghz = (double)hcyc / (ms * 1e-3) / 1e9;
     printf("%s NS %d flags %3d %-46s: %6.0f cycles/chunk (MFMA %d = %4.1f %% of the cycles)  clock %.3f GHz  %7.1f TFLOP/s  %.2f ms  err=%s\n",
-           SHAPE == 3 ? "16x16 rf" : SHAPE == 2 ? "16x16 lv" : SHAPE ? "16x16x32" : "32x32x16", NS, FLAGS, what,
+           SHAPE == 5 ? "16x16 cp" : SHAPE == 4 ? "16x16 sl" : SHAPE == 3 ? "16x16 rf" : SHAPE == 2 ? "16x16 lv" : SHAPE ? "16x16x32" : "32x32x16", NS, FLAGS, what,
            (double)hcyc / iters, nm * 32, 100.0 * nm * 32 * iters / (double)hcyc, ghz, tf, ms, hipGetErrorString(hipGetLastError()));
     if (cyc_out) *cyc_out = (double)hcyc / iters;
     return tf;
 }
 
-int main() {
+int main(int argc, char** argv) {
+    const bool only_copy = argc > 1 && !strcmp(argv[1], "copy");      // `kloop_model_v6 copy`: the copy A/B alone
+    const int REPS = 4, LONG = 32768;
+    double least = 1e9;
     long* d; char* src;
     hipMalloc(&d, 64);
     const size_t nsrc = (size_t)8 * 32 * TILE_B;
@@ -562,6 +609,7 @@ int main() {
         }
         printf("dma immediate offset advances global AND lds address: %s\n", ok ? "YES" : "NO");
     }
+    if (!only_copy) {
     run<0, 3>(d, src, "48 MFMA only");
     run<16, 3>(d, src, "+ 16 W2 fragment reads");
     run<16 | 8, 3>(d, src, "+ H1 (4 MFMA, 2 LDS reads)");
@@ -588,7 +636,6 @@ int main() {
 
     // Shape A/B: bare stream and full model (the production configuration: 3 slots, asm H1) of both shapes, alternating,
     // at 16 x the iterations (launches of tens of ms, so the clock the chip settles at is the one measured)
-    const int REPS = 4, LONG = 32768;
     double worst_bare = 1e9, worst_full = 1e9;
     for (int r = 0; r < REPS; ++r) {
         printf("shape A/B repetition %d\n", r);
@@ -610,7 +657,7 @@ int main() {
     run<64 | 16 | 8 | 1 | 32, 3, 2>(d, src, "+ 128 live Z registers");
     run<64 | 16 | 8 | 1 | 32 | 2, 3, 2>(d, src, "+ s_barrier per chunk");
     run<64 | 16 | 8 | 1 | 32 | 2 | 4, 3, 2>(d, src, "+ DMA ring, wait per chunk (FULL)");
-    double least = 1e9;
+    least = 1e9;
     for (int r = 0; r < REPS; ++r) {
         printf("schedule A/B repetition %d\n", r);
         double ca = 0, cb = 0;
@@ -636,5 +683,22 @@ int main() {
         if (ca - cb < least) least = ca - cb;
     }
     printf("fragment A/B least saving over %d repetitions: %.1f cycles per chunk (gate: > 0 in every repetition)\n", REPS, least);
+    }
+
+    // Copy A/B: a peeled chunk of the image variant (resident sets + the side loads of chunks 3-5) with tied accumulators against the
+    // same chunk with the accumulator copies hipcc places there, and the steady chunk next to them: what the side loads cost on their
+    // own (SHAPE 4 - SHAPE 3) and what the copies cost (SHAPE 5 - SHAPE 4).  The gate for tied product MFMAs in the kernel: a saving
+    // in EVERY repetition
+    least = 1e9;
+    for (int r = 0; r < REPS; ++r) {
+        printf("copy A/B repetition %d\n", r);
+        double c3 = 0, ca = 0, cb = 0;
+        run<64 | 16 | 8 | 1 | 32 | 2 | 4, 3, 3>(d, src, "FULL model, steady chunk", LONG, &c3);
+        const double fa = run<64 | 16 | 8 | 1 | 32 | 2 | 4, 3, 5>(d, src, "FULL model, peeled chunk, 32 copies", LONG, &ca);
+        const double fb = run<64 | 16 | 8 | 1 | 32 | 2 | 4, 3, 4>(d, src, "FULL model, peeled chunk, tied", LONG, &cb);
+        printf("  cycles per chunk: side loads %.1f, copies %.1f   tied / copies FLOP/s %.4f\n", cb - c3, ca - cb, fb / fa);
+        if (ca - cb < least) least = ca - cb;
+    }
+    printf("copy A/B least saving over %d repetitions: %.1f cycles per chunk (gate: > 0 in every repetition)\n", REPS, least);
     return 0;
 }
