@@ -44,15 +44,20 @@ ACCUMULATE_GRAD_HIDDEN = os.environ.get("GPDE_ACCUMULATE_DLDH", "1") != "0"
 CAN_TELL_BACKWARD_PASS = hasattr(torch._C, "_current_graph_task_id")
 
 
+def backward_pass() -> int:
+    """The autograd graph task id of the backward pass the caller runs in; -1 outside one, and where this torch cannot tell."""
+    return torch._C._current_graph_task_id() if CAN_TELL_BACKWARD_PASS else -1
+
+
 def in_backward_pass() -> bool:
     """Whether the caller runs inside an autograd backward pass - a forward does when torch.utils.checkpoint recomputes a segment.
     The running sums and (x, grad_out) pairs that the applications of a module leave on their shared token then belong to the pass
     in flight: forward-time housekeeping must not clear them.
     On a torch without `torch._C._current_graph_task_id` the question cannot be answered (`CAN_TELL_BACKWARD_PASS` is False, this
-    returns False): the in-place sums on the H / W_e tokens are off there anyway (their `share` conditions need the same symbol,
+    returns False): the in-place sums on the H / W_e tokens are off there anyway (`HiddenToken.start` needs a pass to key on,
     nothing is ever in flight on them), and hidden_cache.lookup_deferred hands out no virtual-H node - the one place where a
     forward inside a backward pass would lose work - so such calls take the direct operator."""
-    return CAN_TELL_BACKWARD_PASS and torch._C._current_graph_task_id() >= 0
+    return backward_pass() >= 0
 
 
 def saved_tensor_hooks_active() -> bool:
@@ -132,6 +137,48 @@ class HiddenToken:
         self.side_acc = None    # (W_e token) the (grad_root, grad_bias) the applications of that pass add to in place as well
         self.side_in = None     # (W_e token) (root, bias) behind SharedParamFunction: private nodes only WeConvFunction consumes
 
+    # The in-place gradient sums of the applications sharing this node (dL/dH; on a W_e token dL/dW_e with grad_root, grad_bias).
+    # The invariant: ONE backward pass owns ONE set of running tensors - the first application of the pass hands autograd its
+    # own (`start`), the others add to them inside their kernels (`find`, `added`) and return nothing, and nobody else
+    # contributes, which the node's backward verifies when autograd hands it the sum (`taken`).  Another pass (retain_graph, a
+    # checkpointed segment, a pass abandoned half way) never finds them: it starts new ones.
+    def find(self, shape):
+        """The running tensors of the pass in flight, (sum,) or (sum, grad_root, grad_bias), when it has started them in this
+        shape; else None."""
+        tid = backward_pass()
+        if tid < 0 or self.gh_acc is None or self.gh_tid != tid or self.gh_acc.shape != shape:
+            return None
+        return (self.gh_acc, *(self.side_acc or ()))
+
+    def start(self, acc, *side):
+        """The first application of a pass hands over its tensors (no pass to key on: nothing is remembered, nothing is ever added)."""
+        tid = backward_pass()
+        if tid >= 0:
+            self.gh_acc, self.gh_tid, self.gh_adds, self.side_acc = acc, tid, 0, (side or None)
+
+    def added(self):
+        """An application added in place to the tensors `find` gave it."""
+        self.gh_adds += 1
+
+    def drop(self):
+        """Forget the running tensors: forward time outside a backward pass, a released cache, the end of the node's backward."""
+        self.gh_acc, self.gh_adds, self.side_acc = None, 0, None
+
+    def check(self, grad, lost: str, which=None):
+        """`grad` arrives at a node's backward: RuntimeError(`lost`) when the applications of this pass added in place to ANOTHER
+        buffer (a second kind of consumer contributed and autograd formed the sum out of place: the additions are not in `grad`).
+        `which`: 0 / 1 for grad_root / grad_bias instead of the sum itself."""
+        if self.gh_acc is None or self.gh_adds == 0 or self.gh_tid != backward_pass():
+            return
+        mine = self.gh_acc if which is None else self.side_acc[which]
+        if mine is not None and grad.data_ptr() != mine.data_ptr():
+            raise RuntimeError(lost)
+
+    def taken(self, grad, lost: str):
+        """`check`, then `drop`: `grad` IS the running sum when the applications summed in place, held by autograd from here."""
+        self.check(grad, lost)
+        self.drop()
+
 
 class HiddenFunction(torch.autograd.Function):
     """H [E, K2P] = relu(L_{n-1}(... relu(L_1(edge_attr)))) in CSR row order (gpde_hidden_fwd)."""
@@ -155,13 +202,8 @@ class HiddenFunction(torch.autograd.Function):
                 "gradient with respect to edge_attr is not built (no reference script needs it)")
         tok = ctx.token
         tok.valid = False
-        if tok.gh_acc is not None and tok.gh_adds > 0 and hasattr(torch._C, "_current_graph_task_id") and \
-                tok.gh_tid == torch._C._current_graph_task_id() and grad_h.data_ptr() != tok.gh_acc.data_ptr():
-            # applications added their dL/dH in place to the tensor the first one returned - and autograd hands over another one
-            # (a second kind of consumer of H contributed and the sum was formed out of place): those additions are not in grad_h
-            raise RuntimeError("graph_pde_amd: the in-place sum of dL/dH lost its buffer (H has a consumer outside NNConvHiddenFunction); "
-                               "set GPDE_ACCUMULATE_DLDH=0")
-        tok.gh_acc, tok.gh_adds = None, 0   # (grad_h IS that buffer when the applications summed in place: held by autograd from here)
+        tok.taken(grad_h, "graph_pde_amd: the in-place sum of dL/dH lost its buffer (H has a consumer outside NNConvHiddenFunction); "
+                          "set GPDE_ACCUMULATE_DLDH=0")
         edge_attr, *params = ctx.saved_tensors
         edge_attr = _saved_attr(ctx, edge_attr)
         n = ctx.n_hidden
@@ -190,25 +232,20 @@ class NNConvHiddenFunction(torch.autograd.Function):
         # The applications of a module that shares H each produce dL/dH [E, K2P]; autograd would keep the first and add the others
         # to it one by one (at s=61, depth 6: 4 of a 38 ms step; at s=121 five 72 GB passes).  Here the first application of a
         # backward pass hands autograd its tensor and remembers it on the H token; the others ADD to it inside the per-edge
-        # kernel (same additions, same order: the same bits) and return nothing.  Keyed on the autograd graph task: a new
-        # backward pass (retain_graph, a checkpointed segment, a pass abandoned half way) always starts a new tensor.
-        tok, acc, tid = ctx.token, None, -1
-        share = tok is not None and ACCUMULATE_GRAD_HIDDEN and ctx.needs_input_grad[1] and \
-            ctx.csr.n_edges >= 32 * ctx.csr.n_nodes and hasattr(torch._C, "_current_graph_task_id")
-        if share:
-            tid = torch._C._current_graph_task_id()
-            if tid >= 0 and tok.gh_acc is not None and tok.gh_tid == tid and tok.gh_acc.shape == hidden.shape:
-                acc = tok.gh_acc
+        # kernel (same additions, same order: the same bits) and return nothing (the transitions: HiddenToken).
+        tok = ctx.token
+        share = tok is not None and ACCUMULATE_GRAD_HIDDEN and ctx.needs_input_grad[1] and ctx.csr.n_edges >= 32 * ctx.csr.n_nodes
+        acc = tok.find(hidden.shape) if share else None
         gx, gh, gw, gb, groot, gbias = ops.nnconv_backward_hidden_raw(
             x, ctx.csr, hidden, ctx.dims, w_last, b_last, root, ctx.aggr, grad_out,
-            need_root=root is not None, need_bias=ctx.has_bias, z_saved=ctx.z, grad_hidden_acc=acc)
+            need_root=root is not None, need_bias=ctx.has_bias, z_saved=ctx.z, grad_hidden_acc=None if acc is None else acc[0])
         ctx.z = None
         if acc is not None:
             gh = None                       # added in place to the tensor the first application returned
-            tok.gh_adds += 1
+            tok.added()
             ops.n_grad_hidden_accumulated += 1
-        elif share and tid >= 0:
-            tok.gh_acc, tok.gh_tid, tok.gh_adds = gh, tid, 0
+        elif share:
+            tok.start(gh)
         return (gx, gh, None, None, gw, gb, groot, gbias if ctx.has_bias else None, None, None, None)
 
 
@@ -339,12 +376,8 @@ class EdgeWeightsFunction(torch.autograd.Function):
     def backward(ctx, grad_we):
         tok = ctx.token
         tok.valid = False
-        if tok.gh_acc is not None and tok.gh_adds > 0 and hasattr(torch._C, "_current_graph_task_id") and \
-                tok.gh_tid == torch._C._current_graph_task_id() and grad_we.data_ptr() != tok.gh_acc.data_ptr():
-            # (as HiddenFunction.backward: the applications added in place to the first one's tensor, autograd hands over another)
-            raise RuntimeError("graph_pde_amd: the in-place sum of dL/dW_e lost its buffer (W_e has a consumer outside WeConvFunction); "
-                               "set GPDE_ACCUMULATE_DLDH=0")
-        tok.gh_acc, tok.gh_adds, tok.side_acc = None, 0, None
+        tok.taken(grad_we, "graph_pde_amd: the in-place sum of dL/dW_e lost its buffer (W_e has a consumer outside WeConvFunction); "
+                           "set GPDE_ACCUMULATE_DLDH=0")
         hidden, w_last = ctx.saved_tensors
         gh, gw, gb = ops.edge_weights_backward_raw(grad_we, hidden, ctx.dims, w_last, need_b=ctx.has_b)
         return gh, None, gw, gb, None
@@ -365,12 +398,8 @@ class SharedParamFunction(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        tok = ctx.token
-        if tok.side_acc is not None and tok.gh_adds > 0 and hasattr(torch._C, "_current_graph_task_id") and \
-                tok.gh_tid == torch._C._current_graph_task_id():
-            mine = tok.side_acc[ctx.which]
-            if mine is not None and g.data_ptr() != mine.data_ptr():
-                raise RuntimeError("graph_pde_amd: the in-place sum of a root / bias gradient lost its buffer; set GPDE_ACCUMULATE_DLDH=0")
+        # (checked, not dropped: the W_e node's backward - before or after this one - drops, after its own check)
+        ctx.token.check(g, "graph_pde_amd: the in-place sum of a root / bias gradient lost its buffer; set GPDE_ACCUMULATE_DLDH=0", ctx.which)
         return g, None, None
 
 
@@ -394,25 +423,19 @@ class WeConvFunction(torch.autograd.Function):
         # parameters); autograd would keep the first and add the others with one elementwise kernel per application and tensor
         # (MGKN training steps: 190 - 220 such launches, 2.3 - 2.6 ms of a 20 - 28 ms step).  As NNConvHiddenFunction does for
         # dL/dH: the first application of a backward pass hands autograd its tensors and remembers them on the W_e token, the
-        # others add to them inside the kernels (gpde_nnconv_bwd_edgeweights_acc: same additions, same order, the same bits)
-        # and return nothing.  Keyed on the autograd graph task: another pass always starts new tensors.
-        tok, acc, tid = ctx.token, None, -1
-        needs = ctx.needs_input_grad
+        # and return nothing (the transitions: HiddenToken).
+        tok, needs = ctx.token, ctx.needs_input_grad
         share = tok is not None and tok.side_in is not None and ACCUMULATE_GRAD_HIDDEN and needs[1] and \
-            hasattr(torch._C, "_current_graph_task_id") and (root is None or needs[3]) and (not ctx.has_bias or needs[4])
-        if share:
-            tid = torch._C._current_graph_task_id()
-            if tid >= 0 and tok.gh_acc is not None and tok.gh_tid == tid and tok.side_acc is not None and \
-                    tok.gh_acc.shape == we.shape:
-                acc = (tok.gh_acc, *tok.side_acc)
+            (root is None or needs[3]) and (not ctx.has_bias or needs[4])
+        acc = tok.find(we.shape) if share else None
         gx, gwe, groot, gbias = ops.nnconv_backward_edgeweights_raw(x, ctx.csr, we, root, ctx.aggr, grad_out,
                                                                     need_root=root is not None, need_bias=ctx.has_bias, acc=acc)
         if acc is not None:
-            tok.gh_adds += 1
+            tok.added()
             ops.n_grad_hidden_accumulated += 1
             return gx, None, None, None, None, None, None
-        if share and tid >= 0:
-            tok.gh_acc, tok.gh_tid, tok.gh_adds, tok.side_acc = gwe, tid, 0, (groot, gbias)
+        if share:
+            tok.start(gwe, groot, gbias)
         return gx, gwe, None, groot, gbias if ctx.has_bias else None, None, None
 
 

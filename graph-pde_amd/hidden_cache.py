@@ -156,7 +156,7 @@ def release_all() -> bool:
     for ent in list(_entries.values()):
         freed = freed or ent.h.value is not None or ent.w.value is not None
         if ent.h.token is not None:
-            ent.h.token.gh_acc, ent.h.token.gh_adds = None, 0
+            ent.h.token.drop()
         # On purpose: the virtual-H node `d` stays (it owns no H of its own, only `hpart`), and no policy state is reset
         for slot in (ent.h, ent.w, ent.tw):        # (nodes of a live graph keep their own references)
             slot.clear()
@@ -220,7 +220,7 @@ def lookup(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, weights, b
         # token: [E, K2P], 24 GB at s=121.  Dropped at forward time - unless this forward runs INSIDE a backward pass
         # (a checkpointed segment recomputing): the sum then belongs to the pass in flight
         if not in_backward_pass():
-            h.token.gh_acc, h.token.gh_adds = None, 0
+            h.token.drop()
         if ent.hn == csr.n_nodes or allow_partial:
             stats["hits"] += 1
             if ent.hn < csr.n_nodes:
@@ -270,7 +270,7 @@ def lookup(module: torch.nn.Module, edge_attr: torch.Tensor, csr, pm, weights, b
         # the budget was measured a moment ago; another module's cache, another process or the caller's own tensors may have
         # taken the room since.  H is an optimisation: drop everything cached and run the direct path.
         if old is not None:
-            old.gh_acc, old.gh_adds = None, 0        # (as release_all does for the token of an H still in its slot)
+            old.drop()        # (as release_all does for the token of an H still in its slot)
         release_all()
         torch.cuda.empty_cache()
         stats["oom_fallbacks"] = stats.get("oom_fallbacks", 0) + 1
@@ -396,7 +396,7 @@ def lookup_edge_weights_train(module: torch.nn.Module, hidden: torch.Tensor, csr
         # (a backward pass that never reached the W_e node left its running sums on the token; a forward inside a backward pass -
         # a checkpointed segment - leaves them alone, as `lookup` does)
         if not in_backward_pass():
-            twe.token.gh_acc, twe.token.gh_adds, twe.token.side_acc = None, 0, None
+            twe.token.drop()
         twe.hit("edge_weights")
         return twe.value
     twe.clear()

@@ -251,6 +251,15 @@ def _stream_ptr(device) -> int:
     return int(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _call(name: str, dev, *args, label: Optional[str] = None, calls: int = 1):
+    """One counted native call: entry point `name` with `args` and, last, the current stream of `dev`, under the device guard; a
+    refusal is raised under `label` (default: the entry point's name); `calls`: operator calls the launch stands for."""
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.lib(), name)(*args, _stream_ptr(dev))
+    _lib.check(rc, label or name)
+    _lib.n_native_calls += calls
+
+
 _ver_memo: "dict | None" = None          # content checksums of inference tensors computed during the current operator call
 
 
@@ -480,11 +489,16 @@ def _mlp_shapes(dims: Sequence[int]):
     return [(dims[l + 1], dims[l]) for l in range(len(dims) - 1)], [(dims[l + 1],) for l in range(len(dims) - 1)]
 
 
+def _mlp_dims(weights) -> List[int]:
+    """The layer widths of a kernel MLP, read off ALL its weights."""
+    return [int(weights[0].size(1))] + [int(w.size(0)) for w in weights]
+
+
 def _mlp_operands(weights, biases, dev, dims: Optional[Sequence[int]] = None):
     """The kernel MLP of a native call: (dims, dims_c, weights, biases) with every given layer checked as an operand (None
     entries pass through).  `dims`: all layer widths where `weights` holds only the first layers; else read off the weights."""
     if dims is None:
-        dims = [int(weights[0].size(1))] + [int(w.size(0)) for w in weights]
+        dims = _mlp_dims(weights)
     w_shapes, b_shapes = _mlp_shapes(dims)
     return (dims, _lib.dims_array(dims), _operands([None if w is None else w.detach() for w in weights], "weights", w_shapes, dev),
             _operands([None if b is None else b.detach() for b in biases], "biases", b_shapes, dev))
@@ -1047,7 +1061,6 @@ def _forward64(label: str, x: torch.Tensor, csr: Csr, pm: PackedMlp, root, bias,
     their max |H| scalar - with `hidden_nodes` None H of EVERY edge, with `hidden_nodes` = k the rows of the in-edges of
     nodes [0, k) only (the general entry point; k = 0: no H).  `residual` / `relu`: out = act(residual + NNConv(x)) in the
     last kernel; `z_keep` (zeros [N, 64 * K2P]): Z of every node is left there for the backward (`z_buffer`)."""
-    lib = _lib.lib()
     _require_cuda(x, "x")
     if aggr not in _AGGR:
         raise NotImplementedError(f"aggr={aggr!r}: 'add' and 'mean' only")
@@ -1090,22 +1103,20 @@ def _forward64(label: str, x: torch.Tensor, csr: Csr, pm: PackedMlp, root, bias,
     head = (x.data_ptr(), n)
     graph = (csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr())
     mlp = (len(pm.dims) - 1, pm.dims_c, pm.packed.data_ptr(), _ptr(root_c), _ptr(bias_c), _AGGR[aggr])
-    tail = (out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+    tail = (out.data_ptr(), ws.data_ptr(), ws.numel())
     act = (_ptr(residual), 1 if relu else 0)
-    with torch.cuda.device(dev):
-        if general:
-            rc = lib.gpde_nnconv_fwd_mixed_keepz(*head, attr_p, na_ref, _ptr(hidden), _ptr(hmax), hidden_nodes or 0, e, *graph, perm_p,
-                                                 *mlp, flags, _ptr(z_keep), *tail)
-        elif z_keep is not None:
-            rc = lib.gpde_nnconv_fwd_keepz(*head, attr_p, _ptr(hidden), _ptr(hmax), e, *graph, perm_p, *mlp, flags, z_keep.data_ptr(), *tail)
-        elif hidden is not None:
-            rc = lib.gpde_nnconv_fwd_hidden_act(*head, hidden.data_ptr(), _ptr(hmax), e, *graph, *mlp, *act, *tail)
-        elif glue:
-            rc = lib.gpde_nnconv_fwd_act(*head, attr_p, e, *graph, perm_p, *mlp, flags, *act, *tail)
-        else:
-            rc = lib.gpde_nnconv_fwd(*head, attr_p, e, *graph, perm_p, *mlp, flags, *tail)
-    _lib.check(rc, label)
-    _lib.n_native_calls += 1
+    if general:
+        name, args = "gpde_nnconv_fwd_mixed_keepz", (*head, attr_p, na_ref, _ptr(hidden), _ptr(hmax), hidden_nodes or 0, e, *graph, perm_p,
+                                                     *mlp, flags, _ptr(z_keep), *tail)
+    elif z_keep is not None:
+        name, args = "gpde_nnconv_fwd_keepz", (*head, attr_p, _ptr(hidden), _ptr(hmax), e, *graph, perm_p, *mlp, flags, z_keep.data_ptr(), *tail)
+    elif hidden is not None:
+        name, args = "gpde_nnconv_fwd_hidden_act", (*head, hidden.data_ptr(), _ptr(hmax), e, *graph, *mlp, *act, *tail)
+    elif glue:
+        name, args = "gpde_nnconv_fwd_act", (*head, attr_p, e, *graph, perm_p, *mlp, flags, *act, *tail)
+    else:
+        name, args = "gpde_nnconv_fwd", (*head, attr_p, e, *graph, perm_p, *mlp, flags, *tail)
+    _call(name, dev, *args, label=label)
     return out
 
 
@@ -1299,6 +1310,100 @@ def fused_kernel_name(n_nodes: int, n_edges: int, pm: PackedMlp, precision: Opti
 # ----------------------------------------------------------------------------------------------
 # backward
 # ----------------------------------------------------------------------------------------------
+_BWD64 = {          # phase (the names of _lib.BWD_TRACE_CODES["phase"]) -> (entry point, its label in a library error)
+    "full": ("gpde_nnconv_bwd", None), "conv": ("gpde_nnconv_bwd", "gpde_nnconv_bwd (hidden given)"), "mlp": ("gpde_hidden_bwd", None),
+    "light": ("gpde_nnconv_bwd_light", None), "deferred": ("gpde_nnconv_bwd_deferred", None)}
+
+
+def _backward64(phase: str, csr: Csr, W, b, *, dims=None, x=None, edge_attr=None, keep_rows: bool = False, root=None, aggr=None,
+                grad_out=None, grad_hidden_in=None, z_saved=None, hidden=None, hpart=None, hpart_nodes: int = 0, grad_hidden_out=None,
+                n_defer: int = 0, x_stack=None, g_stack=None, need_root: bool = False, need_bias: bool = False, need_attr: bool = False,
+                ws=None):
+    """The one body of the 64-wide backward wrappers: one native call on the current stream.  `phase` names the stage of
+    `bwd_impl` that runs, the keywords are the fields of `BwdArgs` (csrc/gpde_bwd.hip) a wrapper gives; each wrapper has raised
+    its own refusals.  `W` / `b`: the Linear layers the phase reads - all of them ("full", "light", "deferred"), the hidden ones
+    ("mlp"), or None in front of the last ("conv": `hidden` is H of every edge); `dims`: all widths where `W` does not tell them.
+    `hidden` of "full" is the H its forward kept, `hpart` / `hpart_nodes` the partial H of the mixed forward, `grad_hidden_out` a
+    tensor dL/dU is ADDED to ("conv").  Gradients are written for the last Linear ("light", "conv"), the hidden ones ("deferred",
+    "mlp") or every layer ("full").  Returns (grad_x, grad_hidden, grad_attr, [grad_W], [grad_b], grad_root, grad_bias), None for
+    what the phase does not write.
+
+    The workspace: a caller-given `ws` ("full" takes one); else "full" allocates by `alloc_bwd_ws` for (n, e) less the bytes of a
+    given H, "mlp" by `alloc_bwd_ws` for (0, e) - both may take the opt-in one-chunk size -, "light" and "conv" the size
+    gpde_nnconv_bwd_workspace_bytes names and "deferred" that of gpde_nnconv_bwd_deferred_workspace_bytes for `n_defer`."""
+    lib = _lib.lib()
+    name, label = _BWD64[phase]
+    for t, nm in ((x, "x"), (edge_attr, "edge_attr"), (hidden, "hidden"), (grad_out, "grad_out"), (grad_hidden_in, "grad_hidden")):
+        if t is not None:
+            _require_cuda(t, nm)
+    n, e, dev = csr.n_nodes, csr.n_edges, (edge_attr if x is None else x).device
+    x = _operand(None if x is None else x.detach(), "x", (n, WIDTH), dev)
+    grad_out = _operand(None if grad_out is None else grad_out.detach().float(), "grad_out", (n, WIDTH), dev)
+    if phase == "conv":                                    # the arrays carry their LAST entries only, under their own names
+        dims_c = _lib.dims_array(dims)
+        front = [None] * (len(dims) - 2)
+        W = front + [_operand(W[-1].detach(), "w_last", (WIDTH * WIDTH, dims[-2]), dev)]
+        b = front + [_operand(None if b[-1] is None else b[-1].detach(), "b_last", (WIDTH * WIDTH,), dev)]
+    else:
+        dims, dims_c, W, b = _mlp_operands(W, b, dev, dims)
+    nl, k2p = len(dims) - 1, hidden_width(dims)
+    W, b = W + [None] * (nl - len(W)), b + [None] * (nl - len(b))
+    root_c, _ = _root_bias(root, None, dev)
+    z_saved = _operand(z_saved, "z_saved", (n, WIDTH * k2p), dev)
+    hidden = _operand(None if hidden is None else hidden.detach(), "hidden" if phase == "conv" else "hidden_saved", (e, k2p), dev)
+    hpart = _operand(hpart, "hidden_part", (None, k2p), dev)
+    grad_hidden_in = _operand(None if grad_hidden_in is None else grad_hidden_in.detach(), "grad_hidden", (e, k2p), dev)
+    accumulate = grad_hidden_out is not None
+    gh = _operand(grad_hidden_out, "grad_hidden_acc", (e, k2p), dev, writable=True)
+    ws = _operand(ws, "ws", (None,), dev, writable=True, dtype=torch.uint8)
+    attr_p, na_ref, perm_p, _alive = _attr_source(csr, None if edge_attr is None else edge_attr.detach(), keep_rows=keep_rows)
+    # the gradients
+    wanted = {"full": range(nl), "light": (nl - 1,), "conv": (nl - 1,), "deferred": range(nl - 1), "mlp": range(nl - 1)}[phase]
+    gW = [torch.empty_like(W[l]) if l in wanted else None for l in range(nl)]
+    gb = [torch.empty_like(b[l]) if l in wanted and b[l] is not None else None for l in range(nl)]
+    gx = None if x is None else torch.empty(n, WIDTH, dtype=torch.float32, device=dev)
+    if phase == "conv" and gh is None:
+        gh = torch.empty_like(hidden)
+    groot, gbias = _update_grads(root, need_root, need_bias, dev)
+    ga = torch.zeros(e, dims[0], dtype=torch.float32, device=dev) if need_attr else None
+    grads = (gx, gh, ga, gW, gb, groot, gbias)
+    if phase == "full" and n == 0:
+        # a graph without nodes (message() of an edgeless graph runs the operator on E = 0 one-edge graphs): every sum is empty
+        for t in gW + gb + [groot, gbias]:
+            if t is not None:
+                t.zero_()
+        return grads
+    if ws is not None:
+        pass
+    elif phase in ("full", "mlp"):
+        ws = alloc_bwd_ws(lib, n if phase == "full" else 0, e, nl, dims_c, dev, 0 if hidden is None else e * k2p * 4)
+    elif phase == "deferred":
+        ws = _queried_ws("gpde_nnconv_bwd_deferred_workspace_bytes", dev, n, e, nl, dims_c, n_defer)
+    else:
+        ws = _queried_ws("gpde_nnconv_bwd_workspace_bytes", dev, n, e, nl, dims_c)
+    # the runs of arguments the entry points share, in the header's order
+    attr = (attr_p, na_ref)
+    mlp = (nl, dims_c, _ptr_array(W), _ptr_array(b))
+    tail = (ws.data_ptr(), ws.numel())
+    if phase == "mlp":
+        args = (*attr, e, perm_p, csr.src.data_ptr(), csr.dst.data_ptr(), *mlp, grad_hidden_in.data_ptr(), _ptr_array(gW), _ptr_array(gb), *tail)
+    else:
+        graph = (e, csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(), perm_p, csr.rowptr_host.data_ptr())
+        hp = (_ptr(hpart) if hpart_nodes > 0 else None, int(hpart_nodes) if hpart is not None else 0)
+        if phase == "deferred":
+            args = (x_stack.data_ptr(), g_stack.data_ptr(), n_defer, n, *attr, *graph, *mlp, _AGGR[aggr], *hp, _ptr_array(gW), _ptr_array(gb), *tail)
+        else:
+            srp, ssl = csr.src_order
+            node = (_ptr(srp), _ptr(ssl), *mlp, _ptr(root_c), _AGGR[aggr], grad_out.data_ptr(), _ptr(z_saved))
+            if phase == "light":
+                args = (x.data_ptr(), n, *attr, *graph, *node, *hp, gx.data_ptr(), gW[-1].data_ptr(), _ptr(gb[-1]), _ptr(groot), _ptr(gbias), *tail)
+            else:
+                args = (x.data_ptr(), n, *attr, _ptr(hidden), *graph, *node, gx.data_ptr(), _ptr(gh), _ptr(ga), _ptr_array(gW), _ptr_array(gb),
+                        _ptr(groot), _ptr(gbias), _lib.GPDE_BWD_ACCUMULATE_GRAD_HIDDEN if accumulate else 0, *tail)
+    _call(name, dev, *args, label=label)
+    return grads
+
+
 def nnconv_backward_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor,
                         weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Tensor]],
                         root: Optional[torch.Tensor], aggr: str, grad_out: torch.Tensor,
@@ -1309,48 +1414,18 @@ def nnconv_backward_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor,
     `hidden_saved`: the last hidden activations [E, K2P] the forward kept (hidden_forward_raw) - read instead of recomputed).
     Returns (grad_x, [grad_W_l], [grad_b_l or None], grad_root or None, grad_bias or None); with `need_attr` a sixth element,
     dL/d edge_attr [E, k0] in the caller's edge order (`grad_edge_attr` of the call)."""
-    lib = _lib.lib()
-    for t, nm in ((x, "x"), (edge_attr, "edge_attr"), (grad_out, "grad_out")):
-        _require_cuda(t, nm)
     if aggr not in _AGGR:
         raise NotImplementedError(f"aggr={aggr!r}")
-    n, e, dev = csr.n_nodes, csr.n_edges, x.device
-    x = _operand(x.detach(), "x", (n, WIDTH), dev)
-    dims, dims_c, ws_, bs_ = _mlp_operands(weights, biases, dev)
-    nl, k2p = len(ws_), hidden_width(dims)
+    dims = _mlp_dims(weights)
     if need_attr and (isinstance(edge_attr, NodeAttr) or dims[0] > 8):
         raise NotImplementedError("the edge-attribute gradient is built for attribute tensors of <= 8 slots")
-    # (`need_attr`: the caller's rows - the gradient goes back by perm)
-    attr_p, na_ref, perm_p, _alive = _attr_source(csr, edge_attr.detach(), keep_rows=need_attr)
-    grad_out = _operand(grad_out.detach().float(), "grad_out", (n, WIDTH), dev)
-    root_c, _ = _root_bias(root, None, dev)
-    ws = _operand(ws, "ws", (None,), dev, writable=True, dtype=torch.uint8)
-    z_saved = _operand(z_saved, "z_saved", (n, WIDTH * k2p), dev)
-    gx = torch.empty(n, WIDTH, dtype=torch.float32, device=dev)
-    gW = [torch.empty_like(w) for w in ws_]
-    gb = [None if b is None else torch.empty_like(b) for b in bs_]
-    groot, gbias = _update_grads(root, need_root, need_bias, dev)
-    ga = torch.zeros(e, dims[0], dtype=torch.float32, device=dev) if need_attr else None
-    if n == 0:
-        # a graph without nodes (message() of an edgeless graph runs the operator on E = 0 one-edge graphs): every sum is empty
-        for t in gW + gb + [groot, gbias]:
-            if t is not None:
-                t.zero_()
-        return (gx, gW, gb, groot, gbias, ga) if need_attr else (gx, gW, gb, groot, gbias)
-    if ws is None:
-        ws = alloc_bwd_ws(lib, n, e, nl, dims_c, dev, 0 if hidden_saved is None else e * k2p * 4)
-    srp, ssl = csr.src_order
+    e, k2p = csr.n_edges, hidden_width(dims)
     if hidden_saved is not None and (need_attr or hidden_saved.dtype != torch.float32 or tuple(hidden_saved.shape) != (e, k2p)):
         raise ValueError(f"hidden_saved must be float32 [{e},{k2p}] (and excludes need_attr)")
-    hidden_saved = _operand(hidden_saved, "hidden_saved", (e, k2p), dev)
-    with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_bwd(x.data_ptr(), n, attr_p, na_ref, _ptr(hidden_saved), e, csr.rowptr.data_ptr(), csr.src.data_ptr(),
-                                 csr.dst.data_ptr(), perm_p, csr.rowptr_host.data_ptr(), _ptr(srp), _ptr(ssl), nl, dims_c,
-                                 _ptr_array(ws_), _ptr_array(bs_), _ptr(root_c), _AGGR[aggr], grad_out.data_ptr(), _ptr(z_saved),
-                                 gx.data_ptr(), None, _ptr(ga), _ptr_array(gW), _ptr_array(gb), _ptr(groot), _ptr(gbias), 0,
-                                 ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "gpde_nnconv_bwd")
-    _lib.n_native_calls += 1
+    # (`need_attr`: the attributes stay in the caller's rows - the gradient goes back by perm)
+    gx, _, ga, gW, gb, groot, gbias = _backward64("full", csr, weights, biases, x=x, edge_attr=edge_attr, keep_rows=need_attr, root=root,
+                                                  aggr=aggr, grad_out=grad_out, z_saved=z_saved, hidden=hidden_saved, need_root=need_root,
+                                                  need_bias=need_bias, need_attr=need_attr, ws=ws)
     return (gx, gW, gb, groot, gbias, ga) if need_attr else (gx, gW, gb, groot, gbias)
 
 
@@ -1383,36 +1458,12 @@ def nnconv_backward_light_raw(x: torch.Tensor, csr: Csr, edge_attr: torch.Tensor
     grad_bias; the hidden layers' gradients come from nnconv_backward_deferred_raw.  `hidden_part` / `hidden_nodes`: the
     partial H of the mixed forward (rows of the in-edges of nodes [0, hidden_nodes)): read instead of recomputed.
     Returns (grad_x, grad_w_last, grad_b_last or None, grad_root or None, grad_bias or None)."""
-    lib = _lib.lib()
-    for t, nm in ((x, "x"), (edge_attr, "edge_attr"), (grad_out, "grad_out")):
-        _require_cuda(t, nm)
     if aggr not in _AGGR:
         raise NotImplementedError(f"aggr={aggr!r}")
-    n, e, dev = csr.n_nodes, csr.n_edges, x.device
-    x = _operand(x.detach(), "x", (n, WIDTH), dev)
-    attr_p, na_ref, perm_p, _alive = _attr_source(csr, edge_attr.detach())
-    grad_out = _operand(grad_out.detach().float(), "grad_out", (n, WIDTH), dev)
-    dims, dims_c, ws_, bs_ = _mlp_operands(weights, biases, dev)
-    nl, k2p = len(ws_), hidden_width(dims)
-    root_c, _ = _root_bias(root, None, dev)
-    z_saved = _operand(z_saved, "z_saved", (n, WIDTH * k2p), dev)
-    hidden_part = _operand(hidden_part, "hidden_part", (None, k2p), dev)
-    gx = torch.empty(n, WIDTH, dtype=torch.float32, device=dev)
-    gw = torch.empty_like(ws_[-1])
-    gb = None if bs_[-1] is None else torch.empty_like(bs_[-1])
-    groot, gbias = _update_grads(root, need_root, need_bias, dev)
-    ws = _queried_ws("gpde_nnconv_bwd_workspace_bytes", dev, n, e, nl, dims_c)
-    srp, ssl = csr.src_order
-    with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_bwd_light(x.data_ptr(), n, attr_p, na_ref, e, csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(),
-                                       perm_p, csr.rowptr_host.data_ptr(), _ptr(srp), _ptr(ssl), nl, dims_c,
-                                       _ptr_array(ws_), _ptr_array(bs_), _ptr(root_c), _AGGR[aggr], grad_out.data_ptr(), _ptr(z_saved),
-                                       _ptr(hidden_part) if hidden_nodes > 0 else None, int(hidden_nodes) if hidden_part is not None else 0,
-                                       gx.data_ptr(), gw.data_ptr(), _ptr(gb), _ptr(groot), _ptr(gbias), ws.data_ptr(), ws.numel(),
-                                       _stream_ptr(dev))
-    _lib.check(rc, "gpde_nnconv_bwd_light")
-    _lib.n_native_calls += 1
-    return gx, gw, gb, groot, gbias
+    gx, _, _, gW, gb, groot, gbias = _backward64("light", csr, weights, biases, x=x, edge_attr=edge_attr, root=root, aggr=aggr,
+                                                 grad_out=grad_out, z_saved=z_saved, hpart=hidden_part, hpart_nodes=hidden_nodes,
+                                                 need_root=need_root, need_bias=need_bias)
+    return gx, gW[-1], gb[-1], groot, gbias
 
 
 def nnconv_backward_deferred_raw(xs: Sequence[torch.Tensor], gs: Sequence[torch.Tensor], csr: Csr, edge_attr: torch.Tensor,
@@ -1421,34 +1472,19 @@ def nnconv_backward_deferred_raw(xs: Sequence[torch.Tensor], gs: Sequence[torch.
     """gpde_nnconv_bwd_deferred: the hidden layers' gradients of ALL the applications (xs[l], gs[l]) = (input, output
     gradient) of a depth-shared module, in one pass over the edges.  `weights` / `biases`: ALL Linear layers (the last one
     is read, not differentiated).  Returns ([grad_W_l], [grad_b_l or None]) for the hidden layers."""
-    lib = _lib.lib()
     L = len(xs)
     if L < 1 or len(gs) != L:
         raise ValueError("one (input, output gradient) pair per deferred application")
-    n, e, dev = csr.n_nodes, csr.n_edges, edge_attr.device
-    Lp = deferred_layers_padded(L)
-    x_stack = torch.zeros(Lp, n, WIDTH, dtype=torch.float32, device=dev)
+    n, dev = csr.n_nodes, edge_attr.device
+    x_stack = torch.zeros(deferred_layers_padded(L), n, WIDTH, dtype=torch.float32, device=dev)      # (zero layers appended)
     g_stack = torch.empty(L, n, WIDTH, dtype=torch.float32, device=dev)
     for l in range(L):
         x_stack[l].copy_(_operand(xs[l].detach(), f"xs[{l}]", (n, WIDTH), dev))
         g_stack[l].copy_(_operand(gs[l].detach().float(), f"gs[{l}]", (n, WIDTH), dev))
-    attr_p, na_ref, perm_p, _alive = _attr_source(csr, edge_attr.detach())
-    dims, dims_c, ws_, bs_ = _mlp_operands(weights, biases, dev)
-    nl = len(ws_)
-    hidden_part = _operand(hidden_part, "hidden_part", (None, hidden_width(dims)), dev)
-    gW = [torch.empty_like(w) for w in ws_[:-1]] + [None]
-    gb = [None if b is None else torch.empty_like(b) for b in bs_[:-1]] + [None]
-    ws = _queried_ws("gpde_nnconv_bwd_deferred_workspace_bytes", dev, n, e, nl, dims_c, L)
-    with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_bwd_deferred(x_stack.data_ptr(), g_stack.data_ptr(), L, n, attr_p, na_ref, e, csr.rowptr.data_ptr(),
-                                          csr.src.data_ptr(), csr.dst.data_ptr(), perm_p, csr.rowptr_host.data_ptr(), nl, dims_c,
-                                          _ptr_array(ws_), _ptr_array(bs_), _AGGR[aggr],
-                                          _ptr(hidden_part) if hidden_nodes > 0 else None,
-                                          int(hidden_nodes) if hidden_part is not None else 0,
-                                          _ptr_array(gW), _ptr_array(gb), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "gpde_nnconv_bwd_deferred")
-    _lib.n_native_calls += 1
+    _, _, _, gW, gb, _, _ = _backward64("deferred", csr, weights, biases, edge_attr=edge_attr, aggr=aggr, hpart=hidden_part,
+                                        hpart_nodes=hidden_nodes, n_defer=L, x_stack=x_stack, g_stack=g_stack)
     return gW[:-1], gb[:-1]
+
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1540,12 +1576,8 @@ def edge_weights_raw(hidden: torch.Tensor, pm: PackedMlp, w_last: torch.Tensor, 
     we = torch.empty(e, WIDTH * WIDTH, dtype=torch.float32, device=dev)
     nl = len(pm.dims) - 1
     ws = torch.empty(max(int(lib.gpde_edge_weights_workspace_bytes(e, nl, pm.dims_c)), 1), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.gpde_edge_weights_fwd(hidden.data_ptr(), e, nl, pm.dims_c, pm.packed.data_ptr(), w_c.data_ptr(),
-                                       None if b_c is None else b_c.data_ptr(), we.data_ptr(), ws.data_ptr(), ws.numel(),
-                                       _stream_ptr(dev))
-    _lib.check(rc, "gpde_edge_weights_fwd")
-    _lib.n_native_calls += 1
+    _call("gpde_edge_weights_fwd", dev, hidden.data_ptr(), e, nl, pm.dims_c, pm.packed.data_ptr(), w_c.data_ptr(), _ptr(b_c), we.data_ptr(),
+          ws.data_ptr(), ws.numel())
     return we
 
 
@@ -1556,7 +1588,6 @@ def nnconv_forward_edgeweights_group(calls: Sequence[dict]) -> List[torch.Tensor
     """gpde_nnconv_fwd_edgeweights_group: INDEPENDENT NNConv calls, each given its per-edge weights, in one launch per
     16 calls.  Every call is a dict: x [N,64], csr, edge_weights [E,4096], root, bias, aggr ('add' | 'mean' | 'max'),
     optional residual [N,64], relu (bool), out.  Returns the outputs in order."""
-    lib = _lib.lib()
     if not calls:
         return []
     dev = calls[0]["x"].device
@@ -1584,14 +1615,9 @@ def nnconv_forward_edgeweights_group(calls: Sequence[dict]) -> List[torch.Tensor
         outs.append(out)
         d = descs[k]
         d.x, d.edge_weights, d.rowptr, d.src = x_c.data_ptr(), we.data_ptr(), csr.rowptr.data_ptr(), csr.src.data_ptr()
-        d.root = None if root_c is None else root_c.data_ptr()
-        d.bias = None if bias_c is None else bias_c.data_ptr()
-        d.residual = None if res is None else res.data_ptr()
+        d.root, d.bias, d.residual = _ptr(root_c), _ptr(bias_c), _ptr(res)
         d.out, d.n_nodes, d.aggr, d.relu, d.reserved = out.data_ptr(), n, _AGGR_WE[aggr], 1 if c.get("relu") else 0, 0
-    with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_fwd_edgeweights_group(descs, len(calls), _stream_ptr(dev))
-    _lib.check(rc, "gpde_nnconv_fwd_edgeweights_group")
-    _lib.n_native_calls += len(calls)
+    _call("gpde_nnconv_fwd_edgeweights_group", dev, descs, len(calls), calls=len(calls))
     return outs
 
 
@@ -1629,16 +1655,11 @@ def nnconv_backward_edgeweights_raw(x: torch.Tensor, csr: Csr, edge_weights: tor
         bits = _lib.GPDE_ACC_EDGE_WEIGHTS | (_lib.GPDE_ACC_ROOT if want_root else 0) | (_lib.GPDE_ACC_BIAS if need_bias else 0)
     else:
         gwe = torch.empty(e, WIDTH * WIDTH, dtype=torch.float32, device=dev)
-        groot = torch.empty(WIDTH, WIDTH, dtype=torch.float32, device=dev) if want_root else None
-        gbias = torch.empty(WIDTH, dtype=torch.float32, device=dev) if need_bias else None
+        groot, gbias = _update_grads(root, need_root, need_bias, dev)
     ws = _alloc_ws(int(lib.gpde_nnconv_bwd_edgeweights_workspace_bytes(n, e)), dev)
     srp, ssl = csr.src_order
-    with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_bwd_edgeweights_acc(x.data_ptr(), n, we.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(), _ptr(srp), _ptr(ssl),
-                                                 _ptr(root_c), _AGGR[aggr], grad_out.data_ptr(), gx.data_ptr(), gwe.data_ptr(), _ptr(groot), _ptr(gbias),
-                                                 bits, ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "gpde_nnconv_bwd_edgeweights_acc")
-    _lib.n_native_calls += 1
+    _call("gpde_nnconv_bwd_edgeweights_acc", dev, x.data_ptr(), n, we.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(), _ptr(srp), _ptr(ssl),
+          _ptr(root_c), _AGGR[aggr], grad_out.data_ptr(), gx.data_ptr(), gwe.data_ptr(), _ptr(groot), _ptr(gbias), bits, ws.data_ptr(), ws.numel())
     return gx, gwe, groot, gbias
 
 
@@ -1889,10 +1910,7 @@ def _any_native(stem: str, xs, xd, csr: Csr, widths, before, after):
     one, dev = xd is _ONE_SET, xs.device
     name = f"gpde_nnconv_{stem}_{'any' if one else 'bip'}"
     tables = (xs.data_ptr(), csr.n_nodes) if one else (xs.data_ptr(), csr.n_src, _ptr(xd), csr.n_nodes)
-    with torch.cuda.device(dev):
-        rc = getattr(_lib.lib(), name)(*tables, *before, *((widths[0], widths[2]) if one else widths), *after, _stream_ptr(dev))
-    _lib.check(rc, name)
-    _lib.n_native_calls += 1
+    _call(name, dev, *tables, *before, *((widths[0], widths[2]) if one else widths), *after)
 
 
 def _x_name(x_dst) -> str:
@@ -2077,11 +2095,8 @@ def edge_weights_backward_raw(grad_we: torch.Tensor, hidden: torch.Tensor, dims:
     gw = torch.empty_like(w_c)
     gb = torch.empty(WIDTH * WIDTH, dtype=torch.float32, device=dev) if need_b else None
     ws = _alloc_ws(int(lib.gpde_edge_weights_bwd_workspace_bytes(e, nl, dims_c)), dev)
-    with torch.cuda.device(dev):
-        rc = lib.gpde_edge_weights_bwd(grad_we.data_ptr(), hidden.data_ptr(), e, nl, dims_c, w_c.data_ptr(), gh.data_ptr(), gw.data_ptr(),
-                                       None if gb is None else gb.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "gpde_edge_weights_bwd")
-    _lib.n_native_calls += 1
+    _call("gpde_edge_weights_bwd", dev, grad_we.data_ptr(), hidden.data_ptr(), e, nl, dims_c, w_c.data_ptr(), gh.data_ptr(), gw.data_ptr(), _ptr(gb),
+          ws.data_ptr(), ws.numel())
     return gh, gw, gb
 
 
@@ -2109,39 +2124,10 @@ def nnconv_backward_hidden_raw(x: torch.Tensor, csr: Csr, hidden: torch.Tensor, 
     """gpde_nnconv_bwd in its `hidden` form (the last hidden activations given; `z_saved`: the keep-Z forward's buffer;
     `grad_hidden_acc`: a [E, K2P] tensor dL/dU is ADDED to instead of a fresh one - GPDE_BWD_ACCUMULATE_GRAD_HIDDEN).  Returns (grad_x, grad_hidden [E,K2P], grad_w_last, grad_b_last or None,
     grad_root or None, grad_bias or None)."""
-    lib = _lib.lib()
-    n, e, dev = csr.n_nodes, csr.n_edges, x.device
-    nl = len(dims) - 1
-    dims_c = _lib.dims_array(dims)
-    for t, nm in ((x, "x"), (hidden, "hidden"), (grad_out, "grad_out")):
-        _require_cuda(t, nm)
-    x = _operand(x.detach(), "x", (n, WIDTH), dev)
-    grad_out = _operand(grad_out.detach().float(), "grad_out", (n, WIDTH), dev)
-    hidden = _operand(hidden.detach(), "hidden", (e, hidden_width(dims)), dev)
-    w_last = _operand(w_last.detach(), "w_last", (WIDTH * WIDTH, dims[-2]), dev)
-    b_c = _operand(None if b_last is None else b_last.detach(), "b_last", (WIDTH * WIDTH,), dev)
-    root_c, _ = _root_bias(root, None, dev)
-    z_saved = _operand(z_saved, "z_saved", (n, WIDTH * hidden_width(dims)), dev)
-    gx = torch.empty(n, WIDTH, dtype=torch.float32, device=dev)
-    accumulate = grad_hidden_acc is not None
-    grad_hidden_acc = _operand(grad_hidden_acc, "grad_hidden_acc", tuple(hidden.shape), dev, writable=True)
-    gh = grad_hidden_acc if accumulate else torch.empty_like(hidden)
-    gw = torch.empty_like(w_last)
-    gb = None if b_c is None else torch.empty_like(b_c)
-    groot, gbias = _update_grads(root, need_root, need_bias, dev)
-    ws = _queried_ws("gpde_nnconv_bwd_workspace_bytes", dev, n, e, nl, dims_c)
-    srp, ssl = csr.src_order
-    front = [None] * (nl - 1)                              # the hidden form: the arrays carry their LAST entries only
-    Wa, Ba, gWa, gBa = (_ptr_array(front + [t]) for t in (w_last, b_c, gw, gb))
-    with torch.cuda.device(dev):
-        rc = lib.gpde_nnconv_bwd(x.data_ptr(), n, None, None, hidden.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(),
-                                 csr.dst.data_ptr(), None, csr.rowptr_host.data_ptr(), _ptr(srp), _ptr(ssl), nl, dims_c, Wa, Ba,
-                                 _ptr(root_c), _AGGR[aggr], grad_out.data_ptr(), _ptr(z_saved), gx.data_ptr(), gh.data_ptr(), None,
-                                 gWa, gBa, _ptr(groot), _ptr(gbias), _lib.GPDE_BWD_ACCUMULATE_GRAD_HIDDEN if accumulate else 0,
-                                 ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "gpde_nnconv_bwd (hidden given)")
-    _lib.n_native_calls += 1
-    return gx, gh, gw, gb, groot, gbias
+    gx, gh, _, gW, gb, groot, gbias = _backward64("conv", csr, [w_last], [b_last], dims=dims, x=x, hidden=hidden, root=root, aggr=aggr,
+                                                  grad_out=grad_out, z_saved=z_saved, grad_hidden_out=grad_hidden_acc,
+                                                  need_root=need_root, need_bias=need_bias)
+    return gx, gh, gW[-1], gb[-1], groot, gbias
 
 
 def hidden_backward_raw(csr: Csr, edge_attr: torch.Tensor, dims: Sequence[int],
@@ -2150,25 +2136,11 @@ def hidden_backward_raw(csr: Csr, edge_attr: torch.Tensor, dims: Sequence[int],
     """gpde_hidden_bwd: gradients of the hidden Linear layers from the summed dL/dU of the last hidden
     layer.  `weights` / `biases`: the hidden layers only (all but the last Linear); `dims`: all layer
     widths.  Returns ([grad_W_l], [grad_b_l or None]) for the hidden layers."""
-    lib = _lib.lib()
-    e, dev = csr.n_edges, edge_attr.device
-    nl = len(dims) - 1
-    if len(weights) != nl - 1:
+    if len(weights) != len(dims) - 2:
         raise ValueError("hidden_backward_raw takes the hidden layers only")
-    attr_p, na_ref, perm_p, _alive = _attr_source(csr, edge_attr.detach())
-    grad_hidden = _operand(grad_hidden.detach(), "grad_hidden", (e, hidden_width(dims)), dev)
-    _, dims_c, ws_, bs_ = _mlp_operands(weights, biases, dev, dims)
-    ws_, bs_ = ws_ + [None], bs_ + [None]
-    gW = [torch.empty_like(w) for w in ws_[:-1]] + [None]
-    gb = [None if b is None else torch.empty_like(b) for b in bs_[:-1]] + [None]
-    ws = alloc_bwd_ws(lib, 0, e, nl, dims_c, dev)
-    with torch.cuda.device(dev):
-        rc = lib.gpde_hidden_bwd(attr_p, na_ref, e, perm_p, csr.src.data_ptr(), csr.dst.data_ptr(), nl, dims_c,
-                                 _ptr_array(ws_), _ptr_array(bs_), grad_hidden.data_ptr(),
-                                 _ptr_array(gW), _ptr_array(gb), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "gpde_hidden_bwd")
-    _lib.n_native_calls += 1
+    _, _, _, gW, gb, _, _ = _backward64("mlp", csr, weights, biases, dims=dims, edge_attr=edge_attr, grad_hidden_in=grad_hidden)
     return gW[:-1], gb[:-1]
+
 
 
 # ----------------------------------------------------------------------------------------------
@@ -2906,11 +2878,7 @@ def gcn_norm(csr: Csr, edge_weight: Optional[torch.Tensor] = None, improved: boo
     self_coef = torch.empty(n, dtype=torch.float32, device=dev)
     ws = _alloc_ws(int(lib.gpde_gcn_norm_workspace_bytes(n, e)), dev)
     p = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-    with torch.cuda.device(dev):
-        rc = lib.gpde_gcn_norm(csr.rowptr.data_ptr(), p(csr.src), p(csr.perm), p(ew), n, e, flags, p(coef), p(self_coef), ws.data_ptr(),
-                               ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "gpde_gcn_norm")
-    _lib.n_native_calls += 1
+    _call("gpde_gcn_norm", dev, csr.rowptr.data_ptr(), p(csr.src), p(csr.perm), p(ew), n, e, flags, p(coef), p(self_coef), ws.data_ptr(), ws.numel())
     norm = GcnNorm(csr, coef, self_coef, flags)
     norm._rec.stamp(dev)
     # bytes an entry keeps alive once the CSR cache has let go of the graph: rowptr / src / dst / perm, coef, self_coef, edge_weight -
@@ -2944,16 +2912,12 @@ def gcn_route(in_channels: int, out_channels: int) -> str:
 
 
 def _gcn_call(x, csr: Csr, coef, self_coef, w, bias, cin: int, cout: int, relu: bool, want_agg: bool):
-    lib = _lib.lib()
     n, e, dev = csr.n_nodes, csr.n_edges, x.device
     out = torch.empty(n, cout, dtype=torch.float32, device=dev)
     agg = torch.empty(n, cin, dtype=torch.float32, device=dev) if want_agg else None
     p = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-    with torch.cuda.device(dev):
-        rc = lib.gpde_gcn_fwd(p(x), n, e, csr.rowptr.data_ptr(), p(csr.src), p(coef), p(self_coef), p(w), p(bias), cin, cout,
-                              GCN_RELU if relu else 0, p(out), p(agg), _stream_ptr(dev))
-    _lib.check(rc, "gpde_gcn_fwd")
-    _lib.n_native_calls += 1
+    _call("gpde_gcn_fwd", dev, p(x), n, e, csr.rowptr.data_ptr(), p(csr.src), p(coef), p(self_coef), p(w), p(bias), cin, cout,
+          GCN_RELU if relu else 0, p(out), p(agg))
     return out, agg
 
 
@@ -3089,12 +3053,8 @@ def _diagconv_forward(x_src, x_dst, csr: Csr, edge_kernel, root, bias, aggr: str
         for t, nm in ((xs, _x_name(x_dst)), (res, "residual")):
             if t is not None and t.numel() and lo < t.data_ptr() + t.numel() * 4 and t.data_ptr() < hi:
                 raise ValueError(f"out shares memory with {nm}: other waves still read those rows")
-    with torch.cuda.device(dev):
-        rc = _lib.lib().gpde_diagconv_fwd(*_diag_tables(xs, xd, csr), k.data_ptr(), csr.n_edges, csr.rowptr.data_ptr(), csr.src.data_ptr(),
-                                          _ptr(root_c), _ptr(bias_c), _ptr(res), 1 if relu else 0, _AGGR_WE[aggr], w, cind, out.data_ptr(),
-                                          _stream_ptr(dev))
-    _lib.check(rc, "gpde_diagconv_fwd")
-    _lib.n_native_calls += 1
+    _call("gpde_diagconv_fwd", dev, *_diag_tables(xs, xd, csr), k.data_ptr(), csr.n_edges, csr.rowptr.data_ptr(), csr.src.data_ptr(),
+          _ptr(root_c), _ptr(bias_c), _ptr(res), 1 if relu else 0, _AGGR_WE[aggr], w, cind, out.data_ptr())
     return out
 
 
@@ -3128,12 +3088,9 @@ def diagconv_backward_raw(x_src, x_dst, csr: Csr, edge_kernel, root, aggr: str, 
         srp, ssl = csr.src_order
     else:
         srp, ssl = None, None
-    with torch.cuda.device(dev):
-        rc = lib.gpde_diagconv_bwd(*_diag_tables(xs, xd, csr), k.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(),
-                                   _ptr(srp), _ptr(ssl), _ptr(root_c), _AGGR[aggr], w, cind, grad_out.data_ptr(), _ptr(gxs), _ptr(gxd),
-                                   gk.data_ptr(), _ptr(groot), _ptr(gbias), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "gpde_diagconv_bwd")
-    _lib.n_native_calls += 1
+    _call("gpde_diagconv_bwd", dev, *_diag_tables(xs, xd, csr), k.data_ptr(), e, csr.rowptr.data_ptr(), csr.src.data_ptr(), csr.dst.data_ptr(),
+          _ptr(srp), _ptr(ssl), _ptr(root_c), _AGGR[aggr], w, cind, grad_out.data_ptr(), _ptr(gxs), _ptr(gxd), gk.data_ptr(), _ptr(groot),
+          _ptr(gbias), ws.data_ptr(), ws.numel())
     return gxs, (gxd if need_x_dst else None), gk, groot, gbias
 
 

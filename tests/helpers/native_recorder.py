@@ -84,7 +84,9 @@ def named_args():
         w=[r(16, K0), r(K2, 16), r(W * W, K2)], b=[r(16), r(K2), r(W * W)],
         out=torch.zeros(N, W), ws=torch.zeros(4096, dtype=torch.uint8), z=torch.zeros(N, W * K2P),
         gh=r(E, K2P), acc=torch.zeros(E, K2P), x1=r(N, W), x2=r(N, W), g1=r(N, W), g2=r(N, W),
-        ea_sorted=r(E, K0), identity=torch.arange(E, dtype=torch.int32))
+        ea_sorted=r(E, K0), identity=torch.arange(E, dtype=torch.int32),
+        we=r(E, W * W), we2=r(E, W * W), csr2=graph(), gwe=r(E, W * W),
+        acc_we=[torch.zeros(E, W * W), torch.zeros(W, W), torch.zeros(W)])
 
 
 def _names(a):
@@ -143,6 +145,9 @@ def _normalise(name, args, ptr_name):
             out.append(int(a) if not isinstance(a, float) else a)
         elif a is None:
             out.append(None)
+        elif isinstance(a, ctypes.Array) and issubclass(a._type_, ctypes.Structure):
+            assert a._type_ is _lib.GpdeWeConvDesc, a._type_
+            out.append([{f: ptr(getattr(d, f)) if ct is ctypes.c_void_p else int(getattr(d, f)) for f, ct in d._fields_} for d in a])
         elif isinstance(a, ctypes.Array):
             out.append([ptr(v) for v in a] if a._type_ is ctypes.c_void_p else [int(v) for v in a])
         elif hasattr(a, "_obj"):                      # ctypes.byref(...)
@@ -206,6 +211,8 @@ def forms():
     fr, fn, fh, fm = ops.nnconv_forward_raw, ops.nnconv_forward_nodeattr_raw, ops.nnconv_forward_hidden_raw, ops.nnconv_forward_mixed_raw
     hf, br, bl = ops.hidden_forward_raw, ops.nnconv_backward_raw, ops.nnconv_backward_light_raw
     bd, bh, hb = ops.nnconv_backward_deferred_raw, ops.nnconv_backward_hidden_raw, ops.hidden_backward_raw
+    ew, fg, fe = ops.edge_weights_raw, ops.nnconv_forward_edgeweights_group, ops.nnconv_forward_edgeweights_raw
+    be, eb = ops.nnconv_backward_edgeweights_raw, ops.edge_weights_backward_raw
     big = lambda: graph(max_in_degree=ops.EDGE_PATH_MAX_IN_DEGREE + 1)
     e3 = lambda a: int(a["csr"].rowptr[3])
 
@@ -338,6 +345,32 @@ def forms():
     add("hid_b.bias_entry_none", w, lambda a: hb(a["csr"], a["ea"], DIMS, a["w"][:-1], [a["b"][0], None], a["gh"]))
     add("hid_b.slot_order", w, lambda a: _slot_order_patched(a, lambda: hb(a["csr"], a["ea"], DIMS, a["w"][:-1], a["b"][:-1], a["gh"])))
 
+    # ---- edge_weights_raw
+    w = "edge_weights_raw"
+    add("we.plain", w, lambda a: ew(a["hidden"], a["pm"], a["w"][2], a["b"][2]))
+    add("we.b_last_none", w, lambda a: ew(a["hidden"], a["pm"], a["w"][2], None))
+
+    # ---- nnconv_forward_edgeweights_group / nnconv_forward_edgeweights_raw
+    w = "nnconv_forward_edgeweights_group"
+    add("we_group.two_calls", w, lambda a: fg([
+        dict(x=a["x"], csr=a["csr"], edge_weights=a["we"], root=a["root"], bias=a["bias"], aggr="mean", residual=a["residual"], relu=True),
+        dict(x=a["x1"], csr=a["csr2"], edge_weights=a["we2"], root=None, bias=None, aggr="max", out=a["out"])]))
+    w = "nnconv_forward_edgeweights_raw"
+    add("we_fwd.plain", w, lambda a: fe(a["x"], a["csr"], a["we"], a["root"], a["bias"], "mean"))
+    add("we_fwd.glue_out", w, lambda a: fe(a["x"], a["csr"], a["we"], None, a["bias"], "add", residual=a["residual"], relu=True, out=a["out"]))
+
+    # ---- nnconv_backward_edgeweights_raw
+    w = "nnconv_backward_edgeweights_raw"
+    add("we_bwd.plain", w, lambda a: be(a["x"], a["csr"], a["we"], a["root"], "mean", a["g"]))
+    add("we_bwd.acc", w, lambda a: be(a["x"], a["csr"], a["we"], a["root"], "mean", a["g"], acc=tuple(a["acc_we"])))
+    add("we_bwd.root_none", w, lambda a: be(a["x"], a["csr"], a["we"], None, "add", a["g"]))
+    add("we_bwd.no_need_bias", w, lambda a: be(a["x"], a["csr"], a["we"], a["root"], "mean", a["g"], need_bias=False))
+
+    # ---- edge_weights_backward_raw
+    w = "edge_weights_backward_raw"
+    add("we_b.plain", w, lambda a: eb(a["gwe"], a["hidden"], DIMS, a["w"][2]))
+    add("we_b.no_need_b", w, lambda a: eb(a["gwe"], a["hidden"], DIMS, a["w"][2], need_b=False))
+
     # ---- single-fault refusals
     fwd_calls = {
         "nnconv_forward_raw": lambda a, **k: fr(a["x"], a["csr"], a["ea"], a["pm"], a["root"], a["bias"], k.pop("aggr", "mean"), **k),
@@ -405,6 +438,13 @@ def forms():
     w = "hidden_backward_raw"
     add("refuse.hid_b.weight_count", w, lambda a: hb(a["csr"], a["ea"], DIMS, a["w"], a["b"], a["gh"]))
     add("refuse.hid_b.grad_hidden_shape", w, lambda a: hb(a["csr"], a["ea"], DIMS, a["w"][:-1], a["b"][:-1], torch.zeros(E, K2P + 1)))
+    add("refuse.we.w_last_shape", "edge_weights_raw", lambda a: ew(a["hidden"], a["pm"], torch.zeros(W * W, K2 + 1), a["b"][2]))
+    add("refuse.we_group.devices", "nnconv_forward_edgeweights_group", lambda a: fg([
+        dict(x=a["x"], csr=a["csr"], edge_weights=a["we"], root=a["root"], bias=a["bias"]),
+        dict(x=a["x1"].to("meta"), csr=a["csr2"], edge_weights=a["we2"], root=None, bias=None)]))
+    add("refuse.we_fwd.aggr", "nnconv_forward_edgeweights_raw", lambda a: fe(a["x"], a["csr"], a["we"], a["root"], a["bias"], "min"))
+    add("refuse.we_bwd.aggr_max", "nnconv_backward_edgeweights_raw", lambda a: be(a["x"], a["csr"], a["we"], a["root"], "max", a["g"]))
+    add("refuse.we_b.grad_shape", "edge_weights_backward_raw", lambda a: eb(torch.zeros(E + 1, W * W), a["hidden"], DIMS, a["w"][2]))
     assert len({f[0] for f in F}) == len(F), "form ids are unique"
     return F
 
@@ -424,4 +464,7 @@ PAIRS = {
     ("nnconv_backward_raw", "gpde_nnconv_bwd"), ("nnconv_backward_light_raw", "gpde_nnconv_bwd_light"),
     ("nnconv_backward_deferred_raw", "gpde_nnconv_bwd_deferred"), ("nnconv_backward_hidden_raw", "gpde_nnconv_bwd"),
     ("hidden_backward_raw", "gpde_hidden_bwd"),
+    ("edge_weights_raw", "gpde_edge_weights_fwd"), ("nnconv_forward_edgeweights_group", "gpde_nnconv_fwd_edgeweights_group"),
+    ("nnconv_forward_edgeweights_raw", "gpde_nnconv_fwd_edgeweights_group"),
+    ("nnconv_backward_edgeweights_raw", "gpde_nnconv_bwd_edgeweights_acc"), ("edge_weights_backward_raw", "gpde_edge_weights_bwd"),
 }

@@ -1,7 +1,9 @@
-"""The native calls of the 64-wide wrappers, argument by argument (tests/helpers/native_recorder.py): the six forward-side and
-five backward-side wrappers of ops.py run on CPU tensors against a recording stub, and what reaches each entry point - the
-caller's pointers, NULL in the same places, scalars, flags, dims, pointer arrays, GpdeNodeAttr contents, workspace size - and
-every refusal's type and message equal tests/golden/native_calls_w64.json, written before the wrappers shared their bodies.
+"""The native calls of the 64-wide wrappers, argument by argument (tests/helpers/native_recorder.py): the six forward-side, five
+backward-side and five edge-weight wrappers of ops.py run on CPU tensors against a recording stub, and what reaches each entry
+point - the caller's pointers, NULL in the same places, scalars, flags, dims, pointer arrays, GpdeNodeAttr and GpdeWeConvDesc
+contents, workspace size - and every refusal's type and message equal tests/golden/native_calls_w64.json: 144 forms (128 written
+before the forward wrappers shared their body, 16 of the edge-weight wrappers before the backward wrappers shared theirs and every
+call its epilogue), 57 of them refusals, 19 (wrapper, entry point) pairs.
 Workspace-size queries are left out of the comparison: their number may change.  No GPU, no library."""
 import json
 import os

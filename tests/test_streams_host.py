@@ -182,6 +182,9 @@ def test_a_record_orders_its_hits_and_holds_what_it_declared(seams):
 class _Token:
     valid = True
 
+    def drop(self):                                             # (HiddenToken.drop: release_all forgets the token's running sums)
+        self.dropped = True
+
 
 def test_a_slot_holds_only_the_value_built_for_this_key_and_these_parameters(seams):
     p, q = torch.zeros(3), torch.zeros(3)
@@ -220,8 +223,9 @@ def test_release_all_drops_h_and_both_edge_weight_forms_and_nothing_else(seams):
         ent.hidden = torch.zeros(2)
     ent.hn, ent.dcount, ent.repeats, ent.big_key, ent.last_partial, ent.last_key = 64, 2, True, ("big",), (10, 64), ("k",)
     hidden_cache._entries[m] = ent
+    h_token = ent.h.token
     try:
-        assert hidden_cache.release_all()
+        assert hidden_cache.release_all() and h_token.dropped   # (the running sum of dL/dH goes with the H it belongs to)
         for slot in (ent.h, ent.w, ent.tw):
             assert slot.value is None and slot.held() == () and not slot.holds(("k",), [p])
         assert ent.hidden is None and ent.we is None and ent.twe is None and ent.csr is None and ent.dvirtual is not None
